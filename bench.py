@@ -5,7 +5,8 @@ A step = 2^16 sequential-semantics insertions PER GPU (BASELINE.json configs[1])
 (GPU, hash-free), all 2 + 2*32 hashes per insertion (level sweep), every per-insertion output written to HBM: old /
 interim / new root and both 32-sibling proofs.  Values are resident in HBM before the timed region.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+      --dump-outputs (N = 1): after the timed steps, the last step's outputs (a seeded sample) as DIR/<name>.npy
       N > 1 without WORLD_SIZE in the environment: this process only LAUNCHES N ranks (python -m
       torch.distributed.run, child processes; the launcher itself never touches the GPU), relays rank 0's
       line and exits with their status.
@@ -81,6 +82,8 @@ PMC_TRAFFIC_SWEEP_LEVEL = {"bytes": int((2 * 3580.1 + 8067.9) * 1024), "fetch_si
                                      "not changed since; re-collected per round by tools/gpu_round6.sh bench)",
                            "measured_at_commit": "round-5 build (k_sweep unchanged in round 6)"}
 TRACE_ROWS = 1208                   # witnesses per 2-input hash (imt_hash_trace_batch)
+DUMP_SAMPLE = 2048                  # --dump-outputs: insertions of the last timed step written out (~19 MB)
+DUMP_SEED = 0x494D54D0
 DTYPE = "u32 limbs (9 x 29-bit, Montgomery mod p), 64-bit accumulate"
 METRIC = "indexed-tree insertions/sec at depth=32 (bn256::Fr)"
 
@@ -716,6 +719,8 @@ def bench_subtrees(env):
     elif rank == world - 1:         # the last rank's last insertion closes the step: its new root is the global root
         verified = verified and bool((o["new_root"][-1].cpu() == tree.global_root.cpu()).all())
     verified = env.all_true(verified)
+    if args.dump_outputs:           # before the attribution pass: its two steps reuse the output sets
+        dump_outputs(args.dump_outputs, o, root_now)
 
     # ---- kernel attribution pass (not part of `value`): two more steps WITHOUT IMT_PIPELINE, so that each
     # kernel has the GPU to itself.  Secondary figure (roofline.alone).
@@ -743,6 +748,29 @@ def bench_subtrees(env):
            "bytes_gathered_per_step_per_rank": 0 if dist is None else 32 * world,
            "vals_h": vals_h, "ctx": ctx, "be": be}
     return res
+
+
+def dump_outputs(path, o, root):
+    """--dump-outputs DIR: what the timed path handed its caller for its LAST step, as .npy files -- every witness array
+    imt_itree_insert_batch returns (sharded.GpuBackend.FIELDS) at a fixed, seeded sample of DUMP_SAMPLE of the step's insertions
+    (the insertion axis sampled, byte arrays as float32 0..255, low_index as float64), the sampled positions, the step's
+    first new leaf index and the tree's root after the step.  The inputs are seeded, so two builds given the same
+    arguments can be compared file for file."""
+    n = o["new_root"].shape[0]
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+    idx = torch.from_numpy(pick)
+    arrays = {"sample_index": pick.astype(np.float64),
+              "first_new_index": np.array([o["first_new_index"]], dtype=np.float64),
+              "root": root.numpy().astype(np.float32)}
+    for k in ("low_index", "low_leaf", "is_largest", "old_root", "interim_root", "new_root", "new_leaf", "low_sib", "new_sib"):
+        t = o[k].index_select(1 if k.endswith("_sib") else 0, idx.to(o[k].device)).cpu().numpy()
+        arrays[k] = t.astype(np.float64 if t.dtype == np.int64 else np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs would write {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    print(f"bench: {len(arrays)} arrays of the last timed step ({total / 2**20:.1f} MB) written to {path}", file=sys.stderr, flush=True)
 
 
 def stalling_transport(env):
@@ -1064,7 +1092,11 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (one GPU, one process only)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus != 1 or os.environ.get("IMT_BENCH_FORCE_DIST")):
+        raise SystemExit("--dump-outputs needs --gpus 1 in one process (the single tree's outputs)")
     if args.gpus < 1 or args.gpus & (args.gpus - 1):
         raise SystemExit("--gpus must be a power of two (slices / subtrees of equal size)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:

@@ -200,3 +200,39 @@ def test_no_exploration_when_the_plan_was_given_or_time_is_short(tmp_path):
     sub.mkdir()
     rcs, outs, _ = run_supervisors(sub, "explore_better", {"IMT_BENCH_EXPLORE": "1", "IMT_BENCH_ATTEMPTS": "ipc:pools"})
     assert rcs == [0, 0] and len(the_line(outs)["attempts"]) == 1 and the_line(outs)["value"] == 100.0
+
+
+def test_dump_outputs_writes_a_seeded_float_sample(tmp_path):
+    """bench.py --dump-outputs, the part that needs no GPU: bench.dump_outputs writes every witness array of a step at the
+    same seeded insertion positions each time, byte arrays as float32 and indices as float64 with their values unchanged,
+    64 MB at most for a full 2^16-insertion step; and the option is refused where it has no single tree to dump."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n, depth = 1 << 16, 32
+    g = torch.Generator().manual_seed(7)
+    u8 = lambda *shape: torch.randint(0, 256, shape, dtype=torch.uint8, generator=g)
+    o = dict(low_index=torch.randint(0, 1 << 40, (n,), dtype=torch.int64, generator=g), low_leaf=u8(n, 3, 32),
+             is_largest=u8(n), old_root=u8(n, 32), interim_root=u8(n, 32), new_root=u8(n, 32), new_leaf=u8(n, 3, 32),
+             low_sib=u8(depth, n, 32), new_sib=u8(depth, n, 32), first_new_index=1 + 2 * n)
+    root = u8(32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), o, root)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    got = {f[:-len(".npy")]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(np.array_equal(got[k], np.load(tmp_path / "b" / (k + ".npy"))) for k in got)
+    pick = got["sample_index"].astype(np.int64)
+    assert pick.size == bench.DUMP_SAMPLE and (np.diff(pick) > 0).all() and pick[-1] < n
+    assert got["first_new_index"].tolist() == [1.0 + 2 * n] and (got["root"] == root.numpy()).all()
+    for k, t in o.items():
+        if k == "first_new_index":
+            continue
+        w = t.numpy()[:, pick] if k.endswith("_sib") else t.numpy()[pick]
+        assert got[k].dtype == (np.float64 if k == "low_index" else np.float32), k
+        assert got[k].shape == w.shape and (got[k] == w).all(), k
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", str(tmp_path / "c")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--dump-outputs needs --gpus 1" in r.stderr and not os.path.exists(tmp_path / "c")

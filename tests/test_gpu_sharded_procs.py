@@ -276,6 +276,44 @@ def test_bench_gpus4_as_typed_rehearsal():
     assert bad.returncode != 0
 
 
+def test_bench_one_gpu_dumps_what_its_last_step_computed(imt, ctx, tmp_path):
+    """`bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR`: the line's ms_per_step is that of exactly the two
+    timed steps, and DIR holds the LAST timed step's outputs at bench.DUMP_SAMPLE seeded positions as float .npy files,
+    64 MB at most -- equal, value for value, to what imt_itree_insert_batch returns for that step of the same seeded values
+    in this process (the kernel-attribution steps that follow the timed ones do not overwrite them)."""
+    import json
+    import subprocess
+    import bench
+    out = tmp_path / "dump"
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--no-cpu-baseline", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=env,
+                       cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    B = bench.BATCH
+    assert res["verified"] is True and res["steps"] == 2 and res["warmup"] == 1
+    assert abs(res["value"] * res["ms_per_step"] / 1e3 - B) < 1e-6 * B           # value = steps * B / time of the steps
+    got = {f.name[:-len(".npy")]: np.load(f) for f in out.iterdir()}
+    fields = ("low_index", "low_leaf", "is_largest", "old_root", "interim_root", "new_root", "new_leaf", "low_sib", "new_sib")
+    assert set(got) == set(fields) | {"sample_index", "first_new_index", "root"}, sorted(got)
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+    pick = got["sample_index"].astype(np.int64)
+    assert pick.size == bench.DUMP_SAMPLE and (np.diff(pick) > 0).all() and 0 <= pick[0] and pick[-1] < B
+    # bench's values: warmup + steps + the two attribution steps, one seeded draw; the last timed step is step 2
+    vals = bench.synth_values(5 * B, 0, 1, 0x494D5402)
+    ref = imt.IndexedTree(ctx, bench.DEPTH, 1 << 19)
+    for i in range(3):
+        want = ref.insert_batch(vals[i * B:(i + 1) * B])
+    assert got["first_new_index"].tolist() == [float(want["new_index"][0])]
+    assert (got["root"] == imt.to_bytes(ref.root()).astype(np.float32)).all()
+    for k in fields:
+        w = want[k][:, pick] if k.endswith("_sib") else want[k][pick]
+        assert got[k].shape == w.shape and (got[k] == w.astype(got[k].dtype)).all(), k
+    ref.close()
+
+
 def test_bench_keeps_the_first_leg_if_the_second_hangs():
     """A hung headline (single-list) leg must not look like a pass, and another mode's figure must never stand in for
     it.  A time limit far below what the leg needs stands in for the hang, in every attempt of the plan: every rank leaves
