@@ -23,8 +23,6 @@ struct PoseidonConsts {
                           // array so that the round's matrix is an address, not a select over both.
     Fe sp_row[RP][3];     // sparse round: new s0 = row . (y, s1, s2)
     Fe sp_col[RP][2];     // sparse round: new s_i = s_i + col_i * y
-    Fe sp_gamma[RP];      // row[p][1]*col[p-1][0] + row[p][2]*col[p-1][1]: lets round p use the linear
-                          // lanes as they were BEFORE round p-1 (two rounds share one reduction each)
     Fe cap0;              // 2^64 in device form (initial capacity lane)
     Fe one;               // 1 in device form
     Fe from_canon;        // R^2: canonical integer -> device form
@@ -32,6 +30,17 @@ struct PoseidonConsts {
     Fe to_mont256;        // 2^256 as integer: device form -> halo2curves Montgomery form
     Fe int_one;           // integer 1: device form -> canonical integer
     Fe zero_leaf;         // H(0,0,0) in device form
+    // ---- everything above is the lane-cooperative hash's table (imt_coop_device.hpp copies it to LDS) ----
+    // The thread-per-hash schedule (imt_device.hpp::permute) with its lanes rescaled by fifth roots: lane i of
+    // full round f is held as s_i / d_f,i and lane 0 of partial round p as s_0 / lambda_p, so that the S-box
+    // output lands pre-multiplied by d^5 (lambda^5) and the linear layer needs fewer products (imt_params.cpp).
+    Fe sc_rc[RF][3];      // full-round constants c_f,i / d_f,i  ([0] unused: first_rc; [4] = rc_full[4])
+    Fe sc_mats[RF][3][3]; // D_f+1^-1 M D_f^5; row 0 is (1, 1, 1) except in full rounds 0 and 4
+    Fe sc_k[RP];          // k_p / lambda_p
+    Fe sc_row[RP][3];     // new s0 / lambda_p+1 = sc_row . (xi^5, s1, s2),  xi = S-box input / lambda_p
+    Fe sc_gamma[RP];      // sc_row[p][1] + sc_row[p][2] sc_u[p-1]: round p of a pair reads the linear lanes as
+                          // they were before round p-1 ([0] unused)
+    Fe sc_u[RP];          // col[p][1] / col[p][0]: s2 += sc_u xi^5 (s1 += xi^5 needs no product)
 };
 
 // ---- f1: tables of the witness-trace kernel (imt_trace_device.hpp) -------------------------------

@@ -34,8 +34,10 @@ namespace imt {
 namespace dev {
 namespace coop {
 
-constexpr unsigned TAB_DWORDS = sizeof(PoseidonConsts) / 4;     // the whole struct is an array of Fe
+// the struct is an array of Fe; this schedule reads the entries before the thread-per-hash tables (sc_*)
+constexpr unsigned TAB_DWORDS = offsetof(PoseidonConsts, sc_rc) / 4;
 #define IMT_COOP_E(member) ((unsigned)(offsetof(PoseidonConsts, member) / sizeof(Fe)))
+static_assert(TAB_DWORDS * 4 <= 16236, "the coop kernels' LDS table must not grow");
 
 __device__ __forceinline__ void tab_fill(uint32_t* tab, const PoseidonConsts& pc) {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(&pc);

@@ -240,7 +240,7 @@ IMT_HD void sub_p(Fe& a) {
     }
 }
 
-// limb i of (p << SH), SH = 0..3
+// limb i of (p << SH), SH = 0..4
 template <int SH>
 IMT_HD constexpr uint32_t p29_shl(int i) {
     return i == 0 ? ((p29(0) << SH) & MASK29)
@@ -267,8 +267,9 @@ IMT_HD void cond_sub_p_shl(Fe& a) {
     }
 }
 
-// bring a normalised value < 16p into [0, p)
+// bring a normalised value < 32p into [0, p)
 IMT_HD void canonicalize(Fe& a) {
+    cond_sub_p_shl<4>(a);
     cond_sub_p_shl<3>(a);
     cond_sub_p_shl<2>(a);
     cond_sub_p_shl<1>(a);
@@ -326,59 +327,87 @@ IMT_HD void sbox(Fe& x) {   // x <- x^5; limbs of x < 2^30
     mont_mul(x, x4, x);
 }
 
-// One permutation, optimised schedule (same values as the plain 65-round form):
-//   rounds 0..3   : s += c_r; x^5 on all lanes; s = M s  (round 3 uses PRE = N' M)
-//   rounds 4..60  : s0 += k_p; y = s0^5; s0 = row_p . (y, s1, s2); s_i += col_p,i * y
-//   rounds 61..64 : as 0..3 (round 61's constants carry the partial rounds' leftover)
-// The 57 partial rounds run in pairs: the second round of a pair takes the linear lanes as they
-// were before the first one (its row product gets the extra term gamma * y_first), so each linear
-// lane is reduced once per pair, REDC(s_i R + col_p,i y_first + col_p+1,i y_second), instead of once
-// per round: 11 products + 4 reductions per pair instead of 10 + 6.  The odd 57th round runs
-// through the same code with y_second = 0.
+// limb i of 2^261 - p (p's lowest limb is odd: no borrow past limb 0)
+IMT_HD constexpr uint32_t pc29(int i) { return i == 0 ? (1u << 29) - p29(0) : MASK29 - p29(i); }
+constexpr uint32_t FOLD_RECIP = 1354;   // floor(2^264 / p)
+
+// a - q p with q = floor(top * floor(2^264/p) / 2^32) <= a / p: brings a lane that is only ever added to back
+// below 1.2p.  a: normalised limbs, a < 2^261.  Computed as a + q (2^261 - p) - q 2^261 (nine mads, no borrows).
+IMT_HD void fold_p(Fe& a) {
+    const uint32_t q = (uint32_t)(((uint64_t)a.v[NL - 1] * FOLD_RECIP) >> 32);
+    uint64_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < NL; i++) {
+        acc = (acc >> 29) + a.v[i] + (uint64_t)q * pc29(i);
+        a.v[i] = i < NL - 1 ? (uint32_t)acc & MASK29 : (uint32_t)(acc - ((uint64_t)q << 29));
+    }
+}
+
+// One permutation, optimised schedule (same values as the plain 65-round form), on lanes rescaled by fifth
+// roots of constants (imt_params.cpp): every S-box output arrives pre-multiplied by the factor the linear layer
+// would have applied to it, which saves products.
+//   full rounds f = 0..3, 4..7 : s += c_f; x^5 on all lanes; n = M_f s.  Row 0 of M_f is (1, 1, 1), i.e. a sum,
+//                                except in f = 0 (the caller's unscaled input) and f = 4 (the partial rounds' exit)
+//   partial rounds p = 0..56   : xi = s0 + k_p; z = xi^5; s0 = row_p . (z, s1, s2); s1 += z; s2 += u_p z
+// The partial rounds run in pairs: the second round of a pair takes the linear lanes as they were before the
+// first one (its row product gets the extra term gamma * z_first), so s2 is reduced once per pair,
+// REDC(s2 R + u_p z_first + u_p+1 z_second), and s1 takes z_first + z_second with two additions: 9 products +
+// 3 reductions per pair besides the S-boxes (was 11 + 4).  The odd 57th round runs through the same code with
+// z_second = 0.  s1 grows by < 20p per pair and is folded back below 1.2p every fourth pair (it must stay a
+// valid multiplicand: < 2^261, top limb < 2^29).
 // One loop so that each body exists once in the instruction stream.
-// `first_rc` replaces the round-0 constants (sponge padding folded in by the caller).
-// Entry: limbs normalised, lanes < 16p.  Exit: limbs normalised, every lane < 9p.
+// `first_rc` replaces the round-0 constants (sponge padding folded in by the caller); the input and the output
+// are unscaled.  Entry: limbs normalised, lane 0 < 32p, lanes 1, 2 < 16p.  Exit: limbs normalised, lane 0
+// < 30p (a sum of three S-box outputs), lanes 1, 2 < 9p.  Bounds: tests/test_rescaled_schedule.py.
 IMT_HD void permute(const PoseidonConsts& pc, Fe s[3], const Fe* first_rc) {
     constexpr int NSTEP = RF + (RP + 1) / 2;   // 4 full, 29 partial pairs, 4 full
 #pragma unroll 1
     for (int st = 0; st < NSTEP; st++) {
         if (st < RF / 2 || st >= RF / 2 + (RP + 1) / 2) {
             const int fr = st < RF / 2 ? st : st - (RP + 1) / 2;
-            const Fe* rc = (st == 0) ? first_rc : pc.rc_full[fr];
+            const Fe* rc = (st == 0) ? first_rc : pc.sc_rc[fr];
             add_lazy(s[0], s[0], rc[0]);
             add_lazy(s[1], s[1], rc[1]);
             add_lazy(s[2], s[2], rc[2]);
             sbox(s[0]); sbox(s[1]); sbox(s[2]);
-            const Fe(*mat)[3] = pc.mats[st == RF / 2 - 1 ? 1 : 0];
+            const Fe(*mat)[3] = pc.sc_mats[fr];
             Fe n0, n1, n2;
-            mont_dot_uc<3, false>(n0, mat[0], s, s[0]);
+            if (fr == 0 || fr == RF / 2) {
+                mont_dot_uc<3, false>(n0, mat[0], s, s[0]);
+            } else {
+                add_lazy(n0, s[0], s[1]);
+                add_lazy(n0, n0, s[2]);
+                normalize(n0);
+            }
             mont_dot_uc<3, false>(n1, mat[1], s, s[0]);
             mont_dot_uc<3, false>(n2, mat[2], s, s[0]);
             s[0] = n0; s[1] = n1; s[2] = n2;
         } else {
             const int p = 2 * (st - RF / 2);
             const bool second = p + 1 < RP;
-            Fe v[4], y[2], n0;
-            add_lazy(v[0], s[0], pc.k_partial[p]);
+            Fe v[4], z[2], n0;
+            add_lazy(v[0], s[0], pc.sc_k[p]);
             sbox(v[0]);
             v[1] = s[1]; v[2] = s[2];
-            mont_dot_uc<3, false>(n0, pc.sp_row[p], v, v[0]);
-            y[0] = v[0];
+            mont_dot_uc<3, false>(n0, pc.sc_row[p], v, v[0]);
+            z[0] = v[0];
 #pragma unroll
-            for (int i = 0; i < NL; i++) y[1].v[i] = 0;
+            for (int i = 0; i < NL; i++) z[1].v[i] = 0;
             if (second) {
-                add_lazy(v[0], n0, pc.k_partial[p + 1]);
+                add_lazy(v[0], n0, pc.sc_k[p + 1]);
                 sbox(v[0]);
-                v[3] = y[0];
-                const Fe c4[4] = {pc.sp_row[p + 1][0], pc.sp_row[p + 1][1], pc.sp_row[p + 1][2], pc.sp_gamma[p + 1]};
+                v[3] = z[0];
+                const Fe c4[4] = {pc.sc_row[p + 1][0], pc.sc_row[p + 1][1], pc.sc_row[p + 1][2], pc.sc_gamma[p + 1]};
                 mont_dot_uc<4, false>(n0, c4, v, v[0]);
-                y[1] = v[0];
+                z[1] = v[0];
             }
-            const int q = second ? p + 1 : p;    // with y[1] = 0 the second column constant is unused
-            const Fe c1[2] = {pc.sp_col[p][0], pc.sp_col[q][0]};
-            const Fe c2[2] = {pc.sp_col[p][1], pc.sp_col[q][1]};
-            mont_dot_uc<2, true, false>(s[1], c1, y, s[1]);   // narrow digits: these lanes only accumulate
-            mont_dot_uc<2, true, false>(s[2], c2, y, s[2]);
+            const int q = second ? p + 1 : p;    // with z[1] = 0 the second constant is unused
+            const Fe cu[2] = {pc.sc_u[p], pc.sc_u[q]};
+            mont_dot_uc<2, true, false>(s[2], cu, z, s[2]);   // narrow digits: this lane only accumulates
+            add_lazy(s[1], s[1], z[0]);
+            add_lazy(s[1], s[1], z[1]);
+            normalize(s[1]);
+            if ((p & 7) == 6) fold_p(s[1]);      // after pairs 3, 7, .., 27
             s[0] = n0;
         }
     }

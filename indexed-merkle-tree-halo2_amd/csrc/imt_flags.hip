@@ -60,17 +60,22 @@ __global__ void k_copy16_multi(imt::launch::CopyJobs jobs, size_t n16, const uin
 }
 
 // ---- which streams share a hardware queue (imt_sliced.cpp: QueueProbe) ----
-// k_spin holds its stream's hardware queue for `ticks` of the 100 MHz wall clock and writes when it ended; k_stamp
-// writes when it RAN.  A stamp taken on another stream that is not earlier than the spin's end could not start before
-// the spin had finished: the two streams share an in-order hardware queue.  One wave each, bounded, GPU clock only.
-__global__ void k_spin(uint64_t ticks, uint64_t* end_stamp) {
+// k_spin holds its stream's hardware queue until `n` stamps have been counted or `ticks` of the 100 MHz wall clock have
+// passed, and writes when it ended; k_stamp writes when it RAN and counts itself.  A stamp taken on another stream that
+// is not earlier than the spin's end could not start before the spin had finished: the two streams share an in-order
+// hardware queue.  One wave each, bounded, GPU clock only.
+__global__ void k_spin(uint64_t ticks, uint64_t* end_stamp, const uint64_t* count, uint64_t n) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const uint64_t t0 = wall_clock64();
-    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
+    while (wall_clock64() - t0 < ticks && __hip_atomic_load(count, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < n)
+        __builtin_amdgcn_s_sleep(32);
     *end_stamp = wall_clock64();
 }
-__global__ void k_stamp(uint64_t* stamp) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) *stamp = wall_clock64();
+__global__ void k_stamp(uint64_t* stamp, uint64_t* count) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        *stamp = wall_clock64();
+        __hip_atomic_fetch_add(count, (uint64_t)1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 
 }  // namespace
@@ -98,8 +103,10 @@ void flag_set_checked(hipStream_t s, uint64_t* flag, uint64_t value, const uint3
     hipLaunchKernelGGL(k_flag_set_checked, dim3(1), dim3(64), 0, s, flag, value, poison);
 }
 
-void spin(hipStream_t s, uint64_t ticks, uint64_t* end_stamp) { hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, s, ticks, end_stamp); }
-void stamp(hipStream_t s, uint64_t* out) { hipLaunchKernelGGL(k_stamp, dim3(1), dim3(64), 0, s, out); }
+void spin(hipStream_t s, uint64_t ticks, uint64_t* end_stamp, const uint64_t* count, uint64_t n) {
+    hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, s, ticks, end_stamp, count, n);
+}
+void stamp(hipStream_t s, uint64_t* out, uint64_t* count) { hipLaunchKernelGGL(k_stamp, dim3(1), dim3(64), 0, s, out, count); }
 
 void flag_set(hipStream_t s, uint64_t* flag, uint64_t value) { hipLaunchKernelGGL(k_flag_set, dim3(1), dim3(64), 0, s, flag, value); }
 

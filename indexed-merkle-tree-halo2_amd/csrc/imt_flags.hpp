@@ -31,8 +31,8 @@ void copy16_multi(hipStream_t s, const CopyJobs& jobs, size_t bytes, const uint3
 void flag_set_checked(hipStream_t s, uint64_t* flag, uint64_t value, const uint32_t* poison);
 // the hardware-queue probe: hold stream s for `ticks` of the 100 MHz wall clock and write the end time / write the time
 // the kernel ran (one wave each)
-void spin(hipStream_t s, uint64_t ticks, uint64_t* end_stamp);
-void stamp(hipStream_t s, uint64_t* out);
+void spin(hipStream_t s, uint64_t ticks, uint64_t* end_stamp, const uint64_t* count, uint64_t n);
+void stamp(hipStream_t s, uint64_t* out, uint64_t* count);
 
 }  // namespace launch
 }  // namespace imt

@@ -129,14 +129,34 @@ struct HField {
         HFr t = mul(a, HFr{{1, 0, 0, 0}});
         std::memcpy(out, t.l, 32);
     }
-    HFr inverse(const HFr& a) const {   // a^(p-2)
-        uint64_t e[4] = {P[0] - 2, P[1], P[2], P[3]};
+    HFr pow(const HFr& a, const uint64_t e[4]) const {   // a^e, e a little-endian 256-bit integer
         HFr acc = r1, base = a;
         for (int i = 0; i < 256; i++) {
             if ((e[i / 64] >> (i % 64)) & 1) acc = mul(acc, base);
             base = mul(base, base);
         }
         return acc;
+    }
+    HFr inverse(const HFr& a) const {   // a^(p-2)
+        const uint64_t e[4] = {P[0] - 2, P[1], P[2], P[3]};
+        return pow(a, e);
+    }
+    // the unique b with b^5 = a: gcd(5, p-1) = 1, so b = a^d with d = 5^-1 mod (p-1) = (4(p-1) + 1) / 5
+    HFr fifth_root(const HFr& a) const {
+        uint64_t e[4];
+        u128 c = 1;                                   // 4 (p - 1) + 1 = 4p - 3
+        for (int i = 0; i < 4; i++) {
+            c += (u128)P[i] * 4 - (i == 0 ? 4 : 0);
+            e[i] = (uint64_t)c;
+            c >>= 64;
+        }
+        u128 rem = 0;                                 // long division by 5, most significant word first
+        for (int i = 3; i >= 0; i--) {
+            u128 cur = (rem << 64) | e[i];
+            e[i] = (uint64_t)(cur / 5);
+            rem = cur % 5;
+        }
+        return pow(a, e);
     }
     bool is_zero(const HFr& a) const { return (a.l[0] | a.l[1] | a.l[2] | a.l[3]) == 0; }
 };

@@ -9,7 +9,8 @@
 //   * partial-round constants of the linear lanes are pushed forward through M into the
 //     lane-0 constants and the first constants of the second half of the full rounds;
 //   * M = S * N' with N' = diag(1, D) commuting with the partial S-box; every N' is pulled
-//     back into the previous round, leaving one dense PRE matrix and 57 sparse ones.
+//     back into the previous round, leaving one dense PRE matrix and 57 sparse ones;
+//   * for the device, the lanes of that schedule rescaled by fifth roots of its constants (sc_* tables).
 // Any such schedule is value-identical to the plain form; init() checks that.
 #include "imt_params.hpp"
 
@@ -89,6 +90,47 @@ void HostPoseidon::permute_opt(HFr s[3]) const {
             s[0] = n0;
         }
     }
+}
+
+// The device schedule (imt_device.hpp::permute) on plain field elements: full rounds on rescaled lanes with the
+// (1, 1, 1) row as a sum, partial rounds in pairs on the rescaled lane 0 (the second round of a pair reads the
+// linear lanes as they were before the first, plus gamma * z_first), s1 += z with no product.
+void HostPoseidon::permute_scaled(HFr s[3]) const {
+    auto sbox = [&](HFr& x) {
+        HFr x2 = F.mul(x, x), x4 = F.mul(x2, x2);
+        x = F.mul(x4, x);
+    };
+    auto dot = [&](const HFr* c, const HFr* v, int n) {
+        HFr o = F.zero();
+        for (int i = 0; i < n; i++) o = F.add(o, F.mul(c[i], v[i]));
+        return o;
+    };
+    auto full = [&](int f) {
+        for (int i = 0; i < 3; i++) s[i] = F.add(s[i], sc_rc[f][i]);
+        for (int i = 0; i < 3; i++) sbox(s[i]);
+        const HFr n0 = (f == 0 || f == 4) ? dot(sc_mats[f][0], s, 3) : F.add(F.add(s[0], s[1]), s[2]);
+        const HFr n1 = dot(sc_mats[f][1], s, 3), n2 = dot(sc_mats[f][2], s, 3);
+        s[0] = n0; s[1] = n1; s[2] = n2;
+    };
+    for (int f = 0; f < 4; f++) full(f);
+    for (int p = 0; p < 57; p += 2) {
+        HFr z0 = F.add(s[0], sc_k[p]);
+        sbox(z0);
+        const HFr v3[3] = {z0, s[1], s[2]};
+        HFr n0 = dot(sc_row[p], v3, 3), z1 = F.zero();
+        if (p + 1 < 57) {
+            z1 = F.add(n0, sc_k[p + 1]);
+            sbox(z1);
+            const HFr c4[4] = {sc_row[p + 1][0], sc_row[p + 1][1], sc_row[p + 1][2], sc_gamma[p + 1]};
+            const HFr v4[4] = {z1, s[1], s[2], z0};
+            n0 = dot(c4, v4, 4);
+        }
+        s[1] = F.add(s[1], F.add(z0, z1));
+        s[2] = F.add(s[2], F.mul(sc_u[p], z0));
+        if (p + 1 < 57) s[2] = F.add(s[2], F.mul(sc_u[p + 1], z1));
+        s[0] = n0;
+    }
+    for (int f = 4; f < 8; f++) full(f);
 }
 
 // The permutation as halo2-base's PoseidonState::permutation / pse-poseidon's Spec::permute run it (no
@@ -231,6 +273,68 @@ bool HostPoseidon::init(std::string& err) {
     }
     std::memcpy(pre, cur, sizeof pre);
 
+    // ---- the device schedule: lanes rescaled by fifth roots (x -> x^5 is a bijection: gcd(5, p - 1) = 1) ----
+    // Partial round p holds its S-box input as xi = x / lambda_p with lambda_p^5 = 1 / col[p][0]: the S-box gives
+    // xi^5 = col[p][0] y, so s1 += col[p][0] y is a plain addition and s2 += col[p][1] y is (col[p][1]/col[p][0]) xi^5.
+    // 1 / lambda_p goes into k_p and into the row that produces lane 0 (the previous round's, or full round 3's);
+    // lambda_57 = 1.  Lanes 1 and 2 are never rescaled.
+    // Full round f holds lane i as s_i / d_f,i; its matrix is D_f+1^-1 M D_f^5 and its constants c_f,i / d_f,i.
+    // Choosing d_f,j^5 = d_f+1,0 / M[0][j] makes row 0 (1, 1, 1); solved backwards from D_8 = I (the output is
+    // unscaled) and from D_4 = diag(lambda_0, 1, 1) (the partial rounds' entry).  D_0 = I (the caller's input: the
+    // first constants stay rc_full[0] / rc_h2p2) and D_4 = I (the partial rounds' exit), so full rounds 0 and 4
+    // keep a general row 0.
+    {
+        HFr lam[58];
+        for (int p = 0; p < 57; p++) {
+            if (F.is_zero(sp_col[p][0])) { err = "sparse column entry col[p][0] is zero: no fifth-root rescaling"; return false; }
+            lam[p] = F.fifth_root(F.inverse(sp_col[p][0]));
+            HFr l2 = F.mul(lam[p], lam[p]);
+            if (!(F.mul(F.mul(l2, l2), F.mul(lam[p], sp_col[p][0])) == F.one())) { err = "fifth root check failed"; return false; }
+        }
+        lam[57] = F.one();
+        for (int p = 0; p < 57; p++) {
+            const HFr li = F.inverse(lam[p]), ln = F.inverse(lam[p + 1]);
+            sc_k[p] = F.mul(k_partial[p], li);
+            sc_row[p][0] = F.mul(sp_row[p][0], F.mul(F.inverse(sp_col[p][0]), ln));
+            sc_row[p][1] = F.mul(sp_row[p][1], ln);
+            sc_row[p][2] = F.mul(sp_row[p][2], ln);
+            sc_u[p] = F.mul(sp_col[p][1], F.inverse(sp_col[p][0]));
+        }
+        sc_gamma[0] = F.zero();
+        for (int p = 1; p < 57; p++) sc_gamma[p] = F.add(sc_row[p][1], F.mul(sc_row[p][2], sc_u[p - 1]));
+
+        HFr d[9][3];                                   // d[f] scales the input of full round f; d[8] the output
+        for (int i = 0; i < 3; i++) d[0][i] = d[4][i] = d[8][i] = F.one();
+        const HFr d4in[3] = {lam[0], F.one(), F.one()};   // input scaling of partial round 0
+        auto solve = [&](int f, const HFr m[3][3], const HFr& dn0) {
+            for (int j = 0; j < 3; j++) {
+                if (F.is_zero(m[0][j])) { err = "zero entry in row 0 of a full-round matrix"; return false; }
+                d[f][j] = F.fifth_root(F.mul(dn0, F.inverse(m[0][j])));
+            }
+            return true;
+        };
+        for (int f = 7; f >= 5; f--)
+            if (!solve(f, mds, d[f + 1][0])) return false;
+        if (!solve(3, pre, d4in[0])) return false;
+        for (int f = 2; f >= 1; f--)
+            if (!solve(f, mds, d[f + 1][0])) return false;
+        for (int f = 0; f < 8; f++) {
+            const HFr(*m)[3] = f == 3 ? pre : mds;
+            const HFr* dn = f == 3 ? d4in : d[f + 1];
+            for (int i = 0; i < 3; i++) {
+                sc_rc[f][i] = F.mul(rc_full[f][i], F.inverse(d[f][i]));
+                const HFr dni = F.inverse(dn[i]);
+                for (int j = 0; j < 3; j++) {
+                    HFr d2 = F.mul(d[f][j], d[f][j]);
+                    sc_mats[f][i][j] = F.mul(F.mul(m[i][j], dni), F.mul(F.mul(d2, d2), d[f][j]));
+                }
+            }
+            if (f != 0 && f != 4)
+                for (int j = 0; j < 3; j++)
+                    if (!(sc_mats[f][0][j] == F.one())) { err = "rescaled full-round row 0 is not (1, 1, 1)"; return false; }
+        }
+    }
+
     // ---- the halo2-base / pse-poseidon spec (Spec::new): needed value by value by the witness trace ----
     {
         typedef HFr M3[3][3];
@@ -301,17 +405,23 @@ bool HostPoseidon::init(std::string& err) {
             for (int j = 0; j < 3; j++) tr_pre[i][j] = a[j][i];
     }
 
-    // ---- self-check: optimised == plain ----
-    for (uint64_t t = 0; t < 4; t++) {
+    // ---- self-check: optimised == rescaled == plain ----
+    for (uint64_t t = 0; t < 6; t++) {
         HFr a[3] = {F.from_u64(t * 7919), F.from_u64(t * t + 1), F.mul(cap0, F.from_u64(t + 3))};
-        HFr b[3] = {a[0], a[1], a[2]};
+        if (t == 4) a[0] = a[1] = a[2] = F.sub(F.zero(), F.one());           // p - 1 on every lane
+        if (t == 5) a[0] = a[1] = a[2] = F.mul(cap0, cap0);                  // all lanes equal
+        HFr b[3] = {a[0], a[1], a[2]}, sc[3] = {a[0], a[1], a[2]}, c3[3] = {a[0], a[1], a[2]};
         permute_plain(a);
         permute_opt(b);
+        permute_scaled(sc);
         if (!(a[0] == b[0] && a[1] == b[1] && a[2] == b[2])) {
             err = "optimised Poseidon schedule disagrees with the plain form";
             return false;
         }
-        HFr c3[3] = {F.from_u64(t * 7919), F.from_u64(t * t + 1), F.mul(cap0, F.from_u64(t + 3))};
+        if (!(a[0] == sc[0] && a[1] == sc[1] && a[2] == sc[2])) {
+            err = "rescaled Poseidon schedule disagrees with the plain form";
+            return false;
+        }
         // permute_spec adds start[0] itself (absorb_with_pre_constants does it in the gadget); the plain form adds
         // c_0 in round 0, and start[0] == c_0
         permute_spec(c3);
@@ -373,14 +483,20 @@ void HostPoseidon::fill_consts(dev::PoseidonConsts& pc) const {
     pc.rc_h2p2[0] = to_dev(rc_full[0][0]);
     pc.rc_h2p2[1] = to_dev(F.add(rc_full[0][1], F.one()));
     pc.rc_h2p2[2] = to_dev(rc_full[0][2]);
-    pc.sp_gamma[0] = to_dev(F.zero());
-    for (int p = 1; p < 57; p++)
-        pc.sp_gamma[p] = to_dev(F.add(F.mul(sp_row[p][1], sp_col[p - 1][0]), F.mul(sp_row[p][2], sp_col[p - 1][1])));
     for (int p = 0; p < 57; p++) {
         pc.k_partial[p] = to_dev(k_partial[p]);
         for (int i = 0; i < 3; i++) pc.sp_row[p][i] = to_dev(sp_row[p][i]);
         for (int i = 0; i < 2; i++) pc.sp_col[p][i] = to_dev(sp_col[p][i]);
+        pc.sc_k[p] = to_dev(sc_k[p]);
+        for (int i = 0; i < 3; i++) pc.sc_row[p][i] = to_dev(sc_row[p][i]);
+        pc.sc_gamma[p] = to_dev(sc_gamma[p]);
+        pc.sc_u[p] = to_dev(sc_u[p]);
     }
+    for (int f = 0; f < 8; f++)
+        for (int i = 0; i < 3; i++) {
+            pc.sc_rc[f][i] = to_dev(sc_rc[f][i]);
+            for (int j = 0; j < 3; j++) pc.sc_mats[f][i][j] = to_dev(sc_mats[f][i][j]);
+        }
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) {
             pc.mats[0][i][j] = to_dev(mds[i][j]);

@@ -131,25 +131,29 @@ int bounded_wait(imt_ctx* ctx, long limit_ms, Query query, const char* what) {
 // submission order, one packet after the other, and an event wait blocks the whole queue: a stream that shares a queue
 // with a busy one stands behind that stream's backlog.  Where the sliced mode's streams land therefore decides how much
 // of the schedule's overlap is real (tests/hwq_model.py is the CPU model of exactly this).  The probe: hold
-// one stream with a one-wave kernel that spins for 200 us of the GPU's wall clock and notes when it ended, stamp the
-// time on every other stream; a stamp not earlier than the end was taken behind the spin -- same queue.  GPU clock
-// only; the streams are idle when it runs (creation time).
+// one stream with a one-wave kernel that waits until a stamp has run on every other stream, or 50 ms of the GPU's wall
+// clock have passed, and notes when it ended; stamp the time on every other stream.  A stamp not earlier than the end
+// was taken behind the waiting kernel -- same queue.  GPU clock only; the streams are idle when it runs (creation
+// time).  The wait ends on the stamps, not after a fixed time, because with other processes on the device the hardware
+// scheduler can leave a queue of its own unserved for milliseconds (stamps 8-11 ms late were seen with a second process
+// hashing): a fixed short spin read those as shared queues.  Only a stream that really shares the queue costs 50 ms.
 struct QueueProbe {
     imt_ctx* ctx = nullptr;
-    uint64_t* d = nullptr;
+    uint64_t* d = nullptr;                    // [0, MAXS): stamps, [MAXS]: end of the wait, [MAXS + 1]: stamps counted
     static constexpr int MAXS = 16;
-    uint64_t spin_ticks = 20000;
+    uint64_t spin_ticks = 5000000;
     int probes = 0;
 
     int init(imt_ctx* c) {
         ctx = c;
         int khz = 100000;
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) != hipSuccess || khz <= 0) khz = 100000;
-        spin_ticks = (uint64_t)khz / 5;      // 200 us
-        IMT_HIP(c, hipMalloc((void**)&d, sizeof(uint64_t) * (MAXS + 1)));
+        spin_ticks = (uint64_t)khz * 50;      // 50 ms
+        IMT_HIP(c, hipMalloc((void**)&d, sizeof(uint64_t) * (MAXS + 2)));
+        IMT_HIP(c, hipMemsetAsync(d, 0, sizeof(uint64_t) * (MAXS + 2), c->stream));
         // both kernels once, so that no first-launch cost (code object load) sits inside a measurement
-        imt::launch::spin(c->stream, 1, d + MAXS);
-        imt::launch::stamp(c->stream, d);
+        imt::launch::spin(c->stream, 1, d + MAXS, d + MAXS + 1, 0);
+        imt::launch::stamp(c->stream, d, d + MAXS + 1);
         IMT_HIP(c, hipStreamSynchronize(c->stream));
         return IMT_OK;
     }
@@ -162,10 +166,10 @@ struct QueueProbe {
         uint64_t h[MAXS + 1];
         IMT_HIP(ctx, hipStreamSynchronize(busy));
         for (int j = 0; j < n; j++) IMT_HIP(ctx, hipStreamSynchronize(others[j]));
-        IMT_HIP(ctx, hipMemsetAsync(d, 0, sizeof(uint64_t) * (MAXS + 1), ctx->stream));
+        IMT_HIP(ctx, hipMemsetAsync(d, 0, sizeof(uint64_t) * (MAXS + 2), ctx->stream));
         IMT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        imt::launch::spin(busy, spin_ticks, d + MAXS);
-        for (int j = 0; j < n; j++) imt::launch::stamp(others[j], d + j);
+        imt::launch::spin(busy, spin_ticks, d + MAXS, d + MAXS + 1, (uint64_t)n);
+        for (int j = 0; j < n; j++) imt::launch::stamp(others[j], d + j, d + MAXS + 1);
         IMT_HIP(ctx, hipGetLastError());
         IMT_HIP(ctx, hipStreamSynchronize(busy));
         for (int j = 0; j < n; j++) IMT_HIP(ctx, hipStreamSynchronize(others[j]));
