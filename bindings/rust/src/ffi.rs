@@ -133,6 +133,13 @@ pub const IMT_F_NEXT_IDX: u8 = 0x20;
 pub const IMT_F_NEW_ROOT: u8 = 0x40;
 pub const IMT_F_BAD_BIT: u8 = 0x80;
 
+// status of a value (imt_itree_insert_filtered / imt_itree_lookup_batch)
+pub const IMT_VAL_NEW: u8 = 0;
+pub const IMT_VAL_ZERO: u8 = 1;
+pub const IMT_VAL_PRESENT: u8 = 2;
+pub const IMT_VAL_REPEATED: u8 = 3;
+pub const IMT_VAL_FOREIGN: u8 = 4;
+
 pub const IMT_PROF_LEAVES: usize = 0;
 pub const IMT_PROF_INDEX: usize = 1;
 pub const IMT_PROF_LEVEL: usize = 2;
@@ -244,6 +251,8 @@ extern "C" {
     pub fn imt_itree_get_leaves(t: *mut imt_itree, index: *const u64, n: usize, preimage: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_load(t: *mut imt_itree, preimages: *const c_void, n: u64, flags: c_uint) -> c_int;
     pub fn imt_itree_find_low_batch(t: *mut imt_itree, vals: *const c_void, n: usize, low_index: *mut u64, flags: c_uint) -> c_int;
+    pub fn imt_itree_insert_filtered(t: *mut imt_itree, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, n_inserted: *mut u64, out: *const imt_insert_out, flags: c_uint) -> c_int;
+    pub fn imt_itree_lookup_batch(t: *mut imt_itree, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, flags: c_uint) -> c_int;
     pub fn imt_itree_non_membership_witness(t: *mut imt_itree, vals: *const c_void, n: usize, low_index: *mut u64, low_leaf: *mut c_void, is_largest: *mut u8, low_sib: *mut c_void, flags: c_uint) -> c_int;
 
     // ---- e: the tree as one subtree of a deeper tree

@@ -435,6 +435,38 @@ int imt_itree_load(imt_itree *t, const void *preimages /*[n][3][32]*/, uint64_t 
 int imt_itree_find_low_batch(imt_itree *t, const void *vals /*[n][32]*/, size_t n,
                              uint64_t *low_index /*[n]*/, unsigned flags);
 
+/* Status of one value of imt_itree_insert_filtered / imt_itree_lookup_batch.  When several apply, the first in this
+ * order wins: ZERO, FOREIGN, PRESENT, REPEATED, NEW (a value both stored and repeated in the batch is PRESENT at every
+ * occurrence). */
+#define IMT_VAL_NEW 0         /* insert_filtered: inserted; lookup: absent */
+#define IMT_VAL_ZERO 1        /* 0, the sentinel (:373-376): refused */
+#define IMT_VAL_PRESENT 2     /* already stored: skipped */
+#define IMT_VAL_REPEATED 3    /* insert_filtered only: an earlier occurrence in the same batch was inserted; skipped */
+#define IMT_VAL_FOREIGN 4     /* another subtree's residue (imt_itree_set_value_partition): skipped */
+/* A sequencer's batch that may hold double spends: the reference's sequence of insert_leaf calls with the rejected
+ * values skipped.  Let A be the values whose status is IMT_VAL_NEW, in input order: the call IS
+ * imt_itree_insert_batch(t, A, |A|, out, flags) -- the same tree, byte for byte the same witness rows.  Row r of every
+ * out array belongs to the r-th accepted value and rows [0, *n_inserted) are written; sibling arrays keep the caller's
+ * dimensions (level-major [depth][n][32] with level stride n, not *n_inserted; or item-major [n][depth][32]).
+ * leaf_index[i]: NEW -> the leaf it was written to; PRESENT -> the stored leaf that holds it; REPEATED -> the leaf its
+ * first occurrence was written to; ZERO -> the sentinel; FOREIGN -> UINT64_MAX (global indices on a placed tree).
+ * status / leaf_index are host or device memory per flags, *n_inserted is host memory; all three are complete when the
+ * call returns (it waits for the classification on the GPU, as imt_itree_insert_batch waits for its value check).
+ * Every flag means what it means to imt_itree_insert_batch.  Errors, the tree untouched: IMT_ERR_FULL if size +
+ * *n_inserted exceeds the capacity, IMT_ERR_NONCANONICAL for a value >= p (malformed input, not a rejection), and the
+ * calls imt_itree_insert_batch refuses.  Nothing accepted: IMT_OK, *n_inserted = 0, only status / leaf_index written.
+ * NULL status or n_inserted -> IMT_ERR_ARG. */
+int imt_itree_insert_filtered(imt_itree *t, const void *vals /*[n][32]*/, size_t n, uint8_t *status /*[n]*/,
+                              uint64_t *leaf_index /*[n] or NULL*/, uint64_t *n_inserted /*host*/,
+                              const imt_insert_out *out /*may be NULL*/, unsigned flags);
+/* Read-only query of the device-resident index for any mix of values (one kernel, k_lookup): status ZERO / FOREIGN /
+ * PRESENT / NEW and leaf_index = the sentinel / UINT64_MAX / the stored leaf / the low leaf (what find_low returns).
+ * Fails only for its arguments, a value >= p (IMT_ERR_NONCANONICAL) or a HIP error, never for a value's class.  With
+ * imt_itree_get_leaves and imt_itree_get_proof_batch a PRESENT index gives the membership witness verify_proof takes
+ * (src/utils.rs:87). */
+int imt_itree_lookup_batch(imt_itree *t, const void *vals /*[n][32]*/, size_t n, uint8_t *status /*[n]*/,
+                           uint64_t *leaf_index /*[n] or NULL*/, unsigned flags);
+
 /* Witness of verify_non_inclusion for n candidate values against the current tree, produced on the
  * GPU from the device-resident index: the low leaf (greatest stored value below the candidate), its
  * preimage, the is_largest flag and its `depth` siblings.  Outputs feed imt_non_membership_batch

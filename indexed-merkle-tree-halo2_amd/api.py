@@ -603,6 +603,41 @@ class IndexedTree:
         res["new_index"] = np.arange(self.size - n, self.size, dtype=np.uint64) + np.uint64(self.index_base)
         return res
 
+    def insert_filtered(self, vals, proofs=True, item_major=False, host_prep=False):
+        """insert_batch() of the values that are neither 0, stored, repeated in the batch nor of another subtree
+        (imt_itree_insert_filtered): the insert_batch dict cut to the n_inserted accepted rows, plus status (VAL_* per
+        value), leaf_index (per value) and n_inserted."""
+        v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
+        n, d = v.shape[0], self.global_depth
+        res = dict(low_index=np.empty(n, np.uint64), low_leaf=np.empty((n, 3, 32), np.uint8),
+                   is_largest=np.empty(n, np.uint8), old_root=np.empty((n, 32), np.uint8),
+                   interim_root=np.empty((n, 32), np.uint8), new_root=np.empty((n, 32), np.uint8),
+                   new_leaf=np.empty((n, 3, 32), np.uint8))
+        if proofs:
+            shape = (n, d, 32) if item_major else (d, n, 32)
+            res["low_sib"] = np.empty(shape, np.uint8)
+            res["new_sib"] = np.empty(shape, np.uint8)
+        out = _ffi.InsertOut(**{k: a.ctypes.data for k, a in res.items()})
+        status, leaf = np.empty(n, np.uint8), np.empty(n, np.uint64)
+        n_ins = ctypes.c_uint64()
+        flags = (_ffi.SIB_ITEM_MAJOR if item_major else 0) | (_ffi.HOST_PREP if host_prep else 0)
+        self.ctx._check(lib.imt_itree_insert_filtered(self.h, _p(v), n, _p(status), _p(leaf), ctypes.byref(n_ins),
+                                                      ctypes.byref(out), flags))
+        m = n_ins.value
+        for k in list(res):
+            res[k] = res[k][:, :m] if k.endswith("_sib") and not item_major else res[k][:m]
+        res["new_index"] = np.arange(self.size - m, self.size, dtype=np.uint64) + np.uint64(self.index_base)
+        res.update(status=status, leaf_index=leaf, n_inserted=m)
+        return res
+
+    def lookup(self, vals):
+        """(status, leaf_index) of every value against the stored tree (imt_itree_lookup_batch): VAL_PRESENT with the
+        leaf that holds it, VAL_NEW with its low leaf, VAL_ZERO with the sentinel, VAL_FOREIGN with 2^64 - 1."""
+        v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
+        status, leaf = np.empty(v.shape[0], np.uint8), np.empty(v.shape[0], np.uint64)
+        self.ctx._check(lib.imt_itree_lookup_batch(self.h, _p(v), v.shape[0], _p(status), _p(leaf), 0))
+        return status, leaf
+
     def get_proof_batch(self, index, item_major=False):
         idx = np.ascontiguousarray(index, dtype=np.uint64)
         out = np.empty((idx.size, self.depth, 32) if item_major else (self.depth, idx.size, 32), dtype=np.uint8)

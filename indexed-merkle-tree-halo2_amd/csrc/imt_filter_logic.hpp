@@ -1,0 +1,88 @@
+// imt_filter_logic.hpp -- the per-value rule of imt_itree_insert_filtered and imt_itree_lookup_batch (include/imt.h),
+// kept free of HIP types like imt_prep_logic.hpp: the kernels of imt_prep.hip and a host build
+// (tests/test_filter_rules.py) include the same code.
+//
+// The filtered batch is the reference's sequence of insert_leaf calls with the rejected ones skipped.  Every value has
+// one status; when several apply the first in this order wins: ZERO, FOREIGN, PRESENT, REPEATED, NEW.  ZERO and FOREIGN
+// depend on the value alone, PRESENT on the stored index, REPEATED on the batch in value order (ties by input position,
+// a total order, so the outcome does not depend on how the sort breaks ties): the head of a run of equal values is its
+// first occurrence, the rest repeat it.
+#pragma once
+#include <cstdint>
+#include "imt_prep_logic.hpp"
+
+namespace imt {
+namespace prep {
+
+// include/imt.h IMT_VAL_*
+constexpr uint8_t VAL_NEW = 0, VAL_ZERO = 1, VAL_PRESENT = 2, VAL_REPEATED = 3, VAL_FOREIGN = 4;
+constexpr uint64_t LEAF_NONE = ~(uint64_t)0;
+
+// what a value is by itself: ZERO, FOREIGN, or NEW (not decided yet).  0 is the sentinel whatever the partition.
+IMT_PL_HD uint8_t filter_class(const uint8_t* v, uint32_t part_mod, uint32_t part_res) {
+    const uint64_t* x = reinterpret_cast<const uint64_t*>(v);
+    if ((x[0] | x[1] | x[2] | x[3]) == 0) return VAL_ZERO;
+    if (part_mod > 1 && mod_small(v, part_mod) != part_res) return VAL_FOREIGN;
+    return VAL_NEW;
+}
+
+// the batch order: by value, equal values by input position
+IMT_PL_HD bool pos_less(const uint8_t* vals, uint32_t a, uint32_t b) {
+    const uint8_t* x = vals + (uint64_t)a * 32;
+    const uint8_t* y = vals + (uint64_t)b * 32;
+    if (lt256(x, y)) return true;
+    if (lt256(y, x)) return false;
+    return a < b;
+}
+
+// Status of the value at rank j of the batch order (ord[r] = input position of rank r; cls = its filter_class), against
+// the stored index (val / sorted[0..M), imt_prep.hpp).  *aux = the stored leaf (PRESENT, local index) or the input
+// position of the first occurrence (REPEATED); untouched otherwise.
+IMT_PL_HD uint8_t filter_rank(const uint8_t* vals, const uint32_t* ord, uint32_t j, uint8_t cls, const uint8_t* val,
+                              const uint32_t* sorted, uint32_t M, uint32_t* aux) {
+    if (cls != VAL_NEW) return cls;
+    const uint8_t* x = vals + (uint64_t)ord[j] * 32;
+    const uint32_t g = count_below(val, sorted, M, x);
+    if (g < M && eq256(val + (uint64_t)sorted[g] * 32, x)) {
+        *aux = sorted[g];
+        return VAL_PRESENT;
+    }
+    uint32_t lo = 0, hi = j;                // first rank whose value is >= x: the head of x's run
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (lt256(vals + (uint64_t)ord[mid] * 32, x)) lo = mid + 1; else hi = mid;
+    }
+    if (lo < j) {
+        *aux = ord[lo];
+        return VAL_REPEATED;
+    }
+    return VAL_NEW;
+}
+
+// Leaf index reported for input position i.  rank = exclusive scan of the accepted flags in input order, M = leaves
+// before the batch, base = the placement (imt_itree_set_placement).
+IMT_PL_HD uint64_t filter_leaf(uint8_t st, uint32_t aux, const uint32_t* rank, uint32_t i, uint64_t base, uint64_t M) {
+    switch (st) {
+        case VAL_NEW: return base + M + rank[i];
+        case VAL_REPEATED: return base + M + rank[aux];
+        case VAL_PRESENT: return base + aux;
+        case VAL_ZERO: return base;
+        default: return LEAF_NONE;
+    }
+}
+
+// imt_itree_lookup_batch: status of one candidate against the stored index; *leaf = the stored leaf (PRESENT), the low
+// leaf (NEW: greatest stored value below x), the sentinel (ZERO) or LEAF_NONE (FOREIGN)
+IMT_PL_HD uint8_t lookup_one(const uint8_t* x, const uint8_t* val, const uint32_t* sorted, uint32_t M, uint64_t base,
+                             uint32_t part_mod, uint32_t part_res, uint64_t* leaf) {
+    const uint8_t cls = filter_class(x, part_mod, part_res);
+    if (cls == VAL_ZERO) { *leaf = base; return cls; }
+    if (cls == VAL_FOREIGN) { *leaf = LEAF_NONE; return cls; }
+    const uint32_t g = count_below(val, sorted, M, x);      // >= 1: the sentinel 0 is stored and x > 0
+    if (g < M && eq256(val + (uint64_t)sorted[g] * 32, x)) { *leaf = base + sorted[g]; return VAL_PRESENT; }
+    *leaf = base + sorted[g > 0 ? g - 1 : 0];
+    return VAL_NEW;
+}
+
+}  // namespace prep
+}  // namespace imt

@@ -10,6 +10,7 @@
 #include "imt_ctx.hpp"
 #include "imt_prep.hpp"
 #include "imt_prep_logic.hpp"
+#include "imt_filter_logic.hpp"
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -90,6 +91,7 @@ struct PlanSet {
     uint32_t* d_timen = nullptr; // [levels][E] time table of level l+1
     uint8_t* d_val[2] = {nullptr, nullptr};
     prep::Workspace ws;                  // GPU-prepare scratch
+    prep::FilterWs fw;                   // classification scratch of imt_itree_insert_filtered
     uint32_t* d_slot = nullptr;          // [levels + 1][E] slot of every event per level (sharded mode)
     const uint8_t** d_valptr = nullptr;  // [levels + 1] device array of level value pointers (sharded mode)
     uint8_t* d_root = nullptr;           // stored root right after this batch (device format)
@@ -137,6 +139,7 @@ struct imt_itree {
     int sorted_cur = 0;
     bool mirror_valid = true, dev_index_valid = true;
     int* h_err_pin = nullptr;        // pinned word for the prepare kernels' error bits
+    uint32_t* h_cnt_pin = nullptr;   // pinned word for the accepted count of imt_itree_insert_filtered
     // a sharded batch between imt_itree_batch_begin and _end
     struct Pending { bool active = false; size_t n = 0; unsigned l0 = 0; int set = 0; } pending;
     static constexpr int NPIPE = IMT_NPIPE;     // batches in flight on the GPU under IMT_PIPELINE
@@ -197,6 +200,9 @@ static void plan_free(PlanSet& p) {
     for (void* q : {(void*)p.ws.iota, (void*)p.ws.bsorted, (void*)p.ws.gap, (void*)p.ws.st, (void*)p.ws.low,
                     (void*)p.ws.succ, (void*)p.ws.keys, (void*)p.ws.keys_sorted, p.ws.tmp, (void*)p.ws.err})
         if (q) hipFree(q);
+    for (void* q : {(void*)p.fw.idx, (void*)p.fw.ord, (void*)p.fw.st, (void*)p.fw.aux, (void*)p.fw.flag, (void*)p.fw.rank,
+                    (void*)p.fw.count, (void*)p.fw.acc, (void*)p.fw.status, (void*)p.fw.leaf, p.fw.tmp})
+        if (q) hipFree(q);
     PlanSet keep;
     keep.done = p.done;
     keep.prep_done = p.prep_done;
@@ -245,6 +251,19 @@ static int plan_reserve(imt_ctx* c, PlanSet& p, size_t events, unsigned levels, 
         A((void**)&p.ws.o_largest, N);
         A((void**)&p.ws.o_lowleaf, N * 96);
         A((void**)&p.ws.o_newleaf, N * 96);
+        p.fw.cap_n = N;
+        A((void**)&p.fw.idx, N * 4);
+        A((void**)&p.fw.ord, N * 4);
+        A((void**)&p.fw.st, N);
+        A((void**)&p.fw.aux, N * 4);
+        A((void**)&p.fw.flag, N * 4);
+        A((void**)&p.fw.rank, N * 4);
+        A((void**)&p.fw.count, sizeof(uint32_t));
+        A((void**)&p.fw.acc, N * 32);
+        A((void**)&p.fw.status, N);
+        A((void**)&p.fw.leaf, N * 8);
+        p.fw.tmp_bytes = prep::filter_temp_bytes(N);
+        A((void**)&p.fw.tmp, p.fw.tmp_bytes);
     }
     A((void**)&p.d_slot, (size_t)(L + 1) * E * 4);
     A((void**)&p.d_valptr, (size_t)(L + 1) * sizeof(void*));
@@ -301,6 +320,7 @@ extern "C" void imt_itree_free(imt_itree* t) {
     for (auto q : t->d_sorted)
         if (q) hipFree(q);
     if (t->h_err_pin) hipHostFree(t->h_err_pin);
+    if (t->h_cnt_pin) hipHostFree(t->h_cnt_pin);
     for (void* q : {(void*)t->fws.iota, (void*)t->fws.bsorted, (void*)t->fws.gap, (void*)t->fws.st, t->fws.tmp,
                     (void*)t->d_canon_all, (void*)t->d_sorted_extra})
         if (q) hipFree(q);
@@ -335,6 +355,7 @@ extern "C" int imt_itree_new(imt_ctx* c, unsigned depth, uint64_t capacity, imt_
         (e = hipMalloc((void**)&t->d_sorted[0], capacity * 4)) != hipSuccess ||
         (e = hipMalloc((void**)&t->d_sorted[1], capacity * 4)) != hipSuccess ||
         (e = hipHostMalloc((void**)&t->h_err_pin, sizeof(int), hipHostMallocDefault)) != hipSuccess ||
+        (e = hipHostMalloc((void**)&t->h_cnt_pin, sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess ||
         (e = hipMalloc((void**)&t->d_nodes, off * 32)) != hipSuccess ||
         (e = hipMalloc((void**)&t->d_off, (depth + 1) * 8)) != hipSuccess ||
         (e = hipMalloc((void**)&t->d_len, (depth + 1) * 8)) != hipSuccess ||
@@ -1128,13 +1149,14 @@ void host_commit(imt_itree* t, const HostPlan& hp, size_t n) {
 
 // GPU prepare (default): the same on the device (imt_prep.hip), on the side stream.  The hash-free
 // outputs go straight to device buffers (the user's, or scratch in host-pointer mode).  The batch is
-// committed to the device index only if its values are acceptable.
+// committed to the device index only if its values are acceptable.  vals_ready: `vals` are canonical device values
+// already on the side stream (the accepted values of imt_itree_insert_filtered): no upload, no conversion.
 struct GpuOuts {
     uint64_t* low = nullptr;
     uint8_t *largest = nullptr, *lowleaf = nullptr, *newleaf = nullptr;
 };
 int gpu_prepare(imt_itree* t, PlanSet& P, const void* vals, size_t n, unsigned flags, const imt_insert_out* out,
-                size_t& slot, GpuOuts& go, double& wait_ms) {
+                size_t& slot, GpuOuts& go, double& wait_ms, bool vals_ready) {
     imt_ctx* c = t->ctx;
     const bool dev = flags & IMT_DEVICE_PTRS;
     const unsigned fmt = flags & IMT_FMT_MASK;
@@ -1142,14 +1164,14 @@ int gpu_prepare(imt_itree* t, PlanSet& P, const void* vals, size_t n, unsigned f
     if (rc) return rc;
     hipStream_t ps = t->up_stream;
     const uint8_t* d_vals = (const uint8_t*)vals;
-    if (!dev) {
+    if (!dev && !vals_ready) {
         uint8_t* up = (uint8_t*)c->dev_scratch(slot++, n * 32);
         if (!up) return IMT_ERR_HIP;
         IMT_HIP(c, hipMemcpyAsync(up, vals, n * 32, hipMemcpyHostToDevice, ps));
         d_vals = up;
     }
     IMT_HIP(c, hipMemsetAsync(P.ws.err, 0, sizeof(int), ps));
-    if (fmt != IMT_FMT_CANONICAL) {
+    if (fmt != IMT_FMT_CANONICAL && !vals_ready) {
         // the plan's own buffer, not context scratch: this runs on the side stream, which IMT_INPUTS_READY leaves
         // unordered behind the context's stream, where an earlier asynchronous call (imt_itree_lift_batch,
         // imt_insert_trace_batch) may still be using the context's scratch slots
@@ -1190,8 +1212,11 @@ int gpu_prepare(imt_itree* t, PlanSet& P, const void* vals, size_t n, unsigned f
 
 }  // namespace
 
-extern "C" int imt_itree_insert_batch(imt_itree* t, const void* vals, size_t n, const imt_insert_out* out,
-                                      unsigned flags) {
+// The body of imt_itree_insert_batch.  filtered: `vals` are the accepted values of imt_itree_insert_filtered, canonical,
+// in device memory of the plan set (default prepare) or host memory (IMT_HOST_PREP), whatever IMT_DEVICE_PTRS says of
+// the outputs.  Level-major sibling arrays have level stride sib_stride (>= n).
+static int insert_core(imt_itree* t, const void* vals, size_t n, const imt_insert_out* out, unsigned flags, bool filtered,
+                       size_t sib_stride) {
     if (!t) return IMT_ERR_ARG;
     imt_ctx* c = t->ctx;
     IMT_NOT_SLICED(t);
@@ -1204,7 +1229,7 @@ extern "C" int imt_itree_insert_batch(imt_itree* t, const void* vals, size_t n, 
     int rc = c->set_device();
     if (rc) return rc;
     const bool dev = flags & IMT_DEVICE_PTRS;
-    if ((rc = check_fe_ptrs(c, dev, {vals})) || (rc = check_out_ptrs(c, dev, out))) return rc;
+    if ((rc = check_fe_ptrs(c, dev && !filtered, {vals})) || (rc = check_out_ptrs(c, dev, out))) return rc;
     const bool gpu_prep = (flags & IMT_HOST_PREP) == 0;
     const unsigned fmt = flags & IMT_FMT_MASK;
     const uint64_t M = t->size;
@@ -1241,9 +1266,9 @@ extern "C" int imt_itree_insert_batch(imt_itree* t, const void* vals, size_t n, 
     HostPlan hp;
     GpuOuts go;
     if (gpu_prep)
-        rc = gpu_prepare(t, P, vals, n, flags, out, slot, go, host_wait_ms);
+        rc = gpu_prepare(t, P, vals, n, flags, out, slot, go, host_wait_ms, filtered);
     else
-        rc = host_prepare(t, P, vals, n, flags, out && out->low_leaf, out && out->new_leaf, hp);
+        rc = host_prepare(t, P, vals, n, filtered ? IMT_FMT_CANONICAL : flags, out && out->low_leaf, out && out->new_leaf, hp);
     if (rc) return rc;
     IMT_HIP(c, hipEventRecord(t->up_done, t->up_stream));
 
@@ -1270,7 +1295,8 @@ extern "C" int imt_itree_insert_batch(imt_itree* t, const void* vals, size_t n, 
         if (dev) return (uint8_t*)user;
         return (uint8_t*)c->dev_scratch(slot++, bytes);
     };
-    const size_t sib_bytes = (size_t)t->global_depth * n * 32;
+    const bool item_major = flags & IMT_SIB_ITEM_MAJOR;
+    const size_t sib_bytes = (size_t)t->global_depth * (item_major ? n : sib_stride) * 32;
     if (out) {
         g_old = gpu_out(out->old_root, n * 32);
         g_int = gpu_out(out->interim_root, n * 32);
@@ -1282,7 +1308,7 @@ extern "C" int imt_itree_insert_batch(imt_itree* t, const void* vals, size_t n, 
             return IMT_ERR_HIP;
     }
     // a placed tree writes rows [0, depth) of sibling arrays dimensioned for global_depth levels
-    launch::SibLayout lay = (flags & IMT_SIB_ITEM_MAJOR) ? launch::SibLayout{1, t->global_depth} : launch::SibLayout{n, 1};
+    launch::SibLayout lay = item_major ? launch::SibLayout{1, t->global_depth} : launch::SibLayout{sib_stride, 1};
 
     // ---- leaf hashes, index phase (no hashing), then the hash sweep ----
     int pf = c->prof_begin(IMT_PROF_LEAVES, s);
@@ -1413,9 +1439,17 @@ extern "C" int imt_itree_insert_batch(imt_itree* t, const void* vals, size_t n, 
         if (out->interim_root) IMT_HIP(c, hipMemcpyAsync(out->interim_root, g_int, n * 32, hipMemcpyDeviceToHost, s));
         if (out->new_root) IMT_HIP(c, hipMemcpyAsync(out->new_root, g_new, n * 32, hipMemcpyDeviceToHost, s));
         // level-major: only rows [0, depth) were written (a placed tree's upper rows come from imt_itree_lift_batch)
-        const size_t sib_copy = (flags & IMT_SIB_ITEM_MAJOR) ? sib_bytes : (size_t)t->depth * n * 32;
-        if (out->low_sib) IMT_HIP(c, hipMemcpyAsync(out->low_sib, g_ls, sib_copy, hipMemcpyDeviceToHost, s));
-        if (out->new_sib) IMT_HIP(c, hipMemcpyAsync(out->new_sib, g_ns, sib_copy, hipMemcpyDeviceToHost, s));
+        if (item_major || sib_stride == n) {
+            const size_t sib_copy = item_major ? sib_bytes : (size_t)t->depth * n * 32;
+            if (out->low_sib) IMT_HIP(c, hipMemcpyAsync(out->low_sib, g_ls, sib_copy, hipMemcpyDeviceToHost, s));
+            if (out->new_sib) IMT_HIP(c, hipMemcpyAsync(out->new_sib, g_ns, sib_copy, hipMemcpyDeviceToHost, s));
+        } else {    // rows [0, n) of every level, level stride sib_stride
+            const size_t pitch = sib_stride * 32;
+            if (out->low_sib)
+                IMT_HIP(c, hipMemcpy2DAsync(out->low_sib, pitch, g_ls, pitch, n * 32, t->depth, hipMemcpyDeviceToHost, s));
+            if (out->new_sib)
+                IMT_HIP(c, hipMemcpy2DAsync(out->new_sib, pitch, g_ns, pitch, n * 32, t->depth, hipMemcpyDeviceToHost, s));
+        }
     }
     if (c->profiling) {
         c->prof_ms[IMT_PROF_HOST] +=
@@ -1423,6 +1457,222 @@ extern "C" int imt_itree_insert_batch(imt_itree* t, const void* vals, size_t n, 
         c->prof_n[IMT_PROF_HOST] += 1;
     }
     if (!dev) IMT_HIP(c, hipStreamSynchronize(s));
+    return IMT_OK;
+}
+
+extern "C" int imt_itree_insert_batch(imt_itree* t, const void* vals, size_t n, const imt_insert_out* out,
+                                      unsigned flags) {
+    return insert_core(t, vals, n, out, flags, false, n);
+}
+
+// ------------------------------------------------------------------------------------
+// filtered batch insertion and value lookup (imt_filter_logic.hpp)
+// ------------------------------------------------------------------------------------
+namespace {
+
+// position in t->sorted of the first stored value >= v
+size_t find_ge(const imt_itree* t, const U256& v) {
+    size_t lo = 0, hi = t->sorted.size();
+    while (lo < hi) {
+        const size_t mid = (lo + hi) / 2;
+        if (cmp_ent(t, t->sorted[mid], v) < 0) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// The classification on the device (prep::filter), on the side stream behind everything the batches before this one
+// enqueued there: the index it reads is the one committed when the last of them was prepared.  The accepted values end
+// up in P.fw.acc; one synchronisation for their number and the error bits.
+int gpu_filter(imt_itree* t, PlanSet& P, const void* vals, size_t n, unsigned flags, uint8_t* status,
+               uint64_t* leaf_index, size_t& n_acc) {
+    imt_ctx* c = t->ctx;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    int rc = ensure_device_index(t);
+    if (rc) return rc;
+    hipStream_t ps = t->up_stream;
+    IMT_HIP(c, hipMemsetAsync(P.ws.err, 0, sizeof(int), ps));
+    const uint8_t* d_vals = (const uint8_t*)vals;
+    if (!dev) {         // the plan's own buffers, not context scratch (see gpu_prepare)
+        IMT_HIP(c, hipMemcpyAsync(P.d_canon, vals, n * 32, hipMemcpyHostToDevice, ps));
+        d_vals = P.d_canon;
+    }
+    if (fmt != IMT_FMT_CANONICAL) {
+        launch::convert(ps, d_vals, P.d_canon, n, fmt, IMT_FMT_CANONICAL, P.ws.err);   // sets bit 0 = non-canonical
+        d_vals = P.d_canon;
+    }
+    uint8_t* d_st = dev ? status : P.fw.status;
+    uint64_t* d_leaf = leaf_index ? (dev ? leaf_index : P.fw.leaf) : nullptr;
+    IMT_HIP(c, prep::filter(ps, P.fw, d_vals, (uint32_t)n, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)t->size,
+                            t->index_base, t->part_mod, t->part_res, d_st, d_leaf, P.ws.err));
+    IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, P.fw.count, sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
+    IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, ps));
+    if (!dev) {
+        IMT_HIP(c, hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, ps));
+        if (leaf_index) IMT_HIP(c, hipMemcpyAsync(leaf_index, d_leaf, n * 8, hipMemcpyDeviceToHost, ps));
+    }
+    IMT_HIP(c, hipStreamSynchronize(ps));
+    if (*t->h_err_pin & prep::ERR_NONCANONICAL) return c->fail(IMT_ERR_NONCANONICAL, "a value is not reduced (>= p)");
+    n_acc = *t->h_cnt_pin;
+    return IMT_OK;
+}
+
+// IMT_HOST_PREP: the same rule over the host mirror -- a binary search per value, a sort of the batch -- stated
+// independently of the kernels.  The accepted values, canonical, go to `acc` in input order.
+int host_filter(imt_itree* t, const void* vals, size_t n, unsigned flags, uint8_t* status, uint64_t* leaf_index,
+                std::vector<U256>& acc) {
+    imt_ctx* c = t->ctx;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    int rc = ensure_mirror(t);
+    if (rc) return rc;
+    std::vector<U256> v;
+    if ((rc = fetch_canonical(c, dev ? t->up_stream : c->stream, vals, n, flags, v))) return rc;
+    const uint64_t M = t->size, base = t->index_base;
+    std::vector<uint8_t> st(n);
+    std::vector<uint64_t> aux(n, 0), leaf(n);
+    std::vector<uint32_t> ord;
+    for (size_t i = 0; i < n; i++) {
+        st[i] = prep::filter_class(reinterpret_cast<const uint8_t*>(v[i].data()), t->part_mod, t->part_res);
+        if (st[i] != prep::VAL_NEW) continue;
+        const size_t q = find_ge(t, v[i]);
+        if (q < t->sorted.size() && cmp_ent(t, t->sorted[q], v[i]) == 0) {
+            st[i] = prep::VAL_PRESENT;
+            aux[i] = t->sorted[q].idx;
+        } else {
+            ord.push_back((uint32_t)i);
+        }
+    }
+    std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return lt256(v[a], v[b]) || (v[a] == v[b] && a < b); });
+    for (size_t r = 1, head = 0; r < ord.size(); r++) {
+        if (v[ord[r]] != v[ord[head]]) { head = r; continue; }
+        st[ord[r]] = prep::VAL_REPEATED;
+        aux[ord[r]] = ord[head];
+    }
+    acc.clear();
+    std::vector<uint64_t> rank(n, 0);
+    for (size_t i = 0; i < n; i++)
+        if (st[i] == prep::VAL_NEW) {
+            rank[i] = acc.size();
+            acc.push_back(v[i]);
+        }
+    for (size_t i = 0; i < n; i++) {
+        switch (st[i]) {
+            case prep::VAL_NEW: leaf[i] = base + M + rank[i]; break;
+            case prep::VAL_REPEATED: leaf[i] = base + M + rank[aux[i]]; break;
+            case prep::VAL_PRESENT: leaf[i] = base + aux[i]; break;
+            case prep::VAL_ZERO: leaf[i] = base; break;
+            default: leaf[i] = prep::LEAF_NONE;
+        }
+    }
+    if (dev) {
+        IMT_HIP(c, hipMemcpyAsync(status, st.data(), n, hipMemcpyHostToDevice, t->up_stream));
+        if (leaf_index) IMT_HIP(c, hipMemcpyAsync(leaf_index, leaf.data(), n * 8, hipMemcpyHostToDevice, t->up_stream));
+        IMT_HIP(c, hipStreamSynchronize(t->up_stream));
+    } else {
+        std::memcpy(status, st.data(), n);
+        if (leaf_index) std::memcpy(leaf_index, leaf.data(), n * 8);
+    }
+    return IMT_OK;
+}
+
+}  // namespace
+
+extern "C" int imt_itree_insert_filtered(imt_itree* t, const void* vals, size_t n, uint8_t* status, uint64_t* leaf_index,
+                                         uint64_t* n_inserted, const imt_insert_out* out, unsigned flags) {
+    if (!t) return IMT_ERR_ARG;
+    imt_ctx* c = t->ctx;
+    IMT_NOT_SLICED(t);
+    if (!status || !n_inserted) return c->fail(IMT_ERR_ARG, "null status / n_inserted");
+    if (n == 0) {
+        *n_inserted = 0;
+        return IMT_OK;
+    }
+    if (!vals) return c->fail(IMT_ERR_ARG, "null vals");
+    if ((flags & IMT_FMT_MASK) == 3) return c->fail(IMT_ERR_ARG, "unknown field-element format");
+    if (n > ((size_t)1 << 30)) return c->fail(IMT_ERR_RANGE, "batch too large");
+    if (t->pending.active) return c->fail(IMT_ERR_ARG, "a sharded batch is open (imt_itree_batch_end first)");
+    if (slice_open(t)) return c->fail(IMT_ERR_ARG, "a slice is open (issue its remaining units first)");
+    int rc = c->set_device();
+    if (rc) return rc;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    if ((rc = check_fe_ptrs(c, dev, {vals})) || (rc = check_out_ptrs(c, dev, out))) return rc;
+    if (dev && ((uintptr_t)leaf_index & 7u)) return c->fail(IMT_ERR_ARG, "device leaf_index array is not 8-byte aligned");
+    *n_inserted = 0;
+
+    // the plan set the batch will run on: its buffers hold the classification too (insert_core reuses it as it is)
+    const size_t E = 2 * n;
+    PlanSet& P = t->plan[t->cur];
+    if (P.in_flight) {
+        IMT_HIP(c, hipEventSynchronize(P.done));
+        P.in_flight = false;
+    }
+    if ((rc = plan_reserve(c, P, E, t->depth, t->cap))) return rc;
+    if (dev && (flags & IMT_PIPELINE) && (rc = reserve_all_plans(t, E))) return rc;
+    if (!(dev && (flags & IMT_INPUTS_READY))) {    // as in insert_core: the side stream reads the caller's buffers
+        IMT_HIP(c, hipEventRecord(t->in_mark, c->stream));
+        IMT_HIP(c, hipStreamWaitEvent(t->up_stream, t->in_mark, 0));
+    }
+    size_t n_acc = 0;
+    const void* acc = nullptr;
+    std::vector<U256> h_acc;
+    if (flags & IMT_HOST_PREP) {
+        rc = host_filter(t, vals, n, flags, status, leaf_index, h_acc);
+        acc = h_acc.data();
+        n_acc = h_acc.size();
+    } else {
+        rc = gpu_filter(t, P, vals, n, flags, status, leaf_index, n_acc);
+        acc = P.fw.acc;
+    }
+    if (rc) return rc;
+    if (n_acc && (rc = insert_core(t, acc, n_acc, out, flags, true, n))) return rc;
+    *n_inserted = n_acc;
+    return IMT_OK;
+}
+
+extern "C" int imt_itree_lookup_batch(imt_itree* t, const void* vals, size_t n, uint8_t* status, uint64_t* leaf_index,
+                                      unsigned flags) {
+    if (!t) return IMT_ERR_ARG;
+    imt_ctx* c = t->ctx;
+    IMT_NOT_SLICED(t);
+    if (!status) return c->fail(IMT_ERR_ARG, "null status");
+    if (n == 0) return IMT_OK;
+    if (!vals) return c->fail(IMT_ERR_ARG, "null vals");
+    int rc = c->set_device();
+    if (rc) return rc;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    if ((rc = check_fe_ptrs(c, dev, {vals}))) return rc;
+    if (fmt == 3) return c->fail(IMT_ERR_ARG, "unknown field-element format");
+    if (n > ((size_t)1 << 31)) return c->fail(IMT_ERR_RANGE, "batch too large");
+    if (dev && ((uintptr_t)leaf_index & 7u)) return c->fail(IMT_ERR_ARG, "device leaf_index array is not 8-byte aligned");
+    if ((rc = ensure_device_index(t))) return rc;
+    if ((rc = join_top(t))) return rc;
+    hipStream_t s = c->stream;
+    IMT_HIP(c, hipStreamSynchronize(t->up_stream));
+    const uint8_t* d_vals = (const uint8_t*)vals;
+    int* d_perr = (int*)c->dev_scratch(2, sizeof(int));
+    if (!d_perr) return IMT_ERR_HIP;
+    IMT_HIP(c, hipMemsetAsync(d_perr, 0, sizeof(int), s));
+    if (!dev || fmt != IMT_FMT_CANONICAL) {
+        uint8_t* buf = (uint8_t*)c->dev_scratch(0, n * 32);
+        if (!buf) return IMT_ERR_HIP;
+        if (!dev) IMT_HIP(c, hipMemcpyAsync(buf, vals, n * 32, hipMemcpyHostToDevice, s));
+        if (fmt != IMT_FMT_CANONICAL) launch::convert(s, dev ? d_vals : buf, buf, n, fmt, IMT_FMT_CANONICAL, d_perr);
+        d_vals = buf;
+    }
+    uint8_t* d_st = dev ? status : (uint8_t*)c->dev_scratch(3, n);
+    uint64_t* d_leaf = (dev || !leaf_index) ? leaf_index : (uint64_t*)c->dev_scratch(1, n * 8);
+    if (!d_st || (leaf_index && !d_leaf)) return IMT_ERR_HIP;
+    prep::lookup(s, d_vals, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)t->size, (uint32_t)n, t->index_base,
+                 t->part_mod, t->part_res, d_st, d_leaf, d_perr);
+    int perr = 0;
+    IMT_HIP(c, hipMemcpyAsync(&perr, d_perr, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (!dev) {
+        IMT_HIP(c, hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, s));
+        if (leaf_index) IMT_HIP(c, hipMemcpyAsync(leaf_index, d_leaf, n * 8, hipMemcpyDeviceToHost, s));
+    }
+    IMT_HIP(c, hipStreamSynchronize(s));
+    if (perr & prep::ERR_NONCANONICAL) return c->fail(IMT_ERR_NONCANONICAL, "a value is not reduced (>= p)");
     return IMT_OK;
 }
 

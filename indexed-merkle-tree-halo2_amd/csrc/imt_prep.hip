@@ -6,6 +6,7 @@
 #include <rocprim/rocprim.hpp>
 #include "imt_prep.hpp"
 #include "imt_prep_logic.hpp"
+#include "imt_filter_logic.hpp"
 
 namespace imt {
 namespace prep {
@@ -196,6 +197,67 @@ k_nm_witness(const uint8_t* __restrict__ vals, const uint8_t* __restrict__ d_val
     }
 }
 
+// ---- filtered insertion and lookup (imt_filter_logic.hpp) ----
+struct PosLess {                       // order input positions by value, then position
+    const uint8_t* vals;
+    __device__ bool operator()(uint32_t a, uint32_t b) const { return pos_less(vals, a, b); }
+};
+
+__global__ void __launch_bounds__(BLOCK) k_filter_class(const uint8_t* __restrict__ vals, uint32_t n, uint32_t part_mod,
+                                                        uint32_t part_res, uint32_t* __restrict__ idx,
+                                                        uint8_t* __restrict__ st, int* err) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t* v = vals + (uint64_t)i * 32;
+    if (geq_p(v)) atomicOr(err, ERR_NONCANONICAL);
+    st[i] = filter_class(v, part_mod, part_res);
+    idx[i] = i;
+}
+
+// over the batch order: PRESENT against the stored index, REPEATED against the head of the run
+__global__ void __launch_bounds__(BLOCK) k_filter_rank(const uint8_t* __restrict__ vals, const uint32_t* __restrict__ ord,
+                                                       uint32_t n, const uint8_t* __restrict__ d_val,
+                                                       const uint32_t* __restrict__ sorted, uint32_t M,
+                                                       uint8_t* __restrict__ st, uint32_t* __restrict__ aux,
+                                                       uint32_t* __restrict__ flag) {
+    const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t i = ord[j];
+    uint32_t a = 0;
+    const uint8_t s = filter_rank(vals, ord, j, st[i], d_val, sorted, M, &a);
+    st[i] = s;
+    aux[i] = a;
+    flag[i] = s == VAL_NEW ? 1u : 0u;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_filter_compact(const uint8_t* __restrict__ vals, uint32_t n,
+                                                          const uint8_t* __restrict__ st, const uint32_t* __restrict__ aux,
+                                                          const uint32_t* __restrict__ flag,
+                                                          const uint32_t* __restrict__ rank, uint64_t base, uint32_t M,
+                                                          uint8_t* __restrict__ acc, uint8_t* __restrict__ status,
+                                                          uint64_t* __restrict__ leaf, uint32_t* __restrict__ count) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t s = st[i];
+    if (s == VAL_NEW) copy32(acc + (uint64_t)rank[i] * 32, vals + (uint64_t)i * 32);
+    status[i] = s;
+    if (leaf) leaf[i] = filter_leaf(s, aux[i], rank, i, base, M);
+    if (i + 1 == n) *count = rank[i] + flag[i];
+}
+
+__global__ void __launch_bounds__(BLOCK) k_lookup(const uint8_t* __restrict__ vals, const uint8_t* __restrict__ d_val,
+                                                  const uint32_t* __restrict__ sorted, uint32_t M, uint32_t n, uint64_t base,
+                                                  uint32_t part_mod, uint32_t part_res, uint8_t* __restrict__ status,
+                                                  uint64_t* __restrict__ leaf, int* err) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t* x = vals + (uint64_t)i * 32;
+    if (geq_p(x)) atomicOr(err, ERR_NONCANONICAL);
+    uint64_t l = 0;
+    status[i] = lookup_one(x, d_val, sorted, M, base, part_mod, part_res, &l);
+    if (leaf) leaf[i] = l;
+}
+
 // ---- snapshot: imt_itree_load's list check and imt_itree_get_leaves, on the device ----
 struct PreLess {                       // order leaf indices by the val field of their [3][32] preimage
     const uint8_t* pre;
@@ -317,6 +379,41 @@ hipError_t index_only(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t
         hipSuccess)
         return e;
     return hipGetLastError();
+}
+
+size_t filter_temp_bytes(size_t n) {
+    size_t a = 0, b = 0;
+    (void)rocprim::merge_sort(nullptr, a, (uint32_t*)nullptr, (uint32_t*)nullptr, n, PosLess{nullptr}, nullptr);
+    (void)rocprim::exclusive_scan(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n, rocprim::plus<uint32_t>(),
+                                  nullptr);
+    return (a > b ? a : b) + 256;
+}
+
+hipError_t filter(hipStream_t s, FilterWs& ws, const uint8_t* vals, uint32_t n, const uint8_t* d_val,
+                  const uint32_t* sorted, uint32_t M, uint64_t base, uint32_t part_mod, uint32_t part_res,
+                  uint8_t* status, uint64_t* leaf, int* err) {
+    hipError_t e;
+    if (n == 0 || n > ws.cap_n || filter_temp_bytes(n) > ws.tmp_bytes) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_filter_class, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, n, part_mod, part_res, ws.idx, ws.st, err);
+    size_t tb = ws.tmp_bytes;
+    if ((e = rocprim::merge_sort(ws.tmp, tb, ws.idx, ws.ord, (size_t)n, PosLess{vals}, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_filter_rank, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, ws.ord, n, d_val, sorted, M, ws.st, ws.aux,
+                       ws.flag);
+    tb = ws.tmp_bytes;
+    if ((e = rocprim::exclusive_scan(ws.tmp, tb, ws.flag, ws.rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), s)) !=
+        hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_filter_compact, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, n, ws.st, ws.aux, ws.flag, ws.rank, base,
+                       M, ws.acc, status, leaf, ws.count);
+    return hipGetLastError();
+}
+
+void lookup(hipStream_t s, const uint8_t* vals, const uint8_t* d_val, const uint32_t* sorted, uint32_t M, uint32_t n,
+            uint64_t base, uint32_t part_mod, uint32_t part_res, uint8_t* status, uint64_t* leaf, int* err) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_lookup, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, d_val, sorted, M, n, base, part_mod, part_res,
+                       status, leaf, err);
 }
 
 void nm_witness(hipStream_t s, const uint8_t* vals, const uint8_t* d_val, const uint32_t* sorted, uint32_t M, uint32_t n,

@@ -72,6 +72,35 @@ hipError_t run(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t* d_val
 hipError_t index_only(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t* d_val, const uint32_t* sorted_old,
                       uint32_t* sorted_new, uint32_t M, uint32_t n);
 
+// ---- filtered insertion (imt_itree_insert_filtered): which values of a batch are inserted ----
+struct FilterWs {             // per plan set, sized for `cap_n` values
+    size_t cap_n = 0;
+    uint32_t* idx = nullptr;       // [n]   input positions
+    uint32_t* ord = nullptr;       // [n]   input positions in batch order (value, then position)
+    uint8_t* st = nullptr;         // [n]   class, then status (input order)
+    uint32_t* aux = nullptr;       // [n]   stored leaf (PRESENT) / first occurrence (REPEATED)
+    uint32_t* flag = nullptr;      // [n]   1 = accepted
+    uint32_t* rank = nullptr;      // [n]   exclusive scan of flag
+    uint32_t* count = nullptr;     // [1]   accepted values
+    uint8_t* acc = nullptr;        // [n][32] accepted values in input order (canonical)
+    uint8_t* status = nullptr;     // [n]   staging of the status for host-pointer callers
+    uint64_t* leaf = nullptr;      // [n]   ... and of the leaf indices
+    void* tmp = nullptr;           // rocPRIM temporary storage
+    size_t tmp_bytes = 0;
+};
+size_t filter_temp_bytes(size_t n);
+
+// Classifies vals [n][32] (canonical, device) against the stored index (d_val, sorted[M]; imt_filter_logic.hpp):
+// status[i] / leaf[i] (leaf may be NULL; global with `base`), the accepted values compacted into ws.acc in input order,
+// their number into *ws.count.  ERR_NONCANONICAL is OR-ed into *err.  Writes nothing but ws, status, leaf and err.
+hipError_t filter(hipStream_t s, FilterWs& ws, const uint8_t* vals, uint32_t n, const uint8_t* d_val,
+                  const uint32_t* sorted, uint32_t M, uint64_t base, uint32_t part_mod, uint32_t part_res,
+                  uint8_t* status, uint64_t* leaf, int* err);
+
+// imt_itree_lookup_batch: status and leaf index (may be NULL) of every candidate (lookup_one, imt_filter_logic.hpp)
+void lookup(hipStream_t s, const uint8_t* vals, const uint8_t* d_val, const uint32_t* sorted, uint32_t M, uint32_t n,
+            uint64_t base, uint32_t part_mod, uint32_t part_res, uint8_t* status, uint64_t* leaf, int* err);
+
 // non-membership witness: low leaf index, its preimage {val, next_val, next_idx} (canonical) and the
 // is_largest flag of every candidate; any output may be NULL.  part_mod > 1: candidates with v % part_mod != part_res
 // belong to another subtree's list (ERR_FOREIGN)
