@@ -16,8 +16,8 @@
 // ~54 k instructions per permutation on every lane instead of 92 k on one: the hash takes 0.6x the time and 2.3x the
 // lane-instructions, so it is used only while the launch fits one wave per SIMD (imt_launch: coop_max_events).
 // Same values as hash23 (plain-form-identical schedule; all products with 29-bit quotient digits so that the linear
-// lanes, which only accumulate for 57 rounds, stay below 2^261: s_i grows by < p per round, the S-box lane is reset by
-// every squaring).
+// lanes, which only accumulate for 57 rounds, stay below 2^261: s_i grows by < 1.01p per round and every operand stays
+// below 60p from entry lanes below 32p, the S-box lane is reset by every squaring; tests/test_fe_forms.py).
 //
 // A lane's "constant" is its neighbour's "state", so no factor can be an SGPR operand here: the tables are copied from
 // __constant__ memory into LDS once per block and every lane reads the entry its role needs (lanes of one role read

@@ -155,3 +155,88 @@ extern "C" int emul_less_than_layout(int lookup_bits, imt_trace_cell* cells, siz
     return imt_less_than_trace_layout(fake, (unsigned)lookup_bits, cells, cells_cap, n_cells, constants, const_cap, n_constants,
                                       out_row, flags);
 }
+
+// ---- raw limbs in and out, no canonical check (tests/test_fe_forms.py) ----
+// the constant tables as the device sees them
+extern "C" void emul_consts_raw(uint32_t* out) { std::memcpy(out, &g_consts, sizeof g_consts); }
+extern "C" int emul_trace_consts_size(void) { return (int)sizeof(dev::TraceConsts); }
+extern "C" void emul_trace_consts_raw(uint32_t* out) { std::memcpy(out, &g_tconsts, sizeof g_tconsts); }
+// The C++ form each assembly form replaces (numbering: tests/fe_model.py FORMS).  in: [n][slots][9], the operand slots
+// in call order (a0, b0, a1, b1, .., addend; one slot for a squaring or a REDC); out: [n][9].
+extern "C" int emul_form(int form, const uint32_t* in, uint32_t* out, size_t n) {
+    for (size_t j = 0; j < n; j++) {
+        dev::Fe x[9] = {}, r;
+        const int slots[13] = {2, 1, 6, 8, 5, 1, 3, 2, 3, 1, 2, 3, 6};
+        if (form < 0 || form >= 13) return -1;
+        for (int s = 0; s < slots[form]; s++)
+            for (int i = 0; i < dev::NL; i++) x[s].v[i] = in[(j * slots[form] + s) * dev::NL + i];
+        dev::Fe a[4], b[4];
+        for (int t = 0; t < 4; t++) { a[t] = x[2 * t]; b[t] = x[2 * t + 1]; }
+        switch (form) {
+            case 0: dev::mont_dot<1, false, true>(r, a, b, a[0]); break;           // mul_vv
+            case 1: dev::mont_sqr(r, x[0]); break;                                  // sqr_v
+            case 2: dev::mont_dot<3, false, true>(r, a, b, a[0]); break;           // dot3_uc
+            case 3: dev::mont_dot<4, false, true>(r, a, b, a[0]); break;           // dot4_uc
+            case 4: dev::mont_dot<2, true, false>(r, a, b, x[4]); break;           // dot2_add_uc_narrow
+            case 5: dev::mont_dot<1, false, false>(r, &x[0], &x[0], x[0]); break;  // sqr_v_narrow
+            case 6: dev::mont_dot<1, true, false>(r, a, b, x[2]); break;           // mul_vv_adds_narrow
+            case 7: dev::mont_dot<1, false, false>(r, a, b, a[0]); break;          // mul_uc_narrow
+            case 8: dev::mont_dot<1, true, false>(r, a, b, x[2]); break;           // mul_uc_add_narrow
+            case 9: dev::mont_redc(r, x[0]); break;                                 // redc_v_narrow
+            case 10: dev::mont_dot<1, false, false>(r, a, b, a[0]); break;         // mul_vv_narrow
+            case 11: dev::mont_dot<1, true, false>(r, a, b, x[2]); break;          // mul_vv_add_narrow
+            case 12: dev::mont_dot<3, false, false>(r, a, b, a[0]); break;         // dot3_vv_narrow
+        }
+        for (int i = 0; i < dev::NL; i++) out[j * dev::NL + i] = r.v[i];
+    }
+    return 0;
+}
+// one permutation of permute() from raw entry lanes [n][3][9] (first_rc = rc_full[0]); the raw exit lanes, before any
+// canonicalize
+extern "C" void emul_permute_raw(const uint32_t* in, uint32_t* out, size_t n) {
+    for (size_t j = 0; j < n; j++) {
+        dev::Fe s[3];
+        for (int l = 0; l < 3; l++)
+            for (int i = 0; i < dev::NL; i++) s[l].v[i] = in[(j * 3 + l) * dev::NL + i];
+        dev::permute(g_consts, s, g_consts.rc_full[0]);
+        for (int l = 0; l < 3; l++)
+            for (int i = 0; i < dev::NL; i++) out[(j * 3 + l) * dev::NL + i] = s[l].v[i];
+    }
+}
+// The helpers the forms feed, on raw limbs / words (names as in tests/native/fe_forms.hip): in [n][in_words],
+// out [n][out_words]
+extern "C" int emul_helper(const char* name, const uint32_t* in, unsigned in_words, uint32_t* out, unsigned out_words,
+                           size_t n) {
+    const std::string h(name);
+    for (size_t j = 0; j < n; j++) {
+        const uint32_t* I = in + j * in_words;
+        uint32_t* O = out + j * out_words;
+        dev::Fe a, b, r;
+        for (int i = 0; i < dev::NL; i++) a.v[i] = in_words >= (unsigned)dev::NL ? I[i] : 0;
+        alignas(16) uint32_t w[8];
+        std::memcpy(w, I, 32);
+        if (h == "canonicalize") dev::canonicalize(a);
+        else if (h == "fold_p") dev::fold_p(a);
+        else if (h == "normalize") dev::normalize(a);
+        else if (h == "cond_sub_p_shl0") dev::cond_sub_p_shl<0>(a);
+        else if (h == "cond_sub_p_shl1") dev::cond_sub_p_shl<1>(a);
+        else if (h == "cond_sub_p_shl2") dev::cond_sub_p_shl<2>(a);
+        else if (h == "cond_sub_p_shl3") dev::cond_sub_p_shl<3>(a);
+        else if (h == "cond_sub_p_shl4") dev::cond_sub_p_shl<4>(a);
+        else if (h == "csub0") dev::csub<0>(a);
+        else if (h == "csub1") dev::csub<1>(a);
+        else if (h == "t_add") {
+            for (int i = 0; i < dev::NL; i++) b.v[i] = I[dev::NL + i];
+            dev::t_add(r, a, b);
+            a = r;
+        } else if (h == "pack") { dev::pack(w, a); std::memcpy(O, w, 32); continue; }
+        else if (h == "unpack") dev::unpack(a, w);
+        else if (h.rfind("load_fe", 0) == 0) {
+            O[dev::NL] = dev::load_fe(g_consts, a, w, (unsigned)(h[7] - '0')) ? 1u : 0u;
+        } else if (h.rfind("store_fe", 0) == 0) { dev::store_fe(g_consts, w, a, (unsigned)(h[8] - '0')); std::memcpy(O, w, 32); continue; }
+        else if (h == "store_mont256") { dev::store_mont256(w, a); std::memcpy(O, w, 32); continue; }
+        else return -1;
+        for (int i = 0; i < dev::NL; i++) O[i] = a.v[i];
+    }
+    return 0;
+}

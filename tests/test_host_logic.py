@@ -123,6 +123,17 @@ def test_column_accumulator_bounds():
     assert max(lanes) < 9                     # what canonicalize (< 16p) and the next block's entry need
 
 
+# v_mad_u64_u32 per assembly form of csrc/imt_mont_asm.hpp (also checked in the compiled harness, tests/test_fe_forms.py)
+MAD_COUNTS = {"mul_vv": 81 + 81, "sqr_v": 45 + 81, "dot3_uc": 243 + 81, "dot4_uc": 324 + 81,
+              "dot2_add_uc_narrow": 162 + 81 + 8,
+              # the witness-trace kernel's one-product forms; "+ 8": the addend limbs enter as mad(e, 1)
+              "sqr_v_narrow": 45 + 81, "mul_vv_adds_narrow": 81 + 81 + 8, "mul_uc_narrow": 81 + 81,
+              "mul_uc_add_narrow": 81 + 81 + 8,
+              "redc_v_narrow": 9 + 81,       # a / R: the nine limbs enter as mad(a, 1), no limb products
+              # the lane-cooperative hash
+              "mul_vv_narrow": 81 + 81, "mul_vv_add_narrow": 81 + 81 + 8, "dot3_vv_narrow": 243 + 81}
+
+
 def test_generated_assembly_header_is_current(tmp_path):
     """csrc/imt_mont_asm.hpp is generated; the committed copy must be what the generator writes, and
     its instruction counts must be the single-chain minimum (no per-column 64-bit adds)."""
@@ -133,17 +144,10 @@ def test_generated_assembly_header_is_current(tmp_path):
     committed = open(os.path.join(ROOT, "indexed-merkle-tree-halo2_amd", "csrc", "imt_mont_asm.hpp")).read()
     assert out.read_text() == committed
     blocks = committed.split("__device__ __forceinline__ void ")[1:]
-    want = {"mul_vv": 81 + 81, "sqr_v": 45 + 81, "dot3_uc": 243 + 81, "dot4_uc": 324 + 81,
-            "dot2_add_uc_narrow": 162 + 81 + 8,
-            # the witness-trace kernel's one-product forms; "+ 8": the addend limbs enter as mad(e, 1)
-            "sqr_v_narrow": 45 + 81, "mul_vv_adds_narrow": 81 + 81 + 8, "mul_uc_narrow": 81 + 81,
-            "mul_uc_add_narrow": 81 + 81 + 8,
-            "redc_v_narrow": 9 + 81,       # a / R: the nine limbs enter as mad(a, 1), no limb products
-            # the lane-cooperative hash
-            "mul_vv_narrow": 81 + 81, "mul_vv_add_narrow": 81 + 81 + 8, "dot3_vv_narrow": 243 + 81}
+    assert sorted(b.split("(")[0] for b in blocks) == sorted(MAD_COUNTS)
     for b in blocks:
         name = b.split("(")[0]
-        assert b.count('"v_mad_u64_u32') == want[name]
+        assert b.count('"v_mad_u64_u32') == MAD_COUNTS[name]
         assert "v_lshl_add_u64" not in b and "s_nop" not in b
 
 

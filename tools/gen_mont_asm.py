@@ -133,8 +133,10 @@ HEADER = '''// imt_mont_asm.hpp -- GENERATED by tools/gen_mont_asm.py; do not ed
 // build (tests/native/emul_device.cpp) and the value semantics are those of the C++ forms.
 //
 // "_uc" variants take the FIRST factor of every term as wave-uniform constants ("s" constraints:
-// they must come from scalar loads of __constant__ data indexed by uniform values -- a per-lane
-// value passed there would silently be replaced by lane 0's).
+// they must come from scalar loads of __constant__ data indexed by uniform values).  The constraint
+// does not enforce that: hipcc keeps a per-lane value passed there in a VGPR, which the instructions
+// accept, so the values stay right and only the SGPR operands are lost; tests/test_fe_forms.py
+// counts the SGPR factors in the compiled kernels.
 #pragma once
 #if !defined(__HIP_DEVICE_COMPILE__)
 #error "device-only header"
