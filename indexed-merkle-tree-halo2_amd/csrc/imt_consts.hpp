@@ -31,16 +31,17 @@ struct PoseidonConsts {
     Fe int_one;           // integer 1: device form -> canonical integer
     Fe zero_leaf;         // H(0,0,0) in device form
     // ---- everything above is the lane-cooperative hash's table (imt_coop_device.hpp copies it to LDS) ----
-    // The thread-per-hash schedule (imt_device.hpp::permute) with its lanes rescaled by fifth roots: lane i of
-    // full round f is held as s_i / d_f,i and lane 0 of partial round p as s_0 / lambda_p, so that the S-box
-    // output lands pre-multiplied by d^5 (lambda^5) and the linear layer needs fewer products (imt_params.cpp).
-    Fe sc_rc[RF][3];      // full-round constants c_f,i / d_f,i  ([0] unused: first_rc; [4] = rc_full[4])
-    Fe sc_mats[RF][3][3]; // D_f+1^-1 M D_f^5; row 0 is (1, 1, 1) except in full rounds 0 and 4
-    Fe sc_k[RP];          // k_p / lambda_p
-    Fe sc_row[RP][3];     // new s0 / lambda_p+1 = sc_row . (xi^5, s1, s2),  xi = S-box input / lambda_p
-    Fe sc_gamma[RP];      // sc_row[p][1] + sc_row[p][2] sc_u[p-1]: round p of a pair reads the linear lanes as
-                          // they were before round p-1 ([0] unused)
-    Fe sc_u[RP];          // col[p][1] / col[p][0]: s2 += sc_u xi^5 (s1 += xi^5 needs no product)
+    // The thread-per-hash schedule (imt_device.hpp::permute).  Full rounds: lane i of full round f is held as
+    // s_i / d_f,i, so that the S-box output lands pre-multiplied by d^5 and row 0 of the matrix is (1, 1, 1) in
+    // rounds 1-3 and 5-7.  Partial rounds: an order-3 recurrence on the S-box lane alone (imt_params.cpp), the S-box
+    // input of round r held as x_r / lambda_r = w_r + rec_k[r] with lambda_r+1 = M00 lambda_r^5, and
+    //   w_r+1 = rec_c[r] . (w_r, w_r-1, z_r-2, z_r-1) + z_r,   z = (w + rec_k)^5.
+    Fe sc_rc[RF][3];      // full-round constants c_f,i / d_f,i  ([0] unused: first_rc)
+    Fe sc_mats[RF][3][3]; // D_f+1^-1 M D_f^5; round 3's rows 1, 2 are the functionals of lanes 1, 2 that w_1, w_2 need
+    Fe rec_k[RP];         // S-box input constants of the partial rounds
+    Fe rec_c[RP][4];      // recurrence coefficients; [0] unused (w_1 = row 1 of full round 3 + z_0), [1] = (C0, C3, 0, 0)
+    Fe rec_exit[2][3];    // lanes 1, 2 of full round 4's input: rec_exit[i] . (w_57, w_56, z_55) + z_56
+    Fe rec_unused[51];    // zero: keeps the table's size
 };
 
 // ---- f1: tables of the witness-trace kernel (imt_trace_device.hpp) -------------------------------

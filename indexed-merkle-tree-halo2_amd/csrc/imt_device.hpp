@@ -85,6 +85,7 @@ IMT_HD uint32_t mont_digit(uint64_t acc) {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(IMT_NO_MONT_ASM)
 #define IMT_MONT_ASM 1
 #include "imt_mont_asm.hpp"
+#include "imt_mont_asm_rec.hpp"
 #endif
 namespace imt {
 namespace dev {
@@ -136,9 +137,10 @@ IMT_HD void mont_mul(Fe& r, const Fe& a, const Fe& b) {
 template <int NT, bool ADD, bool WIDE_M = true>
 IMT_HD void mont_dot_uc(Fe& r, const Fe* c, const Fe* v, const Fe& addend) {
 #ifdef IMT_MONT_ASM
-    static_assert((NT == 3 && !ADD && WIDE_M) || (NT == 4 && !ADD && WIDE_M) || (NT == 2 && ADD && !WIDE_M),
+    static_assert((NT == 3 && !ADD && WIDE_M) || (NT == 4 && WIDE_M) || (NT == 2 && ADD && !WIDE_M),
                   "no assembly form for this shape");
     if constexpr (NT == 3) masm::dot3_uc(r, c, v);
+    else if constexpr (NT == 4 && ADD) masm::dot4_add_uc(r, c, v, addend);
     else if constexpr (NT == 4) masm::dot4_uc(r, c, v);
     else masm::dot2_add_uc_narrow(r, c, v, addend);
 #else
@@ -343,28 +345,48 @@ IMT_HD void fold_p(Fe& a) {
     }
 }
 
-// One permutation, optimised schedule (same values as the plain 65-round form), on lanes rescaled by fifth
-// roots of constants (imt_params.cpp): every S-box output arrives pre-multiplied by the factor the linear layer
-// would have applied to it, which saves products.
-//   full rounds f = 0..3, 4..7 : s += c_f; x^5 on all lanes; n = M_f s.  Row 0 of M_f is (1, 1, 1), i.e. a sum,
-//                                except in f = 0 (the caller's unscaled input) and f = 4 (the partial rounds' exit)
-//   partial rounds p = 0..56   : xi = s0 + k_p; z = xi^5; s0 = row_p . (z, s1, s2); s1 += z; s2 += u_p z
-// The partial rounds run in pairs: the second round of a pair takes the linear lanes as they were before the
-// first one (its row product gets the extra term gamma * z_first), so s2 is reduced once per pair,
-// REDC(s2 R + u_p z_first + u_p+1 z_second), and s1 takes z_first + z_second with two additions: 9 products +
-// 3 reductions per pair besides the S-boxes (was 11 + 4).  The odd 57th round runs through the same code with
-// z_second = 0.  s1 grows by < 20p per pair and is folded back below 1.2p every fourth pair (it must stay a
-// valid multiplicand: < 2^261, top limb < 2^29).
-// One loop so that each body exists once in the instruction stream.
+// One permutation, optimised schedule (same values as the plain 65-round form; tables from imt_params.cpp).
+//   full rounds f = 0..3, 4..7 : lanes rescaled by fifth roots of constants, so that every S-box output arrives
+//                                pre-multiplied by the factor the linear layer would apply to it: s += c_f; x^5 on all
+//                                lanes; n = M_f s.  Row 0 of M_f is (1, 1, 1), i.e. a sum, except in f = 0 (the
+//                                caller's unscaled input) and f = 4 (the partial rounds' exit)
+//   partial rounds r = 0..56   : an order-3 recurrence on the S-box lane alone (Cayley-Hamilton on the MDS):
+//                                z_r = (w_r + k_r)^5;  w_r+1 = c_r . (w_r, w_r-1, z_r-2, z_r-1) + z_r
+// The S-box input is held rescaled so that z_r enters with coefficient 1, as the REDC addend: 4 products + 1 reduction
+// per round besides the S-box.  Full round 3 seeds the window: its row 0 is w_0, its rows 1 and 2 the two functionals
+// of lanes 1, 2 that w_1 = row 1 + z_0 and w_2 = c_1 . (w_1, z_0) + row 2 + z_1 need.  After round 56 lane 0 is w_57
+// and lanes 1, 2 are rebuilt from (w_57, w_56, z_55, z_56) at the start of full round 4 (one dot3 call, taken twice).
+// The window values are normalised REDC outputs (limbs < 2^29: the column budget of the 4-term form); only the S-box
+// input is a lazy sum.
+// One flat loop, one step per round, so that each body exists once in the instruction stream.  Kept flat on purpose:
+// with the partial rounds as an inner loop of one step, the full rounds' block alone needed 93 VGPRs (75 flat) and the
+// kernels capped at 96 spilled.  Flat, the window costs one extra lane (z3) carried through the full rounds.
 // `first_rc` replaces the round-0 constants (sponge padding folded in by the caller); the input and the output
 // are unscaled.  Entry: limbs normalised, lane 0 < 32p, lanes 1, 2 < 16p.  Exit: limbs normalised, lane 0
-// < 30p (a sum of three S-box outputs), lanes 1, 2 < 9p.  Bounds: tests/test_rescaled_schedule.py.
+// < 30p (a sum of three S-box outputs), lanes 1, 2 < 9p.  Bounds: tests/test_recurrence_schedule_bounds.py.
 IMT_HD void permute(const PoseidonConsts& pc, Fe s[3], const Fe* first_rc) {
-    constexpr int NSTEP = RF + (RP + 1) / 2;   // 4 full, 29 partial pairs, 4 full
+    constexpr int NSTEP = RF + RP;             // 4 full rounds, 57 partial rounds, 4 full rounds
+    // partial round r: s[0] = w_r, s[1] = w_r-1, z3 = z_r-2, s[2] = z_r-1 (rounds 0, 1: the seeds)
+    Fe z3;
+#pragma unroll
+    for (int i = 0; i < NL; i++) z3.v[i] = 0;
 #pragma unroll 1
     for (int st = 0; st < NSTEP; st++) {
-        if (st < RF / 2 || st >= RF / 2 + (RP + 1) / 2) {
-            const int fr = st < RF / 2 ? st : st - (RP + 1) / 2;
+        if (st < RF / 2 || st >= RF / 2 + RP) {
+            const int fr = st < RF / 2 ? st : st - RP;
+            if (fr == RF / 2) {
+                // lanes 1, 2 of full round 4's input: rec_exit[i] . (w_57, w_56, z_55) + z_56
+                const Fe v[3] = {s[0], s[1], z3};
+                const Fe zl = s[2];
+#pragma unroll 1
+                for (int i = 0; i < 2; i++) {
+                    Fe n;
+                    mont_dot_uc<3, false>(n, pc.rec_exit[i], v, v[0]);
+                    add_lazy(n, n, zl);
+                    normalize(n);
+                    s[1] = s[2]; s[2] = n;
+                }
+            }
             const Fe* rc = (st == 0) ? first_rc : pc.sc_rc[fr];
             add_lazy(s[0], s[0], rc[0]);
             add_lazy(s[1], s[1], rc[1]);
@@ -383,32 +405,23 @@ IMT_HD void permute(const PoseidonConsts& pc, Fe s[3], const Fe* first_rc) {
             mont_dot_uc<3, false>(n2, mat[2], s, s[0]);
             s[0] = n0; s[1] = n1; s[2] = n2;
         } else {
-            const int p = 2 * (st - RF / 2);
-            const bool second = p + 1 < RP;
-            Fe v[4], z[2], n0;
-            add_lazy(v[0], s[0], pc.sc_k[p]);
-            sbox(v[0]);
-            v[1] = s[1]; v[2] = s[2];
-            mont_dot_uc<3, false>(n0, pc.sc_row[p], v, v[0]);
-            z[0] = v[0];
-#pragma unroll
-            for (int i = 0; i < NL; i++) z[1].v[i] = 0;
-            if (second) {
-                add_lazy(v[0], n0, pc.sc_k[p + 1]);
-                sbox(v[0]);
-                v[3] = z[0];
-                const Fe c4[4] = {pc.sc_row[p + 1][0], pc.sc_row[p + 1][1], pc.sc_row[p + 1][2], pc.sc_gamma[p + 1]};
-                mont_dot_uc<4, false>(n0, c4, v, v[0]);
-                z[1] = v[0];
+            const int r = st - RF / 2;
+            Fe z, w;
+            add_lazy(z, s[0], pc.rec_k[r]);
+            sbox(z);
+            if (r >= 2) {
+                const Fe v[4] = {s[0], s[1], z3, s[2]};
+                mont_dot_uc<4, true>(w, pc.rec_c[r], v, z);
+            } else if (r == 1) {                       // w_2 = c . (w_1, z_0) + L2 + z_1
+                const Fe v[2] = {s[0], s[2]};
+                Fe e;
+                add_lazy(e, z3, z);
+                mont_dot_uc<2, true, false>(w, pc.rec_c[1], v, e);
+            } else {                                   // w_1 = L1 + z_0
+                add_lazy(w, s[1], z);
+                normalize(w);
             }
-            const int q = second ? p + 1 : p;    // with z[1] = 0 the second constant is unused
-            const Fe cu[2] = {pc.sc_u[p], pc.sc_u[q]};
-            mont_dot_uc<2, true, false>(s[2], cu, z, s[2]);   // narrow digits: this lane only accumulates
-            add_lazy(s[1], s[1], z[0]);
-            add_lazy(s[1], s[1], z[1]);
-            normalize(s[1]);
-            if ((p & 7) == 6) fold_p(s[1]);      // after pairs 3, 7, .., 27
-            s[0] = n0;
+            s[1] = s[0]; s[0] = w; z3 = s[2]; s[2] = z;
         }
     }
 }

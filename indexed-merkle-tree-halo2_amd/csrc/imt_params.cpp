@@ -10,7 +10,8 @@
 //     lane-0 constants and the first constants of the second half of the full rounds;
 //   * M = S * N' with N' = diag(1, D) commuting with the partial S-box; every N' is pulled
 //     back into the previous round, leaving one dense PRE matrix and 57 sparse ones;
-//   * for the device, the lanes of that schedule rescaled by fifth roots of its constants (sc_* tables).
+//   * for the device, full rounds on lanes rescaled by fifth roots of their constants (sc_* tables) and the partial
+//     rounds as an order-3 recurrence on the S-box lane (rec_* tables).
 // Any such schedule is value-identical to the plain form; init() checks that.
 #include "imt_params.hpp"
 
@@ -93,9 +94,9 @@ void HostPoseidon::permute_opt(HFr s[3]) const {
 }
 
 // The device schedule (imt_device.hpp::permute) on plain field elements: full rounds on rescaled lanes with the
-// (1, 1, 1) row as a sum, partial rounds in pairs on the rescaled lane 0 (the second round of a pair reads the
-// linear lanes as they were before the first, plus gamma * z_first), s1 += z with no product.
-void HostPoseidon::permute_scaled(HFr s[3]) const {
+// (1, 1, 1) row as a sum, partial rounds as the recurrence w_r+1 = rec_c[r] . (w_r, w_r-1, z_r-2, z_r-1) + z_r on the
+// rescaled S-box lane, seeded with full round 3's rows (w_0, w_1 - z_0, ., w_2 - z_1 - ..), lanes 1, 2 rebuilt at the exit.
+void HostPoseidon::permute_rec(HFr s[3]) const {
     auto sbox = [&](HFr& x) {
         HFr x2 = F.mul(x, x), x4 = F.mul(x2, x2);
         x = F.mul(x4, x);
@@ -113,23 +114,26 @@ void HostPoseidon::permute_scaled(HFr s[3]) const {
         s[0] = n0; s[1] = n1; s[2] = n2;
     };
     for (int f = 0; f < 4; f++) full(f);
-    for (int p = 0; p < 57; p += 2) {
-        HFr z0 = F.add(s[0], sc_k[p]);
-        sbox(z0);
-        const HFr v3[3] = {z0, s[1], s[2]};
-        HFr n0 = dot(sc_row[p], v3, 3), z1 = F.zero();
-        if (p + 1 < 57) {
-            z1 = F.add(n0, sc_k[p + 1]);
-            sbox(z1);
-            const HFr c4[4] = {sc_row[p + 1][0], sc_row[p + 1][1], sc_row[p + 1][2], sc_gamma[p + 1]};
-            const HFr v4[4] = {z1, s[1], s[2], z0};
-            n0 = dot(c4, v4, 4);
+    HFr a = s[0], b = s[1], z3 = F.zero(), z2 = s[2];
+    for (int r = 0; r < 57; r++) {
+        HFr z = F.add(a, rec_k[r]);
+        sbox(z);
+        HFr w;
+        if (r == 0) {
+            w = F.add(b, z);
+        } else if (r == 1) {
+            const HFr v2[2] = {a, z2};
+            w = F.add(dot(rec_c[1], v2, 2), F.add(z3, z));
+        } else {
+            const HFr v4[4] = {a, b, z3, z2};
+            w = F.add(dot(rec_c[r], v4, 4), z);
         }
-        s[1] = F.add(s[1], F.add(z0, z1));
-        s[2] = F.add(s[2], F.mul(sc_u[p], z0));
-        if (p + 1 < 57) s[2] = F.add(s[2], F.mul(sc_u[p + 1], z1));
-        s[0] = n0;
+        b = a; a = w; z3 = z2; z2 = z;
     }
+    const HFr v3[3] = {a, b, z3};
+    s[0] = a;
+    s[1] = F.add(dot(rec_exit[0], v3, 3), z2);
+    s[2] = F.add(dot(rec_exit[1], v3, 3), z2);
     for (int f = 4; f < 8; f++) full(f);
 }
 
@@ -273,56 +277,143 @@ bool HostPoseidon::init(std::string& err) {
     }
     std::memcpy(pre, cur, sizeof pre);
 
-    // ---- the device schedule: lanes rescaled by fifth roots (x -> x^5 is a bijection: gcd(5, p - 1) = 1) ----
-    // Partial round p holds its S-box input as xi = x / lambda_p with lambda_p^5 = 1 / col[p][0]: the S-box gives
-    // xi^5 = col[p][0] y, so s1 += col[p][0] y is a plain addition and s2 += col[p][1] y is (col[p][1]/col[p][0]) xi^5.
-    // 1 / lambda_p goes into k_p and into the row that produces lane 0 (the previous round's, or full round 3's);
-    // lambda_57 = 1.  Lanes 1 and 2 are never rescaled.
-    // Full round f holds lane i as s_i / d_f,i; its matrix is D_f+1^-1 M D_f^5 and its constants c_f,i / d_f,i.
-    // Choosing d_f,j^5 = d_f+1,0 / M[0][j] makes row 0 (1, 1, 1); solved backwards from D_8 = I (the output is
-    // unscaled) and from D_4 = diag(lambda_0, 1, 1) (the partial rounds' entry).  D_0 = I (the caller's input: the
-    // first constants stay rc_full[0] / rc_h2p2) and D_4 = I (the partial rounds' exit), so full rounds 0 and 4
-    // keep a general row 0.
+    // ---- the device schedule ----
+    // Partial rounds.  In the plain form each is s <- M (s + c_r + e0 (z_r - x_r)) with the same M (x_r the lane-0 S-box
+    // input, z_r = x_r^5).  With M^3 = a2 M^2 + a1 M + a0 I (Cayley-Hamilton), the lane-0 values y_r = x_r - c_r,0 obey
+    //   y_r+3 = (a2 - b0) y_r+2 + (a1 - b1) y_r+1 + a0 z_r + b1 z_r+1 + b0 z_r+2 + K_r,  b0 = M00, b1 = (M^2)00 - a2 M00
+    // (the a0 y_r terms cancel), so lanes 1 and 2 are not needed until the exit.  The device holds the S-box input as
+    // x_r = lambda_r (w_r + rec_k[r]), y_r = lambda_r w_r + off_r, with lambda_r+1 = b0 lambda_r^5: z_r+2 then enters
+    // every step with coefficient 1 (as the REDC addend) and the constants go into rec_k.
+    // Entry: y_1 and y_2 depend on lanes 1, 2 of the entry state t only through L1 = M01 t1 + M02 t2 and
+    // L2 = (M^2)01 t1 + (M^2)02 t2, which full round 3 computes in place of its rows 1 and 2.
+    // Exit: the state after round 56 is affine in (y_57, y_56, z_55, z_56); the scales d_4,i of the next full round
+    // are free, which makes the z_56 coefficient of lanes 1 and 2 one and lambda_57 the scale of lane 0.
+    // Full rounds: lane i of full round f is held as s_i / d_f,i; its matrix is D_f+1^-1 M D_f^5 and its constants
+    // c_f,i / d_f,i.  Choosing d_f,j^5 = d_f+1,0 / M[0][j] makes row 0 (1, 1, 1) (x -> x^5 is a bijection:
+    // gcd(5, p - 1) = 1); solved backwards from D_8 = I (the output is unscaled) and from lambda_0 (the partial rounds'
+    // entry).  D_0 = I (the caller's input) and D_4 (the partial rounds' exit) keep a general row 0 in rounds 0 and 4.
     {
-        HFr lam[58];
-        for (int p = 0; p < 57; p++) {
-            if (F.is_zero(sp_col[p][0])) { err = "sparse column entry col[p][0] is zero: no fifth-root rescaling"; return false; }
-            lam[p] = F.fifth_root(F.inverse(sp_col[p][0]));
-            HFr l2 = F.mul(lam[p], lam[p]);
-            if (!(F.mul(F.mul(l2, l2), F.mul(lam[p], sp_col[p][0])) == F.one())) { err = "fifth root check failed"; return false; }
+        typedef HFr M3[3][3];
+        M3 m2, m3;
+        auto mat_mul3 = [&](const M3 x, const M3 y, M3 o) {
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++) {
+                    o[i][j] = F.mul(x[i][0], y[0][j]);
+                    o[i][j] = F.add(o[i][j], F.mul(x[i][1], y[1][j]));
+                    o[i][j] = F.add(o[i][j], F.mul(x[i][2], y[2][j]));
+                }
+        };
+        mat_mul3(mds, mds, m2);
+        mat_mul3(m2, mds, m3);
+        auto minor = [&](int i, int j) { return F.sub(F.mul(mds[i][i], mds[j][j]), F.mul(mds[i][j], mds[j][i])); };
+        const HFr a2 = F.add(F.add(mds[0][0], mds[1][1]), mds[2][2]);
+        const HFr a1 = F.sub(F.zero(), F.add(F.add(minor(0, 1), minor(0, 2)), minor(1, 2)));
+        const HFr a0 = F.add(F.sub(F.mul(mds[0][0], minor(1, 2)),
+                                   F.mul(mds[0][1], F.sub(F.mul(mds[1][0], mds[2][2]), F.mul(mds[1][2], mds[2][0])))),
+                             F.mul(mds[0][2], F.sub(F.mul(mds[1][0], mds[2][1]), F.mul(mds[1][1], mds[2][0]))));
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                HFr ch = F.add(F.add(F.mul(a2, m2[i][j]), F.mul(a1, mds[i][j])), i == j ? a0 : F.zero());
+                if (!(ch == m3[i][j])) { err = "Cayley-Hamilton check of the MDS failed"; return false; }
+            }
+        const HFr b0 = mds[0][0], b1 = F.sub(m2[0][0], F.mul(a2, mds[0][0]));
+        if (F.is_zero(b0) || F.is_zero(a0)) { err = "MDS entry 00 or determinant is zero: no recurrence schedule"; return false; }
+        const HFr(*c)[3] = rc + 4;                     // the partial rounds' constants, all three lanes
+        auto row0 = [&](const M3 m, const HFr* v) {
+            return F.add(F.add(F.mul(m[0][0], v[0]), F.mul(m[0][1], v[1])), F.mul(m[0][2], v[2]));
+        };
+        M3 nm;                                         // M^2 - a2 M
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) nm[i][j] = F.sub(m2[i][j], F.mul(a2, mds[i][j]));
+        HFr lam[58], l5[58], off[58];
+        lam[0] = F.one();
+        for (int r = 0; r < 58; r++) {
+            const HFr l2 = F.mul(lam[r], lam[r]);
+            l5[r] = F.mul(F.mul(l2, l2), lam[r]);
+            if (r < 57) lam[r + 1] = F.mul(b0, l5[r]);
         }
-        lam[57] = F.one();
-        for (int p = 0; p < 57; p++) {
-            const HFr li = F.inverse(lam[p]), ln = F.inverse(lam[p + 1]);
-            sc_k[p] = F.mul(k_partial[p], li);
-            sc_row[p][0] = F.mul(sp_row[p][0], F.mul(F.inverse(sp_col[p][0]), ln));
-            sc_row[p][1] = F.mul(sp_row[p][1], ln);
-            sc_row[p][2] = F.mul(sp_row[p][2], ln);
-            sc_u[p] = F.mul(sp_col[p][1], F.inverse(sp_col[p][0]));
+        off[0] = F.zero();
+        off[1] = F.add(F.mul(mds[0][1], c[0][1]), F.mul(mds[0][2], c[0][2]));
+        off[2] = F.sub(F.add(F.add(F.mul(m2[0][1], c[0][1]), F.mul(m2[0][2], c[0][2])),
+                             F.add(F.mul(mds[0][1], c[1][1]), F.mul(mds[0][2], c[1][2]))),
+                       F.mul(b0, off[1]));
+        for (int r = 2; r < 57; r++) {
+            const HFr K = F.sub(F.add(F.sub(row0(nm, c[r - 1]), F.mul(b1, c[r - 1][0])), row0(mds, c[r])), F.mul(b0, c[r][0]));
+            off[r + 1] = F.add(F.add(F.mul(F.sub(a2, b0), off[r]), F.mul(F.sub(a1, b1), off[r - 1])), K);
         }
-        sc_gamma[0] = F.zero();
-        for (int p = 1; p < 57; p++) sc_gamma[p] = F.add(sc_row[p][1], F.mul(sc_row[p][2], sc_u[p - 1]));
+        HFr li[58];
+        for (int r = 0; r < 58; r++) li[r] = F.inverse(lam[r]);
+        for (int r = 0; r < 57; r++) rec_k[r] = F.mul(F.add(off[r], c[r][0]), li[r]);
+        for (int t = 0; t < 4; t++) rec_c[0][t] = rec_c[1][t] = F.zero();
+        rec_c[1][0] = F.mul(F.sub(F.zero(), b0), F.mul(lam[1], li[2]));
+        rec_c[1][1] = F.mul(m2[0][0], F.mul(l5[0], li[2]));
+        for (int r = 2; r < 57; r++) {
+            rec_c[r][0] = F.mul(F.sub(a2, b0), F.mul(lam[r], li[r + 1]));
+            rec_c[r][1] = F.mul(F.sub(a1, b1), F.mul(lam[r - 1], li[r + 1]));
+            rec_c[r][2] = F.mul(a0, F.mul(l5[r - 2], li[r + 1]));
+            rec_c[r][3] = F.mul(b1, F.mul(l5[r - 1], li[r + 1]));
+        }
+        // exit: with v = t_56 + c_56 (lane 0: y_56 + c_56,0), the state after round 56 is M (z_56, v1, v2);
+        //   y_57 = M00 z_56 + M01 v1 + M02 v2,   eta . v = eta . c_56 + (eta . M e0) z_55
+        // (eta spans the left kernel of M's columns 1 and 2: t_56 = M (z_55, ., .)), solved for v1, v2
+        const HFr eta[3] = {minor(1, 2), F.sub(F.mul(mds[2][1], mds[0][2]), F.mul(mds[0][1], mds[2][2])),
+                            F.sub(F.mul(mds[0][1], mds[1][2]), F.mul(mds[1][1], mds[0][2]))};
+        const HFr g[2][2] = {{mds[0][1], mds[0][2]}, {eta[1], eta[2]}};
+        const HFr gdet = F.sub(F.mul(g[0][0], g[1][1]), F.mul(g[0][1], g[1][0]));
+        if (F.is_zero(gdet)) { err = "singular exit system of the recurrence schedule"; return false; }
+        const HFr gd = F.inverse(gdet);
+        const HFr gi[2][2] = {{F.mul(g[1][1], gd), F.mul(F.sub(F.zero(), g[0][1]), gd)},
+                              {F.mul(F.sub(F.zero(), g[1][0]), gd), F.mul(g[0][0], gd)}};
+        HFr eta_c = F.zero(), eta_m0 = F.zero();
+        for (int i = 0; i < 3; i++) {
+            eta_c = F.add(eta_c, F.mul(eta[i], c[56][i]));
+            eta_m0 = F.add(eta_m0, F.mul(eta[i], mds[i][0]));
+        }
+        HFr d4[3] = {lam[57], F.zero(), F.zero()}, rc4[3];
+        rc4[0] = F.mul(F.add(rc[61][0], off[57]), li[57]);
+        for (int i = 1; i < 3; i++) {
+            // lane i = h0 (y_57 - M00 z_56) + h1 (eta . c_56 + eta_m0 z_55 - eta0 (y_56 + c_56,0)) + Mi0 z_56
+            const HFr h0 = F.add(F.mul(mds[i][1], gi[0][0]), F.mul(mds[i][2], gi[1][0]));
+            const HFr h1 = F.add(F.mul(mds[i][1], gi[0][1]), F.mul(mds[i][2], gi[1][1]));
+            const HFr cz56 = F.sub(mds[i][0], F.mul(h0, mds[0][0]));
+            d4[i] = F.mul(cz56, l5[56]);
+            if (F.is_zero(d4[i])) { err = "zero z_56 coefficient at the recurrence's exit"; return false; }
+            const HFr di = F.inverse(d4[i]), mh = F.sub(F.zero(), F.mul(eta[0], h1));
+            rec_exit[i - 1][0] = F.mul(F.mul(h0, lam[57]), di);
+            rec_exit[i - 1][1] = F.mul(F.mul(mh, lam[56]), di);
+            rec_exit[i - 1][2] = F.mul(F.mul(F.mul(h1, eta_m0), l5[55]), di);
+            const HFr k = F.add(F.add(F.mul(h0, off[57]), F.mul(mh, F.add(off[56], c[56][0]))), F.mul(h1, eta_c));
+            rc4[i] = F.mul(F.add(rc[61][i], k), di);
+        }
 
+        M3 entry;                                      // full round 3: (t0, L1, L2)
+        for (int j = 0; j < 3; j++) {
+            entry[0][j] = mds[0][j];
+            entry[1][j] = F.add(F.mul(mds[0][1], mds[1][j]), F.mul(mds[0][2], mds[2][j]));
+            entry[2][j] = F.add(F.mul(m2[0][1], mds[1][j]), F.mul(m2[0][2], mds[2][j]));
+        }
         HFr d[9][3];                                   // d[f] scales the input of full round f; d[8] the output
-        for (int i = 0; i < 3; i++) d[0][i] = d[4][i] = d[8][i] = F.one();
-        const HFr d4in[3] = {lam[0], F.one(), F.one()};   // input scaling of partial round 0
+        for (int i = 0; i < 3; i++) { d[0][i] = d[8][i] = F.one(); d[4][i] = d4[i]; }
+        const HFr d4in[3] = {lam[0], lam[1], lam[2]};  // scales of full round 3's outputs: w_0, L1 / lambda_1, L2 / lambda_2
         auto solve = [&](int f, const HFr m[3][3], const HFr& dn0) {
             for (int j = 0; j < 3; j++) {
                 if (F.is_zero(m[0][j])) { err = "zero entry in row 0 of a full-round matrix"; return false; }
                 d[f][j] = F.fifth_root(F.mul(dn0, F.inverse(m[0][j])));
+                const HFr x2 = F.mul(d[f][j], d[f][j]);
+                if (!(F.mul(F.mul(x2, x2), F.mul(d[f][j], m[0][j])) == dn0)) { err = "fifth root check failed"; return false; }
             }
             return true;
         };
         for (int f = 7; f >= 5; f--)
             if (!solve(f, mds, d[f + 1][0])) return false;
-        if (!solve(3, pre, d4in[0])) return false;
+        if (!solve(3, entry, d4in[0])) return false;
         for (int f = 2; f >= 1; f--)
             if (!solve(f, mds, d[f + 1][0])) return false;
         for (int f = 0; f < 8; f++) {
-            const HFr(*m)[3] = f == 3 ? pre : mds;
+            const HFr(*m)[3] = f == 3 ? entry : mds;
             const HFr* dn = f == 3 ? d4in : d[f + 1];
             for (int i = 0; i < 3; i++) {
-                sc_rc[f][i] = F.mul(rc_full[f][i], F.inverse(d[f][i]));
+                sc_rc[f][i] = f == 4 ? rc4[i] : F.mul(rc[f < 4 ? f : f + 57][i], F.inverse(d[f][i]));
                 const HFr dni = F.inverse(dn[i]);
                 for (int j = 0; j < 3; j++) {
                     HFr d2 = F.mul(d[f][j], d[f][j]);
@@ -405,7 +496,7 @@ bool HostPoseidon::init(std::string& err) {
             for (int j = 0; j < 3; j++) tr_pre[i][j] = a[j][i];
     }
 
-    // ---- self-check: optimised == rescaled == plain ----
+    // ---- self-check: optimised == device schedule == plain ----
     for (uint64_t t = 0; t < 6; t++) {
         HFr a[3] = {F.from_u64(t * 7919), F.from_u64(t * t + 1), F.mul(cap0, F.from_u64(t + 3))};
         if (t == 4) a[0] = a[1] = a[2] = F.sub(F.zero(), F.one());           // p - 1 on every lane
@@ -413,13 +504,13 @@ bool HostPoseidon::init(std::string& err) {
         HFr b[3] = {a[0], a[1], a[2]}, sc[3] = {a[0], a[1], a[2]}, c3[3] = {a[0], a[1], a[2]};
         permute_plain(a);
         permute_opt(b);
-        permute_scaled(sc);
+        permute_rec(sc);
         if (!(a[0] == b[0] && a[1] == b[1] && a[2] == b[2])) {
             err = "optimised Poseidon schedule disagrees with the plain form";
             return false;
         }
         if (!(a[0] == sc[0] && a[1] == sc[1] && a[2] == sc[2])) {
-            err = "rescaled Poseidon schedule disagrees with the plain form";
+            err = "device (recurrence) Poseidon schedule disagrees with the plain form";
             return false;
         }
         // permute_spec adds start[0] itself (absorb_with_pre_constants does it in the gadget); the plain form adds
@@ -487,10 +578,8 @@ void HostPoseidon::fill_consts(dev::PoseidonConsts& pc) const {
         pc.k_partial[p] = to_dev(k_partial[p]);
         for (int i = 0; i < 3; i++) pc.sp_row[p][i] = to_dev(sp_row[p][i]);
         for (int i = 0; i < 2; i++) pc.sp_col[p][i] = to_dev(sp_col[p][i]);
-        pc.sc_k[p] = to_dev(sc_k[p]);
-        for (int i = 0; i < 3; i++) pc.sc_row[p][i] = to_dev(sc_row[p][i]);
-        pc.sc_gamma[p] = to_dev(sc_gamma[p]);
-        pc.sc_u[p] = to_dev(sc_u[p]);
+        pc.rec_k[p] = to_dev(rec_k[p]);
+        for (int t = 0; t < 4; t++) pc.rec_c[p][t] = to_dev(rec_c[p][t]);
     }
     for (int f = 0; f < 8; f++)
         for (int i = 0; i < 3; i++) {
@@ -502,6 +591,9 @@ void HostPoseidon::fill_consts(dev::PoseidonConsts& pc) const {
             pc.mats[0][i][j] = to_dev(mds[i][j]);
             pc.mats[1][i][j] = to_dev(pre[i][j]);
         }
+    for (int i = 0; i < 2; i++)
+        for (int j = 0; j < 3; j++) pc.rec_exit[i][j] = to_dev(rec_exit[i][j]);
+    for (auto& u : pc.rec_unused) u = to_dev(F.zero());
     pc.cap0 = to_dev(cap0);
     pc.one = to_dev(F.one());
     // conversions are single Montgomery products (divide by 2^261) on the device

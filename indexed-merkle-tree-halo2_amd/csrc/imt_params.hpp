@@ -18,10 +18,11 @@ struct HostPoseidon {
     HFr sp_row[57][3];
     HFr sp_col[57][2];
     HFr cap0;           // 2^64
-    // the same schedule with lanes rescaled by fifth roots (the device schedule; see imt_params.cpp)
+    // the device schedule (see imt_params.cpp): full rounds on lanes rescaled by fifth roots, partial rounds as a
+    // recurrence on the S-box lane
     HFr sc_rc[8][3];
     HFr sc_mats[8][3][3];
-    HFr sc_k[57], sc_row[57][3], sc_gamma[57], sc_u[57];
+    HFr rec_k[57], rec_c[57][4], rec_exit[2][3];
     // halo2-base / pse-poseidon optimised spec, for the witness trace (f1): derived in init() from rc / mds by
     // the published Spec::new algorithm (calculate_optimized_constants, calculate_sparse_matrices)
     HFr tr_start[5][3], tr_partial[57], tr_end[3][3];
@@ -34,7 +35,7 @@ struct HostPoseidon {
 
     void permute_plain(HFr s[3]) const;
     void permute_opt(HFr s[3]) const;
-    void permute_scaled(HFr s[3]) const;    // host mirror of imt_device.hpp::permute (sc_* tables, pair form)
+    void permute_rec(HFr s[3]) const;       // host mirror of imt_device.hpp::permute (sc_* and rec_* tables)
     void permute_spec(HFr s[3]) const;      // the same permutation in the tr_* (halo2-base) convention
     void fill_trace_consts(dev::TraceConsts& tc) const;
     HFr hash2(const HFr& a, const HFr& b) const;

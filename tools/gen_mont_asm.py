@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Generates indexed-merkle-tree-halo2_amd/csrc/imt_mont_asm.hpp: the Montgomery products of
-imt_device.hpp (mont_dot / mont_sqr) as single inline-asm blocks for gfx950.
+imt_device.hpp (mont_dot / mont_sqr) as single inline-asm blocks for gfx950.  With --rec [path] it writes
+imt_mont_asm_rec.hpp instead: the form of the partial rounds' recurrence (dot4_add_uc).
 
 Why: hipcc re-associates each column sum so that the carry from the previous column is added last
 (one extra v_lshl_add_u64 per column, 17 per reduction) to expose instruction-level parallelism.
@@ -154,7 +155,39 @@ FOOTER = '''}  // namespace masm
 '''
 
 
+REC_HEADER = '''// imt_mont_asm_rec.hpp -- GENERATED by tools/gen_mont_asm.py --rec; do not edit.
+// The Montgomery form of the partial rounds' recurrence (imt_device.hpp::permute) as a single inline-asm block for
+// gfx950, in the style of imt_mont_asm.hpp (one dependent v_mad_u64_u32 chain per column).  Device compilation only.
+#pragma once
+#if !defined(__HIP_DEVICE_COMPILE__)
+#error "device-only header"
+#endif
+
+namespace imt {
+namespace dev {
+namespace masm {
+
+'''
+
+
+def main_rec(path):
+    """The recurrence's form, in a header of its own so that imt_mont_asm.hpp stays as it is."""
+    body = [REC_HEADER]
+    body.append(gen("dot4_add_uc", 4, "s", True, True,
+                    doc="r = (sum_{t<4} a[t]*b[t] + addend*R) / R, a uniform constants, addend per lane, wide digits: "
+                        "r < .../R + addend + 8p"))
+    body.append(FOOTER)
+    with open(path, "w") as f:
+        f.write("\n".join(body))
+    print("wrote", path)
+
+
 def main():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if len(sys.argv) > 1 and sys.argv[1] == "--rec":
+        main_rec(sys.argv[2] if len(sys.argv) > 2 else
+                 os.path.join(root, "indexed-merkle-tree-halo2_amd", "csrc", "imt_mont_asm_rec.hpp"))
+        return
     body = [HEADER]
     body.append(gen("mul_vv", 1, "v", False, True, doc="r = a[0]*b[0] / R, wide digits: r < a*b/R + 8p"))
     body.append(gen("sqr_v", 1, "v", False, True, sqr=True, doc="r = a^2 / R, wide digits; limbs of a < 2^30"))
@@ -177,7 +210,6 @@ def main():
     body.append(gen("mul_vv_add_narrow", 1, "v", True, False, doc="r = (a[0]*b[0] + addend*R) / R, all per lane, 29-bit digits"))
     body.append(gen("dot3_vv_narrow", 3, "v", False, False, doc="r = sum_{t<3} a[t]*b[t] / R, all per lane, 29-bit digits"))
     body.append(FOOTER)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     path = os.path.join(root, "indexed-merkle-tree-halo2_amd", "csrc", "imt_mont_asm.hpp")
     if len(sys.argv) > 1:          # tests regenerate into a scratch file and compare
         path = sys.argv[1]
