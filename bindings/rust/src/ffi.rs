@@ -147,6 +147,11 @@ pub const IMT_PROF_TOP: usize = 3;
 pub const IMT_PROF_WRITEBACK: usize = 4;
 pub const IMT_PROF_HOST: usize = 5;
 pub const IMT_PROF_CLASSES: usize = 6;
+pub const IMT_PROF_APPLY_LISTS: usize = 6;
+pub const IMT_PROF_APPLY_LEAVES: usize = 7;
+pub const IMT_PROF_APPLY_LEVEL: usize = 8;
+pub const IMT_PROF_APPLY_TOP: usize = 9;
+pub const IMT_PROF_ALL_CLASSES: usize = 10;
 
 pub const IMT_OPT_COOP_MAX_EVENTS: c_int = 1;
 pub const IMT_SEG_GLUE: u32 = 0;
@@ -191,6 +196,7 @@ extern "C" {
     pub fn imt_measure_mad_peak(ctx: *mut imt_ctx, gmads: *mut c_double) -> c_int;
     pub fn imt_profile_enable(ctx: *mut imt_ctx, on: c_int) -> c_int;
     pub fn imt_profile_read(ctx: *mut imt_ctx, out: *mut c_double) -> c_int;
+    pub fn imt_profile_read_all(ctx: *mut imt_ctx, out: *mut c_double) -> c_int;
 
     // ---- a1 / a10: batched hashes
     pub fn imt_hash2_batch(ctx: *mut imt_ctx, input: *const c_void, out: *mut c_void, n: usize, flags: c_uint) -> c_int;
@@ -252,6 +258,9 @@ extern "C" {
     pub fn imt_itree_load(t: *mut imt_itree, preimages: *const c_void, n: u64, flags: c_uint) -> c_int;
     pub fn imt_itree_find_low_batch(t: *mut imt_itree, vals: *const c_void, n: usize, low_index: *mut u64, flags: c_uint) -> c_int;
     pub fn imt_itree_insert_filtered(t: *mut imt_itree, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, n_inserted: *mut u64, out: *const imt_insert_out, flags: c_uint) -> c_int;
+    pub fn imt_itree_apply_batch(t: *mut imt_itree, vals: *const c_void, n: usize, root_out: *mut c_void, flags: c_uint) -> c_int;
+    pub fn imt_itree_apply_filtered(t: *mut imt_itree, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, n_inserted: *mut u64, root_out: *mut c_void, flags: c_uint) -> c_int;
+    pub fn imt_itree_apply_stats(t: *mut imt_itree, hashes: *mut u64) -> c_int;
     pub fn imt_itree_lookup_batch(t: *mut imt_itree, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, flags: c_uint) -> c_int;
     pub fn imt_itree_non_membership_witness(t: *mut imt_itree, vals: *const c_void, n: usize, low_index: *mut u64, low_leaf: *mut c_void, is_largest: *mut u8, low_sib: *mut c_void, flags: c_uint) -> c_int;
 

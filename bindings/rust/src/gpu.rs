@@ -149,6 +149,24 @@ impl IndexedTree {
         check(&g, unsafe { imt_itree_root(self.handle, r.as_mut_ptr() as *mut c_void, IMT_FMT_CANONICAL) })?;
         Ok(F::from_bytes_le(&r))
     }
+    /// The tree after `insert_batch(vals)` without the witnesses: every touched node hashed once (3 to 9 hashes per
+    /// insertion instead of 66 at depth 32).  Returns the root after the batch.
+    pub fn apply_batch<F: ScalarField>(&mut self, vals: &[F]) -> Result<F, ImtError> {
+        let g = context().lock().unwrap();
+        let v = to_bytes(vals);
+        let mut r = [0u8; 32];
+        check(&g, unsafe {
+            imt_itree_apply_batch(self.handle, v.as_ptr() as *const c_void, vals.len(), r.as_mut_ptr() as *mut c_void, IMT_FMT_CANONICAL)
+        })?;
+        Ok(F::from_bytes_le(&r))
+    }
+    /// hashes per level of the last `apply_batch`: `[0]` leaf hashes, `[l]` the hash2 calls that made level-l nodes
+    pub fn apply_stats(&self) -> Result<Vec<u64>, ImtError> {
+        let g = context().lock().unwrap();
+        let mut h = vec![0u64; self.depth + 1];
+        check(&g, unsafe { imt_itree_apply_stats(self.handle, h.as_mut_ptr()) })?;
+        Ok(h)
+    }
     /// n sequential insertions; one [`InsertWitness`] each (66 hashes per insertion at depth 32, all on the GPU)
     pub fn insert_batch<F: ScalarField>(&mut self, vals: &[F]) -> Result<Vec<InsertWitness<F>>, ImtError> {
         let g = context().lock().unwrap();

@@ -147,11 +147,19 @@ const char *imt_version(void);
 #define IMT_PROF_WRITEBACK 4   /* k_writeback */
 #define IMT_PROF_HOST 5        /* host side of imt_itree_insert_batch (wall time, waits excluded) */
 #define IMT_PROF_CLASSES 6
+/* The classes of imt_itree_apply_batch, behind the six above: imt_profile_read writes the first IMT_PROF_CLASSES only
+ * (its callers' arrays are that long), imt_profile_read_all all IMT_PROF_ALL_CLASSES; either resets every counter. */
+#define IMT_PROF_APPLY_LISTS 6   /* the scans and the scatter that list every level's touched nodes: no hashing */
+#define IMT_PROF_APPLY_LEAVES 7  /* k_apply_level, leaf launch: one 3-input hash per touched leaf */
+#define IMT_PROF_APPLY_LEVEL 8   /* k_apply_level, the levels below l0 - 1: one hash per touched node */
+#define IMT_PROF_APPLY_TOP 9     /* k_apply_top: the chain from level l0 - 1 to the root */
+#define IMT_PROF_ALL_CLASSES 10
 /* Measures the device's v_mad_u64_u32 issue rate (8 independent chains per lane, 8 waves per SIMD): the
  * ceiling of the VALU roofline bench.py reports.  *gmads = 10^9 lane multiply-adds per second. */
 int imt_measure_mad_peak(imt_ctx *ctx, double *gmads);
 int imt_profile_enable(imt_ctx *ctx, int on);
 int imt_profile_read(imt_ctx *ctx, double *out /*[2*IMT_PROF_CLASSES]*/);
+int imt_profile_read_all(imt_ctx *ctx, double *out /*[2*IMT_PROF_ALL_CLASSES]*/);
 
 /* ---- a1 / a10: batched hashes -------------------------------------------------- */
 /* out[i] = Poseidon::update(&[in[i][0], in[i][1]]) ; squeeze_and_reset()
@@ -459,6 +467,30 @@ int imt_itree_find_low_batch(imt_itree *t, const void *vals /*[n][32]*/, size_t 
 int imt_itree_insert_filtered(imt_itree *t, const void *vals /*[n][32]*/, size_t n, uint8_t *status /*[n]*/,
                               uint64_t *leaf_index /*[n] or NULL*/, uint64_t *n_inserted /*host*/,
                               const imt_insert_out *out /*may be NULL*/, unsigned flags);
+/* WITNESS-FREE INSERTION, for whoever keeps the tree current and proves nothing about the way there (a node following
+ * the chain, a prover catching up on history, a sequencer that filters now and proves elsewhere, the non-membership
+ * service).  The tree after imt_itree_insert_batch(t, vals, n, NULL, flags), and nothing else: same value checks, same
+ * errors with the tree untouched, same index, same stored nodes byte for byte -- but every node the batch touches is
+ * hashed ONCE, from its children's final values (imt_apply.hpp): 3 to 9 hashes per insertion where the witness sweep
+ * spends 2 + 2*depth.  root_out: the root after the batch, [32] in the flags' format, host or device memory per
+ * IMT_DEVICE_PTRS, may be NULL.  n == 0: IMT_OK, root_out = the current root.
+ * IMT_FMT_*, IMT_DEVICE_PTRS, IMT_HOST_PREP and IMT_INPUTS_READY mean what they mean to imt_itree_insert_batch.  The call
+ * runs on the context's stream behind every batch still in flight on the pipeline streams, later calls are ordered
+ * behind it, and witness and apply calls may alternate freely on one tree; apply batches are not pipelined against each
+ * other: IMT_PIPELINE -> IMT_ERR_ARG.  On a placed / partitioned tree the residue check and the global next_idx come
+ * with the shared preparation; only local nodes are written. */
+int imt_itree_apply_batch(imt_itree *t, const void *vals /*[n][32]*/, size_t n, void *root_out /*[32] or NULL*/,
+                          unsigned flags);
+/* imt_itree_insert_filtered without witnesses: status / leaf_index / *n_inserted exactly as that call writes them, then
+ * imt_itree_apply_batch of the accepted values.  Nothing accepted: IMT_OK, *n_inserted = 0, root_out = the current
+ * root. */
+int imt_itree_apply_filtered(imt_itree *t, const void *vals /*[n][32]*/, size_t n, uint8_t *status /*[n]*/,
+                             uint64_t *leaf_index /*[n] or NULL*/, uint64_t *n_inserted /*host*/,
+                             void *root_out /*[32] or NULL*/, unsigned flags);
+/* What the last apply call that inserted something hashed: hashes[0] = leaf hashes, hashes[l] = hash2 calls that
+ * produced level-l nodes, l = 1 .. depth -- the number of distinct nodes the batch touched at every level.  Host memory;
+ * waits for that call.  IMT_ERR_ARG if there has been none. */
+int imt_itree_apply_stats(imt_itree *t, uint64_t *hashes /*[depth + 1]*/);
 /* Read-only query of the device-resident index for any mix of values (one kernel, k_lookup): status ZERO / FOREIGN /
  * PRESENT / NEW and leaf_index = the sentinel / UINT64_MAX / the stored leaf / the low leaf (what find_low returns).
  * Fails only for its arguments, a value >= p (IMT_ERR_NONCANONICAL) or a HIP error, never for a value's class.  With

@@ -381,6 +381,19 @@ public:
         }
         return r;
     }
+    // insert_batch without the witnesses (imt_itree_apply_batch): the same tree afterwards, every touched node hashed
+    // once; returns the root after the batch.  The same errors, the tree unchanged.
+    Fr apply_batch(const std::vector<Fr>& vals) {
+        Fr root;
+        c_->check(imt_itree_apply_batch(t_, vals.data(), vals.size(), &root, IMT_FMT_CANONICAL));
+        return root;
+    }
+    // hashes per level of the last apply_batch: [0] leaf hashes, [l] the hash2 calls that made level-l nodes
+    std::vector<uint64_t> apply_stats() {
+        std::vector<uint64_t> h(depth_ + 1);
+        c_->check(imt_itree_apply_stats(t_, h.data()));
+        return h;
+    }
     std::vector<IndexedMerkleTreeLeaf> get_leaves(const std::vector<uint64_t>& index) {
         std::vector<IndexedMerkleTreeLeaf> out(index.size());
         if (!index.empty()) c_->check(imt_itree_get_leaves(t_, index.data(), index.size(), out.data(), IMT_FMT_CANONICAL));

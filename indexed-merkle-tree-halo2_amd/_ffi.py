@@ -92,6 +92,7 @@ SIGNATURES = {
     "imt_measure_mad_peak": (c_int, [c_void_p, P(ctypes.c_double)]),
     "imt_profile_enable": (c_int, [c_void_p, c_int]),
     "imt_profile_read": (c_int, [c_void_p, P(ctypes.c_double)]),
+    "imt_profile_read_all": (c_int, [c_void_p, P(ctypes.c_double)]),
     "imt_hash2_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_uint]),
     "imt_hash3_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_uint]),
     "imt_permute_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_uint]),
@@ -150,6 +151,9 @@ SIGNATURES = {
     "imt_itree_load": (c_int, [c_void_p, c_void_p, c_u64, c_uint]),
     "imt_itree_find_low_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
     "imt_itree_insert_filtered": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, P(c_u64), P(InsertOut), c_uint]),
+    "imt_itree_apply_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
+    "imt_itree_apply_filtered": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, P(c_u64), c_void_p, c_uint]),
+    "imt_itree_apply_stats": (c_int, [c_void_p, P(c_u64)]),
     "imt_itree_lookup_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_uint]),
     "imt_itree_batch_begin": (c_int, [c_void_p, c_void_p, c_size_t, c_uint, P(ctypes.c_uint32), P(ctypes.c_uint32)]),
     "imt_itree_batch_leaves": (c_int, [c_void_p, c_void_p, ctypes.c_uint32, ctypes.c_uint32]),
@@ -216,6 +220,7 @@ F_RANGE_PRED, F_LOW_IN_ROOT, F_LOW_LT_NEW, F_ZERO_SLOT, F_NEXT_VAL, F_NEXT_IDX, 
 CELL_CONST, CELL_INPUT, CELL_INIT, CELL_WITNESS, CELL_COPY = 0, 1, 2, 3, 4
 TRACE_ITEM_MAJOR = SIB_ITEM_MAJOR
 OPT_COOP_MAX_EVENTS = 1
+PROF_NAMES = ("leaves", "index", "level", "top", "writeback", "host", "apply_lists", "apply_leaves", "apply_level", "apply_top")
 SEG_GLUE, SEG_HASH = 0, 1
 SLICED_ROUNDS = 4
 (SLICED_OPT_COMM_STREAMS, SLICED_OPT_COMM_PRIORITY, SLICED_OPT_ROUND_PRIORITIES, SLICED_OPT_APPLY_STREAMS, SLICED_OPT_PREP_STREAM,

@@ -630,6 +630,33 @@ class IndexedTree:
         res.update(status=status, leaf_index=leaf, n_inserted=m)
         return res
 
+    def apply_batch(self, vals, host_prep=False):
+        """insert_batch() without witnesses (imt_itree_apply_batch): the same tree afterwards, every touched node hashed
+        once; returns the root after the batch."""
+        v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
+        root = np.empty(32, dtype=np.uint8)
+        rc = lib.imt_itree_apply_batch(self.h, _p(v), v.shape[0], _p(root), _ffi.HOST_PREP if host_prep else 0)
+        if rc == _ffi.ERR["VALUE"]:
+            raise ValueError(lib.imt_last_error(self.ctx.h).decode())
+        self.ctx._check(rc)
+        return to_int(root)
+
+    def apply_filtered(self, vals, host_prep=False):
+        """insert_filtered() without witnesses (imt_itree_apply_filtered): (status, leaf_index, n_inserted, root)."""
+        v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
+        n = v.shape[0]
+        status, leaf, root = np.empty(n, np.uint8), np.empty(n, np.uint64), np.empty(32, dtype=np.uint8)
+        n_ins = ctypes.c_uint64()
+        self.ctx._check(lib.imt_itree_apply_filtered(self.h, _p(v), n, _p(status), _p(leaf), ctypes.byref(n_ins), _p(root),
+                                                     _ffi.HOST_PREP if host_prep else 0))
+        return status, leaf, n_ins.value, to_int(root)
+
+    def apply_stats(self):
+        """hashes per level of the last apply call: [0] leaf hashes, [l] the hash2 calls that made level-l nodes."""
+        out = np.empty(self.depth + 1, dtype=np.uint64)
+        self.ctx._check(lib.imt_itree_apply_stats(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return out
+
     def lookup(self, vals):
         """(status, leaf_index) of every value against the stored tree (imt_itree_lookup_batch): VAL_PRESENT with the
         leaf that holds it, VAL_NEW with its low leaf, VAL_ZERO with the sentinel, VAL_FOREIGN with 2^64 - 1."""

@@ -130,7 +130,7 @@ extern "C" int imt_profile_enable(imt_ctx* c, int on) {
     c->profiling = on != 0;
     return IMT_OK;
 }
-extern "C" int imt_profile_read(imt_ctx* c, double* out) {
+static int profile_read(imt_ctx* c, double* out, int classes) {
     if (!c || !out) return IMT_ERR_ARG;
     int rc = c->set_device();
     if (rc) return rc;
@@ -146,13 +146,17 @@ extern "C" int imt_profile_read(imt_ctx* c, double* out) {
         c->prof_pool.push_back(p.b);
     }
     c->prof_pending.clear();
-    for (int k = 0; k < IMT_PROF_CLASSES; k++) {
-        out[2 * k] = c->prof_ms[k];
-        out[2 * k + 1] = c->prof_n[k];
+    for (int k = 0; k < IMT_PROF_ALL_CLASSES; k++) {
+        if (k < classes) {
+            out[2 * k] = c->prof_ms[k];
+            out[2 * k + 1] = c->prof_n[k];
+        }
         c->prof_ms[k] = c->prof_n[k] = 0;
     }
     return IMT_OK;
 }
+extern "C" int imt_profile_read(imt_ctx* c, double* out) { return profile_read(c, out, IMT_PROF_CLASSES); }
+extern "C" int imt_profile_read_all(imt_ctx* c, double* out) { return profile_read(c, out, IMT_PROF_ALL_CLASSES); }
 
 extern "C" int imt_ctx_set_option(imt_ctx* c, int option, uint64_t value) {
     if (!c) return IMT_ERR_ARG;

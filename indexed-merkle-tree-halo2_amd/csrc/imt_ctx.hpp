@@ -27,8 +27,8 @@ struct imt_ctx {
     struct ProfPair { hipEvent_t a, b; int cls; };
     std::vector<ProfPair> prof_pending;
     std::vector<hipEvent_t> prof_pool;
-    double prof_ms[IMT_PROF_CLASSES] = {0};
-    double prof_n[IMT_PROF_CLASSES] = {0};
+    double prof_ms[IMT_PROF_ALL_CLASSES] = {0};
+    double prof_n[IMT_PROF_ALL_CLASSES] = {0};
     hipEvent_t prof_event();
     // RAII-less helpers: begin returns an index into prof_pending (or -1 when off)
     int prof_begin(int cls, hipStream_t on = nullptr);

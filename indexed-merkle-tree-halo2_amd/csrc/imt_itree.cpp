@@ -177,6 +177,9 @@ struct imt_itree {
     double slice_backpressure_ms = 0;        // ... the part of it spent waiting for the plan set's previous slice (all-time total)
     bool sliced_busy = false;                // an imt_sliced world has steps in flight on this replica (until its flush)
     size_t reserved_events = 0;              // every plan set holds at least this many events (reserve_all_plans)
+    // imt_itree_apply_batch: hashes per level of the last apply call, written by its kernels (imt_itree_apply_stats)
+    uint64_t* d_apply_stats = nullptr;       // [IMT_MAX_DEPTH + 1]
+    bool apply_seen = false;
 };
 
 static void plan_free(PlanSet& p) {
@@ -317,6 +320,7 @@ extern "C" void imt_itree_free(imt_itree* t) {
     if (t->d_off) hipFree(t->d_off);
     if (t->d_len) hipFree(t->d_len);
     if (t->d_val) hipFree(t->d_val);
+    if (t->d_apply_stats) hipFree(t->d_apply_stats);
     for (auto q : t->d_sorted)
         if (q) hipFree(q);
     if (t->h_err_pin) hipHostFree(t->h_err_pin);
@@ -359,6 +363,7 @@ extern "C" int imt_itree_new(imt_ctx* c, unsigned depth, uint64_t capacity, imt_
         (e = hipMalloc((void**)&t->d_nodes, off * 32)) != hipSuccess ||
         (e = hipMalloc((void**)&t->d_off, (depth + 1) * 8)) != hipSuccess ||
         (e = hipMalloc((void**)&t->d_len, (depth + 1) * 8)) != hipSuccess ||
+        (e = hipMalloc((void**)&t->d_apply_stats, (IMT_MAX_DEPTH + 1) * 8)) != hipSuccess ||
         (e = hipStreamCreateWithFlags(&t->up_stream, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&t->up_done, hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&t->in_mark, hipEventDisableTiming)) != hipSuccess ||
@@ -1215,8 +1220,14 @@ int gpu_prepare(imt_itree* t, PlanSet& P, const void* vals, size_t n, unsigned f
 // The body of imt_itree_insert_batch.  filtered: `vals` are the accepted values of imt_itree_insert_filtered, canonical,
 // in device memory of the plan set (default prepare) or host memory (IMT_HOST_PREP), whatever IMT_DEVICE_PTRS says of
 // the outputs.  Level-major sibling arrays have level stride sib_stride (>= n).
+// apply != NULL: imt_itree_apply_batch -- same preparation, same commit, but the hashing is the witness-free schedule
+// (apply_hashes) and the only output is the root.
+struct ApplyReq {
+    void* root_out;
+};
+static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0);
 static int insert_core(imt_itree* t, const void* vals, size_t n, const imt_insert_out* out, unsigned flags, bool filtered,
-                       size_t sib_stride) {
+                       size_t sib_stride, const ApplyReq* apply = nullptr) {
     if (!t) return IMT_ERR_ARG;
     imt_ctx* c = t->ctx;
     IMT_NOT_SLICED(t);
@@ -1230,6 +1241,7 @@ static int insert_core(imt_itree* t, const void* vals, size_t n, const imt_inser
     if (rc) return rc;
     const bool dev = flags & IMT_DEVICE_PTRS;
     if ((rc = check_fe_ptrs(c, dev && !filtered, {vals})) || (rc = check_out_ptrs(c, dev, out))) return rc;
+    if (apply && (rc = check_fe_ptrs(c, dev, {apply->root_out}))) return rc;
     const bool gpu_prep = (flags & IMT_HOST_PREP) == 0;
     const unsigned fmt = flags & IMT_FMT_MASK;
     const uint64_t M = t->size;
@@ -1310,62 +1322,67 @@ static int insert_core(imt_itree* t, const void* vals, size_t n, const imt_inser
     // a placed tree writes rows [0, depth) of sibling arrays dimensioned for global_depth levels
     launch::SibLayout lay = item_major ? launch::SibLayout{1, t->global_depth} : launch::SibLayout{sib_stride, 1};
 
-    // ---- leaf hashes, index phase (no hashing), then the hash sweep ----
-    int pf = c->prof_begin(IMT_PROF_LEAVES, s);
-    launch::sweep_leaves(s, P.d_pre, P.d_tab[0][1], P.d_val[0], 0, (uint32_t)E, IMT_FMT_CANONICAL, c->d_err, c->coop_max_events);
-    c->prof_end(pf, s);
-    pf = c->prof_begin(IMT_PROF_INDEX, s);
-    for (unsigned l = 0; l < L0; l++) {
-        const int a = l & 1, b = a ^ 1;
-        // time table of level l: the uploaded one for l = 0, otherwise slot l-1 of d_timen
-        const uint32_t* time_in = l == 0 ? P.d_tab[0][1] : P.d_timen + (size_t)(l - 1) * P.cap_events;
-        sweep::LevelTable in{P.d_tab[a][0], time_in, P.d_tab[a][2], P.d_tab[a][3]};
-        sweep::LevelOut o{P.d_tab[b][0], P.d_timen + (size_t)l * P.cap_events, P.d_tab[b][2], P.d_tab[b][3],
-                          P.d_from + (size_t)l * P.cap_events, P.d_sibsrc + (size_t)l * P.cap_events,
-                          P.d_nodeb + (size_t)l * P.cap_events, nullptr};
-        launch::merge_level(s, in, o, (uint32_t)E);
-    }
-    c->prof_end(pf, s);
-    for (unsigned l = 0; l < L0; l++) {
-        const uint8_t* vin = P.d_val[l & 1];
-        uint8_t* vout = P.d_val[(l & 1) ^ 1];
-        const size_t o = (size_t)l * P.cap_events;
-        // stored level l must hold the previous batch's final versions: its write-back of that level,
-        // or (at and above its L0) its top kernel
-        if (prev) IMT_HIP(c, hipStreamWaitEvent(s, l < prev->l0 ? prev->wb_done[l] : prev->done, 0));
-        pf = c->prof_begin(IMT_PROF_LEVEL, s);
-        launch::sweep_level(s, vin, vout, P.d_from + o, P.d_sibsrc + o, P.d_nodeb + o, P.d_timen + o,
-                            t->d_nodes + t->h_off[l] * 32, t->h_len[l], c->d_zero + (size_t)l * 32, 0, (uint32_t)E, g_ls,
-                            g_ns, lay, l, fmt, c->coop_max_events);
+    if (apply) {
+        // ---- one hash per touched node, straight into the stored tree (imt_apply.hpp) ----
+        if ((rc = apply_hashes(t, P, s, E, L0))) return rc;
+    } else {
+        // ---- leaf hashes, index phase (no hashing), then the hash sweep ----
+        int pf = c->prof_begin(IMT_PROF_LEAVES, s);
+        launch::sweep_leaves(s, P.d_pre, P.d_tab[0][1], P.d_val[0], 0, (uint32_t)E, IMT_FMT_CANONICAL, c->d_err, c->coop_max_events);
         c->prof_end(pf, s);
-        pf = c->prof_begin(IMT_PROF_WRITEBACK, s);
-        launch::writeback(s, vin, P.d_from + o, P.d_nodeb + o, t->d_nodes + t->h_off[l] * 32, (uint32_t)E);
+        pf = c->prof_begin(IMT_PROF_INDEX, s);
+        for (unsigned l = 0; l < L0; l++) {
+            const int a = l & 1, b = a ^ 1;
+            // time table of level l: the uploaded one for l = 0, otherwise slot l-1 of d_timen
+            const uint32_t* time_in = l == 0 ? P.d_tab[0][1] : P.d_timen + (size_t)(l - 1) * P.cap_events;
+            sweep::LevelTable in{P.d_tab[a][0], time_in, P.d_tab[a][2], P.d_tab[a][3]};
+            sweep::LevelOut o{P.d_tab[b][0], P.d_timen + (size_t)l * P.cap_events, P.d_tab[b][2], P.d_tab[b][3],
+                              P.d_from + (size_t)l * P.cap_events, P.d_sibsrc + (size_t)l * P.cap_events,
+                              P.d_nodeb + (size_t)l * P.cap_events, nullptr};
+            launch::merge_level(s, in, o, (uint32_t)E);
+        }
         c->prof_end(pf, s);
-        if (pipelined) IMT_HIP(c, hipEventRecord(P.wb_done[l], s));
+        for (unsigned l = 0; l < L0; l++) {
+            const uint8_t* vin = P.d_val[l & 1];
+            uint8_t* vout = P.d_val[(l & 1) ^ 1];
+            const size_t o = (size_t)l * P.cap_events;
+            // stored level l must hold the previous batch's final versions: its write-back of that level,
+            // or (at and above its L0) its top kernel
+            if (prev) IMT_HIP(c, hipStreamWaitEvent(s, l < prev->l0 ? prev->wb_done[l] : prev->done, 0));
+            pf = c->prof_begin(IMT_PROF_LEVEL, s);
+            launch::sweep_level(s, vin, vout, P.d_from + o, P.d_sibsrc + o, P.d_nodeb + o, P.d_timen + o,
+                                t->d_nodes + t->h_off[l] * 32, t->h_len[l], c->d_zero + (size_t)l * 32, 0, (uint32_t)E, g_ls,
+                                g_ns, lay, l, fmt, c->coop_max_events);
+            c->prof_end(pf, s);
+            pf = c->prof_begin(IMT_PROF_WRITEBACK, s);
+            launch::writeback(s, vin, P.d_from + o, P.d_nodeb + o, t->d_nodes + t->h_off[l] * 32, (uint32_t)E);
+            c->prof_end(pf, s);
+            if (pipelined) IMT_HIP(c, hipEventRecord(P.wb_done[l], s));
+        }
+        // ---- levels [L0, depth): every event alone in node 0 against the empty subtree of that height.  Ordinary
+        // launches of the same kernel, so consecutive batches overlap here level by level as well; the last event's node
+        // of every level goes back to the stored tree.  old_root[0] is the root the previous batch left: it is read
+        // right before the launch that overwrites the stored root.
+        auto read_old_root = [&]() -> int {
+            if (prev) IMT_HIP(c, hipStreamWaitEvent(s, prev->done, 0));
+            if (g_old) launch::convert(s, t->d_nodes + t->h_off[t->depth] * 32, g_old, 1, IMT_FMT_DEVICE, fmt, c->d_err);
+            return IMT_OK;
+        };
+        for (unsigned l = L0; l < t->depth; l++) {
+            if (l + 1 == t->depth && (rc = read_old_root())) return rc;
+            // the previous batch stored node l + 1 (and node l, at its own L0) from its launch of this level
+            if (prev) IMT_HIP(c, hipStreamWaitEvent(s, l >= prev->l0 ? prev->wb_done[l] : prev->done, 0));
+            pf = c->prof_begin(IMT_PROF_TOP, s);
+            launch::sweep_upper(s, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], c->d_zero + (size_t)l * 32, 0, (uint32_t)E,
+                                (uint32_t)E - 1, l == L0 ? t->d_nodes + t->h_off[l] * 32 : nullptr,
+                                t->d_nodes + t->h_off[l + 1] * 32, g_ls, g_ns, lay, l, fmt, c->coop_max_events);
+            c->prof_end(pf, s);
+            if (pipelined) IMT_HIP(c, hipEventRecord(P.wb_done[l], s));
+        }
+        if (L0 == t->depth && (rc = read_old_root())) return rc;
+        launch::emit_roots(s, P.d_val[t->depth & 1], 0, (uint32_t)E, (uint32_t)E, g_old, g_int, g_new, fmt, nullptr,
+                           L0 == t->depth ? t->d_nodes + t->h_off[t->depth] * 32 : nullptr);
     }
-    // ---- levels [L0, depth): every event alone in node 0 against the empty subtree of that height.  Ordinary
-    // launches of the same kernel, so consecutive batches overlap here level by level as well; the last event's node
-    // of every level goes back to the stored tree.  old_root[0] is the root the previous batch left: it is read
-    // right before the launch that overwrites the stored root.
-    auto read_old_root = [&]() -> int {
-        if (prev) IMT_HIP(c, hipStreamWaitEvent(s, prev->done, 0));
-        if (g_old) launch::convert(s, t->d_nodes + t->h_off[t->depth] * 32, g_old, 1, IMT_FMT_DEVICE, fmt, c->d_err);
-        return IMT_OK;
-    };
-    for (unsigned l = L0; l < t->depth; l++) {
-        if (l + 1 == t->depth && (rc = read_old_root())) return rc;
-        // the previous batch stored node l + 1 (and node l, at its own L0) from its launch of this level
-        if (prev) IMT_HIP(c, hipStreamWaitEvent(s, l >= prev->l0 ? prev->wb_done[l] : prev->done, 0));
-        pf = c->prof_begin(IMT_PROF_TOP, s);
-        launch::sweep_upper(s, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], c->d_zero + (size_t)l * 32, 0, (uint32_t)E,
-                            (uint32_t)E - 1, l == L0 ? t->d_nodes + t->h_off[l] * 32 : nullptr,
-                            t->d_nodes + t->h_off[l + 1] * 32, g_ls, g_ns, lay, l, fmt, c->coop_max_events);
-        c->prof_end(pf, s);
-        if (pipelined) IMT_HIP(c, hipEventRecord(P.wb_done[l], s));
-    }
-    if (L0 == t->depth && (rc = read_old_root())) return rc;
-    launch::emit_roots(s, P.d_val[t->depth & 1], 0, (uint32_t)E, (uint32_t)E, g_old, g_int, g_new, fmt, nullptr,
-                       L0 == t->depth ? t->d_nodes + t->h_off[t->depth] * 32 : nullptr);
     IMT_HIP(c, hipMemcpyAsync(P.d_root, t->d_nodes + t->h_off[t->depth] * 32, 32, hipMemcpyDeviceToDevice, s));
     P.has_root = true;
     IMT_HIP(c, hipEventRecord(P.done, s));
@@ -1434,6 +1451,12 @@ static int insert_core(imt_itree* t, const void* vals, size_t n, const imt_inser
             }
         }
     }
+    if (apply && apply->root_out) {
+        uint8_t* d = dev ? (uint8_t*)apply->root_out : (uint8_t*)c->dev_scratch(slot++, 32);
+        if (!d) return IMT_ERR_HIP;
+        launch::convert(s, P.d_root, d, 1, IMT_FMT_DEVICE, fmt, c->d_err);
+        if (!dev) IMT_HIP(c, hipMemcpyAsync(apply->root_out, d, 32, hipMemcpyDeviceToHost, s));
+    }
     if (out && !dev) {
         if (out->old_root) IMT_HIP(c, hipMemcpyAsync(out->old_root, g_old, n * 32, hipMemcpyDeviceToHost, s));
         if (out->interim_root) IMT_HIP(c, hipMemcpyAsync(out->interim_root, g_int, n * 32, hipMemcpyDeviceToHost, s));
@@ -1467,9 +1490,64 @@ static int insert_core(imt_itree* t, const void* vals, size_t n, const imt_inser
     return IMT_OK;
 }
 
+// The hashing of imt_itree_apply_batch on stream s, behind the preparation: the lists of every level (index work), the
+// touched leaves from their final preimages, then level by level every touched parent from the stored level below --
+// which the launch before has just made final -- and from level L0 - 1 up the single chain to the root.  The launches
+// are sized by host-side bounds; the counts stay on the device (t->d_apply_stats), so nothing here waits for the GPU.
+static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0) {
+    imt_ctx* c = t->ctx;
+    const size_t stride = P.cap_events;
+    const apply::Lists lists{P.d_nodeb, P.d_timen, t->d_apply_stats, stride};
+    auto level_nodes = [&](unsigned l) { return t->d_nodes + t->h_off[l] * 32; };
+    int pf = c->prof_begin(IMT_PROF_APPLY_LISTS, s);
+    IMT_HIP(c, prep::apply_lists(s, P.ws.tmp, P.ws.tmp_bytes, P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][3], (uint32_t)E, L0,
+                                 t->depth, P.d_from, lists));
+    c->prof_end(pf, s);
+    pf = c->prof_begin(IMT_PROF_APPLY_LEAVES, s);
+    launch::apply_leaves(s, lists.count, apply::bound((uint32_t)E, L0, 0), lists.node, lists.src, P.d_pre, IMT_FMT_CANONICAL,
+                         c->d_err, level_nodes(0), t->h_len[0], c->coop_max_events);
+    c->prof_end(pf, s);
+    for (unsigned l = 0; l + 1 < L0; l++) {
+        pf = c->prof_begin(IMT_PROF_APPLY_LEVEL, s);
+        launch::apply_level(s, lists.count + l + 1, apply::bound((uint32_t)E, L0, l + 1), lists.node + (size_t)(l + 1) * stride,
+                            level_nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, level_nodes(l + 1), t->h_len[l + 1],
+                            c->coop_max_events);
+        c->prof_end(pf, s);
+    }
+    pf = c->prof_begin(IMT_PROF_APPLY_TOP, s);
+    launch::apply_top(s, t->d_nodes, t->d_off, t->d_len, c->d_zero, L0 - 1, t->depth);
+    c->prof_end(pf, s);
+    t->apply_seen = true;
+    return IMT_OK;
+}
+
 extern "C" int imt_itree_insert_batch(imt_itree* t, const void* vals, size_t n, const imt_insert_out* out,
                                       unsigned flags) {
     return insert_core(t, vals, n, out, flags, false, n);
+}
+
+extern "C" int imt_itree_apply_batch(imt_itree* t, const void* vals, size_t n, void* root_out, unsigned flags) {
+    if (!t) return IMT_ERR_ARG;
+    if (flags & IMT_PIPELINE) return t->ctx->fail(IMT_ERR_ARG, "apply batches are not pipelined (IMT_PIPELINE)");
+    if (n == 0) {
+        IMT_NOT_SLICED(t);
+        return root_out ? imt_itree_root(t, root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS)) : IMT_OK;
+    }
+    const ApplyReq req{root_out};
+    return insert_core(t, vals, n, nullptr, flags, false, n, &req);
+}
+
+extern "C" int imt_itree_apply_stats(imt_itree* t, uint64_t* hashes) {
+    if (!t || !hashes) return IMT_ERR_ARG;
+    imt_ctx* c = t->ctx;
+    IMT_NOT_SLICED(t);
+    if (!t->apply_seen) return c->fail(IMT_ERR_ARG, "no apply call has inserted anything into this tree");
+    int rc = c->set_device();
+    if (rc) return rc;
+    // the apply call ran on the context's stream, which is therefore behind its last kernel
+    IMT_HIP(c, hipMemcpyAsync(hashes, t->d_apply_stats, (t->depth + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    IMT_HIP(c, hipStreamSynchronize(c->stream));
+    return IMT_OK;
 }
 
 // ------------------------------------------------------------------------------------
@@ -1584,15 +1662,21 @@ int host_filter(imt_itree* t, const void* vals, size_t n, unsigned flags, uint8_
 
 }  // namespace
 
-extern "C" int imt_itree_insert_filtered(imt_itree* t, const void* vals, size_t n, uint8_t* status, uint64_t* leaf_index,
-                                         uint64_t* n_inserted, const imt_insert_out* out, unsigned flags) {
+// the body of imt_itree_insert_filtered and (apply != NULL) imt_itree_apply_filtered
+static int filtered_core(imt_itree* t, const void* vals, size_t n, uint8_t* status, uint64_t* leaf_index,
+                         uint64_t* n_inserted, const imt_insert_out* out, unsigned flags, const ApplyReq* apply) {
     if (!t) return IMT_ERR_ARG;
     imt_ctx* c = t->ctx;
     IMT_NOT_SLICED(t);
     if (!status || !n_inserted) return c->fail(IMT_ERR_ARG, "null status / n_inserted");
+    if (apply && (flags & IMT_PIPELINE)) return c->fail(IMT_ERR_ARG, "apply batches are not pipelined (IMT_PIPELINE)");
+    auto unchanged_root = [&]() -> int {      // nothing inserted: an apply call still reports the root
+        if (!apply || !apply->root_out) return IMT_OK;
+        return imt_itree_root(t, apply->root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS));
+    };
     if (n == 0) {
         *n_inserted = 0;
-        return IMT_OK;
+        return unchanged_root();
     }
     if (!vals) return c->fail(IMT_ERR_ARG, "null vals");
     if ((flags & IMT_FMT_MASK) == 3) return c->fail(IMT_ERR_ARG, "unknown field-element format");
@@ -1631,9 +1715,21 @@ extern "C" int imt_itree_insert_filtered(imt_itree* t, const void* vals, size_t 
         acc = P.fw.acc;
     }
     if (rc) return rc;
-    if (n_acc && (rc = insert_core(t, acc, n_acc, out, flags, true, n))) return rc;
+    if (n_acc && (rc = insert_core(t, acc, n_acc, out, flags, true, n, apply))) return rc;
+    if (!n_acc && (rc = unchanged_root())) return rc;
     *n_inserted = n_acc;
     return IMT_OK;
+}
+
+extern "C" int imt_itree_insert_filtered(imt_itree* t, const void* vals, size_t n, uint8_t* status, uint64_t* leaf_index,
+                                         uint64_t* n_inserted, const imt_insert_out* out, unsigned flags) {
+    return filtered_core(t, vals, n, status, leaf_index, n_inserted, out, flags, nullptr);
+}
+
+extern "C" int imt_itree_apply_filtered(imt_itree* t, const void* vals, size_t n, uint8_t* status, uint64_t* leaf_index,
+                                        uint64_t* n_inserted, void* root_out, unsigned flags) {
+    const ApplyReq req{root_out};
+    return filtered_core(t, vals, n, status, leaf_index, n_inserted, nullptr, flags, &req);
 }
 
 extern "C" int imt_itree_lookup_batch(imt_itree* t, const void* vals, size_t n, uint8_t* status, uint64_t* leaf_index,

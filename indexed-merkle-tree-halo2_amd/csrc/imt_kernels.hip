@@ -932,6 +932,96 @@ k_emit_roots(const uint8_t* __restrict__ val, uint32_t e_begin, uint32_t e_count
     }
 }
 
+// -----------------------------------------------------------------------------------------------
+// Witness-free insertion (imt_apply.hpp): the hash kernel of imt_itree_apply_batch.  One hash per LISTED node, the
+// hash inlined once, the result written straight into the stored tree -- no versions, no value tables, no write-back.
+//   LEAVES  stored leaf list[j] = H(preimage of event src[j]), the last event of that leaf's run
+//   LEVEL   stored node p = list[j] of level l + 1 = hash2(stored nodes 2p, 2p + 1 of level l).  Level l is final when
+//           this runs (it was written by the launch before); a child outside the stored prefix is the empty subtree of
+//           height l, by the rule k_sweep and k_gather_proof use.
+// The launch is sized by a host-side bound; the count of the list is a device word (the call does not wait for it).
+// An apply batch runs alone on its stream (imt.h: not pipelined), so like k_tree_level this kernel owns its copy of the
+// hash body without sharing the instruction cache with another one.
+// -----------------------------------------------------------------------------------------------
+__global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_apply_level(launch::ApplyArgs a) {
+    __shared__ uint32_t stash[NL][BLOCK];
+    const size_t j = gtid();
+    if (j >= a.bound || j >= *a.count) return;
+    const uint64_t p = a.list[j];
+    if (p >= a.len_out) return;                      // never by construction: a stray index must not become a stray store
+    Fe A, B, o;
+    if (a.mode == launch::APPLY_LEAVES) {
+        const uint8_t* q = a.pre + (size_t)a.src[j] * 96;
+        Fe C;
+        bool ok = load_fe(g_pc, A, q, a.fmt_in);
+        ok &= load_fe(g_pc, B, q + 32, a.fmt_in);
+        ok &= load_fe(g_pc, C, q + 64, a.fmt_in);
+#pragma unroll
+        for (int i = 0; i < NL; i++) stash[i][threadIdx.x] = C.v[i];
+        flag_err(a.err, ok);
+    } else {
+        const uint64_t c0 = 2 * p, c1 = 2 * p + 1;
+        load_packed(A, c0 < a.len_in ? a.tree_in + c0 * 32 : a.zero_in);
+        load_packed(B, c1 < a.len_in ? a.tree_in + c1 * 32 : a.zero_in);
+    }
+    hash23_stashed(g_pc, o, A, B, a.mode == launch::APPLY_LEAVES, &stash[0][threadIdx.x], BLOCK);
+    store_packed(a.tree_out + p * 32, o);
+}
+
+// The same for levels with few nodes -- near the root, or every level of a small batch: a quad of lanes per node
+// (imt_coop_device.hpp).  Those launches are one hash's latency each and most of an apply batch's floor.
+__global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_apply_level_coop(launch::ApplyArgs a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ uint32_t tab[coop::TAB_DWORDS];
+    coop::tab_fill(tab, g_pc);                       // before anyone leaves: it ends in a barrier
+    const size_t t = gtid();
+    const size_t j = t >> 2;
+    if (j >= a.bound || j >= *a.count) return;       // whole quads leave together
+    const unsigned role = (unsigned)t & 3u, ri = role == 3u ? 0u : role;
+    const uint64_t p = a.list[j];
+    if (p >= a.len_out) return;
+    Fe X, C3, o;
+    C3 = g_pc.one;                                   // any value: only read for LEAVES
+    if (a.mode == launch::APPLY_LEAVES) {
+        const uint8_t* q = a.pre + (size_t)a.src[j] * 96;
+        bool ok = load_fe(g_pc, X, q + (ri == 2u ? 32 : 0), a.fmt_in);     // lane 1: val, lane 2: next_val
+        ok &= load_fe(g_pc, C3, q + 64, a.fmt_in);                         // next_idx, absorbed by lane 1
+        if (ri == 1u) ok &= load_fe(g_pc, o, q + 32, a.fmt_in);            // (every element validated once)
+        flag_err(a.err, ok);
+    } else {
+        const uint64_t ch = 2 * p + (ri == 2u ? 1u : 0u);                  // lane 1: left child, lane 2: right child
+        load_packed(X, ch < a.len_in ? a.tree_in + ch * 32 : a.zero_in);
+    }
+    coop::hash23(tab, o, X, C3, a.mode == launch::APPLY_LEAVES, ri);
+    if (role == 1u) store_packed(a.tree_out + p * 32, o);
+#endif
+}
+
+// Levels [from, to), from = l0 - 1: the batch's only node of every level above is node 0.  Its right sibling is stored
+// node 1 at level l0 - 1 (the other half of the occupied tree) and the empty subtree of that height from l0 up.  A chain
+// of dependent hashes, so one quad runs it (k_zero_chain is the model); every link goes to the stored tree, the last one
+// is the root.
+__global__ IMT_HASH_WAVES void k_apply_top(uint8_t* nodes, const uint64_t* __restrict__ off, const uint64_t* __restrict__ len,
+                                           const uint8_t* __restrict__ zero, unsigned from, unsigned to) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ uint32_t tab[coop::TAB_DWORDS];
+    coop::tab_fill(tab, g_pc);
+    if (blockIdx.x != 0 || threadIdx.x >= 4) return;
+    const unsigned role = threadIdx.x, ri = role == 3u ? 0u : role;
+    Fe cur;
+    load_packed(cur, nodes + off[from] * 32);
+#pragma unroll 1
+    for (unsigned l = from; l < to; l++) {
+        Fe z, X, o;
+        load_packed(z, l == from && len[l] > 1 ? nodes + (off[l] + 1) * 32 : zero + (size_t)l * 32);
+        coop::sel(X, ri == 2u, z, cur);              // lane 1: node 0, lane 2: its right sibling
+        coop::hash23(tab, o, X, X, false, ri);
+        coop::quad_bcast<1>(cur, o);
+        if (role == 1u) store_packed(nodes + off[l + 1] * 32, cur);
+    }
+#endif
+}
+
 // ---- subtree placement (imt_itree_lift_batch) ---------------------------------------------------
 // A tree placed as subtree g of a deeper tree produces subtree-level roots; the enclosing tree's root
 // after the same event is `levels` more hash2 up a path whose siblings are the same for the whole batch.
@@ -1375,6 +1465,35 @@ void sweep_upper(hipStream_t s, const uint8_t* val_in, uint8_t* val_out, const u
     a.low_sib = low_sib; a.new_sib = new_sib; a.lay = lay; a.fmt_out = fmt_out;
     a.last_event = last_event; a.node_in = node_in; a.node_out = node_out;
     launch_sweep(s, a, coop_max);
+}
+// one thread per listed node, or -- while the launch is small enough to leave most SIMDs idle -- one quad per node
+static void launch_apply(hipStream_t s, const ApplyArgs& a, uint32_t coop_max) {
+    if (!a.bound) return;
+    if (a.bound <= coop_max)
+        hipLaunchKernelGGL(k_apply_level_coop, dim3(nblk((size_t)a.bound * 4)), dim3(BLOCK), 0, s, a);
+    else
+        hipLaunchKernelGGL(k_apply_level, dim3(nblk(a.bound)), dim3(BLOCK), 0, s, a);
+}
+void apply_leaves(hipStream_t s, const uint64_t* count, uint32_t bound, const uint32_t* list, const uint32_t* src,
+                  const uint8_t* pre, unsigned fmt_in, int* err, uint8_t* tree0, uint64_t len0, uint32_t coop_max) {
+    ApplyArgs a{};
+    a.mode = APPLY_LEAVES;
+    a.count = count; a.bound = bound; a.list = list; a.tree_out = tree0; a.len_out = len0;
+    a.src = src; a.pre = pre; a.fmt_in = fmt_in; a.err = err;
+    launch_apply(s, a, coop_max);
+}
+void apply_level(hipStream_t s, const uint64_t* count, uint32_t bound, const uint32_t* list, const uint8_t* tree_in,
+                 uint64_t len_in, const uint8_t* zero_in, uint8_t* tree_out, uint64_t len_out, uint32_t coop_max) {
+    ApplyArgs a{};
+    a.mode = APPLY_LEVEL;
+    a.count = count; a.bound = bound; a.list = list; a.tree_out = tree_out; a.len_out = len_out;
+    a.tree_in = tree_in; a.len_in = len_in; a.zero_in = zero_in;
+    launch_apply(s, a, coop_max);
+}
+void apply_top(hipStream_t s, uint8_t* nodes, const uint64_t* off, const uint64_t* len, const uint8_t* zero, unsigned from,
+               unsigned to) {
+    if (from >= to) return;
+    hipLaunchKernelGGL(k_apply_top, dim3(1), dim3(64), 0, s, nodes, off, len, zero, from, to);
 }
 void emit_roots(hipStream_t s, const uint8_t* val, uint32_t e_begin, uint32_t e_count, uint32_t total, uint8_t* old_root,
                 uint8_t* interim_root, uint8_t* new_root, unsigned fmt_out, uint8_t* roots_dev, uint8_t* node_store) {

@@ -170,6 +170,36 @@ void sweep_upper(hipStream_t s, const uint8_t* val_in, uint8_t* val_out, const u
 void emit_roots(hipStream_t s, const uint8_t* val, uint32_t e_begin, uint32_t e_count, uint32_t total, uint8_t* old_root,
                 uint8_t* interim_root, uint8_t* new_root, unsigned fmt_out, uint8_t* roots_dev, uint8_t* node_store);
 
+// ---- witness-free batch insertion (imt_apply.hpp): one hash per touched node, straight into the stored tree ----
+// argument block of k_apply_level.  The launch is sized by `bound`; the number of listed nodes is read on the device.
+enum : int { APPLY_LEAVES = 0, APPLY_LEVEL = 1 };
+struct ApplyArgs {
+    int mode;
+    const uint64_t* count;                // device word: listed nodes (<= bound)
+    uint32_t bound;
+    const uint32_t* list;                 // [count] nodes of the level that is written, ascending
+    uint8_t* tree_out;                    // that stored level (device format) and its length
+    uint64_t len_out;
+    // LEAVES: node list[j] = H(preimage of event src[j])
+    const uint32_t* src;
+    const uint8_t* pre;
+    unsigned fmt_in;
+    int* err;
+    // LEVEL: node p = hash2(children 2p, 2p + 1 of the stored level below; outside its prefix: zero_in)
+    const uint8_t* tree_in;
+    uint64_t len_in;
+    const uint8_t* zero_in;
+};
+// coop_max as for the sweep: a launch of at most that many nodes (by its bound) takes the quad form
+void apply_leaves(hipStream_t s, const uint64_t* count, uint32_t bound, const uint32_t* list, const uint32_t* src,
+                  const uint8_t* pre, unsigned fmt_in, int* err, uint8_t* tree0, uint64_t len0, uint32_t coop_max);
+void apply_level(hipStream_t s, const uint64_t* count, uint32_t bound, const uint32_t* list, const uint8_t* tree_in,
+                 uint64_t len_in, const uint8_t* zero_in, uint8_t* tree_out, uint64_t len_out, uint32_t coop_max);
+// levels [from, to), from = l0 - 1: stored node 0 of level l + 1 = hash2(stored node 0 of level l, its right sibling):
+// stored node 1 at level `from`, zero[l] above.  off / len: the tree's device arrays.  One quad.
+void apply_top(hipStream_t s, uint8_t* nodes, const uint64_t* off, const uint64_t* len, const uint8_t* zero, unsigned from,
+               unsigned to);
+
 // ---- subtree placement: lift subtree-level witnesses to the depth of the enclosing tree ----
 // top[j] (device format, j < levels) = sibling of this subtree's ancestor at height sub_depth + j;
 // bit j of pos_bits = that ancestor is a RIGHT child.  Roots are lifted in place (format fmt):

@@ -320,7 +320,50 @@ int levels_for(uint32_t n) {
     return k;   // table rows 0 .. k-1, 2^(k-1) <= n
 }
 
+// ---- the lists of imt_itree_apply_batch (imt_apply.hpp) ----
+struct HeadFlag {
+    const uint32_t* node;
+    unsigned l;
+    __device__ uint32_t operator()(uint32_t x) const { return apply::head(node, x, l); }
+};
+typedef rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, HeadFlag, uint32_t> HeadIter;
+inline HeadIter head_iter(const uint32_t* node, unsigned l) {
+    return HeadIter(rocprim::counting_iterator<uint32_t>(0), HeadFlag{node, l});
+}
+size_t apply_scan_bytes(size_t total) {
+    size_t a = 0;
+    (void)rocprim::exclusive_scan(nullptr, a, head_iter(nullptr, 0), (uint32_t*)nullptr, 0u, total, rocprim::plus<uint32_t>(),
+                                  nullptr);
+    return a;
+}
+// blockIdx.y = level: every slot of every level in one launch
+__global__ void __launch_bounds__(BLOCK) k_apply_scatter(const uint32_t* __restrict__ node, const uint32_t* __restrict__ time,
+                                                         const uint32_t* __restrict__ re, uint32_t total, unsigned l0,
+                                                         unsigned depth, const uint32_t* __restrict__ pos, apply::Lists o) {
+    const uint32_t x = blockIdx.x * BLOCK + threadIdx.x;
+    if (x >= total) return;
+    const unsigned l = blockIdx.y;
+    apply::scatter_element(node, time, re, total, x, l, pos[(size_t)l * o.stride + x], l0, depth, o);
+}
+
 }  // namespace
+
+hipError_t apply_lists(hipStream_t s, void* tmp, size_t tmp_bytes, const uint32_t* node, const uint32_t* time,
+                       const uint32_t* re, uint32_t total, unsigned l0, unsigned depth, uint32_t* pos,
+                       const apply::Lists& lists) {
+    hipError_t e;
+    if (total == 0 || l0 == 0 || l0 > 31 || l0 > depth || total > lists.stride || apply_scan_bytes(total) > tmp_bytes)
+        return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    for (unsigned l = 0; l < l0; l++) {
+        size_t tb = tmp_bytes;
+        if ((e = rocprim::exclusive_scan(tmp, tb, head_iter(node, l), pos + (size_t)l * lists.stride, 0u, (size_t)total,
+                                         rocprim::plus<uint32_t>(), s)) != hipSuccess)
+            return e;
+    }
+    hipLaunchKernelGGL(k_apply_scatter, dim3(nblk(total), l0), dim3(BLOCK), 0, s, node, time, re, total, l0, depth, pos, lists);
+    return hipGetLastError();
+}
 
 size_t temp_bytes_needed(size_t n, size_t max_size) {
     size_t a = 0, b = 0, c = 0;
@@ -328,8 +371,10 @@ size_t temp_bytes_needed(size_t n, size_t max_size) {
     (void)rocprim::merge(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, max_size, n,
                          ValLess{nullptr}, nullptr);
     (void)rocprim::radix_sort_keys(nullptr, c, (uint64_t*)nullptr, (uint64_t*)nullptr, 2 * n, 0, 64, nullptr);
+    const size_t d = apply_scan_bytes(2 * n);       // the scans of apply_lists run over the 2n events
     size_t m = a > b ? a : b;
-    return (m > c ? m : c) + 256;
+    m = m > c ? m : c;
+    return (m > d ? m : d) + 256;
 }
 
 hipError_t run(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t* d_val, const uint32_t* sorted_old,

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime_api.h>
 #include <cstddef>
 #include <cstdint>
+#include "imt_apply.hpp"
 
 namespace imt {
 namespace prep {
@@ -71,6 +72,13 @@ hipError_t run(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t* d_val
 // only iota / bsorted / gap / st[n] / tmp / err of the workspace.
 hipError_t index_only(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t* d_val, const uint32_t* sorted_old,
                       uint32_t* sorted_new, uint32_t M, uint32_t n);
+
+// ---- witness-free insertion (imt_itree_apply_batch): the touched nodes of every level (imt_apply.hpp) ----
+// From the level-0 tables run() left ([total] each): lists.node rows 0 .. l0-1, lists.src and lists.count[0 .. depth].
+// pos = [l0][lists.stride] scratch for the scans; tmp as in the workspace (temp_bytes_needed covers it).
+hipError_t apply_lists(hipStream_t s, void* tmp, size_t tmp_bytes, const uint32_t* node, const uint32_t* time,
+                       const uint32_t* re, uint32_t total, unsigned l0, unsigned depth, uint32_t* pos,
+                       const apply::Lists& lists);
 
 // ---- filtered insertion (imt_itree_insert_filtered): which values of a batch are inserted ----
 struct FilterWs {             // per plan set, sized for `cap_n` values
