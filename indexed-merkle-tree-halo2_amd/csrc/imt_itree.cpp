@@ -112,6 +112,16 @@ struct PlanSet {
     unsigned slice_next_unit = 0;
     uint64_t slice_size_before = 0;      // leaves in the tree before this slice (its own first new leaf)
     launch::SibLayout slice_lay = {0, 0};
+    // row l of the per-level tables: written by the index phase, read by the sweep and the write-back of level l
+    struct Level {
+        uint32_t* from;
+        int32_t* sibsrc;
+        uint32_t *nodeb, *timen;
+    };
+    Level level(unsigned l) const {
+        const size_t o = (size_t)l * cap_events;
+        return {d_from + o, d_sibsrc + o, d_nodeb + o, d_timen + o};
+    }
 };
 
 }  // namespace
@@ -130,6 +140,7 @@ struct imt_itree {
     uint8_t* d_nodes = nullptr;
     uint64_t* d_off = nullptr;
     uint64_t* d_len = nullptr;
+    uint8_t* nodes(unsigned l) const { return d_nodes + h_off[l] * 32; }   // stored level l (h_len[l] nodes, device format)
     std::vector<Pre> pre;            // host mirror of the leaf preimages
     std::vector<SortedEnt> sorted;   // leaves ordered by val
     // device-resident index (default prepare path): values in leaf order + leaf indices in value order.
@@ -404,7 +415,7 @@ extern "C" int imt_itree_new(imt_ctx* c, unsigned depth, uint64_t capacity, imt_
         return c->hip_fail(e, "imt_itree_new init copies");
     }
     for (unsigned l = 0; l <= depth; l++)   // every stored node starts as the empty subtree of its height
-        launch::fill_level(c->stream, t->d_nodes + t->h_off[l] * 32, t->h_len[l], c->d_zero + (size_t)l * 32);
+        launch::fill_level(c->stream, t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32);
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) {
         imt_itree_free(t);
         return c->hip_fail(e, "imt_itree_new init");
@@ -484,6 +495,135 @@ static int ensure_device_index(imt_itree* t) {
     return IMT_OK;
 }
 
+// ------------------------------------------------------------------------------------
+// The stages the ways into the tree are built from.  A batch enters through imt_itree_insert_batch / _apply_batch,
+// through _insert_filtered / _apply_filtered, through _batch_begin (sharded) or through _slice_prepare + _slice_unit
+// (sliced); each of those is a sequence of the stages below and of what is its own.  None of the stages asks who calls.
+// ------------------------------------------------------------------------------------
+struct HostTimer {      // host milliseconds since it was made
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// A host wait with a time limit (limit_ms <= 0: wait as long as it takes): the sliced mode's waits stand behind work
+// that stands behind collectives, i.e. behind other ranks -- a peer that died would otherwise hang the caller for good.
+// IMT_ERR_TIMEOUT leaves the stream as it is (still busy); the caller gives the world up.
+template <class Query, class Sync>
+static int bounded_wait(imt_ctx* c, double limit_ms, Query query, Sync sync, const char* what) {
+    if (limit_ms <= 0) {
+        const hipError_t e = sync();
+        return e == hipSuccess ? IMT_OK : c->hip_fail(e, what);
+    }
+    const HostTimer waited;
+    for (unsigned spins = 0;; spins++) {
+        const hipError_t e = query();
+        if (e == hipSuccess) return IMT_OK;
+        if (e != hipErrorNotReady) return c->hip_fail(e, what);
+        if (spins > 2000) std::this_thread::sleep_for(std::chrono::microseconds(50));     // ~0.1 ms of pure polling first
+        if ((spins & 63) == 63 && waited.ms() > limit_ms)
+            return c->fail(IMT_ERR_TIMEOUT, "gave up after %.0f ms waiting for %s", limit_ms, what);
+    }
+}
+
+// The refusals the batch entries share, in the order imt_itree_insert_batch has always made them, then the device.
+// What one entry alone refuses, or refuses in other words or at another point of its own order, stays with that entry.
+static int check_batch_call(imt_itree* t, size_t n, unsigned flags) {
+    imt_ctx* c = t->ctx;
+    if ((flags & IMT_FMT_MASK) == 3) return c->fail(IMT_ERR_ARG, "unknown field-element format");
+    if (n > ((size_t)1 << 30)) return c->fail(IMT_ERR_RANGE, "batch too large");
+    if (t->pending.active) return c->fail(IMT_ERR_ARG, "a sharded batch is open (imt_itree_batch_end first)");
+    if (slice_open(t)) return c->fail(IMT_ERR_ARG, "a slice is open (issue its remaining units first)");
+    return c->set_device();
+}
+static int check_room(imt_itree* t, size_t n) {
+    if (t->size + n > t->cap) return t->ctx->fail(IMT_ERR_FULL, "tree capacity %llu exceeded", (unsigned long long)t->cap);
+    return IMT_OK;
+}
+
+// The plan set of the next batch (t->plan[t->cur]): wait until the batch that used it last has left the GPU --
+// back-pressure, at most NSETS batches in flight; limit_ms as in bounded_wait -- then make it large enough, all levels
+// up front: growing later would stall the pipeline.  The time waited is added to waited_ms, also when the wait fails;
+// which counters it belongs in is the caller's business.
+static int acquire_plan(imt_itree* t, size_t events, double limit_ms, double& waited_ms) {
+    imt_ctx* c = t->ctx;
+    PlanSet& P = t->plan[t->cur];
+    if (P.in_flight) {
+        const HostTimer w;
+        const int rc = bounded_wait(c, limit_ms, [&] { return hipEventQuery(P.done); }, [&] { return hipEventSynchronize(P.done); },
+                                    "the plan set's previous batch or slice");
+        waited_ms += w.ms();
+        if (rc) return rc;
+        P.in_flight = false;
+    }
+    return plan_reserve(c, P, events, t->depth, t->cap);
+}
+
+// The hash-free part of a batch runs on a side stream, reads the caller's `vals` and writes the caller's hash-free
+// outputs (low_index, is_largest, low_leaf, new_leaf), so with device pointers that stream is first ordered behind
+// everything the caller has enqueued on the context's stream (imt.h: "work is enqueued on the context's stream").
+// IMT_INPUTS_READY waives that: the caller guarantees those buffers are idle.
+// (Host-pointer calls are ordered too: their staging scratch may still be read by an asynchronous
+// device-pointer call, e.g. imt_itree_lift_batch, enqueued earlier on the context's stream.)
+static int order_behind_caller(imt_itree* t, hipStream_t side, unsigned flags) {
+    imt_ctx* c = t->ctx;
+    if ((flags & IMT_DEVICE_PTRS) && (flags & IMT_INPUTS_READY)) return IMT_OK;
+    IMT_HIP(c, hipEventRecord(t->in_mark, c->stream));
+    IMT_HIP(c, hipStreamWaitEvent(side, t->in_mark, 0));
+    return IMT_OK;
+}
+
+// n values, wherever `flags` says they are and in whatever format, to canonical device memory on stream s: the error
+// word cleared, host values copied to `up`, any other format converted into `canon` (a value >= p sets bit 0 of the
+// error word; `up` and `canon` may be one buffer, the conversion works in place).  *d_vals is where they end up -- `vals`
+// itself when they were canonical device values all along.  The buffers are the caller's choice and encode on which
+// stream they are safe: a buffer that is not needed may be NULL, a NULL that is needed is a scratch slot that could not
+// be had.
+static int stage_canonical(imt_ctx* c, hipStream_t s, const void* vals, size_t n, unsigned flags, uint8_t* up, uint8_t* canon,
+                           int* d_err, const uint8_t** d_vals) {
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    if ((!dev && !up) || (fmt != IMT_FMT_CANONICAL && !canon)) return IMT_ERR_HIP;
+    const uint8_t* d = (const uint8_t*)vals;
+    IMT_HIP(c, hipMemsetAsync(d_err, 0, sizeof(int), s));
+    if (!dev) {
+        IMT_HIP(c, hipMemcpyAsync(up, vals, n * 32, hipMemcpyHostToDevice, s));
+        d = up;
+    }
+    if (fmt != IMT_FMT_CANONICAL) {
+        launch::convert(s, d, canon, n, fmt, IMT_FMT_CANONICAL, d_err);
+        d = canon;
+    }
+    *d_vals = d;
+    return IMT_OK;
+}
+
+// What the prepare kernels (prep::run) found wrong with the values, as the call's result; `noun`: a batch or a step
+static int insertion_verdict(imt_itree* t, int perr, const char* noun) {
+    imt_ctx* c = t->ctx;
+    if (perr & prep::ERR_NONCANONICAL) return c->fail(IMT_ERR_NONCANONICAL, "a value is not reduced (>= p)");
+    if (perr & prep::ERR_ZERO) return c->fail(IMT_ERR_VALUE, "value 0 cannot be inserted");
+    if (perr & prep::ERR_FOREIGN)
+        return c->fail(IMT_ERR_VALUE, "a value belongs to another subtree (v %% %u != %u)", t->part_mod, t->part_res);
+    if (perr & prep::ERR_DUPLICATE)
+        return c->fail(IMT_ERR_VALUE, "duplicate value (inside the %s or already in the tree)", noun);
+    return IMT_OK;
+}
+
+// The index phase (no hashing): from the prepared level-0 table in P.d_tab[0] the tables of every level below L0, the
+// two table sets taking turns.  slots: NULL, or [levels + 1][cap_events] for the slot of every event per level.
+static void index_phase(const PlanSet& P, hipStream_t s, size_t E, unsigned L0, uint32_t* slots) {
+    for (unsigned l = 0; l < L0; l++) {
+        const int a = l & 1, b = a ^ 1;
+        const PlanSet::Level row = P.level(l);
+        // time table of level l: the prepared one for l = 0, otherwise row l - 1 of d_timen
+        const uint32_t* time_in = l == 0 ? P.d_tab[0][1] : P.level(l - 1).timen;
+        sweep::LevelTable in{P.d_tab[a][0], time_in, P.d_tab[a][2], P.d_tab[a][3]};
+        sweep::LevelOut o{P.d_tab[b][0], row.timen, P.d_tab[b][2], P.d_tab[b][3], row.from, row.sibsrc, row.nodeb,
+                          slots ? slots + (size_t)(l + 1) * P.cap_events : nullptr};
+        launch::merge_level(s, in, o, (uint32_t)E);
+    }
+}
+
 extern "C" uint64_t imt_itree_size(const imt_itree* t) { return t ? t->size : 0; }
 // internal (imt_itree_internal.hpp): what imt_sliced.cpp needs to know about a tree
 imt_ctx* imt_itree_ctx(const imt_itree* t) { return t ? t->ctx : nullptr; }
@@ -530,7 +670,7 @@ extern "C" int imt_itree_root(imt_itree* t, void* root, unsigned flags) {
     if ((rc = check_fe_ptrs(c, flags & IMT_DEVICE_PTRS, {root}))) return rc;
     if ((rc = join_top(t))) return rc;
     const unsigned fmt = flags & IMT_FMT_MASK;
-    const uint8_t* src = t->d_nodes + t->h_off[t->depth] * 32;
+    const uint8_t* src = t->nodes(t->depth);
     if (flags & IMT_DEVICE_PTRS) {
         launch::convert(c->stream, src, (uint8_t*)root, 1, IMT_FMT_DEVICE, fmt, c->d_err);
         return IMT_OK;
@@ -641,17 +781,11 @@ extern "C" int imt_itree_find_low_batch(imt_itree* t, const void* vals, size_t n
         if ((rc = join_top(t))) return rc;
         hipStream_t s = c->stream;
         IMT_HIP(c, hipStreamSynchronize(t->up_stream));
-        const uint8_t* d_vals = (const uint8_t*)vals;
+        const uint8_t* d_vals = nullptr;
         int* d_perr = (int*)c->dev_scratch(2, sizeof(int));
         if (!d_perr) return IMT_ERR_HIP;
-        IMT_HIP(c, hipMemsetAsync(d_perr, 0, sizeof(int), s));
-        if (!dev || fmt != IMT_FMT_CANONICAL) {
-            uint8_t* buf = (uint8_t*)c->dev_scratch(0, n * 32);
-            if (!buf) return IMT_ERR_HIP;
-            if (!dev) IMT_HIP(c, hipMemcpyAsync(buf, vals, n * 32, hipMemcpyHostToDevice, s));
-            if (fmt != IMT_FMT_CANONICAL) launch::convert(s, dev ? d_vals : buf, buf, n, fmt, IMT_FMT_CANONICAL, d_perr);
-            d_vals = buf;
-        }
+        uint8_t* buf = (!dev || fmt != IMT_FMT_CANONICAL) ? (uint8_t*)c->dev_scratch(0, n * 32) : nullptr;
+        if ((rc = stage_canonical(c, s, vals, n, flags, buf, buf, d_perr, &d_vals))) return rc;
         uint64_t* d_low = dev ? low_index : (uint64_t*)c->dev_scratch(1, n * 8);
         if (!d_low) return IMT_ERR_HIP;
         prep::find_low(s, d_vals, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)t->size, (uint32_t)n, t->index_base,
@@ -810,22 +944,12 @@ extern "C" int imt_itree_non_membership_witness(imt_itree* t, const void* vals, 
     IMT_HIP(c, hipStreamSynchronize(t->up_stream));     // the index may have been written on the side stream
     size_t slot = 0;
     auto scratch = [&](size_t bytes) { return (uint8_t*)c->dev_scratch(slot++, bytes); };
-    const uint8_t* d_vals = (const uint8_t*)vals;
-    if (!dev) {
-        uint8_t* up = scratch(n * 32);
-        if (!up) return IMT_ERR_HIP;
-        IMT_HIP(c, hipMemcpyAsync(up, vals, n * 32, hipMemcpyHostToDevice, s));
-        d_vals = up;
-    }
+    const uint8_t* d_vals = nullptr;
+    uint8_t* up = dev ? nullptr : scratch(n * 32);
     int* d_perr = (int*)scratch(sizeof(int));
     if (!d_perr) return IMT_ERR_HIP;
-    IMT_HIP(c, hipMemsetAsync(d_perr, 0, sizeof(int), s));
-    if (fmt != IMT_FMT_CANONICAL) {
-        uint8_t* can = scratch(n * 32);
-        if (!can) return IMT_ERR_HIP;
-        launch::convert(s, d_vals, can, n, fmt, IMT_FMT_CANONICAL, d_perr);
-        d_vals = can;
-    }
+    uint8_t* can = fmt == IMT_FMT_CANONICAL ? nullptr : scratch(n * 32);
+    if ((rc = stage_canonical(c, s, vals, n, flags, up, can, d_perr, &d_vals))) return rc;
     auto outbuf = [&](void* user, size_t bytes) -> uint8_t* {
         if (!user) return nullptr;
         return dev ? (uint8_t*)user : scratch(bytes);
@@ -937,17 +1061,16 @@ extern "C" int imt_itree_load(imt_itree* t, const void* preimages, uint64_t n, u
     prep::load_commit(s, d_pre, (uint32_t)n, t->d_val);
     IMT_HIP(c, hipMemcpyAsync(t->d_sorted[t->sorted_cur], d_order, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     for (unsigned l = 0; l <= t->depth; l++)
-        launch::fill_level(s, t->d_nodes + t->h_off[l] * 32, t->h_len[l], c->d_zero + (size_t)l * 32);
+        launch::fill_level(s, t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32);
     launch::hash_batch(s, d_pre, t->d_nodes, (size_t)n, 3, IMT_FMT_CANONICAL, IMT_FMT_DEVICE, c->d_err);
     uint64_t filled = n;
     for (unsigned l = 0; l < t->depth; l++) {
         const uint64_t parents = (filled + 1) / 2;
         if (t->h_len[l] >= 2) {
-            launch::tree_level(s, t->d_nodes + t->h_off[l] * 32, t->d_nodes + t->h_off[l + 1] * 32, parents);
+            launch::tree_level(s, t->nodes(l), t->nodes(l + 1), parents);
         } else {   // a single stored node: its sibling is the empty subtree of this height
-            IMT_HIP(c, hipMemcpyAsync(t->d_nodes + t->h_off[l + 1] * 32, t->d_nodes + t->h_off[l] * 32, 32,
-                                      hipMemcpyDeviceToDevice, s));
-            launch::extend_root(s, t->d_nodes + t->h_off[l + 1] * 32, c->d_zero, l, l + 1);
+            IMT_HIP(c, hipMemcpyAsync(t->nodes(l + 1), t->nodes(l), 32, hipMemcpyDeviceToDevice, s));
+            launch::extend_root(s, t->nodes(l + 1), c->d_zero, l, l + 1);
         }
         filled = parents;
     }
@@ -1152,140 +1275,258 @@ void host_commit(imt_itree* t, const HostPlan& hp, size_t n) {
     t->size = M + n;
 }
 
-// GPU prepare (default): the same on the device (imt_prep.hip), on the side stream.  The hash-free
-// outputs go straight to device buffers (the user's, or scratch in host-pointer mode).  The batch is
-// committed to the device index only if its values are acceptable.  vals_ready: `vals` are canonical device values
-// already on the side stream (the accepted values of imt_itree_insert_filtered): no upload, no conversion.
-struct GpuOuts {
-    uint64_t* low = nullptr;
-    uint8_t *largest = nullptr, *lowleaf = nullptr, *newleaf = nullptr;
-};
-int gpu_prepare(imt_itree* t, PlanSet& P, const void* vals, size_t n, unsigned flags, const imt_insert_out* out,
-                size_t& slot, GpuOuts& go, double& wait_ms, bool vals_ready) {
+// Where the kernels write an output the caller asked for: the caller's own array with device pointers, otherwise the
+// context's next scratch slot, copied back at the end of the call.  False: that scratch could not be had.
+template <class T>
+bool stage_out(imt_ctx* c, bool dev, size_t& slot, T* user, size_t bytes, T*& d) {
+    d = !user ? nullptr : dev ? user : (T*)c->dev_scratch(slot++, bytes);
+    return !user || d;
+}
+
+// GPU prepare (default): the same on the device (imt_prep.hip), on the side stream.  `val_flags` say where the values
+// are and in which format, `dev` where the outputs go.  The hash-free outputs go straight to device buffers (the user's,
+// or scratch in host-pointer mode), noted in `d`.  The batch is committed to the device index only if its values are
+// acceptable.
+int gpu_prepare(imt_itree* t, PlanSet& P, const void* vals, unsigned val_flags, size_t n, const imt_insert_out* out, bool dev,
+                size_t& slot, imt_insert_out& d, double& wait_ms) {
     imt_ctx* c = t->ctx;
-    const bool dev = flags & IMT_DEVICE_PTRS;
-    const unsigned fmt = flags & IMT_FMT_MASK;
     int rc = ensure_device_index(t);
     if (rc) return rc;
     hipStream_t ps = t->up_stream;
-    const uint8_t* d_vals = (const uint8_t*)vals;
-    if (!dev && !vals_ready) {
-        uint8_t* up = (uint8_t*)c->dev_scratch(slot++, n * 32);
-        if (!up) return IMT_ERR_HIP;
-        IMT_HIP(c, hipMemcpyAsync(up, vals, n * 32, hipMemcpyHostToDevice, ps));
-        d_vals = up;
-    }
-    IMT_HIP(c, hipMemsetAsync(P.ws.err, 0, sizeof(int), ps));
-    if (fmt != IMT_FMT_CANONICAL && !vals_ready) {
-        // the plan's own buffer, not context scratch: this runs on the side stream, which IMT_INPUTS_READY leaves
-        // unordered behind the context's stream, where an earlier asynchronous call (imt_itree_lift_batch,
-        // imt_insert_trace_batch) may still be using the context's scratch slots
-        launch::convert(ps, d_vals, P.d_canon, n, fmt, IMT_FMT_CANONICAL, P.ws.err);   // sets bit 0 = non-canonical
-        d_vals = P.d_canon;
-    }
-    if (out) {
-        auto dev_out = [&](void* user, size_t bytes) -> void* {
-            if (!user) return nullptr;
-            return dev ? user : c->dev_scratch(slot++, bytes);
-        };
-        go.low = (uint64_t*)dev_out(out->low_index, n * 8);
-        go.largest = (uint8_t*)dev_out(out->is_largest, n);
-        go.lowleaf = (uint8_t*)dev_out(out->low_leaf, n * 96);
-        go.newleaf = (uint8_t*)dev_out(out->new_leaf, n * 96);
-        if ((out->low_index && !go.low) || (out->is_largest && !go.largest) || (out->low_leaf && !go.lowleaf) ||
-            (out->new_leaf && !go.newleaf))
-            return IMT_ERR_HIP;
-    }
+    const uint8_t* d_vals = nullptr;
+    uint8_t* up = (val_flags & IMT_DEVICE_PTRS) ? nullptr : (uint8_t*)c->dev_scratch(slot++, n * 32);
+    // converted into the plan's own buffer, not context scratch: this runs on the side stream, which IMT_INPUTS_READY
+    // leaves unordered behind the context's stream, where an earlier asynchronous call (imt_itree_lift_batch,
+    // imt_insert_trace_batch) may still be using the context's scratch slots
+    if ((rc = stage_canonical(c, ps, vals, n, val_flags, up, P.d_canon, P.ws.err, &d_vals))) return rc;
+    if (out && (!stage_out(c, dev, slot, out->low_index, n * 8, d.low_index) ||
+                !stage_out(c, dev, slot, out->is_largest, n, d.is_largest) ||
+                !stage_out(c, dev, slot, out->low_leaf, n * 96, d.low_leaf) ||
+                !stage_out(c, dev, slot, out->new_leaf, n * 96, d.new_leaf)))
+        return IMT_ERR_HIP;
     P.ws.part_mod = t->part_mod;
     P.ws.part_res = t->part_res;
     IMT_HIP(c, prep::run(ps, P.ws, d_vals, t->d_val, t->d_sorted[t->sorted_cur], t->d_sorted[t->sorted_cur ^ 1],
                          (uint32_t)t->size, (uint32_t)n, t->index_base, P.d_pre, P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][2],
-                         P.d_tab[0][3], go.low, go.largest, go.lowleaf, go.newleaf));
+                         P.d_tab[0][3], d.low_index, d.is_largest, (uint8_t*)d.low_leaf, (uint8_t*)d.new_leaf));
     IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, ps));
-    const auto w0 = std::chrono::steady_clock::now();
+    const HostTimer w;
     IMT_HIP(c, hipStreamSynchronize(ps));
-    wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-    const int perr = *t->h_err_pin;
-    if (perr & prep::ERR_NONCANONICAL) return c->fail(IMT_ERR_NONCANONICAL, "a value is not reduced (>= p)");
-    if (perr & prep::ERR_ZERO) return c->fail(IMT_ERR_VALUE, "value 0 cannot be inserted");
-    if (perr & prep::ERR_FOREIGN)
-        return c->fail(IMT_ERR_VALUE, "a value belongs to another subtree (v %% %u != %u)", t->part_mod, t->part_res);
-    if (perr & prep::ERR_DUPLICATE)
-        return c->fail(IMT_ERR_VALUE, "duplicate value (inside the batch or already in the tree)");
-    return IMT_OK;     // the merged index sits in d_sorted[sorted_cur ^ 1]; the caller flips when it commits
+    wait_ms += w.ms();
+    // accepted: the merged index sits in d_sorted[sorted_cur ^ 1]; the caller flips when it commits
+    return insertion_verdict(t, *t->h_err_pin, "batch");
+}
+
+// ---- one step each of the witness schedule on stream s, with its profile brackets.  `d` holds the device pointers of
+// the outputs (NULL: not wanted), `lay` the layout of its sibling arrays, `fmt` the format of both. ----
+void sweep_leaf_hashes(imt_itree* t, const PlanSet& P, hipStream_t s, size_t E) {
+    imt_ctx* c = t->ctx;
+    const int pf = c->prof_begin(IMT_PROF_LEAVES, s);
+    launch::sweep_leaves(s, P.d_pre, P.d_tab[0][1], P.d_val[0], 0, (uint32_t)E, IMT_FMT_CANONICAL, c->d_err, c->coop_max_events);
+    c->prof_end(pf, s);
+}
+// level l < L0 -> l + 1: reads the stored level l, which the caller has made sure holds what came before this batch
+void sweep_one_level(imt_itree* t, const PlanSet& P, hipStream_t s, unsigned l, size_t E, const imt_insert_out& d,
+                     launch::SibLayout lay, unsigned fmt) {
+    imt_ctx* c = t->ctx;
+    const PlanSet::Level row = P.level(l);
+    const int pf = c->prof_begin(IMT_PROF_LEVEL, s);
+    launch::sweep_level(s, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], row.from, row.sibsrc, row.nodeb, row.timen, t->nodes(l),
+                        t->h_len[l], c->d_zero + (size_t)l * 32, 0, (uint32_t)E, (uint8_t*)d.low_sib, (uint8_t*)d.new_sib, lay, l,
+                        fmt, c->coop_max_events);
+    c->prof_end(pf, s);
+}
+// old_root[0] is the root the batch before left: read right before the launch that overwrites the stored root
+void read_old_root(imt_itree* t, hipStream_t s, const imt_insert_out& d, unsigned fmt) {
+    if (d.old_root) launch::convert(s, t->nodes(t->depth), (uint8_t*)d.old_root, 1, IMT_FMT_DEVICE, fmt, t->ctx->d_err);
+}
+// level l >= L0 -> l + 1: every event alone in node 0 against the empty subtree of that height.  Ordinary launches of
+// the same kernel, so consecutive batches overlap here level by level as well; the last event's node of every level goes
+// back to the stored tree.
+void sweep_one_upper(imt_itree* t, const PlanSet& P, hipStream_t s, unsigned l, size_t E, unsigned L0, const imt_insert_out& d,
+                     launch::SibLayout lay, unsigned fmt) {
+    imt_ctx* c = t->ctx;
+    const int pf = c->prof_begin(IMT_PROF_TOP, s);
+    launch::sweep_upper(s, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], c->d_zero + (size_t)l * 32, 0, (uint32_t)E, (uint32_t)E - 1,
+                        l == L0 ? t->nodes(l) : nullptr, t->nodes(l + 1), (uint8_t*)d.low_sib, (uint8_t*)d.new_sib, lay, l, fmt,
+                        c->coop_max_events);
+    c->prof_end(pf, s);
+}
+// the roots of every event from the top values; a batch that fills the tree to its full depth stores its root here
+void finish_roots(imt_itree* t, const PlanSet& P, hipStream_t s, size_t E, unsigned L0, const imt_insert_out& d, unsigned fmt) {
+    launch::emit_roots(s, P.d_val[t->depth & 1], 0, (uint32_t)E, (uint32_t)E, (uint8_t*)d.old_root, (uint8_t*)d.interim_root,
+                       (uint8_t*)d.new_root, fmt, nullptr, L0 == t->depth ? t->nodes(t->depth) : nullptr);
 }
 
 }  // namespace
 
-// The body of imt_itree_insert_batch.  filtered: `vals` are the accepted values of imt_itree_insert_filtered, canonical,
-// in device memory of the plan set (default prepare) or host memory (IMT_HOST_PREP), whatever IMT_DEVICE_PTRS says of
-// the outputs.  Level-major sibling arrays have level stride sib_stride (>= n).
-// apply != NULL: imt_itree_apply_batch -- same preparation, same commit, but the hashing is the witness-free schedule
-// (apply_hashes) and the only output is the root.
+// apply != NULL: imt_itree_apply_batch / _apply_filtered -- same preparation, same commit, but the hashing is the
+// witness-free schedule (apply_hashes) and the only output is the root.
 struct ApplyReq {
     void* root_out;
 };
 static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0);
-static int insert_core(imt_itree* t, const void* vals, size_t n, const imt_insert_out* out, unsigned flags, bool filtered,
-                       size_t sib_stride, const ApplyReq* apply = nullptr) {
-    if (!t) return IMT_ERR_ARG;
+
+// The hashing of imt_itree_insert_batch on stream s, behind the preparation: leaf hashes, index phase (no hashing), then
+// the hash sweep level by level with each level's write-back.  prev: the batch before this one if it is still on a
+// pipeline stream -- this batch then runs one level behind it; pipelined: this one records its own per-level events.
+static int witness_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, const PlanSet* prev, bool pipelined,
+                          const imt_insert_out& d, launch::SibLayout lay, unsigned fmt) {
     imt_ctx* c = t->ctx;
-    IMT_NOT_SLICED(t);
-    if (n == 0) return IMT_OK;
-    if (!vals) return c->fail(IMT_ERR_ARG, "null vals");
-    if ((flags & IMT_FMT_MASK) == 3) return c->fail(IMT_ERR_ARG, "unknown field-element format");
-    if (n > ((size_t)1 << 30)) return c->fail(IMT_ERR_RANGE, "batch too large");
-    if (t->pending.active) return c->fail(IMT_ERR_ARG, "a sharded batch is open (imt_itree_batch_end first)");
-    if (slice_open(t)) return c->fail(IMT_ERR_ARG, "a slice is open (issue its remaining units first)");
-    int rc = c->set_device();
-    if (rc) return rc;
+    sweep_leaf_hashes(t, P, s, E);
+    int pf = c->prof_begin(IMT_PROF_INDEX, s);
+    index_phase(P, s, E, L0, nullptr);
+    c->prof_end(pf, s);
+    for (unsigned l = 0; l < L0; l++) {
+        // stored level l must hold the previous batch's final versions: its write-back of that level,
+        // or (at and above its L0) its top kernel
+        if (prev) IMT_HIP(c, hipStreamWaitEvent(s, l < prev->l0 ? prev->wb_done[l] : prev->done, 0));
+        sweep_one_level(t, P, s, l, E, d, lay, fmt);
+        pf = c->prof_begin(IMT_PROF_WRITEBACK, s);
+        launch::writeback(s, P.d_val[l & 1], P.level(l).from, P.level(l).nodeb, t->nodes(l), (uint32_t)E);
+        c->prof_end(pf, s);
+        if (pipelined) IMT_HIP(c, hipEventRecord(P.wb_done[l], s));
+    }
+    auto old_root = [&]() -> int {
+        if (prev) IMT_HIP(c, hipStreamWaitEvent(s, prev->done, 0));
+        read_old_root(t, s, d, fmt);
+        return IMT_OK;
+    };
+    int rc;
+    for (unsigned l = L0; l < t->depth; l++) {
+        if (l + 1 == t->depth && (rc = old_root())) return rc;
+        // the previous batch stored node l + 1 (and node l, at its own L0) from its launch of this level
+        if (prev) IMT_HIP(c, hipStreamWaitEvent(s, l >= prev->l0 ? prev->wb_done[l] : prev->done, 0));
+        sweep_one_upper(t, P, s, l, E, L0, d, lay, fmt);
+        if (pipelined) IMT_HIP(c, hipEventRecord(P.wb_done[l], s));
+    }
+    if (L0 == t->depth && (rc = old_root())) return rc;
+    finish_roots(t, P, s, E, L0, d, fmt);
+    return IMT_OK;
+}
+
+// The hash-free outputs of a batch to the caller, behind the hashing on stream s.  Prepared on the GPU they are in
+// d.low_index .. d.new_leaf already (gpu_prepare); prepared on the host they are in the tree's work arrays and in hp.
+static int deliver_hashfree_outputs(imt_itree* t, hipStream_t s, size_t n, const imt_insert_out* out, const imt_insert_out& d,
+                                    const HostPlan& hp, unsigned flags, size_t& slot) {
+    imt_ctx* c = t->ctx;
     const bool dev = flags & IMT_DEVICE_PTRS;
-    if ((rc = check_fe_ptrs(c, dev && !filtered, {vals})) || (rc = check_out_ptrs(c, dev, out))) return rc;
-    if (apply && (rc = check_fe_ptrs(c, dev, {apply->root_out}))) return rc;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    if (!(flags & IMT_HOST_PREP)) {
+        // written by k_events in canonical form; other formats are converted in place behind up_done
+        if (fmt != IMT_FMT_CANONICAL) {
+            if (d.low_leaf) launch::convert(s, (uint8_t*)d.low_leaf, (uint8_t*)d.low_leaf, n * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
+            if (d.new_leaf) launch::convert(s, (uint8_t*)d.new_leaf, (uint8_t*)d.new_leaf, n * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
+        }
+        if (!dev) {
+            if (d.low_index) IMT_HIP(c, hipMemcpyAsync(out->low_index, d.low_index, n * 8, hipMemcpyDeviceToHost, s));
+            if (d.is_largest) IMT_HIP(c, hipMemcpyAsync(out->is_largest, d.is_largest, n, hipMemcpyDeviceToHost, s));
+            if (d.low_leaf) IMT_HIP(c, hipMemcpyAsync(out->low_leaf, d.low_leaf, n * 96, hipMemcpyDeviceToHost, s));
+            if (d.new_leaf) IMT_HIP(c, hipMemcpyAsync(out->new_leaf, d.new_leaf, n * 96, hipMemcpyDeviceToHost, s));
+        }
+        return IMT_OK;
+    }
+    int rc;
+    auto host_out = [&](void* user, const void* src, size_t bytes) -> int {
+        if (!user) return IMT_OK;
+        if (dev) {   // side stream: does not wait for the sweep; src is host memory of this call
+            IMT_HIP(c, hipMemcpyAsync(user, src, bytes, hipMemcpyHostToDevice, t->up_stream));
+            IMT_HIP(c, hipStreamSynchronize(t->up_stream));
+        } else {
+            std::memcpy(user, src, bytes);
+        }
+        return IMT_OK;
+    };
+    if (t->index_base && out->low_index) {
+        std::vector<uint64_t> glob(t->w_low);
+        for (auto& x : glob) x += t->index_base;
+        if ((rc = host_out(out->low_index, glob.data(), n * 8))) return rc;
+    } else if ((rc = host_out(out->low_index, t->w_low.data(), n * 8))) return rc;
+    if ((rc = host_out(out->is_largest, t->w_largest.data(), n))) return rc;
+    if (fmt == IMT_FMT_CANONICAL) {
+        if ((rc = host_out(out->low_leaf, hp.lowleaf.data(), n * 96))) return rc;
+        return host_out(out->new_leaf, hp.newleaf.data(), n * 96);
+    }
+    for (int w = 0; w < 2; w++) {
+        void* user = w ? out->new_leaf : out->low_leaf;
+        if (!user) continue;
+        const std::vector<uint8_t>& src = w ? hp.newleaf : hp.lowleaf;
+        uint8_t* d_in = (uint8_t*)c->dev_scratch(slot++, n * 96);
+        if (!d_in) return IMT_ERR_HIP;
+        IMT_HIP(c, hipMemcpyAsync(d_in, src.data(), n * 96, hipMemcpyHostToDevice, s));
+        uint8_t* d_o = dev ? (uint8_t*)user : (uint8_t*)c->dev_scratch(slot++, n * 96);
+        if (!d_o) return IMT_ERR_HIP;
+        launch::convert(s, d_in, d_o, n * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
+        if (!dev) IMT_HIP(c, hipMemcpyAsync(user, d_o, n * 96, hipMemcpyDeviceToHost, s));
+        IMT_HIP(c, hipStreamSynchronize(s));
+    }
+    return IMT_OK;
+}
+
+// The roots and sibling paths of a host-pointer call from their staging in `d` to the caller's arrays.
+static int deliver_witness_outputs(imt_itree* t, hipStream_t s, size_t n, const imt_insert_out* out, const imt_insert_out& d,
+                                   bool item_major, size_t sib_stride) {
+    imt_ctx* c = t->ctx;
+    if (out->old_root) IMT_HIP(c, hipMemcpyAsync(out->old_root, d.old_root, n * 32, hipMemcpyDeviceToHost, s));
+    if (out->interim_root) IMT_HIP(c, hipMemcpyAsync(out->interim_root, d.interim_root, n * 32, hipMemcpyDeviceToHost, s));
+    if (out->new_root) IMT_HIP(c, hipMemcpyAsync(out->new_root, d.new_root, n * 32, hipMemcpyDeviceToHost, s));
+    // only rows [0, depth) were written: a placed tree's rows [depth, global_depth) stay the caller's until
+    // imt_itree_lift_batch, so they are not copied over with the scratch behind them
+    if (item_major ? t->global_depth == t->depth : sib_stride == n) {
+        const size_t sib_copy = (size_t)t->depth * n * 32;
+        if (out->low_sib) IMT_HIP(c, hipMemcpyAsync(out->low_sib, d.low_sib, sib_copy, hipMemcpyDeviceToHost, s));
+        if (out->new_sib) IMT_HIP(c, hipMemcpyAsync(out->new_sib, d.new_sib, sib_copy, hipMemcpyDeviceToHost, s));
+    } else if (item_major) {    // the first depth rows of every item's global_depth
+        const size_t pitch = (size_t)t->global_depth * 32, width = (size_t)t->depth * 32;
+        if (out->low_sib)
+            IMT_HIP(c, hipMemcpy2DAsync(out->low_sib, pitch, d.low_sib, pitch, width, n, hipMemcpyDeviceToHost, s));
+        if (out->new_sib)
+            IMT_HIP(c, hipMemcpy2DAsync(out->new_sib, pitch, d.new_sib, pitch, width, n, hipMemcpyDeviceToHost, s));
+    } else {    // rows [0, n) of every level, level stride sib_stride
+        const size_t pitch = sib_stride * 32;
+        if (out->low_sib)
+            IMT_HIP(c, hipMemcpy2DAsync(out->low_sib, pitch, d.low_sib, pitch, n * 32, t->depth, hipMemcpyDeviceToHost, s));
+        if (out->new_sib)
+            IMT_HIP(c, hipMemcpy2DAsync(out->new_sib, pitch, d.new_sib, pitch, n * 32, t->depth, hipMemcpyDeviceToHost, s));
+    }
+    return IMT_OK;
+}
+
+// A batch behind its validation: n values (val_flags: where they are and in which format) into the tree, the outputs as
+// `flags` say.  Level-major sibling arrays have level stride sib_stride (>= n).  The sequence: plan set, side stream
+// behind the caller, hash-free part, compute stream, hashing, record, commit, outputs.
+static int insert_core(imt_itree* t, const void* vals, unsigned val_flags, size_t n, const imt_insert_out* out, unsigned flags,
+                       size_t sib_stride, const ApplyReq* apply) {
+    imt_ctx* c = t->ctx;
+    const bool dev = flags & IMT_DEVICE_PTRS;
     const bool gpu_prep = (flags & IMT_HOST_PREP) == 0;
+    const bool pipelined = dev && (flags & IMT_PIPELINE);
     const unsigned fmt = flags & IMT_FMT_MASK;
     const uint64_t M = t->size;
-    if (M + n > t->cap) return c->fail(IMT_ERR_FULL, "tree capacity %llu exceeded", (unsigned long long)t->cap);
-    const auto host_t0 = std::chrono::steady_clock::now();
+    const size_t E = 2 * n;
+    const unsigned L0 = std::min(ceil_log2(M + n), t->depth);
+    const HostTimer host;
     double host_wait_ms = 0;
 
     // ---- plan buffers ----
-    const size_t E = 2 * n;
-    const unsigned L0 = std::min(ceil_log2(M + n), t->depth);
     PlanSet& P = t->plan[t->cur];
-    if (P.in_flight) {   // back-pressure: at most NSETS batches in flight
-        const auto w0 = std::chrono::steady_clock::now();
-        IMT_HIP(c, hipEventSynchronize(P.done));
-        host_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-        P.in_flight = false;
-    }
-    rc = plan_reserve(c, P, E, t->depth, t->cap);   // all levels up front: growing later would stall the pipeline
+    int rc = acquire_plan(t, E, 0, host_wait_ms);
     if (rc) return rc;
-    if (dev && (flags & IMT_PIPELINE) && (rc = reserve_all_plans(t, E))) return rc;
+    if (pipelined && (rc = reserve_all_plans(t, E))) return rc;
 
     // ---- hash-free part: low leaves, event preimages, event order (side stream) ----
-    // The side stream reads the caller's `vals` and writes the caller's hash-free outputs (low_index,
-    // is_largest, low_leaf, new_leaf), so with device pointers it is first ordered behind everything the
-    // caller has enqueued on the context's stream (imt.h: "work is enqueued on the context's stream").
-    // IMT_INPUTS_READY waives that: the caller guarantees those buffers are idle.
-    // (Host-pointer calls are ordered too: their staging scratch may still be read by an asynchronous
-    // device-pointer call, e.g. imt_itree_lift_batch, enqueued earlier on the context's stream.)
-    if (!(dev && (flags & IMT_INPUTS_READY))) {
-        IMT_HIP(c, hipEventRecord(t->in_mark, c->stream));
-        IMT_HIP(c, hipStreamWaitEvent(t->up_stream, t->in_mark, 0));
-    }
-    size_t slot = 2;
+    if ((rc = order_behind_caller(t, t->up_stream, flags))) return rc;
+    size_t slot = 2;                 // context scratch slots, handed out in one order from here to the last output
     HostPlan hp;
-    GpuOuts go;
+    imt_insert_out d = {};           // where on the device each requested output is written
     if (gpu_prep)
-        rc = gpu_prepare(t, P, vals, n, flags, out, slot, go, host_wait_ms, filtered);
+        rc = gpu_prepare(t, P, vals, val_flags, n, out, dev, slot, d, host_wait_ms);
     else
-        rc = host_prepare(t, P, vals, n, filtered ? IMT_FMT_CANONICAL : flags, out && out->low_leaf, out && out->new_leaf, hp);
+        rc = host_prepare(t, P, vals, n, val_flags, out && out->low_leaf, out && out->new_leaf, hp);
     if (rc) return rc;
     IMT_HIP(c, hipEventRecord(t->up_done, t->up_stream));
 
     // ---- compute stream: the context's, or one of the NPIPE pipeline streams ----
-    const bool pipelined = dev && (flags & IMT_PIPELINE);
     hipStream_t s = c->stream;
     const PlanSet* prev = nullptr;      // the batch before this one, if it is still on a pipeline stream
     if (pipelined) {
@@ -1300,90 +1541,20 @@ static int insert_core(imt_itree* t, const void* vals, size_t n, const imt_inser
     }
     IMT_HIP(c, hipStreamWaitEvent(s, t->up_done, 0));
 
-    // ---- GPU outputs ----
-    uint8_t *g_old = nullptr, *g_int = nullptr, *g_new = nullptr, *g_ls = nullptr, *g_ns = nullptr;
-    auto gpu_out = [&](void* user, size_t bytes) -> uint8_t* {
-        if (!user) return nullptr;
-        if (dev) return (uint8_t*)user;
-        return (uint8_t*)c->dev_scratch(slot++, bytes);
-    };
+    // ---- hashing: one hash per touched node straight into the stored tree (imt_apply.hpp), or the witness sweep ----
     const bool item_major = flags & IMT_SIB_ITEM_MAJOR;
     const size_t sib_bytes = (size_t)t->global_depth * (item_major ? n : sib_stride) * 32;
-    if (out) {
-        g_old = gpu_out(out->old_root, n * 32);
-        g_int = gpu_out(out->interim_root, n * 32);
-        g_new = gpu_out(out->new_root, n * 32);
-        g_ls = gpu_out(out->low_sib, sib_bytes);
-        g_ns = gpu_out(out->new_sib, sib_bytes);
-        if ((out->old_root && !g_old) || (out->interim_root && !g_int) || (out->new_root && !g_new) ||
-            (out->low_sib && !g_ls) || (out->new_sib && !g_ns))
-            return IMT_ERR_HIP;
-    }
+    if (out && (!stage_out(c, dev, slot, out->old_root, n * 32, d.old_root) ||
+                !stage_out(c, dev, slot, out->interim_root, n * 32, d.interim_root) ||
+                !stage_out(c, dev, slot, out->new_root, n * 32, d.new_root) ||
+                !stage_out(c, dev, slot, out->low_sib, sib_bytes, d.low_sib) ||
+                !stage_out(c, dev, slot, out->new_sib, sib_bytes, d.new_sib)))
+        return IMT_ERR_HIP;
     // a placed tree writes rows [0, depth) of sibling arrays dimensioned for global_depth levels
-    launch::SibLayout lay = item_major ? launch::SibLayout{1, t->global_depth} : launch::SibLayout{sib_stride, 1};
-
-    if (apply) {
-        // ---- one hash per touched node, straight into the stored tree (imt_apply.hpp) ----
-        if ((rc = apply_hashes(t, P, s, E, L0))) return rc;
-    } else {
-        // ---- leaf hashes, index phase (no hashing), then the hash sweep ----
-        int pf = c->prof_begin(IMT_PROF_LEAVES, s);
-        launch::sweep_leaves(s, P.d_pre, P.d_tab[0][1], P.d_val[0], 0, (uint32_t)E, IMT_FMT_CANONICAL, c->d_err, c->coop_max_events);
-        c->prof_end(pf, s);
-        pf = c->prof_begin(IMT_PROF_INDEX, s);
-        for (unsigned l = 0; l < L0; l++) {
-            const int a = l & 1, b = a ^ 1;
-            // time table of level l: the uploaded one for l = 0, otherwise slot l-1 of d_timen
-            const uint32_t* time_in = l == 0 ? P.d_tab[0][1] : P.d_timen + (size_t)(l - 1) * P.cap_events;
-            sweep::LevelTable in{P.d_tab[a][0], time_in, P.d_tab[a][2], P.d_tab[a][3]};
-            sweep::LevelOut o{P.d_tab[b][0], P.d_timen + (size_t)l * P.cap_events, P.d_tab[b][2], P.d_tab[b][3],
-                              P.d_from + (size_t)l * P.cap_events, P.d_sibsrc + (size_t)l * P.cap_events,
-                              P.d_nodeb + (size_t)l * P.cap_events, nullptr};
-            launch::merge_level(s, in, o, (uint32_t)E);
-        }
-        c->prof_end(pf, s);
-        for (unsigned l = 0; l < L0; l++) {
-            const uint8_t* vin = P.d_val[l & 1];
-            uint8_t* vout = P.d_val[(l & 1) ^ 1];
-            const size_t o = (size_t)l * P.cap_events;
-            // stored level l must hold the previous batch's final versions: its write-back of that level,
-            // or (at and above its L0) its top kernel
-            if (prev) IMT_HIP(c, hipStreamWaitEvent(s, l < prev->l0 ? prev->wb_done[l] : prev->done, 0));
-            pf = c->prof_begin(IMT_PROF_LEVEL, s);
-            launch::sweep_level(s, vin, vout, P.d_from + o, P.d_sibsrc + o, P.d_nodeb + o, P.d_timen + o,
-                                t->d_nodes + t->h_off[l] * 32, t->h_len[l], c->d_zero + (size_t)l * 32, 0, (uint32_t)E, g_ls,
-                                g_ns, lay, l, fmt, c->coop_max_events);
-            c->prof_end(pf, s);
-            pf = c->prof_begin(IMT_PROF_WRITEBACK, s);
-            launch::writeback(s, vin, P.d_from + o, P.d_nodeb + o, t->d_nodes + t->h_off[l] * 32, (uint32_t)E);
-            c->prof_end(pf, s);
-            if (pipelined) IMT_HIP(c, hipEventRecord(P.wb_done[l], s));
-        }
-        // ---- levels [L0, depth): every event alone in node 0 against the empty subtree of that height.  Ordinary
-        // launches of the same kernel, so consecutive batches overlap here level by level as well; the last event's node
-        // of every level goes back to the stored tree.  old_root[0] is the root the previous batch left: it is read
-        // right before the launch that overwrites the stored root.
-        auto read_old_root = [&]() -> int {
-            if (prev) IMT_HIP(c, hipStreamWaitEvent(s, prev->done, 0));
-            if (g_old) launch::convert(s, t->d_nodes + t->h_off[t->depth] * 32, g_old, 1, IMT_FMT_DEVICE, fmt, c->d_err);
-            return IMT_OK;
-        };
-        for (unsigned l = L0; l < t->depth; l++) {
-            if (l + 1 == t->depth && (rc = read_old_root())) return rc;
-            // the previous batch stored node l + 1 (and node l, at its own L0) from its launch of this level
-            if (prev) IMT_HIP(c, hipStreamWaitEvent(s, l >= prev->l0 ? prev->wb_done[l] : prev->done, 0));
-            pf = c->prof_begin(IMT_PROF_TOP, s);
-            launch::sweep_upper(s, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], c->d_zero + (size_t)l * 32, 0, (uint32_t)E,
-                                (uint32_t)E - 1, l == L0 ? t->d_nodes + t->h_off[l] * 32 : nullptr,
-                                t->d_nodes + t->h_off[l + 1] * 32, g_ls, g_ns, lay, l, fmt, c->coop_max_events);
-            c->prof_end(pf, s);
-            if (pipelined) IMT_HIP(c, hipEventRecord(P.wb_done[l], s));
-        }
-        if (L0 == t->depth && (rc = read_old_root())) return rc;
-        launch::emit_roots(s, P.d_val[t->depth & 1], 0, (uint32_t)E, (uint32_t)E, g_old, g_int, g_new, fmt, nullptr,
-                           L0 == t->depth ? t->d_nodes + t->h_off[t->depth] * 32 : nullptr);
-    }
-    IMT_HIP(c, hipMemcpyAsync(P.d_root, t->d_nodes + t->h_off[t->depth] * 32, 32, hipMemcpyDeviceToDevice, s));
+    const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->global_depth} : launch::SibLayout{sib_stride, 1};
+    rc = apply ? apply_hashes(t, P, s, E, L0) : witness_hashes(t, P, s, E, L0, prev, pipelined, d, lay, fmt);
+    if (rc) return rc;
+    IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
     P.has_root = true;
     IMT_HIP(c, hipEventRecord(P.done, s));
     P.pipelined = pipelined;
@@ -1402,92 +1573,38 @@ static int insert_core(imt_itree* t, const void* vals, size_t n, const imt_inser
         host_commit(t, hp, n);
     }
 
-    // ---- hash-free outputs ----
-    if (out && gpu_prep) {
-        // written by k_events in canonical form; other formats are converted in place behind up_done
-        if (fmt != IMT_FMT_CANONICAL) {
-            if (go.lowleaf) launch::convert(s, go.lowleaf, go.lowleaf, n * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
-            if (go.newleaf) launch::convert(s, go.newleaf, go.newleaf, n * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
-        }
-        if (!dev) {
-            if (go.low) IMT_HIP(c, hipMemcpyAsync(out->low_index, go.low, n * 8, hipMemcpyDeviceToHost, s));
-            if (go.largest) IMT_HIP(c, hipMemcpyAsync(out->is_largest, go.largest, n, hipMemcpyDeviceToHost, s));
-            if (go.lowleaf) IMT_HIP(c, hipMemcpyAsync(out->low_leaf, go.lowleaf, n * 96, hipMemcpyDeviceToHost, s));
-            if (go.newleaf) IMT_HIP(c, hipMemcpyAsync(out->new_leaf, go.newleaf, n * 96, hipMemcpyDeviceToHost, s));
-        }
-    } else if (out) {
-        auto host_out = [&](void* user, const void* src, size_t bytes) -> int {
-            if (!user) return IMT_OK;
-            if (dev) {   // side stream: does not wait for the sweep; src is host memory of this call
-                IMT_HIP(c, hipMemcpyAsync(user, src, bytes, hipMemcpyHostToDevice, t->up_stream));
-                IMT_HIP(c, hipStreamSynchronize(t->up_stream));
-            } else {
-                std::memcpy(user, src, bytes);
-            }
-            return IMT_OK;
-        };
-        if (t->index_base && out->low_index) {
-            std::vector<uint64_t> glob(t->w_low);
-            for (auto& x : glob) x += t->index_base;
-            if ((rc = host_out(out->low_index, glob.data(), n * 8))) return rc;
-        } else if ((rc = host_out(out->low_index, t->w_low.data(), n * 8))) return rc;
-        if ((rc = host_out(out->is_largest, t->w_largest.data(), n))) return rc;
-        if (fmt == IMT_FMT_CANONICAL) {
-            if ((rc = host_out(out->low_leaf, hp.lowleaf.data(), n * 96))) return rc;
-            if ((rc = host_out(out->new_leaf, hp.newleaf.data(), n * 96))) return rc;
-        } else {
-            for (int w = 0; w < 2; w++) {
-                void* user = w ? out->new_leaf : out->low_leaf;
-                if (!user) continue;
-                const std::vector<uint8_t>& src = w ? hp.newleaf : hp.lowleaf;
-                uint8_t* d_in = (uint8_t*)c->dev_scratch(slot++, n * 96);
-                if (!d_in) return IMT_ERR_HIP;
-                IMT_HIP(c, hipMemcpyAsync(d_in, src.data(), n * 96, hipMemcpyHostToDevice, s));
-                uint8_t* d_o = dev ? (uint8_t*)user : (uint8_t*)c->dev_scratch(slot++, n * 96);
-                if (!d_o) return IMT_ERR_HIP;
-                launch::convert(s, d_in, d_o, n * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
-                if (!dev) IMT_HIP(c, hipMemcpyAsync(user, d_o, n * 96, hipMemcpyDeviceToHost, s));
-                IMT_HIP(c, hipStreamSynchronize(s));
-            }
-        }
-    }
+    // ---- outputs ----
+    if (out && (rc = deliver_hashfree_outputs(t, s, n, out, d, hp, flags, slot))) return rc;
     if (apply && apply->root_out) {
-        uint8_t* d = dev ? (uint8_t*)apply->root_out : (uint8_t*)c->dev_scratch(slot++, 32);
-        if (!d) return IMT_ERR_HIP;
-        launch::convert(s, P.d_root, d, 1, IMT_FMT_DEVICE, fmt, c->d_err);
-        if (!dev) IMT_HIP(c, hipMemcpyAsync(apply->root_out, d, 32, hipMemcpyDeviceToHost, s));
+        uint8_t* r = dev ? (uint8_t*)apply->root_out : (uint8_t*)c->dev_scratch(slot++, 32);
+        if (!r) return IMT_ERR_HIP;
+        launch::convert(s, P.d_root, r, 1, IMT_FMT_DEVICE, fmt, c->d_err);
+        if (!dev) IMT_HIP(c, hipMemcpyAsync(apply->root_out, r, 32, hipMemcpyDeviceToHost, s));
     }
-    if (out && !dev) {
-        if (out->old_root) IMT_HIP(c, hipMemcpyAsync(out->old_root, g_old, n * 32, hipMemcpyDeviceToHost, s));
-        if (out->interim_root) IMT_HIP(c, hipMemcpyAsync(out->interim_root, g_int, n * 32, hipMemcpyDeviceToHost, s));
-        if (out->new_root) IMT_HIP(c, hipMemcpyAsync(out->new_root, g_new, n * 32, hipMemcpyDeviceToHost, s));
-        // only rows [0, depth) were written: a placed tree's rows [depth, global_depth) stay the caller's until
-        // imt_itree_lift_batch, so they are not copied over with the scratch behind them
-        if (item_major ? t->global_depth == t->depth : sib_stride == n) {
-            const size_t sib_copy = (size_t)t->depth * n * 32;
-            if (out->low_sib) IMT_HIP(c, hipMemcpyAsync(out->low_sib, g_ls, sib_copy, hipMemcpyDeviceToHost, s));
-            if (out->new_sib) IMT_HIP(c, hipMemcpyAsync(out->new_sib, g_ns, sib_copy, hipMemcpyDeviceToHost, s));
-        } else if (item_major) {    // the first depth rows of every item's global_depth
-            const size_t pitch = (size_t)t->global_depth * 32, width = (size_t)t->depth * 32;
-            if (out->low_sib)
-                IMT_HIP(c, hipMemcpy2DAsync(out->low_sib, pitch, g_ls, pitch, width, n, hipMemcpyDeviceToHost, s));
-            if (out->new_sib)
-                IMT_HIP(c, hipMemcpy2DAsync(out->new_sib, pitch, g_ns, pitch, width, n, hipMemcpyDeviceToHost, s));
-        } else {    // rows [0, n) of every level, level stride sib_stride
-            const size_t pitch = sib_stride * 32;
-            if (out->low_sib)
-                IMT_HIP(c, hipMemcpy2DAsync(out->low_sib, pitch, g_ls, pitch, n * 32, t->depth, hipMemcpyDeviceToHost, s));
-            if (out->new_sib)
-                IMT_HIP(c, hipMemcpy2DAsync(out->new_sib, pitch, g_ns, pitch, n * 32, t->depth, hipMemcpyDeviceToHost, s));
-        }
-    }
+    if (out && !dev && (rc = deliver_witness_outputs(t, s, n, out, d, item_major, sib_stride))) return rc;
     if (c->profiling) {
-        c->prof_ms[IMT_PROF_HOST] +=
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count() - host_wait_ms;
+        c->prof_ms[IMT_PROF_HOST] += host.ms() - host_wait_ms;
         c->prof_n[IMT_PROF_HOST] += 1;
     }
     if (!dev) IMT_HIP(c, hipStreamSynchronize(s));
     return IMT_OK;
+}
+
+// imt_itree_insert_batch and imt_itree_apply_batch: the refusals, then the batch
+static int insert_call(imt_itree* t, const void* vals, size_t n, const imt_insert_out* out, unsigned flags,
+                       const ApplyReq* apply) {
+    if (!t) return IMT_ERR_ARG;
+    imt_ctx* c = t->ctx;
+    IMT_NOT_SLICED(t);
+    if (n == 0) return IMT_OK;
+    if (!vals) return c->fail(IMT_ERR_ARG, "null vals");
+    int rc = check_batch_call(t, n, flags);
+    if (rc) return rc;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    if ((rc = check_fe_ptrs(c, dev, {vals})) || (rc = check_out_ptrs(c, dev, out))) return rc;
+    if (apply && (rc = check_fe_ptrs(c, dev, {apply->root_out}))) return rc;
+    if ((rc = check_room(t, n))) return rc;
+    return insert_core(t, vals, flags, n, out, flags, n, apply);
 }
 
 // The hashing of imt_itree_apply_batch on stream s, behind the preparation: the lists of every level (index work), the
@@ -1496,21 +1613,19 @@ static int insert_core(imt_itree* t, const void* vals, size_t n, const imt_inser
 // are sized by host-side bounds; the counts stay on the device (t->d_apply_stats), so nothing here waits for the GPU.
 static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0) {
     imt_ctx* c = t->ctx;
-    const size_t stride = P.cap_events;
-    const apply::Lists lists{P.d_nodeb, P.d_timen, t->d_apply_stats, stride};
-    auto level_nodes = [&](unsigned l) { return t->d_nodes + t->h_off[l] * 32; };
+    const apply::Lists lists{P.d_nodeb, P.d_timen, t->d_apply_stats, P.cap_events};
     int pf = c->prof_begin(IMT_PROF_APPLY_LISTS, s);
     IMT_HIP(c, prep::apply_lists(s, P.ws.tmp, P.ws.tmp_bytes, P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][3], (uint32_t)E, L0,
                                  t->depth, P.d_from, lists));
     c->prof_end(pf, s);
     pf = c->prof_begin(IMT_PROF_APPLY_LEAVES, s);
     launch::apply_leaves(s, lists.count, apply::bound((uint32_t)E, L0, 0), lists.node, lists.src, P.d_pre, IMT_FMT_CANONICAL,
-                         c->d_err, level_nodes(0), t->h_len[0], c->coop_max_events);
+                         c->d_err, t->nodes(0), t->h_len[0], c->coop_max_events);
     c->prof_end(pf, s);
     for (unsigned l = 0; l + 1 < L0; l++) {
         pf = c->prof_begin(IMT_PROF_APPLY_LEVEL, s);
-        launch::apply_level(s, lists.count + l + 1, apply::bound((uint32_t)E, L0, l + 1), lists.node + (size_t)(l + 1) * stride,
-                            level_nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, level_nodes(l + 1), t->h_len[l + 1],
+        launch::apply_level(s, lists.count + l + 1, apply::bound((uint32_t)E, L0, l + 1), P.level(l + 1).nodeb,
+                            t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, t->nodes(l + 1), t->h_len[l + 1],
                             c->coop_max_events);
         c->prof_end(pf, s);
     }
@@ -1523,7 +1638,7 @@ static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsig
 
 extern "C" int imt_itree_insert_batch(imt_itree* t, const void* vals, size_t n, const imt_insert_out* out,
                                       unsigned flags) {
-    return insert_core(t, vals, n, out, flags, false, n);
+    return insert_call(t, vals, n, out, flags, nullptr);
 }
 
 extern "C" int imt_itree_apply_batch(imt_itree* t, const void* vals, size_t n, void* root_out, unsigned flags) {
@@ -1534,7 +1649,7 @@ extern "C" int imt_itree_apply_batch(imt_itree* t, const void* vals, size_t n, v
         return root_out ? imt_itree_root(t, root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS)) : IMT_OK;
     }
     const ApplyReq req{root_out};
-    return insert_core(t, vals, n, nullptr, flags, false, n, &req);
+    return insert_call(t, vals, n, nullptr, flags, &req);
 }
 
 extern "C" int imt_itree_apply_stats(imt_itree* t, uint64_t* hashes) {
@@ -1572,20 +1687,12 @@ int gpu_filter(imt_itree* t, PlanSet& P, const void* vals, size_t n, unsigned fl
                uint64_t* leaf_index, size_t& n_acc) {
     imt_ctx* c = t->ctx;
     const bool dev = flags & IMT_DEVICE_PTRS;
-    const unsigned fmt = flags & IMT_FMT_MASK;
     int rc = ensure_device_index(t);
     if (rc) return rc;
     hipStream_t ps = t->up_stream;
-    IMT_HIP(c, hipMemsetAsync(P.ws.err, 0, sizeof(int), ps));
-    const uint8_t* d_vals = (const uint8_t*)vals;
-    if (!dev) {         // the plan's own buffers, not context scratch (see gpu_prepare)
-        IMT_HIP(c, hipMemcpyAsync(P.d_canon, vals, n * 32, hipMemcpyHostToDevice, ps));
-        d_vals = P.d_canon;
-    }
-    if (fmt != IMT_FMT_CANONICAL) {
-        launch::convert(ps, d_vals, P.d_canon, n, fmt, IMT_FMT_CANONICAL, P.ws.err);   // sets bit 0 = non-canonical
-        d_vals = P.d_canon;
-    }
+    const uint8_t* d_vals = nullptr;
+    // the plan's own buffer for the upload as well, not context scratch (see gpu_prepare)
+    if ((rc = stage_canonical(c, ps, vals, n, flags, P.d_canon, P.d_canon, P.ws.err, &d_vals))) return rc;
     uint8_t* d_st = dev ? status : P.fw.status;
     uint64_t* d_leaf = leaf_index ? (dev ? leaf_index : P.fw.leaf) : nullptr;
     IMT_HIP(c, prep::filter(ps, P.fw, d_vals, (uint32_t)n, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)t->size,
@@ -1679,44 +1786,44 @@ static int filtered_core(imt_itree* t, const void* vals, size_t n, uint8_t* stat
         return unchanged_root();
     }
     if (!vals) return c->fail(IMT_ERR_ARG, "null vals");
-    if ((flags & IMT_FMT_MASK) == 3) return c->fail(IMT_ERR_ARG, "unknown field-element format");
-    if (n > ((size_t)1 << 30)) return c->fail(IMT_ERR_RANGE, "batch too large");
-    if (t->pending.active) return c->fail(IMT_ERR_ARG, "a sharded batch is open (imt_itree_batch_end first)");
-    if (slice_open(t)) return c->fail(IMT_ERR_ARG, "a slice is open (issue its remaining units first)");
-    int rc = c->set_device();
+    int rc = check_batch_call(t, n, flags);
     if (rc) return rc;
     const bool dev = flags & IMT_DEVICE_PTRS;
     if ((rc = check_fe_ptrs(c, dev, {vals})) || (rc = check_out_ptrs(c, dev, out))) return rc;
     if (dev && ((uintptr_t)leaf_index & 7u)) return c->fail(IMT_ERR_ARG, "device leaf_index array is not 8-byte aligned");
     *n_inserted = 0;
 
-    // the plan set the batch will run on: its buffers hold the classification too (insert_core reuses it as it is)
-    const size_t E = 2 * n;
+    // the plan set the batch will run on: its buffers hold the classification too
+    double waited_ms = 0;            // not part of any profile: the host time of the insertion starts in insert_core
     PlanSet& P = t->plan[t->cur];
-    if (P.in_flight) {
-        IMT_HIP(c, hipEventSynchronize(P.done));
-        P.in_flight = false;
-    }
-    if ((rc = plan_reserve(c, P, E, t->depth, t->cap))) return rc;
-    if (dev && (flags & IMT_PIPELINE) && (rc = reserve_all_plans(t, E))) return rc;
-    if (!(dev && (flags & IMT_INPUTS_READY))) {    // as in insert_core: the side stream reads the caller's buffers
-        IMT_HIP(c, hipEventRecord(t->in_mark, c->stream));
-        IMT_HIP(c, hipStreamWaitEvent(t->up_stream, t->in_mark, 0));
-    }
+    if ((rc = acquire_plan(t, 2 * n, 0, waited_ms))) return rc;
+    if (dev && (flags & IMT_PIPELINE) && (rc = reserve_all_plans(t, 2 * n))) return rc;
+    if ((rc = order_behind_caller(t, t->up_stream, flags))) return rc;
     size_t n_acc = 0;
-    const void* acc = nullptr;
+    const void* acc = nullptr;       // the accepted values, canonical: in the plan set (device), or in h_acc (host)
+    unsigned acc_flags = 0;
     std::vector<U256> h_acc;
     if (flags & IMT_HOST_PREP) {
         rc = host_filter(t, vals, n, flags, status, leaf_index, h_acc);
         acc = h_acc.data();
+        acc_flags = IMT_FMT_CANONICAL;
         n_acc = h_acc.size();
     } else {
         rc = gpu_filter(t, P, vals, n, flags, status, leaf_index, n_acc);
         acc = P.fw.acc;
+        acc_flags = IMT_FMT_CANONICAL | IMT_DEVICE_PTRS;
     }
     if (rc) return rc;
-    if (n_acc && (rc = insert_core(t, acc, n_acc, out, flags, true, n, apply))) return rc;
-    if (!n_acc && (rc = unchanged_root())) return rc;
+    if (!n_acc) {
+        if ((rc = unchanged_root())) return rc;
+    } else {
+        if (apply && (rc = check_fe_ptrs(c, dev, {apply->root_out}))) return rc;
+        if ((rc = check_room(t, n_acc))) return rc;
+        // The insertion of the accepted values, on the plan set taken above: insert_core's own acquire_plan finds it idle
+        // and reserved for 2 * n >= 2 * n_acc events, so P.fw.acc stays where it is, and its order_behind_caller repeats
+        // the one above.  The outputs keep the caller's dimensions: level stride n, not n_acc.
+        if ((rc = insert_core(t, acc, acc_flags, n_acc, out, flags, n, apply))) return rc;
+    }
     *n_inserted = n_acc;
     return IMT_OK;
 }
@@ -1752,17 +1859,11 @@ extern "C" int imt_itree_lookup_batch(imt_itree* t, const void* vals, size_t n, 
     if ((rc = join_top(t))) return rc;
     hipStream_t s = c->stream;
     IMT_HIP(c, hipStreamSynchronize(t->up_stream));
-    const uint8_t* d_vals = (const uint8_t*)vals;
+    const uint8_t* d_vals = nullptr;
     int* d_perr = (int*)c->dev_scratch(2, sizeof(int));
     if (!d_perr) return IMT_ERR_HIP;
-    IMT_HIP(c, hipMemsetAsync(d_perr, 0, sizeof(int), s));
-    if (!dev || fmt != IMT_FMT_CANONICAL) {
-        uint8_t* buf = (uint8_t*)c->dev_scratch(0, n * 32);
-        if (!buf) return IMT_ERR_HIP;
-        if (!dev) IMT_HIP(c, hipMemcpyAsync(buf, vals, n * 32, hipMemcpyHostToDevice, s));
-        if (fmt != IMT_FMT_CANONICAL) launch::convert(s, dev ? d_vals : buf, buf, n, fmt, IMT_FMT_CANONICAL, d_perr);
-        d_vals = buf;
-    }
+    uint8_t* buf = (!dev || fmt != IMT_FMT_CANONICAL) ? (uint8_t*)c->dev_scratch(0, n * 32) : nullptr;
+    if ((rc = stage_canonical(c, s, vals, n, flags, buf, buf, d_perr, &d_vals))) return rc;
     uint8_t* d_st = dev ? status : (uint8_t*)c->dev_scratch(3, n);
     uint64_t* d_leaf = (dev || !leaf_index) ? leaf_index : (uint64_t*)c->dev_scratch(1, n * 8);
     if (!d_st || (leaf_index && !d_leaf)) return IMT_ERR_HIP;
@@ -1788,14 +1889,11 @@ extern "C" int imt_itree_batch_begin(imt_itree* t, const void* vals, size_t n, u
     imt_ctx* c = t->ctx;
     IMT_NOT_SLICED(t);
     if (!vals || n == 0) return c->fail(IMT_ERR_ARG, "null / empty batch");
-    if ((flags & IMT_FMT_MASK) == 3) return c->fail(IMT_ERR_ARG, "unknown field-element format");
     if (t->pending.active) return c->fail(IMT_ERR_ARG, "a sharded batch is already open");
-    if (slice_open(t)) return c->fail(IMT_ERR_ARG, "a slice is open (issue its remaining units first)");
-    if (n > ((size_t)1 << 30)) return c->fail(IMT_ERR_RANGE, "batch too large");
-    int rc = c->set_device();
+    int rc = check_batch_call(t, n, flags);
     if (rc) return rc;
     const uint64_t M = t->size;
-    if (M + n > t->cap) return c->fail(IMT_ERR_FULL, "tree capacity %llu exceeded", (unsigned long long)t->cap);
+    if ((rc = check_room(t, n))) return rc;
     if ((rc = join_top(t))) return rc;
     if ((rc = ensure_device_index(t))) return rc;
     const bool dev = flags & IMT_DEVICE_PTRS;
@@ -1804,27 +1902,16 @@ extern "C" int imt_itree_batch_begin(imt_itree* t, const void* vals, size_t n, u
     const size_t E = 2 * n;
     const unsigned L0 = std::min(ceil_log2(M + n), t->depth);
     PlanSet& P = t->plan[t->cur];
-    if (P.in_flight) {
-        IMT_HIP(c, hipEventSynchronize(P.done));
-        P.in_flight = false;
-    }
-    if ((rc = plan_reserve(c, P, E, t->depth, t->cap))) return rc;
+    double waited_ms = 0;       // no profile counts a sharded batch's host time
+    if ((rc = acquire_plan(t, E, 0, waited_ms))) return rc;
     hipStream_t s = c->stream;
+    // context scratch is safe here, unlike in gpu_prepare: everything runs on the context's own stream, behind
+    // whatever used those slots last
     size_t slot = 2;
-    const uint8_t* d_vals = (const uint8_t*)vals;
-    if (!dev) {
-        uint8_t* up = (uint8_t*)c->dev_scratch(slot++, n * 32);
-        if (!up) return IMT_ERR_HIP;
-        IMT_HIP(c, hipMemcpyAsync(up, vals, n * 32, hipMemcpyHostToDevice, s));
-        d_vals = up;
-    }
-    IMT_HIP(c, hipMemsetAsync(P.ws.err, 0, sizeof(int), s));
-    if (fmt != IMT_FMT_CANONICAL) {
-        uint8_t* can = (uint8_t*)c->dev_scratch(slot++, n * 32);
-        if (!can) return IMT_ERR_HIP;
-        launch::convert(s, d_vals, can, n, fmt, IMT_FMT_CANONICAL, P.ws.err);
-        d_vals = can;
-    }
+    const uint8_t* d_vals = nullptr;
+    uint8_t* up = dev ? nullptr : (uint8_t*)c->dev_scratch(slot++, n * 32);
+    uint8_t* can = fmt == IMT_FMT_CANONICAL ? nullptr : (uint8_t*)c->dev_scratch(slot++, n * 32);
+    if ((rc = stage_canonical(c, s, vals, n, flags, up, can, P.ws.err, &d_vals))) return rc;
     IMT_HIP(c, hipStreamSynchronize(t->up_stream));
     P.ws.part_mod = t->part_mod;
     P.ws.part_res = t->part_res;
@@ -1833,23 +1920,10 @@ extern "C" int imt_itree_batch_begin(imt_itree* t, const void* vals, size_t n, u
                          P.ws.o_low, P.ws.o_largest, P.ws.o_lowleaf, P.ws.o_newleaf));
     IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, s));
     IMT_HIP(c, hipStreamSynchronize(s));
-    const int perr = *t->h_err_pin;
-    if (perr & prep::ERR_NONCANONICAL) return c->fail(IMT_ERR_NONCANONICAL, "a value is not reduced (>= p)");
-    if (perr & prep::ERR_ZERO) return c->fail(IMT_ERR_VALUE, "value 0 cannot be inserted");
-    if (perr & prep::ERR_FOREIGN)
-        return c->fail(IMT_ERR_VALUE, "a value belongs to another subtree (v %% %u != %u)", t->part_mod, t->part_res);
-    if (perr & prep::ERR_DUPLICATE) return c->fail(IMT_ERR_VALUE, "duplicate value (inside the batch or already in the tree)");
+    if ((rc = insertion_verdict(t, *t->h_err_pin, "batch"))) return rc;
     // index phase for every level, with the slot of every event per level
     launch::slot0(s, P.d_tab[0][1], P.d_slot, (uint32_t)E);
-    for (unsigned l = 0; l < L0; l++) {
-        const int a = l & 1, b = a ^ 1;
-        const uint32_t* time_in = l == 0 ? P.d_tab[0][1] : P.d_timen + (size_t)(l - 1) * P.cap_events;
-        sweep::LevelTable in{P.d_tab[a][0], time_in, P.d_tab[a][2], P.d_tab[a][3]};
-        sweep::LevelOut o{P.d_tab[b][0], P.d_timen + (size_t)l * P.cap_events, P.d_tab[b][2], P.d_tab[b][3],
-                          P.d_from + (size_t)l * P.cap_events, P.d_sibsrc + (size_t)l * P.cap_events,
-                          P.d_nodeb + (size_t)l * P.cap_events, P.d_slot + (size_t)(l + 1) * P.cap_events};
-        launch::merge_level(s, in, o, (uint32_t)E);
-    }
+    index_phase(P, s, E, L0, P.d_slot);
     t->pending.active = true;
     t->pending.n = n;
     t->pending.l0 = L0;
@@ -1884,9 +1958,9 @@ extern "C" int imt_itree_batch_level(imt_itree* t, unsigned level, const void* v
     if (level >= L0) return c->fail(IMT_ERR_RANGE, "level %u >= l0 %u", level, L0);
     if (!val_in || !val_out || (size_t)k_begin + k_count > E) return c->fail(IMT_ERR_RANGE, "slot range outside the batch");
     if (int rc = check_fe_ptrs(c, true, {val_in, val_out})) return rc;
-    const size_t o = (size_t)level * P.cap_events;
-    launch::sweep_level(c->stream, (const uint8_t*)val_in, (uint8_t*)val_out, P.d_from + o, P.d_sibsrc + o, P.d_nodeb + o,
-                        P.d_timen + o, t->d_nodes + t->h_off[level] * 32, t->h_len[level], c->d_zero + (size_t)level * 32,
+    const PlanSet::Level row = P.level(level);
+    launch::sweep_level(c->stream, (const uint8_t*)val_in, (uint8_t*)val_out, row.from, row.sibsrc, row.nodeb, row.timen,
+                        t->nodes(level), t->h_len[level], c->d_zero + (size_t)level * 32,
                         k_begin, k_count, nullptr, nullptr, launch::SibLayout{0, 0}, level, IMT_FMT_DEVICE,
                         c->coop_max_events);
     return IMT_OK;
@@ -1980,13 +2054,10 @@ extern "C" int imt_itree_batch_end(imt_itree* t, const void* const* val_levels, 
     for (unsigned l = 0; l < L0; l++)
         if (int rc = check_fe_ptrs(c, true, {val_levels[l]})) return rc;
     hipStream_t s = c->stream;
-    for (unsigned l = 0; l < L0; l++) {
-        const size_t o = (size_t)l * P.cap_events;
-        launch::writeback(s, (const uint8_t*)val_levels[l], P.d_from + o, P.d_nodeb + o, t->d_nodes + t->h_off[l] * 32,
-                          (uint32_t)E);
-    }
+    for (unsigned l = 0; l < L0; l++)
+        launch::writeback(s, (const uint8_t*)val_levels[l], P.level(l).from, P.level(l).nodeb, t->nodes(l), (uint32_t)E);
     launch::store_top_path(s, (const uint8_t*)top_path, t->d_nodes, t->d_off, L0, t->depth);
-    IMT_HIP(c, hipMemcpyAsync(P.d_root, t->d_nodes + t->h_off[t->depth] * 32, 32, hipMemcpyDeviceToDevice, s));
+    IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
     P.has_root = true;
     IMT_HIP(c, hipEventRecord(P.done, s));
     P.in_flight = true;
@@ -2069,27 +2140,6 @@ extern "C" size_t imt_itree_slice_unit_bytes(const imt_itree* t, uint64_t size_b
     return slice_unit_bytes(size_before, n, unit, t->depth);
 }
 
-// A host wait with a time limit (limit_ms <= 0: wait as long as it takes): the sliced mode's waits stand behind work
-// that stands behind collectives, i.e. behind other ranks -- a peer that died would otherwise hang the caller for good.
-// IMT_ERR_TIMEOUT leaves the stream as it is (still busy); the caller gives the world up.
-template <class Query, class Sync>
-static int bounded_wait(imt_ctx* c, double limit_ms, Query query, Sync sync, const char* what) {
-    if (limit_ms <= 0) {
-        const hipError_t e = sync();
-        return e == hipSuccess ? IMT_OK : c->hip_fail(e, what);
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0;; spins++) {
-        const hipError_t e = query();
-        if (e == hipSuccess) return IMT_OK;
-        if (e != hipErrorNotReady) return c->hip_fail(e, what);
-        if (spins > 2000) std::this_thread::sleep_for(std::chrono::microseconds(50));     // ~0.1 ms of pure polling first
-        if ((spins & 63) == 63 &&
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > limit_ms)
-            return c->fail(IMT_ERR_TIMEOUT, "gave up after %.0f ms waiting for %s", limit_ms, what);
-    }
-}
-
 extern "C" int imt_itree_slice_prepare(imt_itree* t, const void* vals, size_t n_before, size_t n_own, size_t n_after,
                                        const imt_insert_out* out, unsigned flags, int* slice_out, uint32_t* l0_out) {
     if (!t) return IMT_ERR_ARG;
@@ -2102,26 +2152,20 @@ extern "C" int imt_itree_slice_prepare(imt_itree* t, const void* vals, size_t n_
     const size_t n_all = n_before + n_own + n_after;
     if (n_all > ((size_t)1 << 30)) return c->fail(IMT_ERR_RANGE, "step too large");
     const uint64_t M0 = t->size;
-    if (M0 + n_all > t->cap) return c->fail(IMT_ERR_FULL, "tree capacity %llu exceeded", (unsigned long long)t->cap);
-    int rc = c->set_device();
+    int rc = check_room(t, n_all);
     if (rc) return rc;
+    if ((rc = c->set_device())) return rc;
     if ((rc = ensure_device_index(t))) return rc;
     if ((rc = check_fe_ptrs(c, true, {vals})) || (rc = check_out_ptrs(c, true, out))) return rc;
     const unsigned fmt = flags & IMT_FMT_MASK;
     const int set = t->cur;
     PlanSet& P = t->plan[set];
     if (P.open) return c->fail(IMT_ERR_ARG, "too many slices prepared ahead (%d plan sets)", imt_itree::NSETS);
-    if (P.in_flight) {
-        const auto w0 = std::chrono::steady_clock::now();
-        rc = bounded_wait(c, t->slice_wait_limit_ms, [&] { return hipEventQuery(P.done); }, [&] { return hipEventSynchronize(P.done); },
-                          "the plan set's previous slice");
-        const double waited = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-        t->slice_wait_ms += waited;
-        t->slice_backpressure_ms += waited;
-        if (rc) return rc;
-        P.in_flight = false;
-    }
-    if ((rc = plan_reserve(c, P, 2 * n_own, t->depth, t->cap))) return rc;
+    double waited_ms = 0;
+    rc = acquire_plan(t, 2 * n_own, t->slice_wait_limit_ms, waited_ms);
+    t->slice_wait_ms += waited_ms;
+    t->slice_backpressure_ms += waited_ms;
+    if (rc) return rc;
     if ((rc = reserve_all_plans(t, 2 * n_own))) return rc;
     if (n_before || n_after)
         if ((rc = fws_reserve(t, std::max(n_before, n_after)))) return rc;
@@ -2132,24 +2176,19 @@ extern "C" int imt_itree_slice_prepare(imt_itree* t, const void* vals, size_t n_
     // host: each is waited for (the verdict) before the call returns.
     hipStream_t ps = t->slice_prep_stream ? t->slice_prep_stream : t->up_stream;
     if (t->slice_prep_stream) IMT_HIP(c, hipStreamSynchronize(t->up_stream));      // whatever an earlier call left there
-    if (!(flags & IMT_INPUTS_READY)) {
-        IMT_HIP(c, hipEventRecord(t->in_mark, c->stream));
-        IMT_HIP(c, hipStreamWaitEvent(ps, t->in_mark, 0));
+    if ((rc = order_behind_caller(t, ps, flags))) return rc;
+    // the whole step's values go through a buffer of the tree's own: the plan set's holds one slice, and context scratch
+    // is not safe on this stream (see gpu_prepare)
+    if (fmt != IMT_FMT_CANONICAL && t->canon_all_cap < n_all * 32) {
+        IMT_HIP(c, hipStreamSynchronize(ps));
+        if (t->d_canon_all) hipFree(t->d_canon_all);
+        t->d_canon_all = nullptr;
+        t->canon_all_cap = 0;
+        IMT_HIP(c, hipMalloc((void**)&t->d_canon_all, n_all * 40));
+        t->canon_all_cap = n_all * 40;
     }
-    IMT_HIP(c, hipMemsetAsync(P.ws.err, 0, sizeof(int), ps));
-    const uint8_t* d_vals = (const uint8_t*)vals;
-    if (fmt != IMT_FMT_CANONICAL) {
-        if (t->canon_all_cap < n_all * 32) {
-            IMT_HIP(c, hipStreamSynchronize(ps));
-            if (t->d_canon_all) hipFree(t->d_canon_all);
-            t->d_canon_all = nullptr;
-            t->canon_all_cap = 0;
-            IMT_HIP(c, hipMalloc((void**)&t->d_canon_all, n_all * 40));
-            t->canon_all_cap = n_all * 40;
-        }
-        launch::convert(ps, d_vals, t->d_canon_all, n_all, fmt, IMT_FMT_CANONICAL, P.ws.err);
-        d_vals = t->d_canon_all;
-    }
+    const uint8_t* d_vals = nullptr;
+    if ((rc = stage_canonical(c, ps, vals, n_all, flags, nullptr, t->d_canon_all, P.ws.err, &d_vals))) return rc;
     // ---- the index, in the order of the step: the slices before this one, this one (with its events), those after.
     // Up to three merges, none of which may write the committed index (a refused step leaves the tree as it was): they
     // go committed -> ... -> spare, through a third buffer when there are two or three of them.
@@ -2187,15 +2226,7 @@ extern "C" int imt_itree_slice_prepare(imt_itree* t, const void* vals, size_t n_
     // ---- this slice's index phase (no hashing) on the side stream as well ----
     const size_t E = 2 * n_own;
     const unsigned L0 = std::min(ceil_log2(M_own + n_own), t->depth);
-    for (unsigned l = 0; l < L0; l++) {
-        const int a = l & 1, b = a ^ 1;
-        const uint32_t* time_in = l == 0 ? P.d_tab[0][1] : P.d_timen + (size_t)(l - 1) * P.cap_events;
-        sweep::LevelTable in{P.d_tab[a][0], time_in, P.d_tab[a][2], P.d_tab[a][3]};
-        sweep::LevelOut o{P.d_tab[b][0], P.d_timen + (size_t)l * P.cap_events, P.d_tab[b][2], P.d_tab[b][3],
-                          P.d_from + (size_t)l * P.cap_events, P.d_sibsrc + (size_t)l * P.cap_events,
-                          P.d_nodeb + (size_t)l * P.cap_events, nullptr};
-        launch::merge_level(ps, in, o, (uint32_t)E);
-    }
+    index_phase(P, ps, E, L0, nullptr);
     if (out && fmt != IMT_FMT_CANONICAL) {
         if (out->low_leaf) launch::convert(ps, (uint8_t*)out->low_leaf, (uint8_t*)out->low_leaf, n_own * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
         if (out->new_leaf) launch::convert(ps, (uint8_t*)out->new_leaf, (uint8_t*)out->new_leaf, n_own * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
@@ -2208,16 +2239,14 @@ extern "C" int imt_itree_slice_prepare(imt_itree* t, const void* vals, size_t n_
         if (&pl != &P && pl.in_flight && !pl.sliced) IMT_HIP(c, hipStreamWaitEvent(ps, pl.done, 0));
     IMT_HIP(c, hipEventRecord(P.prep_done, ps));
     {
-        const auto w0 = std::chrono::steady_clock::now();
+        const HostTimer w;
         rc = bounded_wait(c, t->slice_wait_limit_ms, [&] { return hipStreamQuery(ps); }, [&] { return hipStreamSynchronize(ps); },
                           "the step's preparation (its value check)");
-        t->slice_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+        t->slice_wait_ms += w.ms();
         if (rc) return rc;
     }
-    const int perr = *t->h_err_pin;      // the same verdict on every GPU: they all see all values of the step
-    if (perr & prep::ERR_NONCANONICAL) return c->fail(IMT_ERR_NONCANONICAL, "a value is not reduced (>= p)");
-    if (perr & prep::ERR_ZERO) return c->fail(IMT_ERR_VALUE, "value 0 cannot be inserted");
-    if (perr & prep::ERR_DUPLICATE) return c->fail(IMT_ERR_VALUE, "duplicate value (inside the step or already in the tree)");
+    // the same verdict on every GPU: they all see all values of the step (none is foreign: a sliced tree has no partition)
+    if ((rc = insertion_verdict(t, *t->h_err_pin, "step"))) return rc;
     // ---- commit the index; the hashing follows unit by unit ----
     t->sorted_cur ^= 1;          // chain[n_merges] == spare
     t->size = M0 + n_all;
@@ -2253,59 +2282,43 @@ extern "C" int imt_itree_slice_unit(imt_itree* t, int slice, unsigned unit, void
     const unsigned L0 = P.l0, depth = t->depth, fmt = P.slice_fmt;
     const imt_insert_out& o = P.slice_out;
     uint8_t* pl = (uint8_t*)payload;
-    uint8_t* root_node = t->d_nodes + t->h_off[depth] * 32;
     P.slice_next_unit = unit + 1;
     if (unit == 0) {
         IMT_HIP(c, hipStreamWaitEvent(s, P.prep_done, 0));
-        int pf = c->prof_begin(IMT_PROF_LEAVES, s);
-        launch::sweep_leaves(s, P.d_pre, P.d_tab[0][1], P.d_val[0], 0, (uint32_t)E, IMT_FMT_CANONICAL, c->d_err, c->coop_max_events);
-        c->prof_end(pf, s);
+        sweep_leaf_hashes(t, P, s, E);
         return IMT_OK;
     }
     const unsigned l = unit - 1;
-    uint8_t* g_old = (uint8_t*)o.old_root;
     if (l < L0) {
-        const size_t off = (size_t)l * P.cap_events;
+        sweep_one_level(t, P, s, l, E, o, P.slice_lay, fmt);
+        const PlanSet::Level row = P.level(l);
         const uint8_t* vin = P.d_val[l & 1];
-        int pf = c->prof_begin(IMT_PROF_LEVEL, s);
-        launch::sweep_level(s, vin, P.d_val[(l & 1) ^ 1], P.d_from + off, P.d_sibsrc + off, P.d_nodeb + off, P.d_timen + off,
-                            t->d_nodes + t->h_off[l] * 32, t->h_len[l], c->d_zero + (size_t)l * 32, 0, (uint32_t)E,
-                            (uint8_t*)o.low_sib, (uint8_t*)o.new_sib, P.slice_lay, l, fmt, c->coop_max_events);
-        c->prof_end(pf, s);
-        pf = c->prof_begin(IMT_PROF_WRITEBACK, s);
+        const int pf = c->prof_begin(IMT_PROF_WRITEBACK, s);
         if (pl) {       // the write-back, and what the other replicas need to repeat it: (node, value) pairs, packed
             const size_t cap = slice_pairs(P.slice_size_before, n, l);
             IMT_HIP(c, hipMemsetAsync(pl + SLICE_COUNT_AT, 0, 4, s));
             // the pack is the last kernel of this unit (unless it is the round's last, or a profile brackets it): it can
             // signal the tick's event itself
             hipEvent_t tail = (l + 1 != depth && pf < 0) ? t->slice_tail_event : nullptr;
-            launch::pack_writeback(s, vin, P.d_from + off, P.d_nodeb + off, (uint32_t)E, t->d_nodes + t->h_off[l] * 32,
-                                   pl + SLICE_HDR, (uint32_t*)(pl + SLICE_HDR + cap * 32), (uint32_t*)(pl + SLICE_COUNT_AT),
-                                   (uint32_t)cap, tail);
+            launch::pack_writeback(s, vin, row.from, row.nodeb, (uint32_t)E, t->nodes(l), pl + SLICE_HDR,
+                                   (uint32_t*)(pl + SLICE_HDR + cap * 32), (uint32_t*)(pl + SLICE_COUNT_AT), (uint32_t)cap, tail);
             if (tail) t->slice_tail_attached = true;
         } else {
-            launch::writeback(s, vin, P.d_from + off, P.d_nodeb + off, t->d_nodes + t->h_off[l] * 32, (uint32_t)E);
+            launch::writeback(s, vin, row.from, row.nodeb, t->nodes(l), (uint32_t)E);
         }
         c->prof_end(pf, s);
     } else {
-        if (l + 1 == depth && g_old)
-            launch::convert(s, root_node, g_old, 1, IMT_FMT_DEVICE, fmt, c->d_err);
-        uint8_t* node_in = l == L0 ? t->d_nodes + t->h_off[l] * 32 : nullptr;
-        uint8_t* node_out = t->d_nodes + t->h_off[l + 1] * 32;
-        int pf = c->prof_begin(IMT_PROF_TOP, s);
-        launch::sweep_upper(s, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], c->d_zero + (size_t)l * 32, 0, (uint32_t)E, (uint32_t)E - 1,
-                            node_in, node_out, (uint8_t*)o.low_sib, (uint8_t*)o.new_sib, P.slice_lay, l, fmt, c->coop_max_events);
-        c->prof_end(pf, s);
-        if (pl) {
-            if (node_in) IMT_HIP(c, hipMemcpyAsync(pl, node_in, 32, hipMemcpyDeviceToDevice, s));
-            IMT_HIP(c, hipMemcpyAsync(pl + 32, node_out, 32, hipMemcpyDeviceToDevice, s));
+        if (l + 1 == depth) read_old_root(t, s, o, fmt);
+        sweep_one_upper(t, P, s, l, E, L0, o, P.slice_lay, fmt);
+        if (pl) {       // the two nodes the launch stored: the one at L0 (its own input), the one above
+            if (l == L0) IMT_HIP(c, hipMemcpyAsync(pl, t->nodes(l), 32, hipMemcpyDeviceToDevice, s));
+            IMT_HIP(c, hipMemcpyAsync(pl + 32, t->nodes(l + 1), 32, hipMemcpyDeviceToDevice, s));
         }
     }
     if (l + 1 == depth) {       // the last unit: roots of every event, the batch's root, done
-        if (L0 == depth && g_old) launch::convert(s, root_node, g_old, 1, IMT_FMT_DEVICE, fmt, c->d_err);
-        launch::emit_roots(s, P.d_val[depth & 1], 0, (uint32_t)E, (uint32_t)E, g_old, (uint8_t*)o.interim_root,
-                           (uint8_t*)o.new_root, fmt, nullptr, L0 == depth ? root_node : nullptr);
-        if (pl && L0 == depth) IMT_HIP(c, hipMemcpyAsync(pl + 64, root_node, 32, hipMemcpyDeviceToDevice, s));
+        if (L0 == depth) read_old_root(t, s, o, fmt);
+        finish_roots(t, P, s, E, L0, o, fmt);
+        if (pl && L0 == depth) IMT_HIP(c, hipMemcpyAsync(pl + 64, t->nodes(depth), 32, hipMemcpyDeviceToDevice, s));
         P.has_root = false;         // the root after THIS slice is a mid-step root on every rank but the last: not offered
         IMT_HIP(c, hipEventRecord(P.done, s));
         P.in_flight = true;
@@ -2335,13 +2348,13 @@ extern "C" int imt_itree_slice_apply(imt_itree* t, uint64_t size_before, size_t 
     if (l < L0) {
         const size_t cap = slice_pairs(size_before, n, l);
         launch::apply_packed(s, pl + SLICE_HDR, (const uint32_t*)(pl + SLICE_HDR + cap * 32), (const uint32_t*)(pl + SLICE_COUNT_AT),
-                             (uint32_t)cap, t->d_nodes + t->h_off[l] * 32, t->h_len[l]);
+                             (uint32_t)cap, t->nodes(l), t->h_len[l]);
     } else {
-        if (l == L0) IMT_HIP(c, hipMemcpyAsync(t->d_nodes + t->h_off[l] * 32, pl, 32, hipMemcpyDeviceToDevice, s));
-        IMT_HIP(c, hipMemcpyAsync(t->d_nodes + t->h_off[l + 1] * 32, pl + 32, 32, hipMemcpyDeviceToDevice, s));
+        if (l == L0) IMT_HIP(c, hipMemcpyAsync(t->nodes(l), pl, 32, hipMemcpyDeviceToDevice, s));
+        IMT_HIP(c, hipMemcpyAsync(t->nodes(l + 1), pl + 32, 32, hipMemcpyDeviceToDevice, s));
     }
     if (l + 1 == depth && L0 == depth)
-        IMT_HIP(c, hipMemcpyAsync(t->d_nodes + t->h_off[depth] * 32, pl + 64, 32, hipMemcpyDeviceToDevice, s));
+        IMT_HIP(c, hipMemcpyAsync(t->nodes(depth), pl + 64, 32, hipMemcpyDeviceToDevice, s));
     return IMT_OK;
 }
 
@@ -2377,11 +2390,11 @@ extern "C" int imt_itree_slice_apply_gathered(imt_itree* t, const void* gathered
         if (l < L0) {
             j.pairs = 1;
             j.cap = (uint32_t)slice_pairs(size_before[r], (size_t)n[r], l);
-            j.tree_l = t->d_nodes + t->h_off[l] * 32;
+            j.tree_l = t->nodes(l);
             j.len_l = t->h_len[l];
         } else {
-            if (l == L0) j.node_in = t->d_nodes + t->h_off[l] * 32;
-            j.node_out = t->d_nodes + t->h_off[l + 1] * 32;
+            if (l == L0) j.node_in = t->nodes(l);
+            j.node_out = t->nodes(l + 1);
         }
         if (l + 1 == depth && L0 == depth) {
             if (j.pairs) {      // pairs and the root from one payload: the root goes as a job of its own
@@ -2389,9 +2402,9 @@ extern "C" int imt_itree_slice_apply_gathered(imt_itree* t, const void* gathered
                 launch::ApplyJobs::Job& k = jobs.j[jobs.n_jobs++];
                 k = launch::ApplyJobs::Job{};
                 k.payload = (const uint8_t*)gathered + r * stride;
-                k.root = t->d_nodes + t->h_off[depth] * 32;
+                k.root = t->nodes(depth);
             } else {
-                j.root = t->d_nodes + t->h_off[depth] * 32;
+                j.root = t->nodes(depth);
             }
         }
         if (jobs.n_jobs >= 15) { launch::apply_gathered(s, jobs); jobs.n_jobs = 0; }
