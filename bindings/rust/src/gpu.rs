@@ -167,6 +167,17 @@ impl IndexedTree {
         check(&g, unsafe { imt_itree_apply_stats(self.handle, h.as_mut_ptr()) })?;
         Ok(h)
     }
+    /// The tree as it was when it held `new_size` leaves (sentinel included): what a reorg needs.  Returns the root and
+    /// the hashes per level the call spent.
+    pub fn rewind<F: ScalarField>(&mut self, new_size: u64) -> Result<(F, Vec<u64>), ImtError> {
+        let g = context().lock().unwrap();
+        let mut r = [0u8; 32];
+        let mut h = vec![0u64; self.depth + 1];
+        check(&g, unsafe {
+            imt_itree_rewind(self.handle, new_size, r.as_mut_ptr() as *mut c_void, h.as_mut_ptr(), IMT_FMT_CANONICAL)
+        })?;
+        Ok((F::from_bytes_le(&r), h))
+    }
     /// n sequential insertions; one [`InsertWitness`] each (66 hashes per insertion at depth 32, all on the GPU)
     pub fn insert_batch<F: ScalarField>(&mut self, vals: &[F]) -> Result<Vec<InsertWitness<F>>, ImtError> {
         let g = context().lock().unwrap();

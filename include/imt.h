@@ -491,6 +491,34 @@ int imt_itree_apply_filtered(imt_itree *t, const void *vals /*[n][32]*/, size_t 
  * produced level-l nodes, l = 1 .. depth -- the number of distinct nodes the batch touched at every level.  Host memory;
  * waits for that call.  IMT_ERR_ARG if there has been none. */
 int imt_itree_apply_stats(imt_itree *t, uint64_t *hashes /*[depth + 1]*/);
+/* GOING BACK, for the same callers when the last blocks are dropped (a reorg, a failed proof, a batch the L1 did not
+ * accept).  The tree as it was when it held new_size leaves (sentinel included; 1 = the empty tree): byte for byte --
+ * index, leaf preimages, every stored node, root -- the tree a fresh imt_itree would be after inserting the first
+ * new_size - 1 values this one received.  Nothing is needed from the caller but the size: the tree stores no preimage,
+ * so the earlier one is a function of the values it still holds (imt_rewind.hpp).  With M = imt_itree_size(t) and
+ * k = M - new_size: one pass over the 4-byte-per-leaf index, the stored nodes [ceil(new_size / 2^l), ceil(M / 2^l)) of
+ * every level back to the empty subtree, and one hash per node of
+ *     S_0 = { kept leaves whose successor in value order was removed } + { new_size },  S_(l+1) = { x >> 1 : x in S_l }
+ * -- of the order of an apply batch of k values, where imt_itree_load of a snapshot hashes about 2 * new_size nodes.
+ * Measured against the load of a snapshot already on the device (profiles/rewind.txt): 2.0 to 2.8 times faster for
+ * k = 2^10 .. 2^16 at 2^20 leaves, 4.8 to 19 times for k = 2^10 .. 2^20 at 2^24; no measured k / M, up to 1 / 16, made the
+ * load the better call.
+ * new_size counts local leaves, as imt_itree_size does, on a placed tree too.  new_size == 0 or > M -> IMT_ERR_RANGE, the
+ * tree untouched.  new_size == M: IMT_OK, nothing runs, root_out = the current root, hashes all zero.
+ * root_out: the root afterwards, [32] in the flags' format (IMT_FMT_*), host or device memory per IMT_DEVICE_PTRS, may be
+ * NULL.  hashes, if not NULL: host memory, hashes[l] = |S_l| for l < ceil(log2(M)), 1 for every level from there to depth
+ * (the single chain to the root) -- what the call hashed, level by level.  imt_itree_apply_stats keeps reporting the last
+ * apply call.
+ * The call is rare and synchronous: it orders itself behind everything in flight on this tree (pipelined batches
+ * included; the caller need not synchronise first), returns when the tree is the earlier one, and later calls of any kind
+ * are ordered behind it.  IMT_PIPELINE -> IMT_ERR_ARG.  Refused with the tree untouched, like imt_itree_load: a replica of
+ * a sliced world with steps in flight (imt_sliced_flush first; every replica may then be rewound to the same size), an
+ * open slice, and a sharded batch between imt_itree_batch_begin and _end (IMT_ERR_ARG).
+ * Placement and value partition stay as they are (the relinked leaves' next_idx is global).  Afterwards the host mirror
+ * is rebuilt on demand, so an IMT_HOST_PREP batch works, and imt_itree_root_lagged behaves as after imt_itree_load: it has
+ * no root to give until the next batch. */
+int imt_itree_rewind(imt_itree *t, uint64_t new_size, void *root_out /*[32] or NULL*/,
+                     uint64_t *hashes /*[depth + 1] host, or NULL*/, unsigned flags);
 /* Read-only query of the device-resident index for any mix of values (one kernel, k_lookup): status ZERO / FOREIGN /
  * PRESENT / NEW and leaf_index = the sentinel / UINT64_MAX / the stored leaf / the low leaf (what find_low returns).
  * Fails only for its arguments, a value >= p (IMT_ERR_NONCANONICAL) or a HIP error, never for a value's class.  With

@@ -394,6 +394,14 @@ public:
         c_->check(imt_itree_apply_stats(t_, h.data()));
         return h;
     }
+    // the tree as it was when it held new_size leaves, sentinel included (imt_itree_rewind); returns its root.
+    // hashes, if given: what the call hashed per level ([depth + 1])
+    Fr rewind(uint64_t new_size, std::vector<uint64_t>* hashes = nullptr) {
+        Fr root;
+        if (hashes) hashes->assign(depth_ + 1, 0);
+        c_->check(imt_itree_rewind(t_, new_size, &root, hashes ? hashes->data() : nullptr, IMT_FMT_CANONICAL));
+        return root;
+    }
     std::vector<IndexedMerkleTreeLeaf> get_leaves(const std::vector<uint64_t>& index) {
         std::vector<IndexedMerkleTreeLeaf> out(index.size());
         if (!index.empty()) c_->check(imt_itree_get_leaves(t_, index.data(), index.size(), out.data(), IMT_FMT_CANONICAL));

@@ -154,6 +154,7 @@ SIGNATURES = {
     "imt_itree_apply_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
     "imt_itree_apply_filtered": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, P(c_u64), c_void_p, c_uint]),
     "imt_itree_apply_stats": (c_int, [c_void_p, P(c_u64)]),
+    "imt_itree_rewind": (c_int, [c_void_p, c_u64, c_void_p, P(c_u64), c_uint]),
     "imt_itree_lookup_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_uint]),
     "imt_itree_batch_begin": (c_int, [c_void_p, c_void_p, c_size_t, c_uint, P(ctypes.c_uint32), P(ctypes.c_uint32)]),
     "imt_itree_batch_leaves": (c_int, [c_void_p, c_void_p, ctypes.c_uint32, ctypes.c_uint32]),

@@ -538,6 +538,7 @@ class IndexedTree:
     def __init__(self, ctx, depth, capacity):
         self.ctx, self.depth, self.capacity = ctx, depth, capacity
         self.global_depth, self.index_base = depth, 0
+        self.rewind_stats = None         # hashes per level of the last rewind() (numpy uint64 [depth + 1])
         h = ctypes.c_void_p()
         ctx._check(lib.imt_itree_new(ctx.h, depth, capacity, ctypes.byref(h)))
         self.h = h
@@ -656,6 +657,15 @@ class IndexedTree:
         out = np.empty(self.depth + 1, dtype=np.uint64)
         self.ctx._check(lib.imt_itree_apply_stats(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         return out
+
+    def rewind(self, size):
+        """The tree as it was when it held `size` leaves, sentinel included (imt_itree_rewind): index, preimages, stored
+        nodes and root of a fresh tree fed the first size - 1 values; returns the root.  The hashes per level of the call
+        are kept in rewind_stats."""
+        root, stats = np.empty(32, dtype=np.uint8), np.zeros(self.depth + 1, dtype=np.uint64)
+        self.ctx._check(lib.imt_itree_rewind(self.h, size, _p(root), stats.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), 0))
+        self.rewind_stats = stats
+        return to_int(root)
 
     def lookup(self, vals):
         """(status, leaf_index) of every value against the stored tree (imt_itree_lookup_batch): VAL_PRESENT with the

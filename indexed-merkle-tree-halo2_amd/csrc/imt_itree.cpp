@@ -191,6 +191,7 @@ struct imt_itree {
     // imt_itree_apply_batch: hashes per level of the last apply call, written by its kernels (imt_itree_apply_stats)
     uint64_t* d_apply_stats = nullptr;       // [IMT_MAX_DEPTH + 1]
     bool apply_seen = false;
+    uint64_t* d_rewind_stats = nullptr;      // [IMT_MAX_DEPTH + 1]: the same of the last imt_itree_rewind
 };
 
 static void plan_free(PlanSet& p) {
@@ -332,6 +333,7 @@ extern "C" void imt_itree_free(imt_itree* t) {
     if (t->d_len) hipFree(t->d_len);
     if (t->d_val) hipFree(t->d_val);
     if (t->d_apply_stats) hipFree(t->d_apply_stats);
+    if (t->d_rewind_stats) hipFree(t->d_rewind_stats);
     for (auto q : t->d_sorted)
         if (q) hipFree(q);
     if (t->h_err_pin) hipHostFree(t->h_err_pin);
@@ -375,6 +377,7 @@ extern "C" int imt_itree_new(imt_ctx* c, unsigned depth, uint64_t capacity, imt_
         (e = hipMalloc((void**)&t->d_off, (depth + 1) * 8)) != hipSuccess ||
         (e = hipMalloc((void**)&t->d_len, (depth + 1) * 8)) != hipSuccess ||
         (e = hipMalloc((void**)&t->d_apply_stats, (IMT_MAX_DEPTH + 1) * 8)) != hipSuccess ||
+        (e = hipMalloc((void**)&t->d_rewind_stats, (IMT_MAX_DEPTH + 1) * 8)) != hipSuccess ||
         (e = hipStreamCreateWithFlags(&t->up_stream, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&t->up_done, hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&t->in_mark, hipEventDisableTiming)) != hipSuccess ||
@@ -1365,7 +1368,7 @@ void finish_roots(imt_itree* t, const PlanSet& P, hipStream_t s, size_t E, unsig
 struct ApplyReq {
     void* root_out;
 };
-static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0);
+static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, uint64_t* count);
 
 // The hashing of imt_itree_insert_batch on stream s, behind the preparation: leaf hashes, index phase (no hashing), then
 // the hash sweep level by level with each level's write-back.  prev: the batch before this one if it is still on a
@@ -1552,8 +1555,9 @@ static int insert_core(imt_itree* t, const void* vals, unsigned val_flags, size_
         return IMT_ERR_HIP;
     // a placed tree writes rows [0, depth) of sibling arrays dimensioned for global_depth levels
     const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->global_depth} : launch::SibLayout{sib_stride, 1};
-    rc = apply ? apply_hashes(t, P, s, E, L0) : witness_hashes(t, P, s, E, L0, prev, pipelined, d, lay, fmt);
+    rc = apply ? apply_hashes(t, P, s, E, L0, t->d_apply_stats) : witness_hashes(t, P, s, E, L0, prev, pipelined, d, lay, fmt);
     if (rc) return rc;
+    if (apply) t->apply_seen = true;
     IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
     P.has_root = true;
     IMT_HIP(c, hipEventRecord(P.done, s));
@@ -1610,10 +1614,12 @@ static int insert_call(imt_itree* t, const void* vals, size_t n, const imt_inser
 // The hashing of imt_itree_apply_batch on stream s, behind the preparation: the lists of every level (index work), the
 // touched leaves from their final preimages, then level by level every touched parent from the stored level below --
 // which the launch before has just made final -- and from level L0 - 1 up the single chain to the root.  The launches
-// are sized by host-side bounds; the counts stay on the device (t->d_apply_stats), so nothing here waits for the GPU.
-static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0) {
+// are sized by host-side bounds; the counts stay on the device (`count`, [depth + 1]: t->d_apply_stats for an apply
+// batch), so nothing here waits for the GPU.  imt_itree_rewind hashes through here too: its table has one event per
+// touched leaf, its L0 is that of the size it finds and its counts are its own.
+static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, uint64_t* count) {
     imt_ctx* c = t->ctx;
-    const apply::Lists lists{P.d_nodeb, P.d_timen, t->d_apply_stats, P.cap_events};
+    const apply::Lists lists{P.d_nodeb, P.d_timen, count, P.cap_events};
     int pf = c->prof_begin(IMT_PROF_APPLY_LISTS, s);
     IMT_HIP(c, prep::apply_lists(s, P.ws.tmp, P.ws.tmp_bytes, P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][3], (uint32_t)E, L0,
                                  t->depth, P.d_from, lists));
@@ -1632,7 +1638,6 @@ static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsig
     pf = c->prof_begin(IMT_PROF_APPLY_TOP, s);
     launch::apply_top(s, t->d_nodes, t->d_off, t->d_len, c->d_zero, L0 - 1, t->depth);
     c->prof_end(pf, s);
-    t->apply_seen = true;
     return IMT_OK;
 }
 
@@ -1662,6 +1667,83 @@ extern "C" int imt_itree_apply_stats(imt_itree* t, uint64_t* hashes) {
     // the apply call ran on the context's stream, which is therefore behind its last kernel
     IMT_HIP(c, hipMemcpyAsync(hashes, t->d_apply_stats, (t->depth + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     IMT_HIP(c, hipStreamSynchronize(c->stream));
+    return IMT_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// going back (imt_rewind.hpp)
+// ------------------------------------------------------------------------------------
+extern "C" int imt_itree_rewind(imt_itree* t, uint64_t new_size, void* root_out, uint64_t* hashes, unsigned flags) {
+    if (!t) return IMT_ERR_ARG;
+    imt_ctx* c = t->ctx;
+    IMT_NOT_SLICED(t);
+    if (flags & IMT_PIPELINE) return c->fail(IMT_ERR_ARG, "a rewind is not pipelined (IMT_PIPELINE)");
+    if ((flags & IMT_FMT_MASK) == 3) return c->fail(IMT_ERR_ARG, "unknown field-element format");
+    if (new_size == 0 || new_size > t->size)
+        return c->fail(IMT_ERR_RANGE, "cannot rewind a tree of %llu leaves to %llu", (unsigned long long)t->size,
+                       (unsigned long long)new_size);
+    if (slice_open(t)) return c->fail(IMT_ERR_ARG, "a slice is open (issue its remaining units first)");
+    if (t->pending.active) return c->fail(IMT_ERR_ARG, "a sharded batch is open (imt_itree_batch_end first)");
+    int rc = c->set_device();
+    if (rc) return rc;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    if ((rc = check_fe_ptrs(c, dev, {root_out}))) return rc;
+    const uint64_t M = t->size, S = new_size;
+    if (S == M) {
+        if (hashes) std::memset(hashes, 0, (t->depth + 1) * 8);
+        return root_out ? imt_itree_root(t, root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS)) : IMT_OK;
+    }
+    // ---- behind everything in flight, the caller's stream included: from here on the tree is this call's alone ----
+    if ((rc = ensure_device_index(t))) return rc;
+    if ((rc = join_top(t))) return rc;
+    for (auto& pl : t->plan)
+        if (pl.in_flight) { IMT_HIP(c, hipEventSynchronize(pl.done)); pl.in_flight = false; pl.pipelined = false; }
+    IMT_HIP(c, hipStreamSynchronize(t->up_stream));
+    hipStream_t s = c->stream;
+    const unsigned L0 = std::min(ceil_log2(M), t->depth);       // of the size the call finds: the nodes in use reach that high
+    const size_t max_rows = (size_t)std::min(M - S, S) + 1;
+    struct Trim {           // the scan's places are 8 bytes per leaf of the tree: not something a context keeps
+        imt_ctx* c;
+        ~Trim() { c->trim_scratch(3, (size_t)64 << 20); }
+    } trim{c};
+    const size_t ws_bytes = prep::rewind_ws_bytes((size_t)M, max_rows);
+    void* ws = c->dev_scratch(3, ws_bytes);
+    uint8_t* d_root = (root_out && !dev) ? (uint8_t*)c->dev_scratch(0, 32) : (uint8_t*)root_out;
+    if (!ws || (root_out && !d_root)) return IMT_ERR_HIP;
+    // ---- the index of the earlier tree into the other buffer, and how many leaves are relinked ----
+    const uint32_t* sorted_old = t->d_sorted[t->sorted_cur];
+    uint32_t* sorted_new = t->d_sorted[t->sorted_cur ^ 1];
+    const uint32_t* d_relinked = nullptr;
+    uint32_t R = 0;
+    IMT_HIP(c, prep::rewind_compact(s, ws, ws_bytes, sorted_old, sorted_new, (uint32_t)M, (uint32_t)S, &d_relinked));
+    IMT_HIP(c, hipMemcpyAsync(&R, d_relinked, sizeof(R), hipMemcpyDeviceToHost, s));
+    IMT_HIP(c, hipStreamSynchronize(s));
+    if ((size_t)R + 1 > max_rows) return c->fail(IMT_ERR_INTERNAL, "rewind: %u relinked leaves, at most %zu expected", R, max_rows - 1);
+    const size_t E = (size_t)R + 1;                             // one event per touched leaf: the relinked ones and slot S
+    // ---- a plan set owns the tables and the lists; nothing of the tree has been written up to here ----
+    PlanSet& P = t->plan[t->cur];
+    double waited = 0;
+    if ((rc = acquire_plan(t, E, 0, waited))) return rc;
+    IMT_HIP(c, prep::rewind_table(s, ws, ws_bytes, t->d_val, sorted_old, sorted_new, (uint32_t)M, (uint32_t)S, t->index_base,
+                                  (uint32_t)E, P.d_tab[1][0], P.d_tab[1][1], P.d_pre, P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][2],
+                                  P.d_tab[0][3]));
+    prep::rewind_refill(s, t->d_nodes, t->d_off, t->d_len, c->d_zero, S, M, L0);
+    if ((rc = apply_hashes(t, P, s, E, L0, t->d_rewind_stats))) return rc;
+    if (root_out) launch::convert(s, t->nodes(t->depth), d_root, 1, IMT_FMT_DEVICE, fmt, c->d_err);
+    if (root_out && !dev) IMT_HIP(c, hipMemcpyAsync(root_out, d_root, 32, hipMemcpyDeviceToHost, s));
+    if (hashes) IMT_HIP(c, hipMemcpyAsync(hashes, t->d_rewind_stats, (t->depth + 1) * 8, hipMemcpyDeviceToHost, s));
+    // ---- everything is enqueued: the earlier tree is the tree ----
+    t->sorted_cur ^= 1;
+    t->size = S;
+    t->pre.clear();
+    t->pre.shrink_to_fit();
+    t->sorted.clear();
+    t->sorted.shrink_to_fit();
+    t->mirror_valid = false;
+    t->dev_index_valid = true;
+    for (auto& pl : t->plan) pl.has_root = false;
+    IMT_HIP(c, hipStreamSynchronize(s));
     return IMT_OK;
 }
 

@@ -7,6 +7,7 @@
 #include "imt_prep.hpp"
 #include "imt_prep_logic.hpp"
 #include "imt_filter_logic.hpp"
+#include "imt_rewind.hpp"
 
 namespace imt {
 namespace prep {
@@ -346,7 +347,106 @@ __global__ void __launch_bounds__(BLOCK) k_apply_scatter(const uint32_t* __restr
     apply::scatter_element(node, time, re, total, x, l, pos[(size_t)l * o.stride + x], l0, depth, o);
 }
 
+
+// ---- going back (imt_itree_rewind, imt_rewind.hpp): 4 .. 36 bytes per index entry, no field arithmetic ----
+struct RewindFlag {
+    const uint32_t* sorted;
+    uint32_t M, s;
+    __device__ uint64_t operator()(uint32_t j) const { return rewind::scan_flag(sorted, M, j, s); }
+};
+typedef rocprim::transform_iterator<rocprim::counting_iterator<uint32_t>, RewindFlag, uint64_t> RewindIter;
+inline RewindIter rewind_iter(const uint32_t* sorted, uint32_t M, uint32_t s) {
+    return RewindIter(rocprim::counting_iterator<uint32_t>(0), RewindFlag{sorted, M, s});
+}
+size_t rewind_tmp_bytes(size_t M, size_t rows) {
+    size_t a = 0, b = 0;
+    (void)rocprim::exclusive_scan(nullptr, a, rewind_iter(nullptr, 0, 0), (uint64_t*)nullptr, (uint64_t)0, M,
+                                  rocprim::plus<uint64_t>(), nullptr);
+    (void)rocprim::radix_sort_pairs(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                                    (uint32_t*)nullptr, rows, 0, 32, nullptr);
+    return (a > b ? a : b) + 256;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_rewind_compact(const uint32_t* __restrict__ sorted, uint32_t M, uint32_t s,
+                                                          const uint64_t* __restrict__ pos, uint32_t* __restrict__ out,
+                                                          uint32_t* __restrict__ n_relinked) {
+    const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= M) return;
+    rewind::compact_element(sorted, M, j, s, pos[j], out, n_relinked);
+}
+
+__global__ void __launch_bounds__(BLOCK) k_rewind_relink(const uint8_t* __restrict__ d_val, const uint32_t* __restrict__ sorted,
+                                                         const uint32_t* __restrict__ compact, uint32_t M, uint32_t s,
+                                                         const uint64_t* __restrict__ pos, uint64_t base, rewind::Table t) {
+    const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= M) return;
+    rewind::relink_element(d_val, sorted, compact, M, j, s, pos[j], base, t);
+}
+
+// blockIdx.y = level: the nodes the earlier tree does not fill are the empty subtree of their height again
+__global__ void __launch_bounds__(BLOCK) k_rewind_refill(uint8_t* __restrict__ nodes, const uint64_t* __restrict__ off,
+                                                         const uint64_t* __restrict__ len, const uint8_t* __restrict__ zero,
+                                                         uint64_t s, uint64_t M) {
+    const unsigned l = blockIdx.y;
+    uint64_t lo, hi;
+    rewind::refill_range(s, M, l, &lo, &hi);
+    const uint64_t x = lo + (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (x >= hi || x >= len[l]) return;
+    copy32(nodes + (off[l] + x) * 32, zero + (size_t)l * 32);
+}
+
 }  // namespace
+
+size_t rewind_ws_bytes(size_t M, size_t rows) { return (M * 8 + 255) / 256 * 256 + 256 + rewind_tmp_bytes(M, rows); }
+
+namespace {
+struct RewindLayout {
+    uint64_t* pos;
+    uint32_t* count;
+    void* tmp;
+    size_t tmp_bytes;
+};
+inline RewindLayout rewind_layout(void* ws, size_t ws_bytes, size_t M) {
+    uint8_t* w = (uint8_t*)ws;
+    const size_t p = (M * 8 + 255) / 256 * 256;
+    return {(uint64_t*)w, (uint32_t*)(w + p), w + p + 256, ws_bytes - p - 256};
+}
+}  // namespace
+
+hipError_t rewind_compact(hipStream_t st, void* ws, size_t ws_bytes, const uint32_t* sorted_old, uint32_t* sorted_new,
+                          uint32_t M, uint32_t s, const uint32_t** n_relinked) {
+    if (s == 0 || s >= M || rewind_ws_bytes(M, 1) > ws_bytes) return hipErrorInvalidValue;
+    const RewindLayout w = rewind_layout(ws, ws_bytes, M);
+    hipError_t e;
+    (void)hipGetLastError();
+    size_t tb = w.tmp_bytes;
+    if ((e = rocprim::exclusive_scan(w.tmp, tb, rewind_iter(sorted_old, M, s), w.pos, (uint64_t)0, (size_t)M,
+                                     rocprim::plus<uint64_t>(), st)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_rewind_compact, dim3(nblk(M)), dim3(BLOCK), 0, st, sorted_old, M, s, w.pos, sorted_new, w.count);
+    *n_relinked = w.count;
+    return hipGetLastError();
+}
+
+hipError_t rewind_table(hipStream_t st, void* ws, size_t ws_bytes, const uint8_t* d_val, const uint32_t* sorted_old,
+                        const uint32_t* sorted_new, uint32_t M, uint32_t s, uint64_t base, uint32_t rows, uint32_t* key,
+                        uint32_t* row, uint8_t* pre, uint32_t* node, uint32_t* time, uint32_t* rs, uint32_t* re) {
+    if (s == 0 || s >= M || rows == 0 || rows > s + 1 || rewind_ws_bytes(M, rows) > ws_bytes) return hipErrorInvalidValue;
+    const RewindLayout w = rewind_layout(ws, ws_bytes, M);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_rewind_relink, dim3(nblk(M)), dim3(BLOCK), 0, st, d_val, sorted_old, sorted_new, M, s, w.pos, base,
+                       rewind::Table{key, row, rs, re, pre, rows});
+    size_t tb = w.tmp_bytes;
+    hipError_t e;
+    if ((e = rocprim::radix_sort_pairs(w.tmp, tb, key, node, row, time, (size_t)rows, 0, 32, st)) != hipSuccess) return e;
+    return hipGetLastError();
+}
+
+void rewind_refill(hipStream_t st, uint8_t* nodes, const uint64_t* off, const uint64_t* len, const uint8_t* zero, uint64_t s,
+                   uint64_t M, unsigned l0) {
+    if (s >= M || l0 == 0) return;
+    hipLaunchKernelGGL(k_rewind_refill, dim3(nblk(M - s), l0), dim3(BLOCK), 0, st, nodes, off, len, zero, s, M);
+}
 
 hipError_t apply_lists(hipStream_t s, void* tmp, size_t tmp_bytes, const uint32_t* node, const uint32_t* time,
                        const uint32_t* re, uint32_t total, unsigned l0, unsigned depth, uint32_t* pos,

@@ -80,6 +80,25 @@ hipError_t apply_lists(hipStream_t s, void* tmp, size_t tmp_bytes, const uint32_
                        const uint32_t* re, uint32_t total, unsigned l0, unsigned depth, uint32_t* pos,
                        const apply::Lists& lists);
 
+// ---- going back (imt_itree_rewind): the index, the relinked leaves and the emptied nodes (imt_rewind.hpp) ----
+// ws: rewind_ws_bytes(M, rows) bytes of device memory, 256-byte aligned, the same block for both calls (rows: the most
+// table rows rewind_table will be asked for; 1 if only rewind_compact runs).
+size_t rewind_ws_bytes(size_t M, size_t rows);
+// sorted_new[0 .. s) = the entries < s of sorted_old[0 .. M) in their order (1 <= s < M); *n_relinked = a device word
+// inside ws that holds the number R of relinked leaves when the stream gets there.  Writes nothing but ws and sorted_new.
+hipError_t rewind_compact(hipStream_t st, void* ws, size_t ws_bytes, const uint32_t* sorted_old, uint32_t* sorted_new,
+                          uint32_t M, uint32_t s, const uint32_t** n_relinked);
+// Behind rewind_compact, rows = R + 1: the preimages pre[rows][96] of the relinked leaves and of the empty slot s, and
+// the level-0 table apply_lists reads -- node (positions ascending), time (the preimage row of each), rs / re (runs of
+// one).  key / row: [rows] scratch for the unsorted table.  Writes nothing of the tree.
+hipError_t rewind_table(hipStream_t st, void* ws, size_t ws_bytes, const uint8_t* d_val, const uint32_t* sorted_old,
+                        const uint32_t* sorted_new, uint32_t M, uint32_t s, uint64_t base, uint32_t rows, uint32_t* key,
+                        uint32_t* row, uint8_t* pre, uint32_t* node, uint32_t* time, uint32_t* rs, uint32_t* re);
+// stored nodes [ceil(s / 2^l), ceil(M / 2^l)) of every level l < l0 (2^l0 >= M) = zero[l], one launch; nodes / off / len:
+// the tree's node array and its per-level offsets and lengths (device), zero: [l0][32] in the stored format
+void rewind_refill(hipStream_t st, uint8_t* nodes, const uint64_t* off, const uint64_t* len, const uint8_t* zero, uint64_t s,
+                   uint64_t M, unsigned l0);
+
 // ---- filtered insertion (imt_itree_insert_filtered): which values of a batch are inserted ----
 struct FilterWs {             // per plan set, sized for `cap_n` values
     size_t cap_n = 0;
