@@ -1,0 +1,258 @@
+"""GPU (MI355X): an indexed tree under mixed sequences of its writers and readers.
+
+imt_itree keeps its sorted list twice -- the host mirror and the device index -- and synchronises the copies lazily:
+every call that changes the tree leaves another combination of mirror_valid / dev_index_valid / sorted_cur / batches in
+flight behind, and every call that reads the list picks its path from those and from the pointer mode.  The other GPU
+tests follow one writer each; this one walks the transitions.  test_sequence plays the committed scripts of
+tests/tree_model.py (every ordered pair of the ten writer kinds adjacent with a light and with a full check between
+them, every kind right after a refused call; tests/test_tree_model.py asserts that coverage) on an IndexedTree beside
+the plain-Python model.  Expected lists come from the model, expected roots, proofs and witness rows from the CPU oracle
+loaded with the model's preimages; every comparison is bit-exact.
+
+  after an accepted step   the call's own outputs (root_out, rewind's root, status / leaf_index / n_inserted, the witness
+                           rows, new_index); a pipelined device-pointer batch is left in flight, its rows are compared at
+                           the next full check
+  after a refused step     the error code; size, root() and the whole snapshot unchanged
+  light check              size and root(): neither touches the two copies of the list
+  full check               size, root(), get_leaves of every slot (host and device pointers), snapshot(), the proof of
+                           every slot, find_low of the probe set (host and device pointers) and its refusals, lookup,
+                           non_membership_witness through the device index and through the host calls, and the witness
+                           against imt_non_membership_batch
+
+Every failure message names the script, the step and the step's kind, so it names the transition.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+import test_gpu_insert_matrix as tm
+import tree_model as tmod
+from oracle_lib import arr_ints, ints_to_arr
+from test_gpu_rewind import DeviceBatches, compare_rows
+
+pytestmark = pytest.mark.gpu
+
+SCRIPTS = {s.name: s for s in tmod.scripts()}
+KIND_NAMES = {1: "insert_batch", 2: "insert_batch host_prep", 3: "insert_batch device pipelined", 4: "insert_filtered",
+              5: "insert_filtered host_prep", 6: "apply_batch", 7: "apply_batch host_prep", 8: "apply_filtered", 9: "rewind",
+              10: "load"}
+N_PROBES = 24
+FOREIGN_PROBES = (5, 6, 8, 9)          # of another residue on the partitioned tree (v % 3 != 1)
+
+
+def _cases():
+    out = [pytest.param(name, "default", id=name) for name in SCRIPTS]
+    for shape_name in ("d32", "part3"):          # two of the scripts on the other two forms of the hash kernels as well
+        name = next(s.name for s in tmod.scripts() if s.shape.name == shape_name)
+        out += [pytest.param(name, form, id=f"{name}-{form}") for form in ("thread", "quad")]
+    return out
+
+
+@pytest.fixture(scope="module")
+def forms(imt):
+    """one context per hash form, all on torch's current stream (the device-pointer calls' buffers are torch's)"""
+    import torch
+    torch.cuda.init()
+    cs = {}
+    for name, coop in tm.FORMS.items():
+        c = imt.Context(0)
+        c.set_stream(torch.cuda.current_stream().cuda_stream)
+        if coop is not None:
+            c.set_option(imt._ffi.OPT_COOP_MAX_EVENTS, coop)
+        cs[name] = c
+    yield cs
+    for c in cs.values():
+        c.close()
+
+
+def _ptr(x):
+    return ctypes.c_void_p(x.data_ptr())
+
+
+class Player:
+    """one script on one tree, the model beside it"""
+
+    def __init__(self, imt, c, script):
+        import torch
+        self.imt, self.c, self.script, self.shape, self.torch = imt, c, script, script.shape, torch
+        sh = script.shape
+        self.t = t = imt.IndexedTree(c, sh.depth, sh.cap)
+        if sh.placement:
+            t.set_placement(*sh.placement)
+        if sh.partition[0]:
+            c._check(imt.lib.imt_itree_set_value_partition(t.h, *sh.partition))
+        self.m = tmod.new_model(sh)
+        self.base = tmod.index_base(sh)
+        self.dv = DeviceBatches(imt, c, t, t.global_depth)
+        self.in_flight = []                       # (device buffers, the oracle's rows, tag) of pipelined batches
+        self.err_name = {v: k for k, v in imt._ffi.ERR.items()}
+
+    def close(self):
+        self.dv.sync()
+        self.t.close()
+
+    def code_of(self, call):
+        """(IMT_ERR_* name or None, the call's result)"""
+        try:
+            return None, call()
+        except ValueError:                        # the Python layer's IMT_ERR_VALUE of insert / apply / load / find_low
+            return "VALUE", None
+        except self.imt.ImtError as e:
+            return self.err_name[e.code], None
+
+    def dev(self, arr):
+        a = np.ascontiguousarray(arr)
+        return self.torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).cuda()
+
+    # ---- the step ----
+    def call(self, st):
+        t, k = self.t, st.kind
+        arr = ints_to_arr(st.vals) if st.vals is not None else None
+        if k in (1, 2):
+            return t.insert_batch(arr, host_prep=(k == 2))
+        if k == 3:
+            return self.dv.insert(arr)
+        if k in (4, 5):
+            return t.insert_filtered(arr, host_prep=(k == 5))
+        if k in (6, 7):
+            return t.apply_batch(arr, host_prep=(k == 7))
+        if k == 8:
+            return t.apply_filtered(arr, host_prep=bool(st.arg))
+        if k == 9:
+            return t.rewind(st.arg)
+        pre = tm.to_fmt(tmod.pre_arr(st.arg["pre"]), st.arg["fmt"])
+        if st.arg["device"]:
+            d = self.dev(pre)
+            return t.load_device(d.data_ptr(), pre.shape[0], st.arg["fmt"])
+        return t.load(pre, st.arg["fmt"])
+
+    def check_rows(self, got, before, acc, tag):
+        n = len(acc)
+        if n == 0:                                # a filtered batch that accepted nothing wrote no row
+            return
+        want = tmod.oracle_rows(self.shape, before, acc)
+        compare_rows(got, want, 0, n, self.shape.depth, tag)
+        new_index = np.arange(len(before), len(before) + n, dtype=np.uint64) + np.uint64(self.base)
+        assert (got["new_index"] == new_index).all(), f"{tag}: new_index"
+
+    def step(self, i, st):
+        t, m, sh = self.t, self.m, self.shape
+        what = f"refused {st.refusal}: {KIND_NAMES[st.kind]}" if st.refusal else KIND_NAMES[st.kind]
+        prev = self.script.steps[i - 1] if i else None
+        came = f" after kind {tmod.writer_kind(prev)} and a {prev.check} check" if prev else ""
+        tag = f"{self.script.name} step {i} kind {tmod.writer_kind(st)} ({what}, size {m.size}){came}"
+        before = tuple(m.vals)
+        code, res = self.code_of(lambda: self.call(st))
+        if st.refusal:
+            assert code == tmod.REFUSAL_CODE[st.refusal], f"{tag}: returned {code}"
+            assert t.size == len(before) and t.root() == tmod.oracle_root(sh, before), f"{tag}: size or root changed"
+            assert (t.snapshot() == tmod.pre_arr(m.preimages(range(m.size)))).all(), f"{tag}: snapshot changed"
+        else:
+            assert code is None, f"{tag}: refused with {code}: {self.imt.lib.imt_last_error(self.c.h)}"
+            out = tmod.play(m, st)
+            after, k = tuple(m.vals), st.kind
+            if k in (1, 2):
+                self.check_rows(res, before, out["acc"], tag)
+            elif k == 3:
+                self.in_flight.append((res, before, out["acc"], tag))
+            elif k in (4, 5):
+                assert res["n_inserted"] == len(out["acc"]), f"{tag}: n_inserted {res['n_inserted']}"
+                assert res["status"].tolist() == out["status"], f"{tag}: status"
+                assert res["leaf_index"].tolist() == out["leaf"], f"{tag}: leaf_index"
+                self.check_rows(res, before, out["acc"], tag)
+            elif k in (6, 7):
+                assert res == tmod.oracle_root(sh, after), f"{tag}: root_out"
+            elif k == 8:
+                status, leaf, n_ins, root = res
+                assert n_ins == len(out["acc"]), f"{tag}: n_inserted {n_ins}"
+                assert status.tolist() == out["status"] and leaf.tolist() == out["leaf"], f"{tag}: status / leaf_index"
+                assert root == tmod.oracle_root(sh, after), f"{tag}: root_out"
+            elif k == 9:
+                assert res == tmod.oracle_root(sh, after), f"{tag}: rewind's root"
+        if st.check == tmod.FULL:
+            self.full_check(tag)
+        else:
+            assert t.size == m.size, f"{tag}: size {t.size}, the model has {m.size}"
+            assert t.root() == tmod.oracle_root(sh, m.vals), f"{tag}: root()"
+
+    # ---- every reader ----
+    def full_check(self, tag):
+        imt, c, t, m, sh, torch = self.imt, self.c, self.t, self.m, self.shape, self.torch
+        f, lib, base, cap, depth = imt._ffi, imt.lib, self.base, sh.cap, sh.depth
+        tag = f"{tag}, full check"
+        assert t.size == m.size, f"{tag}: size {t.size}, the model has {m.size}"
+        assert t.root() == tmod.oracle_root(sh, m.vals), f"{tag}: root()"
+        idx = np.arange(cap, dtype=np.uint64) + np.uint64(base)
+        want_pre = tmod.pre_arr(m.preimages(range(cap)))
+
+        def same_leaves(got, n, how):
+            bad = np.nonzero((got != want_pre[:n]).reshape(n, -1).any(axis=1))[0]
+            assert bad.size == 0, f"{tag}: {how}: preimage of leaf {bad[:1]} is {arr_ints(got[bad[:1]])}"
+
+        same_leaves(t.get_leaves(idx), cap, "get_leaves, host pointers")
+        d_idx, d_pre = self.dev(idx), torch.zeros((cap, 3, 32), dtype=torch.uint8, device="cuda")
+        assert lib.imt_itree_get_leaves(t.h, _ptr(d_idx), cap, _ptr(d_pre), f.DEVICE_PTRS) == 0, lib.imt_last_error(c.h)
+        torch.cuda.synchronize()
+        same_leaves(d_pre.cpu().numpy(), cap, "get_leaves, device pointers")
+        same_leaves(t.snapshot(), m.size, "snapshot()")
+        proofs = tmod.oracle_proofs(sh, m.vals)
+        got = t.get_proof_batch(idx, item_major=True)
+        bad = np.argwhere((got != proofs).any(axis=2))
+        assert bad.size == 0, f"{tag}: get_proof_batch: leaf {bad[:1, 0]} level {bad[:1, 1]}"
+        # find_low: host pointers (the mirror when it is valid), device pointers (always the device index)
+        probes = m.probes()[:N_PROBES]
+        pv = ints_to_arr(probes)
+        want_low = [m.find_low(v) for v in probes]
+        assert t.find_low(pv).tolist() == want_low, f"{tag}: find_low, host pointers"
+        d_vals, d_low = self.dev(pv), torch.zeros(len(probes), dtype=torch.int64, device="cuda")
+        assert lib.imt_itree_find_low_batch(t.h, _ptr(d_vals), len(probes), _ptr(d_low), f.DEVICE_PTRS) == 0, lib.imt_last_error(c.h)
+        torch.cuda.synchronize()
+        assert d_low.cpu().numpy().view(np.uint64).tolist() == want_low, f"{tag}: find_low, device pointers"
+        refused = [0] + ([m.vals[-1], m.order[len(m.order) // 2]] if m.size > 1 else []) + \
+            [v for v in FOREIGN_PROBES if not m.mine(v)]
+        for v in refused:
+            bad_vals = ints_to_arr(probes[:2] + [v])
+            assert self.code_of(lambda: t.find_low(bad_vals))[0] == "VALUE", f"{tag}: find_low of {v:#x}, host pointers"
+            d_bad = self.dev(bad_vals)
+            rc = lib.imt_itree_find_low_batch(t.h, _ptr(d_bad), 3, _ptr(d_low), f.DEVICE_PTRS)
+            assert rc == f.ERR["VALUE"], f"{tag}: find_low of {v:#x}, device pointers: {rc}"
+        # lookup: stored, absent, zero and (on a partitioned tree) another subtree's values
+        mix = probes[:8] + m.vals[1:4] + m.vals[-3:] + [0] + [v for v in FOREIGN_PROBES if not m.mine(v)]
+        status, leaf = t.lookup(ints_to_arr(mix))
+        assert list(zip(status.tolist(), leaf.tolist())) == [m.lookup(v) for v in mix], f"{tag}: lookup"
+        # the non-membership witness, through the device index and through the host calls
+        want = [m.nm_witness(v) for v in probes]
+        want_leaves = tmod.pre_arr([w[1] for w in want])
+        want_sib = proofs[[w[0] - base for w in want]].transpose(1, 0, 2)
+        root = imt.to_bytes(t.root())
+        for host in (False, True):
+            how = f"non_membership_witness(host={host})"
+            low, leaves, sib, largest = t.non_membership_witness(pv, host=host)
+            assert low.tolist() == [w[0] for w in want], f"{tag}: {how}: low index"
+            assert (leaves == want_leaves).all(), f"{tag}: {how}: low leaf"
+            assert largest.tolist() == [w[2] for w in want], f"{tag}: {how}: is_largest"
+            assert (sib == want_sib).all(), f"{tag}: {how}: siblings"
+            fail = c.non_membership(root, leaves, low, sib, depth, pv, largest)
+            assert not fail.any(), f"{tag}: {how}: imt_non_membership_batch rejects the witness: {fail.tolist()}"
+        # the pipelined batches left in flight: their outputs are complete after a synchronisation
+        if self.in_flight:
+            self.dv.sync()
+            for bufs, before, acc, its_tag in self.in_flight:
+                got = DeviceBatches.host(bufs)
+                got["new_index"] = np.arange(len(before), len(before) + len(acc), dtype=np.uint64) + np.uint64(base)
+                self.check_rows(got, before, acc, f"{its_tag}, read at {tag}")
+            self.in_flight = []
+            self.dv.pending = []
+
+
+@pytest.mark.parametrize("name,form", _cases())
+def test_sequence(imt, forms, name, form):
+    script = SCRIPTS[name]
+    p = Player(imt, forms[form], script)
+    try:
+        for i, st in enumerate(script.steps):
+            p.step(i, st)
+        assert not p.in_flight
+    finally:
+        p.close()

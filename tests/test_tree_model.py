@@ -1,0 +1,288 @@
+"""CPU: tests/tree_model.py -- the plain-Python list against the sequential oracle, and the coverage of the committed
+step scripts that tests/test_gpu_tree_sequences.py plays on the GPU.
+
+  test_model_replays_the_corpus    every scenario of tests/insert_corpus.py at depth <= 63 through TreeModel.insert: the
+                                   oracle's low leaf, is_largest and low-leaf preimage of every insertion; the oracle
+                                   loaded with the model's preimages has the corpus's root at every batch boundary (at the
+                                   middle and the last one for the scenario of 16 000 values), also after rewind() to each (there: the
+                                   middle one).
+  test_model_filter_and_readers    classify / lookup / find_low / nm_witness against a brute-force statement.
+  test_model_load_refusals         the breakages of test_oracle_golden's sparse_load cases, and a few more.
+  test_script_coverage             the pair coverage of scripts(), asserted.
+  test_scripts_are_self_consistent every accepted step accepted by the model, every refused one refused with its code.
+"""
+import os
+import sys
+
+import pytest
+
+import insert_corpus as ic
+import oracle_lib
+import tree_model as tmod
+from oracle_lib import P, arr_ints, ints_to_arr
+from tree_model import FULL, KINDS, LIGHT, Refused, TreeModel
+
+CORPUS = [sc.name for sc in ic.SCENARIOS if sc.depth <= ic.ORACLE_MAX_DEPTH]
+
+
+def loaded_root(oracle, sc, m):
+    h = oracle.sparse_new(sc.depth, sc.cap)
+    oracle.sparse_set_index_base(h, sc.index_base)
+    try:
+        if m.size > 1:
+            assert oracle.sparse_load(h, tmod.pre_arr(m.preimages(range(m.size)))) == 0
+        return oracle.sparse_root(h)
+    finally:
+        oracle.sparse_free(h)
+
+
+@pytest.mark.parametrize("name", CORPUS)
+def test_model_replays_the_corpus(oracle, name):
+    sc, exp = ic.BY_NAME[name], ic.expected(name)
+    vals, rec, bounds = exp["vals"], exp["rec"], ic.batch_bounds(sc)
+    m = TreeModel(sc.depth, sc.cap, sc.index_base)
+    checked = set(range(len(bounds))) if len(vals) <= 4096 else {len(bounds) // 2, len(bounds) - 1}
+    assert loaded_root(oracle, sc, m) == exp["batch_roots"][0]
+    for j, (a, b) in enumerate(bounds):
+        rows = m.insert(vals[a:b])
+        assert [r["low"] for r in rows] == rec["low_index"][a:b].tolist(), (name, j)
+        assert [r["largest"] for r in rows] == rec["is_largest"][a:b].tolist(), (name, j)
+        assert [x for r in rows for x in r["low_leaf"]] == arr_ints(rec["low_leaf"][a:b]), (name, j)
+        if j in checked:
+            assert loaded_root(oracle, sc, m) == exp["batch_roots"][j + 1], (name, j)
+    fin = exp["final"]
+    local = [int(i) - sc.index_base for i in fin["index"]]
+    assert [x for p in m.preimages(local) for x in p] == arr_ints(fin["preimages"]), name
+    if sc.full:
+        with pytest.raises(Refused) as e:
+            m.insert([exp["full_value"]])
+        assert e.value.code == "FULL"
+    back = checked if len(vals) <= 4096 else {len(bounds) // 2}
+    for j in sorted(back, reverse=True):                          # back to the boundaries: the oracle's tree of the prefix
+        m.rewind(bounds[j][0] + 1)
+        assert m.vals[1:] == vals[:bounds[j][0]]
+        assert loaded_root(oracle, sc, m) == exp["batch_roots"][j], (name, j)
+    for bad in (0, m.size + 1):
+        with pytest.raises(Refused) as e:
+            m.rewind(bad)
+        assert e.value.code == "RANGE"
+
+
+@pytest.mark.parametrize("part", [(0, 0), (3, 1)])
+def test_model_filter_and_readers(part):
+    base = 5 << 8
+    m = TreeModel(8, 64, base, *part)
+    mine = [v for v in oracle_lib.synth_values(400, 0x544D0001) if m.mine(v)]
+    m.insert(mine[:20])
+    stored = {v: base + 1 + i for i, v in enumerate(mine[:20])}
+    a, b, c = mine[20:23]
+    foreign = next(v for v in range(2, 50) if not m.mine(v)) if part[0] else None
+    batch = [a, 0, mine[3], a, b, mine[3], b, c] + ([foreign, foreign] if foreign else [])
+    status, leaf, acc = m.classify(batch)
+    N, Z, S, R, F = tmod.NEW, tmod.ZERO, tmod.PRESENT, tmod.REPEATED, tmod.FOREIGN
+    assert status == [N, Z, S, R, N, S, R, N] + ([F, F] if foreign else [])
+    assert leaf == [base + 21, base, stored[mine[3]], base + 21, base + 22, stored[mine[3]], base + 22, base + 23] + \
+        ([tmod.NONE] * 2 if foreign else [])
+    assert acc == [a, b, c] and m.size == 21
+    with pytest.raises(Refused) as e:
+        m.classify([a, P])
+    assert e.value.code == "NONCANONICAL"
+    for v in m.probes() + [a, b, c]:
+        below = max(x for x in list(stored) + [0] if x < v)
+        want = stored.get(below, base)
+        above = [x for x in stored if x > v]
+        assert m.find_low(v) == want and m.lookup(v) == (N, want)
+        low, pre, largest = m.nm_witness(v)
+        assert (low, largest) == (want, int(not above))
+        assert pre == (below, min(above) if above else 0, stored[min(above)] if above else 0)
+    assert m.lookup(0) == (Z, base) and m.lookup(mine[7]) == (S, stored[mine[7]])
+    for v, code in ((0, "VALUE"), (mine[7], "VALUE"), (P, "NONCANONICAL")) + (((foreign, "VALUE"),) if foreign else ()):
+        with pytest.raises(Refused) as e:
+            m.find_low(v)
+        assert e.value.code == code
+    if foreign:
+        assert m.lookup(foreign) == (F, tmod.NONE)
+    assert m.preimages([0, 64, 21]) == [(0, min(stored), stored[min(stored)]), (0, 0, 0), (0, 0, 0)]
+    m.filtered(batch)
+    assert m.vals[21:] == [a, b, c]
+    with pytest.raises(Refused) as e:                              # 24 leaves + 41 new values > 64
+        m.filtered(mine[30:71])
+    assert e.value.code == "FULL" and m.size == 24
+
+
+def test_model_load_refusals(oracle):
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
+    from make_config4_digest import preimages_after
+    vals = ints_to_arr(oracle_lib.synth_values(400, 0x494D5404))
+
+    def triples(arr):
+        x = arr_ints(arr)
+        return [tuple(x[3 * i:3 * i + 3]) for i in range(len(x) // 3)]
+
+    def both(pre):
+        """the model's verdict, which must be the oracle's"""
+        m = TreeModel(32, 1024)
+        g = oracle.sparse_new(32, 1024)
+        rc = oracle.sparse_load(g, pre)
+        oracle.sparse_free(g)
+        try:
+            m.load(triples(pre))
+        except Refused as e:
+            assert rc == -10, "the oracle accepts what the model refuses"
+            return e.code, m
+        assert rc == 0, "the oracle refuses what the model accepts"
+        return None, m
+
+    for k in (0, 1, 2, 10, 333):
+        code, m = both(preimages_after(vals, k))
+        assert code is None and m.vals == [0] + arr_ints(vals[:k])
+        assert m.preimages(range(k + 1)) == triples(preimages_after(vals, k))
+    for breakage in ("pointer", "value", "sentinel", "duplicate", "last", "last_idx", "order"):
+        pre = preimages_after(vals, 10).copy()
+        if breakage == "pointer":
+            pre[3, 2, 0] ^= 1
+        elif breakage == "value":
+            pre[4, 1, 5] ^= 1
+        elif breakage == "sentinel":
+            pre[0, 0, 0] = 1
+        elif breakage == "duplicate":
+            pre[7, 0] = pre[6, 0]
+        elif breakage in ("last", "last_idx"):
+            big = max(range(11), key=lambda i: arr_ints(pre[i, 0])[0])
+            pre[big, 1 if breakage == "last" else 2, 0] = 1
+        else:
+            pre[[2, 5]] = pre[[5, 2]]                              # two leaves swapped: every next_idx is off
+        code, m = both(pre)
+        assert code == "VALUE" and m.vals == [0], breakage
+    m = TreeModel(32, 8)
+    for pre, code in (([], "ARG"), (triples(preimages_after(vals, 8)), "FULL"), ([(0, P, 1), (P, 0, 0)], "NONCANONICAL")):
+        with pytest.raises(Refused) as e:
+            m.load(pre)
+        assert e.value.code == code and m.vals == [0]
+    part = TreeModel(32, 8, 0, 3, 1)
+    with pytest.raises(Refused) as e:
+        part.load([(0, 5, 1), (5, 0, 0)])
+    assert e.value.code == "VALUE"
+    part.load([(0, 4, 1), (4, 0, 0)])
+    assert part.vals == [0, 4]
+
+
+# ---------------------------------------------------------------- the committed scripts
+def test_script_coverage():
+    scripts = tmod.scripts()
+    assert scripts is tmod.scripts() and len({s.name for s in scripts}) == len(scripts)
+    pairs, after_refusal, refusals, refused_kinds = set(), set(), set(), set()
+    rewinds, loads, shapes = set(), set(), {s.shape for s in scripts}
+    d3_story = False
+    for s in scripts:
+        assert s.steps[-1].check == FULL, s.name
+        assert all(st.check in (LIGHT, FULL) for st in s.steps)
+        tr = tmod.trace(s)
+        for (st, before, after, res), nxt in zip(tr, list(tr[1:]) + [None]):
+            assert len(after) <= tmod.SIZE_LIMIT and (st.vals is None or 1 <= len(st.vals) <= 16), s.name
+            if nxt is not None and not nxt[0].refusal:
+                if st.refusal:
+                    after_refusal.add(nxt[0].kind)
+                else:
+                    pairs.add((st.kind, nxt[0].kind, st.check))
+            if st.refusal:
+                refusals.add(st.refusal)
+                refused_kinds.add(st.kind)
+            elif st.kind == 9:
+                M = len(before)
+                rewinds.add("noop" if st.arg == M else "one" if st.arg == 1 else "size-1" if st.arg == M - 1 else "interior")
+            elif st.kind == 10:
+                n = len(st.arg["pre"])
+                loads |= {("fmt", st.arg["fmt"]), ("device", st.arg["device"]), st.arg["source"],
+                          "shorter" if n < len(before) else "longer" if n > len(before) else "same"}
+        if s.shape.cap == 8:                     # the tree fills, FULL is reached, and a rewind makes room again
+            sizes = [(st, len(before), len(after)) for st, before, after, _ in tr]
+            for i, (st, M, _) in enumerate(sizes):
+                if st.refusal == "full" and M == 8:
+                    back = [j for j in range(i + 1, len(sizes)) if sizes[j][0].kind == 9 and sizes[j][2] < sizes[j][1]]
+                    d3_story = d3_story or any(b > a for _, a, b in sizes[back[0] + 1:]) if back else d3_story
+    missing = [(a, b, lv) for lv in (LIGHT, FULL) for a in KINDS for b in KINDS if (a, b, lv) not in pairs]
+    assert not missing, f"pairs of writer kinds never adjacent: {missing}"
+    assert after_refusal == set(KINDS), f"never right after a refused call: {sorted(set(KINDS) - after_refusal)}"
+    assert refusals == set(tmod.REFUSALS)
+    assert rewinds == set(tmod.REWIND_VARIANTS)
+    assert loads >= {("fmt", 0), ("fmt", 1), ("fmt", 2), ("device", False), ("device", True), "earlier", "unrelated",
+                     "shorter", "longer"}
+    assert shapes == set(tmod.SHAPES) and d3_story
+    g5 = ic.BY_NAME["placed_g5"]
+    assert any(sh.placement == tuple(g5.placement) and (sh.depth, sh.cap) == (g5.depth, g5.cap) for sh in shapes)
+    assert any(sh.partition == (3, 1) for sh in shapes)
+    assert {(sh.depth, sh.cap) for sh in shapes} >= {(3, 8), (8, 64), (32, 256)}
+    # the values: 1, p - 1, neighbours of stored values, groups that share their top 64 bits
+    stored = [v for s in scripts for st in s.steps if st.vals and not st.refusal for v in st.vals]
+    assert 1 in stored and P - 1 in stored
+    every = set(stored)
+    assert sum(v + 1 in every or v - 1 in every for v in every) >= 20
+    tops = [v >> 192 for v in every]
+    assert max(tops.count(t) for t in tmod.TOPS) >= 20
+    print(f"{len(scripts)} scripts, {sum(len(s.steps) for s in scripts)} steps, refused base kinds {sorted(refused_kinds)}")
+
+
+@pytest.mark.parametrize("script", tmod.scripts(), ids=lambda s: s.name)
+def test_scripts_are_self_consistent(script):
+    for i, (st, before, after, res) in enumerate(tmod.trace(script)):
+        tag = f"{script.name} step {i} kind {tmod.writer_kind(st)}"
+        if st.refusal:
+            assert isinstance(res, Refused) and res.code == tmod.REFUSAL_CODE[st.refusal] and after == before, tag
+        else:
+            assert not isinstance(res, Exception), f"{tag}: refused with {res}"
+            if st.kind in (1, 2, 3, 6, 7):
+                assert after == before + tuple(st.vals), tag
+            elif st.kind in (4, 5, 8):
+                assert after == before + tuple(res["acc"]) and len(res["status"]) == len(st.vals), tag
+            elif st.kind == 9:
+                assert after == before[:st.arg], tag
+            else:
+                assert after == tuple(p[0] for p in st.arg["pre"]), tag
+
+
+def test_scripts_reach_the_states_of_the_two_copies():
+    """The scripts are about the two lazily synchronised copies of the list, so the combinations of the flags (DESIGN.md
+    section 5: mirror_valid, dev_index_valid) must occur where they matter.  Followed here with the rules of DESIGN.md: a
+    GPU-prepared call needs the device index and a batch of it invalidates the mirror, a host-prepared call the other
+    way round, a rewind and a load leave the device index alone valid, a full check calls device-pointer readers."""
+    seen = set()
+    for s in tmod.scripts():
+        mirror = dev = True
+        tr = tmod.trace(s)
+        for i, (st, before, after, res) in enumerate(tr):
+            k = st.kind
+            host_prep = k in (2, 5, 7) or (k == 8 and bool(st.arg))
+            changed = after != before
+            if k in (1, 2, 3, 4, 5, 6, 7, 8):
+                seen.add(("host-prepared call, mirror dropped", ) if host_prep and not mirror else
+                         ("GPU-prepared call, device index stale", ) if not host_prep and not dev else ("batch", ))
+                if host_prep:
+                    mirror, dev = True, dev and not changed
+                else:
+                    mirror, dev = mirror and not changed, True
+            elif k == 9 and not st.refusal and st.arg != len(before):
+                later = [x[0] for x in tr[i + 1:] if not x[0].refusal]
+                nxt = later[0] if later else None
+                if mirror and (st.check == FULL or (nxt is not None and (nxt.kind in (2, 5, 7) or (nxt.kind == 8 and nxt.arg)))):
+                    seen.add(("rewind with the mirror valid, then a reader of the mirror", ))
+                if not dev:
+                    seen.add(("rewind, device index stale", ))
+                mirror, dev = False, True
+            elif k == 10:
+                if not dev:
+                    seen.add(("load, device index stale", "refused" if st.refusal else "accepted"))
+                if not st.refusal:
+                    mirror, dev = False, True
+            if st.check == FULL or st.refusal:
+                if st.check == FULL:
+                    seen.add(("full check", mirror, dev))
+                if st.refusal:
+                    seen.add(("refused call, then a reader", mirror, dev))
+                dev = dev or st.check == FULL or not mirror          # device-pointer readers; snapshot() without a mirror
+    want = {("host-prepared call, mirror dropped", ), ("GPU-prepared call, device index stale", ),
+            ("rewind with the mirror valid, then a reader of the mirror", ), ("rewind, device index stale", ),
+            ("load, device index stale", "accepted"), ("full check", True, False), ("full check", False, True),
+            ("full check", True, True), ("refused call, then a reader", True, False),
+            ("refused call, then a reader", False, True)}
+    assert want <= seen, f"states the scripts never reach: {sorted(map(str, want - seen))}"

@@ -1,0 +1,573 @@
+"""The sorted list of an indexed tree as plain Python, and the step scripts played on it (TEST INFRASTRUCTURE ONLY).
+
+TreeModel is the specification of the list imt_itree keeps: Python integers, a list in insertion order, a sorted list
+beside it.  Its rules are written from include/imt.h and the reference's update_idx_leaf, not from the library's own
+restatements (imt_prep_logic.hpp, imt_filter_logic.hpp, host_filter).  It knows nothing of hashes: roots, proofs and
+witness rows of a state come from the CPU oracle, which is loaded with the model's preimages (oracle_root,
+oracle_proofs, oracle_rows; cached per state).
+
+scripts() returns the committed step scripts of tests/test_gpu_tree_sequences.py: sequences of the ten ways into the
+tree and of refused calls, generated coverage-directed from the literal seeds below so that every ordered pair of
+writer kinds is adjacent somewhere with a light check between the two and somewhere with a full one
+(tests/test_tree_model.py asserts that).  The writer kinds:
+   1 insert_batch, host pointers, GPU prepare        6 apply_batch, GPU prepare
+   2 insert_batch, IMT_HOST_PREP                     7 apply_batch, IMT_HOST_PREP
+   3 insert_batch, device pointers + IMT_PIPELINE,   8 apply_filtered, prepare mode alternating
+     left in flight                                  9 rewind(s)
+   4 insert_filtered, GPU prepare                   10 load of a snapshot taken from the model
+   5 insert_filtered, IMT_HOST_PREP                 11 a refused call of one of the kinds above
+"""
+import bisect
+import random
+from collections import namedtuple
+
+import numpy as np
+
+import insert_corpus as ic
+import oracle_lib
+from oracle_lib import P, ints_to_arr
+
+NEW, ZERO, PRESENT, REPEATED, FOREIGN = 0, 1, 2, 3, 4        # IMT_VAL_*
+NONE = (1 << 64) - 1
+LIGHT, FULL = "light", "full"
+KINDS = tuple(range(1, 11))
+REFUSED = 11
+REFUSALS = ("stored", "repeat", "zero", "full", "ge_p", "broken_link", "rewind_past")
+REFUSAL_CODE = dict(stored="VALUE", repeat="VALUE", zero="VALUE", full="FULL", ge_p="NONCANONICAL", broken_link="VALUE",
+                    rewind_past="RANGE")
+REWIND_VARIANTS = ("interior", "size-1", "noop", "one")
+REWIND_ORDER = ("interior", "size-1", "interior", "noop", "interior", "one")
+SIZE_LIMIT = 150                     # no script grows a tree past this many leaves
+TOPS = (0x1234_5678_9ABC_DEF0, 0x2FFF_0000_0000_0001)      # top 64 bits shared by groups of values (both below p's)
+
+
+class Refused(Exception):
+    """the call is refused with IMT_ERR_<code> and changes nothing"""
+
+    def __init__(self, code):
+        super().__init__(code)
+        self.code = code
+
+
+class TreeModel:
+    """vals[i] = the value of leaf i (vals[0] = 0, the sentinel); indices that leave the model are global."""
+
+    def __init__(self, depth, cap, index_base=0, part_mod=0, part_res=0):
+        self.depth, self.cap, self.index_base, self.part_mod, self.part_res = depth, cap, index_base, part_mod, part_res
+        self._reset([0])
+
+    def _reset(self, vals):
+        self.vals = list(vals)
+        self.where = {v: i for i, v in enumerate(self.vals)}
+        self.order = sorted(self.vals)
+
+    @property
+    def size(self):
+        return len(self.vals)
+
+    def mine(self, v):
+        return self.part_mod <= 1 or v % self.part_mod == self.part_res
+
+    def _append(self, v):
+        pos = bisect.bisect_left(self.order, v)
+        low_val = self.order[pos - 1]                      # pos >= 1: the sentinel is stored and v > 0
+        succ = self.order[pos] if pos < len(self.order) else None
+        row = dict(low=self.index_base + self.where[low_val], largest=int(succ is None),
+                   low_leaf=(low_val, succ or 0, self.index_base + self.where[succ] if succ is not None else 0))
+        self.order.insert(pos, v)
+        self.where[v] = len(self.vals)
+        self.vals.append(v)
+        return row
+
+    # ---- writers ----
+    def insert(self, vals):
+        """imt_itree_insert_batch / _apply_batch: all or nothing.  Returns per insertion the low leaf's index, its
+        preimage before the insertion and is_largest."""
+        vals = list(vals)
+        if self.size + len(vals) > self.cap:
+            raise Refused("FULL")
+        if any(v >= P for v in vals):
+            raise Refused("NONCANONICAL")
+        if len(set(vals)) != len(vals) or any(v == 0 or v in self.where or not self.mine(v) for v in vals):
+            raise Refused("VALUE")
+        return [self._append(v) for v in vals]
+
+    def classify(self, vals):
+        """(status, leaf_index, accepted values) of imt_itree_insert_filtered, nothing changed.  The first that applies:
+        ZERO, FOREIGN, PRESENT, REPEATED, NEW."""
+        if any(v >= P for v in vals):
+            raise Refused("NONCANONICAL")
+        status, leaf, acc, first = [], [], [], {}
+        for v in vals:
+            if v == 0:
+                s, l = ZERO, self.index_base
+            elif not self.mine(v):
+                s, l = FOREIGN, NONE
+            elif v in self.where:
+                s, l = PRESENT, self.index_base + self.where[v]
+            elif v in first:
+                s, l = REPEATED, first[v]
+            else:
+                s, l = NEW, self.index_base + self.size + len(acc)
+                first[v] = l
+                acc.append(v)
+            status.append(s)
+            leaf.append(l)
+        if self.size + len(acc) > self.cap:
+            raise Refused("FULL")
+        return status, leaf, acc
+
+    def filtered(self, vals):
+        status, leaf, acc = self.classify(list(vals))
+        self.insert(acc)
+        return status, leaf, acc
+
+    def rewind(self, s):
+        if s == 0 or s > self.size:
+            raise Refused("RANGE")
+        self._reset(self.vals[:s])
+
+    def load(self, preimages):
+        """preimages: [(val, next_val, next_idx)] in leaf order.  One sorted chain from the sentinel or nothing."""
+        pre = [tuple(p) for p in preimages]
+        n = len(pre)
+        if n == 0:
+            raise Refused("ARG")
+        if n > self.cap:
+            raise Refused("FULL")
+        if any(x >= P for p in pre for x in p):
+            raise Refused("NONCANONICAL")
+        vals = [p[0] for p in pre]
+        if vals[0] != 0 or len(set(vals)) != n or not all(self.mine(v) for v in vals[1:]):
+            raise Refused("VALUE")
+        chain = sorted(range(n), key=vals.__getitem__)
+        for i, j in zip(chain, chain[1:]):
+            if pre[i][1:] != (vals[j], self.index_base + j):
+                raise Refused("VALUE")
+        if pre[chain[-1]][1:] != (0, 0):
+            raise Refused("VALUE")
+        self._reset(vals)
+
+    # ---- readers ----
+    def preimages(self, indices):
+        """{val, next_val, next_idx} of local leaves `indices`: next_idx global, all zero at and beyond size"""
+        out = []
+        for i in indices:
+            if i >= self.size:
+                out.append((0, 0, 0))
+                continue
+            pos = bisect.bisect_right(self.order, self.vals[i])
+            succ = self.order[pos] if pos < len(self.order) else None
+            out.append((self.vals[i], succ or 0, self.index_base + self.where[succ] if succ is not None else 0))
+        return out
+
+    def find_low(self, v):
+        if v >= P:
+            raise Refused("NONCANONICAL")
+        if v == 0 or v in self.where or not self.mine(v):
+            raise Refused("VALUE")
+        return self.index_base + self.where[self.order[bisect.bisect_left(self.order, v) - 1]]
+
+    def lookup(self, v):
+        if v >= P:
+            raise Refused("NONCANONICAL")
+        if v == 0:
+            return ZERO, self.index_base
+        if not self.mine(v):
+            return FOREIGN, NONE
+        if v in self.where:
+            return PRESENT, self.index_base + self.where[v]
+        return NEW, self.find_low(v)
+
+    def nm_witness(self, v):
+        low = self.find_low(v)
+        leaf = self.preimages([low - self.index_base])[0]
+        return low, leaf, int(leaf[1] == 0)
+
+    def probes(self):
+        """the fixed probe set of a state: absent values of this tree's residue -- neighbours of stored values, 1,
+        p - 1, values that share their top 64 bits with a stored one or with each other"""
+        step = max(1, self.part_mod)
+        stored = self.vals[1:]
+        pick = stored[:6] + stored[-6:] + [self.order[-1], self.order[len(self.order) // 2]]
+        cand = [1, P - 1, step, P - step]
+        for v in pick:
+            cand += [v - step, v + step, v ^ (1 << 130), (v >> 192 << 192) | 7, (v >> 192 << 192) | (v & 0xFFFF) << 64]
+        cand += [(TOPS[0] << 192) + k for k in range(1, 7)]
+        out = []
+        for v in cand:
+            if 0 < v < P and self.mine(v) and v not in self.where and v not in out:
+                out.append(v)
+        return out
+
+
+# ---------------------------------------------------------------- shapes, steps, scripts
+Shape = namedtuple("Shape", "name depth cap placement partition")
+Step = namedtuple("Step", "kind refusal vals arg check")
+Script = namedtuple("Script", "name shape steps")
+_G5 = ic.BY_NAME["placed_g5"]
+SHAPES = (
+    Shape("d3", 3, 8, None, (0, 0)),
+    Shape("d8", 8, 64, None, (0, 0)),
+    Shape("d32", 32, 256, None, (0, 0)),
+    Shape("placed_g5", _G5.depth, _G5.cap, tuple(_G5.placement), (0, 0)),
+    Shape("part3", 16, 128, None, (3, 1)),
+)
+SEEDS = (0x54530001, 0x54530002, 0x54530003, 0x54530004, 0x54530005, 0x54530006, 0x54530007, 0x54530008, 0x54530009,
+         0x5453000A, 0x5453000B, 0x5453000C, 0x5453000D, 0x5453000E, 0x5453000F, 0x54530010, 0x54530011, 0x54530012,
+         0x54530013, 0x54530014, 0x54530015, 0x54530016, 0x54530017, 0x54530018, 0x54530019, 0x5453001A, 0x5453001B,
+         0x5453001C, 0x5453001D, 0x5453001E, 0x5453001F, 0x54530020)
+SCRIPT_STEPS = 30
+
+
+def index_base(shape):
+    return shape.placement[1] << shape.depth if shape.placement else 0
+
+
+def new_model(shape, vals=None):
+    m = TreeModel(shape.depth, shape.cap, index_base(shape), *shape.partition)
+    if vals is not None:
+        m._reset(vals)
+    return m
+
+
+def writer_kind(step):
+    return REFUSED if step.refusal else step.kind
+
+
+def play(m, step):
+    """One step on model m.  Accepted: dict(acc=the values inserted, status, leaf) (what applies).  A refused step
+    raises Refused and leaves m as it was."""
+    k = step.kind
+    if k in (1, 2, 3, 6, 7):
+        m.insert(step.vals)
+        return dict(acc=list(step.vals))
+    if k in (4, 5, 8):
+        status, leaf, acc = m.filtered(step.vals)
+        return dict(acc=acc, status=status, leaf=leaf)
+    if k == 9:
+        m.rewind(step.arg)
+        return {}
+    m.load(step.arg["pre"])
+    return {}
+
+
+def trace(script):
+    """[(step, vals before, vals after, outcome or the Refused raised)] of a script on a fresh model"""
+    m, out = new_model(script.shape), []
+    for st in script.steps:
+        before = tuple(m.vals)
+        try:
+            res = play(m, st)
+        except Refused as e:
+            res = e
+        out.append((st, before, tuple(m.vals), res))
+    return out
+
+
+class _Generator:
+    """Chooses every next writer kind among those that still have an uncovered pair behind the step before."""
+
+    def __init__(self):
+        self.need = {(a, b, lv) for a in KINDS for b in KINDS for lv in (LIGHT, FULL)}
+        self.need11 = set(KINDS)
+        self.refusals = list(REFUSALS)
+        self.n_rewind = self.n_load = self.n_refused = self.n_apply_filtered = 0
+        self.d3_full = self.d3_room_again = False
+
+    def done(self):
+        return not (self.need or self.need11 or self.refusals)
+
+    # -- values --
+    def fresh(self, k, exclude=()):
+        m, rng, out = self.m, self.rng, []
+        step = max(1, m.part_mod)
+        while len(out) < k:
+            r = rng.random()
+            if self.specials:
+                v = self.specials.pop()
+            elif r < 0.25 and m.size > 1:
+                v = rng.choice(m.vals[1:]) + rng.choice((-step, step))
+            elif r < 0.45:
+                v = (rng.choice(TOPS) << 192) | rng.getrandbits(192)
+            else:
+                v = self.pool.pop()
+            if 0 < v < P and m.mine(v) and v not in m.where and v not in out and v not in exclude:
+                out.append(v)
+        return out
+
+    def mixed(self, room):
+        m, rng = self.m, self.rng
+        n, out, n_new = rng.randint(1, 16), [], 0
+        for i in range(n):
+            r = rng.random()
+            if (r < 0.55 or (i == 0 and room)) and n_new < room:
+                out += self.fresh(1, out)
+                n_new += 1
+            elif r < 0.67:
+                out.append(0)
+            elif r < 0.82 and m.size > 1:
+                out.append(rng.choice(m.vals[1:]))
+            elif r < 0.94 and out:
+                out.append(rng.choice(out))
+            elif m.part_mod > 1:
+                w = rng.choice(m.vals[1:] + [4])
+                out.append(w + 1 if w + 1 < P else w - 2)             # another subtree's residue
+            else:
+                out.append(0)
+        return out
+
+    # -- what can follow --
+    def room(self):
+        return min(self.m.cap, SIZE_LIMIT) - self.m.size
+
+    def feasible(self, k):
+        return self.room() >= 1 if k in (1, 2, 3, 6, 7) else True
+
+    def refusal_feasible(self, name):
+        m, room = self.m, self.m.cap - self.m.size
+        if name in ("zero", "ge_p"):
+            return room >= 1
+        if name == "stored":
+            return room >= 1 and m.size > 1
+        if name == "repeat":
+            return room >= 2
+        if name == "full":
+            return room + 1 <= 16
+        if name == "broken_link":
+            return m.size >= 2
+        return True
+
+    def out_degree(self, k, levels=(LIGHT, FULL)):
+        return sum((k, b, lv) in self.need for b in KINDS for lv in levels)
+
+    def choose(self, prev, pos):
+        """(kind, refusal name or None) of the next step"""
+        rng = self.rng
+        d3 = self.shape.cap == 8
+        if d3 and self.m.size == self.m.cap and not self.d3_full and not (prev and prev.refusal):
+            self.d3_full = True
+            return None, "full"
+        if d3 and self.d3_full and not self.d3_room_again and self.m.size == self.m.cap:
+            self.d3_room_again = True
+            return 9, None
+        feas = [k for k in KINDS if self.feasible(k)]
+        if prev is None:
+            cands = []
+        elif prev.refusal:
+            cands = [k for k in feas if k in self.need11]
+        else:
+            cands = [k for k in feas if (prev.kind, k, prev.check) in self.need]
+        # once per script a refused call right behind a host-prepared batch: the device index is stale when it arrives
+        stale = prev is not None and not prev.refusal and prev.kind in (2, 5, 7) and not self.stale_refusal and pos >= 3
+        if stale:
+            self.stale_refusal = True
+        if prev is not None and not prev.refusal and (stale or ((self.refusals or self.need11) and (not cands or pos % 9 == 5))):
+            names = [r for r in self.refusals if self.refusal_feasible(r)] or \
+                    [r for r in REFUSALS[self.n_refused % 7:] + REFUSALS[:self.n_refused % 7] if self.refusal_feasible(r)]
+            self.host_side = stale
+            return None, names[0]
+        pool = cands or ([9, 10] if self.room() == 0 else feas)      # nothing uncovered from here: at least make room
+        best = max(self.out_degree(k) for k in pool)
+        return rng.choice([k for k in pool if self.out_degree(k) == best]), None
+
+    def level(self, k):
+        a, b = self.out_degree(k, (LIGHT,)), self.out_degree(k, (FULL,))
+        return LIGHT if a > b else FULL if b > a else self.rng.choice((LIGHT, FULL))
+
+    # -- the steps --
+    def snapshot_of(self, vals):
+        return tuple(new_model(self.shape, vals).preimages(range(len(vals))))
+
+    def make_rewind(self):
+        m = self.m
+        for _ in range(len(REWIND_ORDER)):
+            v = "interior" if self.shape.cap == 8 and m.size == m.cap else REWIND_ORDER[self.n_rewind % len(REWIND_ORDER)]
+            self.n_rewind += 1
+            if v == "interior" and m.size >= 4:
+                return self.rng.randint(2, m.size - 2)
+            if v == "size-1" and m.size >= 2:
+                return m.size - 1
+            if v == "noop":
+                return m.size
+            if v == "one" and m.size >= 2:
+                return 1
+        return m.size
+
+    def make_load(self):
+        m, rng, c = self.m, self.rng, self.n_load
+        self.n_load += 1
+        source, longer = ("earlier", "unrelated")[(c >> 1) & 1], bool((c >> 2) & 1)
+        fits = (lambda n: n > m.size) if longer else (lambda n: n < m.size)
+        vals = None
+        if source == "earlier":
+            states = [s for s in self.history if fits(len(s)) and list(s) != m.vals]
+            if states:
+                vals = list(rng.choice(states))
+        if vals is None:
+            source = "unrelated"
+            lo, hi = (m.size + 1, min(m.cap, SIZE_LIMIT, m.size + 24)) if longer else (1, m.size - 1)
+            if lo > hi:
+                lo, hi = 1, min(m.cap, 12)
+            n = rng.randint(lo, hi)
+            vals = [0] + [self.other.pop() for _ in range(n - 1)]
+        return dict(pre=self.snapshot_of(vals), device=bool(c & 1), fmt=c % 3, source=source)
+
+    def make_refusal(self, name):
+        m, rng, c = self.m, self.rng, self.n_refused
+        self.n_refused += 1
+        room = m.cap - m.size
+        if name == "rewind_past":
+            return Step(9, name, None, m.size + 1, None)
+        if name == "broken_link":
+            pre = [list(p) for p in self.snapshot_of(m.vals)]
+            pre[rng.randrange(m.size)][2] += 1
+            return Step(10, name, None, dict(pre=tuple(tuple(p) for p in pre), device=bool(c & 1), fmt=0, source="broken"), None)
+        if name == "full":
+            kinds = (2, 5, 7) if self.host_side else (1, 4, 6, 2, 5, 7, 8)
+            return Step(kinds[c % len(kinds)], name, tuple(self.fresh(room + 1)), c % 2 == 0, None)
+        k = min(rng.randint(2, 5), room)
+        good = self.fresh(k - 1)
+        if name == "ge_p":
+            kinds = (5, 7, 2) if self.host_side else (4, 1, 7, 5, 6, 8, 2)
+            return Step(kinds[c % len(kinds)], name, tuple(good + [P + rng.randrange(3)]), c % 2 == 0, None)
+        bad = dict(stored=lambda: rng.choice(m.vals[1:]), repeat=lambda: rng.choice(good), zero=lambda: 0)[name]()
+        vals = good + [bad]
+        rng.shuffle(vals)
+        return Step(((2, 7) if self.host_side else (1, 2, 6, 7))[c % (2 if self.host_side else 4)], name, tuple(vals), None, None)
+
+    def make(self, kind, refusal):
+        if refusal:
+            return self.make_refusal(refusal)
+        if kind in (1, 2, 3, 6, 7):
+            return Step(kind, None, tuple(self.fresh(self.rng.randint(1, min(16, self.room())))), None, None)
+        if kind in (4, 5, 8):
+            arg = None
+            if kind == 8:
+                arg = bool(self.n_apply_filtered & 1)        # IMT_HOST_PREP on every other call
+                self.n_apply_filtered += 1
+            return Step(kind, None, tuple(self.mixed(self.room())), arg, None)
+        if kind == 9:
+            return Step(9, None, None, self.make_rewind(), None)
+        return Step(10, None, None, self.make_load(), None)
+
+    def script(self, number, shape, seed):
+        self.shape, self.rng, self.m = shape, random.Random(seed), new_model(shape)
+        own = lambda s, n: [v for v in oracle_lib.synth_values(n, s) if self.m.mine(v)]
+        self.pool, self.other = own(seed, 1500), own(seed ^ 0x00FF0000, 2400)
+        self.specials = [v for v in (P - 1, 1) if self.m.mine(v)]
+        self.history = [tuple(self.m.vals)]
+        self.stale_refusal = self.host_side = False
+        steps, prev = [], None
+        while len(steps) < SCRIPT_STEPS and not (self.done() and len(steps) >= 8):
+            kind, refusal = self.choose(prev, len(steps))
+            st = self.make(kind, refusal)
+            if st.refusal:
+                check = (LIGHT, FULL)[self.n_refused & 1]
+                self.refusals = [r for r in self.refusals if r != st.refusal]
+            else:
+                check = self.level(st.kind)
+                if prev is not None and prev.refusal:
+                    self.need11.discard(st.kind)
+                elif prev is not None:
+                    self.need.discard((prev.kind, st.kind, prev.check))
+                play(self.m, st)
+                self.history.append(tuple(self.m.vals))
+            st = st._replace(check=check)
+            steps.append(st)
+            prev = st
+        steps[-1] = steps[-1]._replace(check=FULL)
+        return Script(f"{shape.name}_{number:02d}", shape, tuple(steps))
+
+
+_SCRIPTS = None
+
+
+def scripts():
+    """the committed scripts: as many as the coverage condition needs, every shape at least once"""
+    global _SCRIPTS
+    if _SCRIPTS is None:
+        g, out = _Generator(), []
+        while not g.done() or len(out) < len(SHAPES):
+            assert len(out) < len(SEEDS), "the generator does not reach its coverage"
+            out.append(g.script(len(out), SHAPES[len(out) % len(SHAPES)], SEEDS[len(out)]))
+        _SCRIPTS = tuple(out)
+    return _SCRIPTS
+
+
+# ---------------------------------------------------------------- the oracle's tree of a model state
+_ROOTS, _PROOFS, _ROWS = {}, {}, {}
+
+
+def pre_arr(pre):
+    """[(val, next_val, next_idx)] -> uint8 [n, 3, 32]"""
+    return ints_to_arr([x for p in pre for x in p]).reshape(-1, 3, 32)
+
+
+def _handle(orc, shape, vals):
+    h = orc.sparse_new(shape.depth, shape.cap)
+    orc.sparse_set_index_base(h, index_base(shape))
+    if len(vals) > 1:
+        rc = orc.sparse_load(h, pre_arr(new_model(shape, vals).preimages(range(len(vals)))))
+        assert rc == 0, f"the oracle refuses the model's list of {len(vals)} leaves: {rc}"
+    return h
+
+
+def _note(orc, h, shape, vals, proofs):
+    key = (shape, tuple(vals))
+    _ROOTS[key] = orc.sparse_root(h)
+    if proofs and key not in _PROOFS:
+        _PROOFS[key] = np.stack([orc.sparse_proof(h, shape.depth, i) for i in range(shape.cap)])
+
+
+def oracle_root(shape, vals):
+    key = (shape, tuple(vals))
+    if key not in _ROOTS:
+        orc = oracle_lib.load()
+        h = _handle(orc, shape, vals)
+        _note(orc, h, shape, vals, False)
+        orc.sparse_free(h)
+    return _ROOTS[key]
+
+
+def oracle_proofs(shape, vals):
+    """uint8 [cap, depth, 32]: the proof of every local leaf index of the state"""
+    key = (shape, tuple(vals))
+    if key not in _PROOFS:
+        orc = oracle_lib.load()
+        h = _handle(orc, shape, vals)
+        _note(orc, h, shape, vals, True)
+        orc.sparse_free(h)
+    return _PROOFS[key]
+
+
+def oracle_rows(shape, before, acc):
+    """the imt_insert_out rows of inserting `acc` one by one into the oracle's tree of state `before` (siblings
+    item-major [n, depth, 32], low_index global): the fields test_gpu_rewind.compare_rows compares"""
+    key = (shape, tuple(before), tuple(acc))
+    if key in _ROWS:
+        return _ROWS[key]
+    orc, depth, base, n = oracle_lib.load(), shape.depth, index_base(shape), len(acc)
+    h = _handle(orc, shape, before)
+    rec = dict(low_index=np.empty(n, np.uint64), is_largest=np.empty(n, np.uint8), low_leaf=np.empty((n, 3, 32), np.uint8),
+               new_leaf=np.empty((n, 3, 32), np.uint8), old_root=np.empty((n, 32), np.uint8),
+               interim_root=np.empty((n, 32), np.uint8), new_root=np.empty((n, 32), np.uint8),
+               low_sib=np.empty((n, depth, 32), np.uint8), new_sib=np.empty((n, depth, 32), np.uint8))
+    try:
+        for k, v in enumerate(acc):
+            old = orc.sparse_root(h)
+            r = orc.sparse_insert(h, depth, v)
+            assert r["rc"] == 0, (shape.name, k, r["rc"])
+            rec["low_index"][k], rec["is_largest"][k], rec["low_leaf"][k] = r["low"] + base, r["largest"], r["low_leaf"]
+            nl = r["low_leaf"].copy()
+            nl[0] = ints_to_arr([v])[0]
+            rec["new_leaf"][k] = nl
+            rec["old_root"][k] = ints_to_arr([old])[0]
+            rec["interim_root"][k] = ints_to_arr([r["interim_root"]])[0]
+            rec["new_root"][k] = ints_to_arr([r["new_root"]])[0]
+            rec["low_sib"][k], rec["new_sib"][k] = r["low_proof"], r["new_proof"]
+        _note(orc, h, shape, tuple(before) + tuple(acc), False)
+    finally:
+        orc.sparse_free(h)
+    _ROWS[key] = rec
+    return rec
