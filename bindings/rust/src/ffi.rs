@@ -18,6 +18,10 @@ pub struct imt_tree {
 pub struct imt_itree {
     _opaque: [u8; 0],
 }
+#[repr(C)]
+pub struct imt_itree_view {
+    _opaque: [u8; 0],
+}
 
 /// `imt_insert_out`: outputs of a batch insertion; every pointer may be null.
 #[repr(C)]
@@ -262,6 +266,15 @@ extern "C" {
     pub fn imt_itree_apply_filtered(t: *mut imt_itree, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, n_inserted: *mut u64, root_out: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_apply_stats(t: *mut imt_itree, hashes: *mut u64) -> c_int;
     pub fn imt_itree_rewind(t: *mut imt_itree, new_size: u64, root_out: *mut c_void, hashes: *mut u64, flags: c_uint) -> c_int;
+    pub fn imt_itree_view_create(t: *mut imt_itree, size: u64, out: *mut *mut imt_itree_view) -> c_int;
+    pub fn imt_itree_view_free(v: *mut imt_itree_view);
+    pub fn imt_itree_view_size(v: *const imt_itree_view) -> u64;
+    pub fn imt_itree_view_root(v: *mut imt_itree_view, root: *mut c_void, flags: c_uint) -> c_int;
+    pub fn imt_itree_view_lookup_batch(v: *mut imt_itree_view, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, flags: c_uint) -> c_int;
+    pub fn imt_itree_view_get_leaves(v: *mut imt_itree_view, index: *const u64, n: usize, preimage: *mut c_void, flags: c_uint) -> c_int;
+    pub fn imt_itree_view_get_proof_batch(v: *mut imt_itree_view, index: *const u64, n: usize, sib: *mut c_void, flags: c_uint) -> c_int;
+    pub fn imt_itree_view_non_membership_witness(v: *mut imt_itree_view, vals: *const c_void, n: usize, low_index: *mut u64, low_leaf: *mut c_void, is_largest: *mut u8, low_sib: *mut c_void, flags: c_uint) -> c_int;
+    pub fn imt_itree_view_stats(v: *mut imt_itree_view, hashes: *mut u64, builds: *mut u64) -> c_int;
     pub fn imt_itree_lookup_batch(t: *mut imt_itree, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, flags: c_uint) -> c_int;
     pub fn imt_itree_non_membership_witness(t: *mut imt_itree, vals: *const c_void, n: usize, low_index: *mut u64, low_leaf: *mut c_void, is_largest: *mut u8, low_sib: *mut c_void, flags: c_uint) -> c_int;
 

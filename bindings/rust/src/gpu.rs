@@ -294,6 +294,82 @@ impl IndexedTree {
     }
 }
 
+/// The tree as it was when it held `size` leaves, read-only, while the [`IndexedTree`] stays where it is and keeps
+/// advancing (`imt_itree_view_*`): what a service bound to the finalized root holds.  It follows the tree: a query after
+/// the tree changed rebuilds the view's side table first, and fails with code -4 while the tree is smaller than the view.
+pub struct IndexedTreeView {
+    handle: *mut imt_itree_view,
+    depth: usize,
+}
+unsafe impl Send for IndexedTreeView {}
+
+impl IndexedTree {
+    /// # Safety
+    /// The view refers to this tree without borrowing it (the tree must stay free to grow): drop the view before the tree.
+    pub unsafe fn view(&self, size: u64) -> Result<IndexedTreeView, ImtError> {
+        let g = context().lock().unwrap();
+        let mut handle = std::ptr::null_mut();
+        check(&g, imt_itree_view_create(self.handle, size, &mut handle))?;
+        Ok(IndexedTreeView { handle, depth: self.depth })
+    }
+}
+
+impl IndexedTreeView {
+    pub fn size(&self) -> u64 {
+        unsafe { imt_itree_view_size(self.handle) }
+    }
+    pub fn root<F: ScalarField>(&self) -> Result<F, ImtError> {
+        let g = context().lock().unwrap();
+        let mut r = [0u8; 32];
+        check(&g, unsafe { imt_itree_view_root(self.handle, r.as_mut_ptr() as *mut c_void, IMT_FMT_CANONICAL) })?;
+        Ok(F::from_bytes_le(&r))
+    }
+    /// (hashes per level of the last rebuild, rebuilds so far)
+    pub fn stats(&self) -> Result<(Vec<u64>, u64), ImtError> {
+        let g = context().lock().unwrap();
+        let mut h = vec![0u64; self.depth + 1];
+        let mut builds = 0u64;
+        check(&g, unsafe { imt_itree_view_stats(self.handle, h.as_mut_ptr(), &mut builds) })?;
+        Ok((h, builds))
+    }
+    /// Non-membership witnesses of n candidate values against the view's root; `Err(code -10)` if a candidate is 0 or
+    /// was stored as of the view's size.
+    pub fn non_inclusion_witnesses<F: ScalarField>(&self, vals: &[F]) -> Result<Vec<NonInclusionWitness<F>>, ImtError> {
+        let root: F = self.root()?;
+        let g = context().lock().unwrap();
+        let (n, d) = (vals.len(), self.depth);
+        let v = to_bytes(vals);
+        let mut low_index = vec![0u64; n];
+        let mut is_largest = vec![0u8; n];
+        let mut low_leaf = vec![0u8; n * 96];
+        let mut low_sib = vec![0u8; n * d * 32];
+        check(&g, unsafe {
+            imt_itree_view_non_membership_witness(self.handle, v.as_ptr() as *const c_void, n, low_index.as_mut_ptr(),
+                                                  low_leaf.as_mut_ptr() as *mut c_void, is_largest.as_mut_ptr(),
+                                                  low_sib.as_mut_ptr() as *mut c_void, IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR)
+        })?;
+        Ok((0..n)
+            .map(|i| NonInclusionWitness {
+                root,
+                low_leaf: [F::from_bytes_le(&low_leaf[i * 96..][..32]), F::from_bytes_le(&low_leaf[i * 96 + 32..][..32]),
+                           F::from_bytes_le(&low_leaf[i * 96 + 64..][..32])],
+                low_leaf_index: low_index[i],
+                low_leaf_proof: from_bytes(&low_sib[i * d * 32..][..d * 32]),
+                low_leaf_proof_helper: (0..d).map(|l| if (low_index[i] >> l) & 1 == 0 { F::from(1) } else { F::from(0) }).collect(),
+                new_leaf_value: vals[i],
+                is_new_leaf_largest: is_largest[i] != 0,
+            })
+            .collect())
+    }
+}
+
+impl Drop for IndexedTreeView {
+    fn drop(&mut self) {
+        let _g = context().lock().unwrap();
+        unsafe { imt_itree_view_free(self.handle) };
+    }
+}
+
 impl Drop for IndexedTree {
     fn drop(&mut self) {
         let _g = context().lock().unwrap();

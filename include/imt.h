@@ -519,6 +519,52 @@ int imt_itree_apply_stats(imt_itree *t, uint64_t *hashes /*[depth + 1]*/);
  * no root to give until the next batch. */
 int imt_itree_rewind(imt_itree *t, uint64_t new_size, void *root_out /*[32] or NULL*/,
                      uint64_t *hashes /*[depth + 1] host, or NULL*/, unsigned flags);
+/* READING AT AN EARLIER SIZE, for whoever answers against a root that lags the head: the non-membership service bound to
+ * the finalized root, a prover catching up on a block that has since been built upon, a node asking whether a value would
+ * have been a double spend at block B.  A view is the tree as it was when it held `size` leaves (sentinel included),
+ * read-only, while the tree stays where it is.  It is neither a second tree nor a rewind: the earlier tree differs from
+ * the stored one only in the nodes imt_itree_rewind would hash (S_l above), which a view keeps in a side table of its own,
+ * and in the nodes at or beyond the cut, which are empty subtrees; every other node is read from the tree (imt_view.hpp).
+ * DEFINED BY THE SIZE ALONE.  Every query answers byte for byte what the imt_itree_* call of the same name answers on a
+ * fresh tree that received the first size - 1 values this tree holds: root, status, leaf indices, preimages, sibling
+ * rows, errors -- IMT_ERR_VALUE for a candidate that is 0, stored as of `size` or foreign, IMT_ERR_RANGE for an index
+ * outside the capacity.  A value inserted after `size` is NEW, its low leaf among the kept leaves.  Placement, value
+ * partition, global indices, IMT_FMT_*, IMT_SIB_ITEM_MAJOR and IMT_DEVICE_PTRS mean what they mean to the tree's calls.
+ * A VIEW NEVER CHANGES THE TREE: no stored node, no index buffer of the tree (not the spare one a rewind uses either), no
+ * plan set.  The tree's own calls answer and behave as before, whether views exist or not.
+ * A VIEW FOLLOWS THE TREE.  The side table is a cache for (size, state of the tree); the tree counts every call that
+ * changes its contents (an insertion of any kind that accepted something, imt_itree_load, a rewind below the current size,
+ * imt_itree_batch_end, a slice), and a query that finds another count rebuilds first: on the context's stream, behind
+ * everything in flight on the tree, pipelined batches included (the caller need not synchronise), and synchronously -- it
+ * reads the number of relinked leaves back.  While the tree is smaller than the view a query returns IMT_ERR_RANGE; the
+ * view stays valid and answers again once the tree has grown, for the prefix of whatever history the tree then has.
+ * imt_itree_view_stats: *builds = rebuilds so far, hashes[l] = what the last one hashed at level l -- what
+ * imt_itree_rewind(t, size) reports for the same pair of sizes; host memory, either may be NULL.
+ * A view at the current size (size == imt_itree_size(t)) hashes nothing and answers as the tree does.
+ * REFUSALS.  size == 0 or above the tree's size at creation: IMT_ERR_RANGE.  IMT_PIPELINE in a query's flags: IMT_ERR_ARG.
+ * Creation and queries are refused like imt_itree_rewind, with IMT_ERR_ARG and everything untouched: a replica of a sliced
+ * world with steps in flight, an open slice, between imt_itree_batch_begin and _end.
+ * Several views of one tree may exist; each owns its memory: 4 * size bytes for the earlier index, and per rebuild 32
+ * bytes per listed node (a level's row is as long as S_0) + 96 bytes per relinked leaf.  A rebuild borrows 8 bytes per
+ * leaf of the tree from the context for the time of the call, as a rewind does.  Free every view before its tree.
+ * A handle that is not a live view (NULL, one already freed, another kind of handle) is IMT_ERR_ARG to every call here,
+ * size 0 to imt_itree_view_size and nothing to imt_itree_view_free: it is looked up before anything is read through it. */
+typedef struct imt_itree_view imt_itree_view;
+int imt_itree_view_create(imt_itree *t, uint64_t size, imt_itree_view **out);
+void imt_itree_view_free(imt_itree_view *v); /* NULL is fine; before imt_itree_free of its tree */
+uint64_t imt_itree_view_size(const imt_itree_view *v);
+int imt_itree_view_root(imt_itree_view *v, void *root /*[32]*/, unsigned flags);
+int imt_itree_view_lookup_batch(imt_itree_view *v, const void *vals /*[n][32]*/, size_t n, uint8_t *status /*[n]*/,
+                                uint64_t *leaf_index /*[n] or NULL*/, unsigned flags);
+int imt_itree_view_get_leaves(imt_itree_view *v, const uint64_t *index /*[n] or NULL*/, size_t n,
+                              void *preimage /*[n][3][32]*/, unsigned flags);
+int imt_itree_view_get_proof_batch(imt_itree_view *v, const uint64_t *index /*[n]*/, size_t n,
+                                   void *sib /*[depth][n][32]*/, unsigned flags);
+int imt_itree_view_non_membership_witness(imt_itree_view *v, const void *vals /*[n][32]*/, size_t n,
+                                          uint64_t *low_index /*[n]*/, void *low_leaf /*[n][3][32]*/,
+                                          uint8_t *is_largest /*[n]*/, void *low_sib /*[depth][n][32]*/,
+                                          unsigned flags);
+int imt_itree_view_stats(imt_itree_view *v, uint64_t *hashes /*[depth + 1] or NULL*/, uint64_t *builds /*or NULL*/);
 /* Read-only query of the device-resident index for any mix of values (one kernel, k_lookup): status ZERO / FOREIGN /
  * PRESENT / NEW and leaf_index = the sentinel / UINT64_MAX / the stored leaf / the low leaf (what find_low returns).
  * Fails only for its arguments, a value >= p (IMT_ERR_NONCANONICAL) or a HIP error, never for a value's class.  With

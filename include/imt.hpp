@@ -437,11 +437,62 @@ public:
         return w;
     }
     imt_itree* get() const { return t_; }
+    Context& context() const { return *c_; }
 
 private:
     Context* c_;
     unsigned depth_;
     imt_itree* t_ = nullptr;
+};
+
+// The tree as it was when it held `size` leaves, read-only, while the IndexedTree stays where it is (imt_itree_view_*):
+// what a service bound to the finalized root holds.  It follows the tree -- a query after the tree changed rebuilds the
+// view's side table first, and throws Error(IMT_ERR_RANGE) while the tree is smaller than the view.  Destroy it before
+// its tree.
+class TreeViewAt {
+public:
+    TreeViewAt(IndexedTree& t, uint64_t size) : c_(&t.context()), depth_(t.depth()) {
+        c_->check(imt_itree_view_create(t.get(), size, &v_));
+    }
+    ~TreeViewAt() { imt_itree_view_free(v_); }
+    TreeViewAt(const TreeViewAt&) = delete;
+    TreeViewAt& operator=(const TreeViewAt&) = delete;
+    uint64_t size() const { return imt_itree_view_size(v_); }
+    Fr root() {
+        Fr r;
+        c_->check(imt_itree_view_root(v_, &r, IMT_FMT_CANONICAL));
+        return r;
+    }
+    std::vector<IndexedMerkleTreeLeaf> get_leaves(const std::vector<uint64_t>& index) {
+        std::vector<IndexedMerkleTreeLeaf> out(index.size());
+        if (!index.empty()) c_->check(imt_itree_view_get_leaves(v_, index.data(), index.size(), out.data(), IMT_FMT_CANONICAL));
+        return out;
+    }
+    std::vector<Fr> get_proof(uint64_t index) {
+        std::vector<Fr> sib(depth_);
+        if (depth_) c_->check(imt_itree_view_get_proof_batch(v_, &index, 1, sib.data(), IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR));
+        return sib;
+    }
+    // the witness of verify_non_inclusion, against root(), for a value that was NOT in the tree of `size` leaves
+    IndexedTree::NonMembership non_membership_witness(const Fr& value) {
+        IndexedTree::NonMembership w;
+        w.low_leaf_proof.resize(depth_);
+        c_->check(imt_itree_view_non_membership_witness(v_, &value, 1, &w.low_index, &w.low_leaf, &w.is_largest,
+                                                        w.low_leaf_proof.data(), IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR));
+        return w;
+    }
+    // hashes per level of the last rebuild ([depth + 1]); builds, if given: rebuilds so far
+    std::vector<uint64_t> stats(uint64_t* builds = nullptr) {
+        std::vector<uint64_t> h(depth_ + 1);
+        c_->check(imt_itree_view_stats(v_, h.data(), builds));
+        return h;
+    }
+    imt_itree_view* get() const { return v_; }
+
+private:
+    Context* c_;
+    unsigned depth_;
+    imt_itree_view* v_ = nullptr;
 };
 
 // ---- several GPUs, the single sorted list: imt_sliced_* --------------------------------------------------------------

@@ -539,6 +539,7 @@ class IndexedTree:
         self.ctx, self.depth, self.capacity = ctx, depth, capacity
         self.global_depth, self.index_base = depth, 0
         self.rewind_stats = None         # hashes per level of the last rewind() (numpy uint64 [depth + 1])
+        self._views = weakref.WeakSet()  # views of this tree: imt.h wants them freed before it
         h = ctypes.c_void_p()
         ctx._check(lib.imt_itree_new(ctx.h, depth, capacity, ctypes.byref(h)))
         self.h = h
@@ -565,6 +566,8 @@ class IndexedTree:
 
     def close(self):
         if getattr(self, "h", None):
+            for v in list(getattr(self, "_views", ())):
+                v.close()
             lib.imt_itree_free(self.h)
             self.h = None
 
@@ -667,6 +670,11 @@ class IndexedTree:
         self.rewind_stats = stats
         return to_int(root)
 
+    def view(self, size):
+        """A read-only IndexedTreeView of this tree as it was when it held `size` leaves (imt_itree_view_create); the tree
+        stays where it is.  Close every view before the tree."""
+        return IndexedTreeView(self, size)
+
     def lookup(self, vals):
         """(status, leaf_index) of every value against the stored tree (imt_itree_lookup_batch): VAL_PRESENT with the
         leaf that holds it, VAL_NEW with its low leaf, VAL_ZERO with the sentinel, VAL_FOREIGN with 2^64 - 1."""
@@ -763,3 +771,76 @@ class IndexedTree:
             raise ValueError(lib.imt_last_error(self.ctx.h).decode())
         self.ctx._check(rc)
         return low, leaves, sib, largest
+
+
+class IndexedTreeView:
+    """The tree at an earlier size, read-only (imt_itree_view): every query answers what the IndexedTree method of the
+    same name answers on a fresh tree fed the first size - 1 values.  It follows the tree: a query after the tree has
+    changed rebuilds the view's side table first, and raises ImtError (RANGE) while the tree is smaller than the view."""
+
+    def __init__(self, tree, size):
+        self.tree, self.ctx, self.depth = tree, tree.ctx, tree.depth
+        h = ctypes.c_void_p()
+        self.ctx._check(lib.imt_itree_view_create(tree.h, size, ctypes.byref(h)))
+        self.h = h
+        tree._views.add(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.imt_itree_view_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def size(self):
+        return lib.imt_itree_view_size(self.h)
+
+    def _checked(self, rc):
+        if rc == _ffi.ERR["VALUE"]:
+            raise ValueError(lib.imt_last_error(self.ctx.h).decode())
+        self.ctx._check(rc)
+
+    def root(self):
+        out = np.empty(32, dtype=np.uint8)
+        self.ctx._check(lib.imt_itree_view_root(self.h, _p(out), 0))
+        return to_int(out)
+
+    def lookup(self, vals):
+        v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
+        status, leaf = np.empty(v.shape[0], np.uint8), np.empty(v.shape[0], np.uint64)
+        self.ctx._check(lib.imt_itree_view_lookup_batch(self.h, _p(v), v.shape[0], _p(status), _p(leaf), 0))
+        return status, leaf
+
+    def get_leaves(self, index):
+        idx = np.ascontiguousarray(index, dtype=np.uint64)
+        out = np.empty((idx.size, 3, 32), dtype=np.uint8)
+        self.ctx._check(lib.imt_itree_view_get_leaves(self.h, _p(idx), idx.size, _p(out), 0))
+        return out
+
+    def get_proof_batch(self, index, item_major=False):
+        idx = np.ascontiguousarray(index, dtype=np.uint64)
+        out = np.empty((idx.size, self.depth, 32) if item_major else (self.depth, idx.size, 32), dtype=np.uint8)
+        self.ctx._check(lib.imt_itree_view_get_proof_batch(self.h, _p(idx), idx.size, _p(out),
+                                                           _ffi.SIB_ITEM_MAJOR if item_major else 0))
+        return out
+
+    def non_membership_witness(self, vals):
+        """(low index, low leaf, siblings, is_largest) of every value against the view's root."""
+        v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
+        n = v.shape[0]
+        low, leaves = np.empty(n, np.uint64), np.empty((n, 3, 32), np.uint8)
+        largest, sib = np.empty(n, np.uint8), np.empty((self.depth, n, 32), np.uint8)
+        self._checked(lib.imt_itree_view_non_membership_witness(self.h, _p(v), n, _p(low), _p(leaves), _p(largest), _p(sib), 0))
+        return low, leaves, sib, largest
+
+    def stats(self):
+        """(hashes per level of the last rebuild [depth + 1], rebuilds so far)."""
+        hashes, builds = np.zeros(self.depth + 1, dtype=np.uint64), ctypes.c_uint64()
+        self.ctx._check(lib.imt_itree_view_stats(self.h, hashes.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                                 ctypes.byref(builds)))
+        return hashes, builds.value

@@ -18,9 +18,11 @@
 #include <cstdint>
 #include <cstring>
 #include <initializer_list>
+#include <mutex>
 #include <new>
 #include <numeric>
 #include <thread>
+#include <unordered_set>
 
 using namespace imt;
 
@@ -192,6 +194,31 @@ struct imt_itree {
     uint64_t* d_apply_stats = nullptr;       // [IMT_MAX_DEPTH + 1]
     bool apply_seen = false;
     uint64_t* d_rewind_stats = nullptr;      // [IMT_MAX_DEPTH + 1]: the same of the last imt_itree_rewind
+    uint64_t gen = 0;                        // bumped by every call that changes the contents: what a view's side table is for
+};
+
+// A read-only view of a tree at an earlier size (imt_view.hpp).  The compacted index and the side table are a cache for
+// (size, t->gen); everything is the view's own memory, so building one writes nothing the tree or another view reads.
+struct imt_itree_view {
+    imt_itree* t = nullptr;
+    uint64_t size = 0;
+    uint64_t gen = ~(uint64_t)0;             // the tree's generation the cache was built for (none yet)
+    bool current = false;                    // size == the tree's size at that generation: nothing cached, the tree answers
+    uint64_t builds = 0;
+    uint64_t h_hashes[IMT_MAX_DEPTH + 1] = {0};
+    uint32_t* d_sorted = nullptr;            // [size] the index as of `size`
+    uint64_t* d_count = nullptr;             // [IMT_MAX_DEPTH + 1] listed nodes per level
+    uint8_t* d_chain = nullptr;              // [IMT_MAX_DEPTH + 1][32] node 0 of the levels from `top` up
+    // per build, for `rows` = relinked leaves + 1 table rows (grow-only)
+    size_t rows_cap = 0;
+    unsigned levels_cap = 0;
+    uint32_t* d_tab[4] = {nullptr};          // node, time, rs, re [rows]
+    uint32_t* d_src = nullptr;               // [rows]
+    uint8_t* d_pre = nullptr;                // [rows][96]
+    uint32_t* d_list = nullptr;              // [levels][rows]
+    uint8_t* d_side = nullptr;               // [levels][rows][32]
+    unsigned top = 0;                        // of the last build
+    view::Side side() const { return {d_list, d_count, rows_cap, top, size, d_side, d_chain}; }
 };
 
 static void plan_free(PlanSet& p) {
@@ -764,6 +791,18 @@ static int find_pred(const imt_itree* t, const U256& v, size_t& pos) {
     return IMT_OK;
 }
 
+// What the read calls below answer from: the tree itself (v == NULL), or a view of it at an earlier size (imt_view.hpp),
+// whose index is its own and whose nodes are (side table | stored node | empty subtree).  The same code serves both, so a
+// view's answers and refusals are the tree's by construction.
+static const uint32_t* read_index(const imt_itree* t, const imt_itree_view* v) { return v ? v->d_sorted : t->d_sorted[t->sorted_cur]; }
+static uint64_t read_size(const imt_itree* t, const imt_itree_view* v) { return v ? v->size : t->size; }
+static void read_proofs(imt_itree* t, const imt_itree_view* v, hipStream_t s, const uint64_t* d_idx, size_t n, uint8_t* d_out,
+                        launch::SibLayout lay, unsigned fmt) {
+    const launch::TreeView tv{t->d_nodes, t->d_off, t->d_len, t->ctx->d_zero, t->index_base};
+    if (v) launch::view_gather_proof(s, v->side(), tv, d_idx, n, t->depth, d_out, lay, fmt);
+    else launch::gather_proof(s, tv, d_idx, n, t->depth, d_out, lay, fmt);
+}
+
 extern "C" int imt_itree_find_low_batch(imt_itree* t, const void* vals, size_t n, uint64_t* low_index, unsigned flags) {
     if (!t) return IMT_ERR_ARG;
     imt_ctx* c = t->ctx;
@@ -822,7 +861,7 @@ extern "C" int imt_itree_find_low_batch(imt_itree* t, const void* vals, size_t n
     return IMT_OK;
 }
 
-extern "C" int imt_itree_get_leaves(imt_itree* t, const uint64_t* index, size_t n, void* preimage, unsigned flags) {
+static int get_leaves(imt_itree* t, const imt_itree_view* v, const uint64_t* index, size_t n, void* preimage, unsigned flags) {
     if (!t) return IMT_ERR_ARG;
     imt_ctx* c = t->ctx;
     IMT_NOT_SLICED(t);
@@ -836,7 +875,7 @@ extern "C" int imt_itree_get_leaves(imt_itree* t, const uint64_t* index, size_t 
     const unsigned fmt = flags & IMT_FMT_MASK;
     if ((rc = check_fe_ptrs(c, dev, {preimage}))) return rc;
     if (dev && index && ((uintptr_t)index & 7u)) return c->fail(IMT_ERR_ARG, "device index array is not 8-byte aligned");
-    if (!dev && t->mirror_valid) {
+    if (!dev && t->mirror_valid && !v) {
         // the host mirror is current (host-prepared batches): answer from it
         std::vector<uint8_t> buf(n * 96);
         for (size_t i = 0; i < n; i++) {
@@ -878,7 +917,7 @@ extern "C" int imt_itree_get_leaves(imt_itree* t, const uint64_t* index, size_t 
     int* d_perr = (int*)c->dev_scratch(2, sizeof(int));
     if (!d_out || !d_perr) return IMT_ERR_HIP;
     IMT_HIP(c, hipMemsetAsync(d_perr, 0, sizeof(int), s));
-    prep::leaves(s, d_idx, t->index_base, (uint32_t)n, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)t->size, t->cap,
+    prep::leaves(s, d_idx, t->index_base, (uint32_t)n, t->d_val, read_index(t, v), (uint32_t)read_size(t, v), t->cap,
                  t->index_base, d_out, d_perr);
     if (fmt != IMT_FMT_CANONICAL) launch::convert(s, d_out, d_out, n * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
     int perr = 0;
@@ -890,8 +929,11 @@ extern "C" int imt_itree_get_leaves(imt_itree* t, const uint64_t* index, size_t 
     if (perr & prep::ERR_RANGE) return c->fail(IMT_ERR_RANGE, "leaf index out of range");
     return IMT_OK;
 }
+extern "C" int imt_itree_get_leaves(imt_itree* t, const uint64_t* index, size_t n, void* preimage, unsigned flags) {
+    return get_leaves(t, nullptr, index, n, preimage, flags);
+}
 
-extern "C" int imt_itree_get_proof_batch(imt_itree* t, const uint64_t* index, size_t n, void* sib, unsigned flags) {
+static int get_proof_batch(imt_itree* t, const imt_itree_view* v, const uint64_t* index, size_t n, void* sib, unsigned flags) {
     if (!t) return IMT_ERR_ARG;
     imt_ctx* c = t->ctx;
     IMT_NOT_SLICED(t);
@@ -914,21 +956,23 @@ extern "C" int imt_itree_get_proof_batch(imt_itree* t, const uint64_t* index, si
         if (!d_idx || !d_out) return IMT_ERR_HIP;
         IMT_HIP(c, hipMemcpyAsync((void*)d_idx, index, n * 8, hipMemcpyHostToDevice, c->stream));
     }
-    launch::TreeView tv{t->d_nodes, t->d_off, t->d_len, c->d_zero, t->index_base};
     launch::SibLayout lay = (flags & IMT_SIB_ITEM_MAJOR) ? launch::SibLayout{1, depth} : launch::SibLayout{n, 1};
-    launch::gather_proof(c->stream, tv, d_idx, n, depth, d_out, lay, flags & IMT_FMT_MASK);
+    read_proofs(t, v, c->stream, d_idx, n, d_out, lay, flags & IMT_FMT_MASK);
     if (!dev) {
         IMT_HIP(c, hipMemcpyAsync(sib, d_out, (size_t)depth * n * 32, hipMemcpyDeviceToHost, c->stream));
         IMT_HIP(c, hipStreamSynchronize(c->stream));
     }
     return IMT_OK;
 }
+extern "C" int imt_itree_get_proof_batch(imt_itree* t, const uint64_t* index, size_t n, void* sib, unsigned flags) {
+    return get_proof_batch(t, nullptr, index, n, sib, flags);
+}
 
 // ------------------------------------------------------------------------------------
 // non-membership witness on the GPU
 // ------------------------------------------------------------------------------------
-extern "C" int imt_itree_non_membership_witness(imt_itree* t, const void* vals, size_t n, uint64_t* low_index,
-                                                void* low_leaf, uint8_t* is_largest, void* low_sib, unsigned flags) {
+static int non_membership_witness(imt_itree* t, const imt_itree_view* v, const void* vals, size_t n, uint64_t* low_index,
+                                  void* low_leaf, uint8_t* is_largest, void* low_sib, unsigned flags) {
     if (!t) return IMT_ERR_ARG;
     imt_ctx* c = t->ctx;
     IMT_NOT_SLICED(t);
@@ -964,13 +1008,12 @@ extern "C" int imt_itree_non_membership_witness(imt_itree* t, const void* vals, 
     const size_t sib_bytes = (size_t)t->depth * n * 32;
     uint8_t* g_sib = outbuf(low_sib, sib_bytes);
     if (!g_low || (low_leaf && !g_leaf) || (is_largest && !g_lg) || (low_sib && !g_sib)) return IMT_ERR_HIP;
-    prep::nm_witness(s, d_vals, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)t->size, (uint32_t)n, t->index_base,
+    prep::nm_witness(s, d_vals, t->d_val, read_index(t, v), (uint32_t)read_size(t, v), (uint32_t)n, t->index_base,
                      t->part_mod, t->part_res, g_low, g_leaf, g_lg, d_perr);
     if (g_leaf && fmt != IMT_FMT_CANONICAL) launch::convert(s, g_leaf, g_leaf, n * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
     if (g_sib) {
-        launch::TreeView tv{t->d_nodes, t->d_off, t->d_len, c->d_zero, t->index_base};
         launch::SibLayout lay = (flags & IMT_SIB_ITEM_MAJOR) ? launch::SibLayout{1, t->depth} : launch::SibLayout{n, 1};
-        launch::gather_proof(s, tv, g_low, n, t->depth, g_sib, lay, fmt);
+        read_proofs(t, v, s, g_low, n, g_sib, lay, fmt);
     }
     int perr = 0;
     IMT_HIP(c, hipMemcpyAsync(&perr, d_perr, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -988,6 +1031,10 @@ extern "C" int imt_itree_non_membership_witness(imt_itree* t, const void* vals, 
     if (perr & (prep::ERR_ZERO | prep::ERR_DUPLICATE))
         return c->fail(IMT_ERR_VALUE, "a candidate is 0 or already in the tree (it has no non-membership witness)");
     return IMT_OK;
+}
+extern "C" int imt_itree_non_membership_witness(imt_itree* t, const void* vals, size_t n, uint64_t* low_index,
+                                                void* low_leaf, uint8_t* is_largest, void* low_sib, unsigned flags) {
+    return non_membership_witness(t, nullptr, vals, n, low_index, low_leaf, is_largest, low_sib, flags);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1088,6 +1135,7 @@ extern "C" int imt_itree_load(imt_itree* t, const void* preimages, uint64_t n, u
     t->mirror_valid = false;
     t->dev_index_valid = true;
     t->pending.active = false;
+    t->gen++;
     for (auto& pl : t->plan) pl.has_root = false;
     return IMT_OK;
 }
@@ -1576,6 +1624,7 @@ static int insert_core(imt_itree* t, const void* vals, unsigned val_flags, size_
     } else {
         host_commit(t, hp, n);
     }
+    t->gen++;
 
     // ---- outputs ----
     if (out && (rc = deliver_hashfree_outputs(t, s, n, out, d, hp, flags, slot))) return rc;
@@ -1742,6 +1791,7 @@ extern "C" int imt_itree_rewind(imt_itree* t, uint64_t new_size, void* root_out,
     t->sorted.shrink_to_fit();
     t->mirror_valid = false;
     t->dev_index_valid = true;
+    t->gen++;
     for (auto& pl : t->plan) pl.has_root = false;
     IMT_HIP(c, hipStreamSynchronize(s));
     return IMT_OK;
@@ -1921,8 +1971,8 @@ extern "C" int imt_itree_apply_filtered(imt_itree* t, const void* vals, size_t n
     return filtered_core(t, vals, n, status, leaf_index, n_inserted, nullptr, flags, &req);
 }
 
-extern "C" int imt_itree_lookup_batch(imt_itree* t, const void* vals, size_t n, uint8_t* status, uint64_t* leaf_index,
-                                      unsigned flags) {
+static int lookup_batch(imt_itree* t, const imt_itree_view* v, const void* vals, size_t n, uint8_t* status,
+                        uint64_t* leaf_index, unsigned flags) {
     if (!t) return IMT_ERR_ARG;
     imt_ctx* c = t->ctx;
     IMT_NOT_SLICED(t);
@@ -1949,7 +1999,7 @@ extern "C" int imt_itree_lookup_batch(imt_itree* t, const void* vals, size_t n, 
     uint8_t* d_st = dev ? status : (uint8_t*)c->dev_scratch(3, n);
     uint64_t* d_leaf = (dev || !leaf_index) ? leaf_index : (uint64_t*)c->dev_scratch(1, n * 8);
     if (!d_st || (leaf_index && !d_leaf)) return IMT_ERR_HIP;
-    prep::lookup(s, d_vals, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)t->size, (uint32_t)n, t->index_base,
+    prep::lookup(s, d_vals, t->d_val, read_index(t, v), (uint32_t)read_size(t, v), (uint32_t)n, t->index_base,
                  t->part_mod, t->part_res, d_st, d_leaf, d_perr);
     int perr = 0;
     IMT_HIP(c, hipMemcpyAsync(&perr, d_perr, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1959,6 +2009,248 @@ extern "C" int imt_itree_lookup_batch(imt_itree* t, const void* vals, size_t n, 
     }
     IMT_HIP(c, hipStreamSynchronize(s));
     if (perr & prep::ERR_NONCANONICAL) return c->fail(IMT_ERR_NONCANONICAL, "a value is not reduced (>= p)");
+    return IMT_OK;
+}
+extern "C" int imt_itree_lookup_batch(imt_itree* t, const void* vals, size_t n, uint8_t* status, uint64_t* leaf_index,
+                                      unsigned flags) {
+    return lookup_batch(t, nullptr, vals, n, status, leaf_index, flags);
+}
+
+// ------------------------------------------------------------------------------------
+// read-only views at an earlier size (imt_view.hpp)
+// ------------------------------------------------------------------------------------
+// The views that exist.  A view handle is looked up here before anything is read through it, so a handle that is not a
+// live view -- a freed one, a tree's -- is an argument error like a NULL one and never a wild read.
+static std::mutex g_views_mu;
+static std::unordered_set<const imt_itree_view*> g_views;
+static bool view_alive(const imt_itree_view* v) {
+    std::lock_guard<std::mutex> lock(g_views_mu);
+    return v && g_views.count(v) != 0;
+}
+
+// what imt_itree_rewind refuses for the state the tree is in, in its words
+static int check_view_call(imt_itree* t, unsigned flags) {
+    imt_ctx* c = t->ctx;
+    IMT_NOT_SLICED(t);
+    if (flags & IMT_PIPELINE) return c->fail(IMT_ERR_ARG, "a view is not pipelined (IMT_PIPELINE)");
+    if ((flags & IMT_FMT_MASK) == 3) return c->fail(IMT_ERR_ARG, "unknown field-element format");
+    if (slice_open(t)) return c->fail(IMT_ERR_ARG, "a slice is open (issue its remaining units first)");
+    if (t->pending.active) return c->fail(IMT_ERR_ARG, "a sharded batch is open (imt_itree_batch_end first)");
+    return c->set_device();
+}
+
+static void view_release_build(imt_itree_view* v) {
+    for (void* q : {(void*)v->d_tab[0], (void*)v->d_tab[1], (void*)v->d_tab[2], (void*)v->d_tab[3], (void*)v->d_src,
+                    (void*)v->d_pre, (void*)v->d_list, (void*)v->d_side})
+        if (q) hipFree(q);
+    for (auto& q : v->d_tab) q = nullptr;
+    v->d_src = nullptr;
+    v->d_pre = nullptr;
+    v->d_list = nullptr;
+    v->d_side = nullptr;
+    v->rows_cap = 0;
+    v->levels_cap = 0;
+}
+
+// the view's buffers for a build of `rows` table rows and `levels` list levels
+static int view_reserve(imt_itree_view* v, size_t rows, unsigned levels) {
+    if (v->rows_cap >= rows && v->levels_cap >= levels) return IMT_OK;
+    imt_ctx* c = v->t->ctx;
+    view_release_build(v);
+    const size_t E = rows + rows / 4;
+    hipError_t e = hipSuccess;
+    auto A = [&](void** ptr, size_t bytes) {
+        if (e == hipSuccess) e = hipMalloc(ptr, bytes);
+    };
+    for (auto& q : v->d_tab) A((void**)&q, E * 4);
+    A((void**)&v->d_src, E * 4);
+    A((void**)&v->d_pre, E * 96);
+    A((void**)&v->d_list, (size_t)levels * E * 4);
+    A((void**)&v->d_side, (size_t)levels * E * 32);
+    if (e != hipSuccess) {
+        view_release_build(v);
+        return c->hip_fail(e, "hipMalloc(view)");
+    }
+    v->rows_cap = E;
+    v->levels_cap = levels;
+    return IMT_OK;
+}
+
+// The cache for (v->size, the tree as it is): the index of the earlier tree and the side table, on the context's stream
+// behind everything in flight on the tree.  imt_itree_rewind's sequence with two differences: every output goes to the
+// view's memory, and nothing is refilled or written back -- the hashes read their children through the rule instead.
+static int view_build(imt_itree_view* v) {
+    imt_itree* t = v->t;
+    imt_ctx* c = t->ctx;
+    const uint64_t M = t->size, S = v->size;
+    int rc;
+    if (S == M) {                                               // the tree answers: nothing to compute, nothing cached
+        std::memset(v->h_hashes, 0, sizeof(v->h_hashes));
+        v->current = true;
+        v->gen = t->gen;
+        v->builds++;
+        return IMT_OK;
+    }
+    if ((rc = ensure_device_index(t))) return rc;
+    if ((rc = join_top(t))) return rc;
+    for (const auto& pl : t->plan)                              // and behind whatever else a plan set still has in flight: the
+        if (pl.in_flight) IMT_HIP(c, hipStreamWaitEvent(c->stream, pl.done, 0));   // sets themselves stay as they are
+    IMT_HIP(c, hipStreamSynchronize(t->up_stream));             // the index is written on the side stream
+    hipStream_t s = c->stream;
+    const unsigned L0 = std::min(ceil_log2(M), t->depth);
+    const size_t max_rows = (size_t)std::min(M - S, S) + 1;
+    struct Trim {
+        imt_ctx* c;
+        ~Trim() { c->trim_scratch(3, (size_t)64 << 20); }
+    } trim{c};
+    const size_t ws_bytes = prep::rewind_ws_bytes((size_t)M, max_rows);
+    void* ws = c->dev_scratch(3, ws_bytes);
+    if (!ws) return IMT_ERR_HIP;
+    const uint32_t* sorted_now = t->d_sorted[t->sorted_cur];
+    const uint32_t* d_relinked = nullptr;
+    uint32_t R = 0;
+    IMT_HIP(c, prep::rewind_compact(s, ws, ws_bytes, sorted_now, v->d_sorted, (uint32_t)M, (uint32_t)S, &d_relinked));
+    IMT_HIP(c, hipMemcpyAsync(&R, d_relinked, sizeof(R), hipMemcpyDeviceToHost, s));
+    IMT_HIP(c, hipStreamSynchronize(s));
+    if ((size_t)R + 1 > max_rows) return c->fail(IMT_ERR_INTERNAL, "view: %u relinked leaves, at most %zu expected", R, max_rows - 1);
+    const size_t E = (size_t)R + 1;
+    if ((rc = view_reserve(v, E, L0))) return rc;
+    const size_t stride = v->rows_cap;
+    // scratch of the build alone: the unsorted table, the scans' places and their temporary storage
+    const size_t tmp_bytes = prep::apply_lists_tmp_bytes(E);
+    const size_t pos_bytes = ((size_t)L0 * stride * 4 + 255) & ~(size_t)255, key_bytes = (E * 4 + 255) & ~(size_t)255;
+    uint8_t* scr = (uint8_t*)c->dev_scratch(0, pos_bytes + 2 * key_bytes + tmp_bytes);
+    if (!scr) return IMT_ERR_HIP;
+    uint32_t* pos = (uint32_t*)scr;
+    uint32_t* key = (uint32_t*)(scr + pos_bytes);
+    uint32_t* row = (uint32_t*)(scr + pos_bytes + key_bytes);
+    void* tmp = scr + pos_bytes + 2 * key_bytes;
+    IMT_HIP(c, prep::rewind_table(s, ws, ws_bytes, t->d_val, sorted_now, v->d_sorted, (uint32_t)M, (uint32_t)S, t->index_base,
+                                  (uint32_t)E, key, row, v->d_pre, v->d_tab[0], v->d_tab[1], v->d_tab[2], v->d_tab[3]));
+    const apply::Lists lists{v->d_list, v->d_src, v->d_count, stride};
+    IMT_HIP(c, prep::apply_lists(s, tmp, tmp_bytes, v->d_tab[0], v->d_tab[1], v->d_tab[3], (uint32_t)E, L0, t->depth, pos, lists));
+    v->top = L0;
+    const view::Side side = v->side();
+    launch::view_leaves(s, lists.count, apply::bound((uint32_t)E, L0, 0), lists.node, lists.src, v->d_pre, IMT_FMT_CANONICAL,
+                        c->d_err, v->d_side, t->h_len[0], c->coop_max_events);
+    for (unsigned l = 0; l + 1 < L0; l++)
+        launch::view_level(s, side, l, apply::bound((uint32_t)E, L0, l + 1), t->nodes(l), t->h_len[l],
+                           c->d_zero + (size_t)l * 32, v->d_side + (size_t)(l + 1) * stride * 32, t->h_len[l + 1],
+                           c->coop_max_events);
+    launch::view_top(s, side, launch::TreeView{t->d_nodes, t->d_off, t->d_len, c->d_zero, t->index_base}, v->d_chain, L0 - 1,
+                     t->depth);
+    IMT_HIP(c, hipMemcpyAsync(v->h_hashes, v->d_count, (t->depth + 1) * 8, hipMemcpyDeviceToHost, s));
+    IMT_HIP(c, hipStreamSynchronize(s));
+    v->current = false;
+    v->gen = t->gen;
+    v->builds++;
+    return IMT_OK;
+}
+
+// every query starts here: the refusals, then the cache brought up to the tree
+static int view_enter(imt_itree_view* v, unsigned flags) {
+    if (!view_alive(v)) return IMT_ERR_ARG;
+    imt_itree* t = v->t;
+    int rc = check_view_call(t, flags);
+    if (rc) return rc;
+    if (t->size < v->size)
+        return t->ctx->fail(IMT_ERR_RANGE, "the tree holds %llu leaves, fewer than the view's %llu", (unsigned long long)t->size,
+                            (unsigned long long)v->size);
+    return v->gen == t->gen ? IMT_OK : view_build(v);
+}
+// the view a query is answered from: none when the tree itself is the answer
+static const imt_itree_view* view_source(const imt_itree_view* v) { return v->current ? nullptr : v; }
+
+extern "C" int imt_itree_view_create(imt_itree* t, uint64_t size, imt_itree_view** out) {
+    if (!t || !out) return IMT_ERR_ARG;
+    *out = nullptr;
+    imt_ctx* c = t->ctx;
+    int rc = check_view_call(t, 0);
+    if (rc) return rc;
+    if (size == 0 || size > t->size)
+        return c->fail(IMT_ERR_RANGE, "no view at %llu leaves of a tree of %llu", (unsigned long long)size, (unsigned long long)t->size);
+    imt_itree_view* v = new (std::nothrow) imt_itree_view();
+    if (!v) return c->fail(IMT_ERR_ALLOC, "out of host memory");
+    v->t = t;
+    v->size = size;
+    hipError_t e;
+    if ((e = hipMalloc((void**)&v->d_sorted, size * 4)) != hipSuccess ||
+        (e = hipMalloc((void**)&v->d_count, (IMT_MAX_DEPTH + 1) * 8)) != hipSuccess ||
+        (e = hipMalloc((void**)&v->d_chain, (IMT_MAX_DEPTH + 1) * 32)) != hipSuccess) {
+        for (void* q : {(void*)v->d_sorted, (void*)v->d_count, (void*)v->d_chain})
+            if (q) hipFree(q);
+        delete v;
+        return c->hip_fail(e, "hipMalloc(view)");
+    }
+    {
+        std::lock_guard<std::mutex> lock(g_views_mu);
+        g_views.insert(v);
+    }
+    *out = v;
+    return IMT_OK;
+}
+
+extern "C" void imt_itree_view_free(imt_itree_view* v) {
+    {
+        std::lock_guard<std::mutex> lock(g_views_mu);
+        if (!v || !g_views.erase(v)) return;
+    }
+    imt_ctx* c = v->t->ctx;
+    hipSetDevice(c->device);
+    hipStreamSynchronize(c->stream);
+    view_release_build(v);
+    for (void* q : {(void*)v->d_sorted, (void*)v->d_count, (void*)v->d_chain})
+        if (q) hipFree(q);
+    delete v;
+}
+
+extern "C" uint64_t imt_itree_view_size(const imt_itree_view* v) { return view_alive(v) ? v->size : 0; }
+
+extern "C" int imt_itree_view_root(imt_itree_view* v, void* root, unsigned flags) {
+    if (!view_alive(v) || !root) return IMT_ERR_ARG;
+    int rc = view_enter(v, flags);
+    if (rc) return rc;
+    imt_itree* t = v->t;
+    if (v->current) return imt_itree_root(t, root, flags);
+    imt_ctx* c = t->ctx;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    if ((rc = check_fe_ptrs(c, dev, {root}))) return rc;
+    const uint8_t* src = v->d_chain + (size_t)t->depth * 32;
+    uint8_t* d = dev ? (uint8_t*)root : (uint8_t*)c->dev_scratch(0, 32);
+    if (!d) return IMT_ERR_HIP;
+    launch::convert(c->stream, src, d, 1, IMT_FMT_DEVICE, flags & IMT_FMT_MASK, c->d_err);
+    if (dev) return IMT_OK;
+    IMT_HIP(c, hipMemcpyAsync(root, d, 32, hipMemcpyDeviceToHost, c->stream));
+    IMT_HIP(c, hipStreamSynchronize(c->stream));
+    return IMT_OK;
+}
+
+extern "C" int imt_itree_view_lookup_batch(imt_itree_view* v, const void* vals, size_t n, uint8_t* status, uint64_t* leaf_index,
+                                           unsigned flags) {
+    int rc = view_enter(v, flags);
+    return rc ? rc : lookup_batch(v->t, view_source(v), vals, n, status, leaf_index, flags);
+}
+
+extern "C" int imt_itree_view_get_leaves(imt_itree_view* v, const uint64_t* index, size_t n, void* preimage, unsigned flags) {
+    int rc = view_enter(v, flags);
+    return rc ? rc : get_leaves(v->t, view_source(v), index, n, preimage, flags);
+}
+
+extern "C" int imt_itree_view_get_proof_batch(imt_itree_view* v, const uint64_t* index, size_t n, void* sib, unsigned flags) {
+    int rc = view_enter(v, flags);
+    return rc ? rc : get_proof_batch(v->t, view_source(v), index, n, sib, flags);
+}
+
+extern "C" int imt_itree_view_non_membership_witness(imt_itree_view* v, const void* vals, size_t n, uint64_t* low_index,
+                                                     void* low_leaf, uint8_t* is_largest, void* low_sib, unsigned flags) {
+    int rc = view_enter(v, flags);
+    return rc ? rc : non_membership_witness(v->t, view_source(v), vals, n, low_index, low_leaf, is_largest, low_sib, flags);
+}
+
+extern "C" int imt_itree_view_stats(imt_itree_view* v, uint64_t* hashes, uint64_t* builds) {
+    if (!view_alive(v)) return IMT_ERR_ARG;
+    if (hashes) std::memcpy(hashes, v->h_hashes, (v->t->depth + 1) * 8);
+    if (builds) *builds = v->builds;
     return IMT_OK;
 }
 
@@ -2151,6 +2443,7 @@ extern "C" int imt_itree_batch_end(imt_itree* t, const void* const* val_levels, 
     t->cur = (t->cur + 1) % imt_itree::NSETS;
     t->batch_no++;
     t->pending.active = false;
+    t->gen++;
     return IMT_OK;
 }
 
@@ -2333,6 +2626,7 @@ extern "C" int imt_itree_slice_prepare(imt_itree* t, const void* vals, size_t n_
     t->sorted_cur ^= 1;          // chain[n_merges] == spare
     t->size = M0 + n_all;
     t->mirror_valid = false;
+    t->gen++;
     P.open = true;
     P.sliced = true;
     P.slice_n = n_own;

@@ -1022,6 +1022,106 @@ __global__ IMT_HASH_WAVES void k_apply_top(uint8_t* nodes, const uint64_t* __res
 #endif
 }
 
+// -----------------------------------------------------------------------------------------------
+// A view of the tree at an earlier size (imt_view.hpp): k_apply_level's hashes with another load and store address.
+//   LEAVES  side row 0, place j = H(preimage of event src[j]): the relinked leaves and the empty slot
+//   LEVEL   side row l + 1, place j = hash2(children 2p, 2p + 1 of level l as of the view's size), p = list[j]: each
+//           child is the side table's entry, the stored node or the empty subtree (view::node_row).
+// Nothing of the tree is written.  The guards are k_apply_level's: the launch bound (<= the side table's stride, so a
+// place is inside its row), the device count, and a listed node the level cannot hold is not hashed.
+// -----------------------------------------------------------------------------------------------
+__global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_view_level(launch::ViewArgs a) {
+    __shared__ uint32_t stash[NL][BLOCK];
+    const size_t j = gtid();
+    if (j >= a.bound || j >= *a.count) return;
+    const uint64_t p = a.list[j];
+    if (p >= a.len_out) return;                      // never by construction
+    Fe A, B, o;
+    if (a.mode == launch::APPLY_LEAVES) {
+        const uint8_t* q = a.pre + (size_t)a.src[j] * 96;
+        Fe C;
+        bool ok = load_fe(g_pc, A, q, a.fmt_in);
+        ok &= load_fe(g_pc, B, q + 32, a.fmt_in);
+        ok &= load_fe(g_pc, C, q + 64, a.fmt_in);
+#pragma unroll
+        for (int i = 0; i < NL; i++) stash[i][threadIdx.x] = C.v[i];
+        flag_err(a.err, ok);
+    } else {
+        load_packed(A, view::node_row(a.side, a.level_in, 2 * p, a.tree_in, a.len_in, a.zero_in));
+        load_packed(B, view::node_row(a.side, a.level_in, 2 * p + 1, a.tree_in, a.len_in, a.zero_in));
+    }
+    hash23_stashed(g_pc, o, A, B, a.mode == launch::APPLY_LEAVES, &stash[0][threadIdx.x], BLOCK);
+    store_packed(a.out + j * 32, o);
+}
+
+// a quad of lanes per listed node (k_apply_level_coop)
+__global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_view_level_coop(launch::ViewArgs a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ uint32_t tab[coop::TAB_DWORDS];
+    coop::tab_fill(tab, g_pc);                       // before anyone leaves: it ends in a barrier
+    const size_t t = gtid();
+    const size_t j = t >> 2;
+    if (j >= a.bound || j >= *a.count) return;       // whole quads leave together
+    const unsigned role = (unsigned)t & 3u, ri = role == 3u ? 0u : role;
+    const uint64_t p = a.list[j];
+    if (p >= a.len_out) return;
+    Fe X, C3, o;
+    C3 = g_pc.one;                                   // any value: only read for LEAVES
+    if (a.mode == launch::APPLY_LEAVES) {
+        const uint8_t* q = a.pre + (size_t)a.src[j] * 96;
+        bool ok = load_fe(g_pc, X, q + (ri == 2u ? 32 : 0), a.fmt_in);     // lane 1: val, lane 2: next_val
+        ok &= load_fe(g_pc, C3, q + 64, a.fmt_in);                         // next_idx, absorbed by lane 1
+        if (ri == 1u) ok &= load_fe(g_pc, o, q + 32, a.fmt_in);            // (every element validated once)
+        flag_err(a.err, ok);
+    } else {
+        const uint64_t ch = 2 * p + (ri == 2u ? 1u : 0u);                  // lane 1: left child, lane 2: right child
+        load_packed(X, view::node_row(a.side, a.level_in, ch, a.tree_in, a.len_in, a.zero_in));
+    }
+    coop::hash23(tab, o, X, C3, a.mode == launch::APPLY_LEAVES, ri);
+    if (role == 1u) store_packed(a.out + j * 32, o);
+#endif
+}
+
+// Levels [from, to), from = side.top - 1: k_apply_top's chain of node 0, every link into chain[l + 1] and none into the
+// tree.  At level `from` node 0 and its right sibling are whatever the rule says; from side.top up the sibling is the
+// empty subtree.
+__global__ IMT_HASH_WAVES void k_view_top(view::Side sd, launch::TreeView tv, uint8_t* chain, unsigned from, unsigned to) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ uint32_t tab[coop::TAB_DWORDS];
+    coop::tab_fill(tab, g_pc);
+    if (blockIdx.x != 0 || threadIdx.x >= 4) return;
+    const unsigned role = threadIdx.x, ri = role == 3u ? 0u : role;
+    const uint8_t* stored = tv.nodes + tv.off[from] * 32;
+    Fe cur;
+    load_packed(cur, view::node_row(sd, from, 0, stored, tv.len[from], tv.zero + (size_t)from * 32));
+#pragma unroll 1
+    for (unsigned l = from; l < to; l++) {
+        Fe z, X, o;
+        load_packed(z, l == from ? view::node_row(sd, from, 1, stored, tv.len[from], tv.zero + (size_t)from * 32)
+                                 : tv.zero + (size_t)l * 32);
+        coop::sel(X, ri == 2u, z, cur);              // lane 1: node 0, lane 2: its right sibling
+        coop::hash23(tab, o, X, X, false, ri);
+        coop::quad_bcast<1>(cur, o);
+        if (role == 1u) store_packed(chain + (size_t)(l + 1) * 32, cur);
+    }
+#endif
+}
+
+// k_gather_proof as of the view's size: items fastest, coalesced level-major stores
+__global__ void __launch_bounds__(BLOCK) k_view_gather_proof(view::Side sd, launch::TreeView tv,
+                                                             const uint64_t* __restrict__ index, size_t n, unsigned depth,
+                                                             uint8_t* __restrict__ out, launch::SibLayout lay,
+                                                             unsigned fmt_out) {
+    const size_t t = gtid();
+    if (t >= n * depth) return;
+    const size_t i = t % n;
+    const unsigned l = (unsigned)(t / n);
+    const uint64_t s = ((index[i] - tv.index_base) >> l) ^ 1;
+    Fe x;
+    load_packed(x, view::node_row(sd, l, s, tv.nodes + tv.off[l] * 32, tv.len[l], tv.zero + (size_t)l * 32));
+    store_fe(g_pc, out + ((uint64_t)l * lay.level_stride + i * lay.item_stride) * 32, x, fmt_out);
+}
+
 // ---- subtree placement (imt_itree_lift_batch) ---------------------------------------------------
 // A tree placed as subtree g of a deeper tree produces subtree-level roots; the enclosing tree's root
 // after the same event is `levels` more hash2 up a path whose siblings are the same for the whole batch.
@@ -1494,6 +1594,41 @@ void apply_top(hipStream_t s, uint8_t* nodes, const uint64_t* off, const uint64_
                unsigned to) {
     if (from >= to) return;
     hipLaunchKernelGGL(k_apply_top, dim3(1), dim3(64), 0, s, nodes, off, len, zero, from, to);
+}
+// the two forms of k_view_level, chosen as launch_apply chooses
+static void launch_view(hipStream_t s, const ViewArgs& a, uint32_t coop_max) {
+    if (!a.bound) return;
+    if (a.bound <= coop_max)
+        hipLaunchKernelGGL(k_view_level_coop, dim3(nblk((size_t)a.bound * 4)), dim3(BLOCK), 0, s, a);
+    else
+        hipLaunchKernelGGL(k_view_level, dim3(nblk(a.bound)), dim3(BLOCK), 0, s, a);
+}
+void view_leaves(hipStream_t s, const uint64_t* count, uint32_t bound, const uint32_t* list, const uint32_t* src,
+                 const uint8_t* pre, unsigned fmt_in, int* err, uint8_t* out, uint64_t len0, uint32_t coop_max) {
+    ViewArgs a{};
+    a.mode = APPLY_LEAVES;
+    a.count = count; a.bound = bound; a.list = list; a.out = out; a.len_out = len0;
+    a.src = src; a.pre = pre; a.fmt_in = fmt_in; a.err = err;
+    launch_view(s, a, coop_max);
+}
+void view_level(hipStream_t s, const view::Side& side, unsigned level_in, uint32_t bound, const uint8_t* tree_in,
+                uint64_t len_in, const uint8_t* zero_in, uint8_t* out, uint64_t len_out, uint32_t coop_max) {
+    ViewArgs a{};
+    a.mode = APPLY_LEVEL;
+    a.count = side.count + level_in + 1; a.bound = bound; a.list = side.node + (size_t)(level_in + 1) * side.stride;
+    a.out = out; a.len_out = len_out;
+    a.side = side; a.level_in = level_in; a.tree_in = tree_in; a.len_in = len_in; a.zero_in = zero_in;
+    launch_view(s, a, coop_max);
+}
+void view_top(hipStream_t s, const view::Side& side, TreeView tv, uint8_t* chain, unsigned from, unsigned to) {
+    if (from >= to) return;
+    hipLaunchKernelGGL(k_view_top, dim3(1), dim3(64), 0, s, side, tv, chain, from, to);
+}
+void view_gather_proof(hipStream_t s, const view::Side& side, TreeView tv, const uint64_t* index, size_t n, unsigned depth,
+                       uint8_t* out, SibLayout lay, unsigned fmt_out) {
+    if (!n || !depth) return;
+    hipLaunchKernelGGL(k_view_gather_proof, dim3(nblk(n * depth)), dim3(BLOCK), 0, s, side, tv, index, n, depth, out, lay,
+                       fmt_out);
 }
 void emit_roots(hipStream_t s, const uint8_t* val, uint32_t e_begin, uint32_t e_count, uint32_t total, uint8_t* old_root,
                 uint8_t* interim_root, uint8_t* new_root, unsigned fmt_out, uint8_t* roots_dev, uint8_t* node_store) {

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include "imt_consts.hpp"
 #include "imt_sweep.hpp"
+#include "imt_view.hpp"
 
 namespace imt {
 namespace launch {
@@ -199,6 +200,40 @@ void apply_level(hipStream_t s, const uint64_t* count, uint32_t bound, const uin
 // stored node 1 at level `from`, zero[l] above.  off / len: the tree's device arrays.  One quad.
 void apply_top(hipStream_t s, uint8_t* nodes, const uint64_t* off, const uint64_t* len, const uint8_t* zero, unsigned from,
                unsigned to);
+
+// ---- a view of the tree at an earlier size (imt_view.hpp): the same hashes into a side table, the tree only read ----
+// argument block of k_view_level: ApplyArgs with another store address -- listed node j goes to out + j * 32 -- and, for a
+// LEVEL launch, the children read through view::node_row.
+struct ViewArgs {
+    int mode;                             // APPLY_LEAVES / APPLY_LEVEL
+    const uint64_t* count;                // device word: listed nodes of the level that is hashed (<= bound)
+    uint32_t bound;                       // <= the side table's stride: rank j < bound stays inside row `out`
+    const uint32_t* list;                 // [count] those nodes, ascending
+    uint8_t* out;                         // the side table's row of that level
+    uint64_t len_out;                     // nodes the level can hold: a listed node beyond it is never hashed
+    // LEAVES: as ApplyArgs
+    const uint32_t* src;
+    const uint8_t* pre;
+    unsigned fmt_in;
+    int* err;
+    // LEVEL: node p = hash2(children 2p, 2p + 1 of level `level_in` as of the view's size)
+    view::Side side;
+    unsigned level_in;
+    const uint8_t* tree_in;               // the stored level below, its length and its empty subtree
+    uint64_t len_in;
+    const uint8_t* zero_in;
+};
+void view_leaves(hipStream_t s, const uint64_t* count, uint32_t bound, const uint32_t* list, const uint32_t* src,
+                 const uint8_t* pre, unsigned fmt_in, int* err, uint8_t* out, uint64_t len0, uint32_t coop_max);
+// row level_in + 1 of the side table from level level_in
+void view_level(hipStream_t s, const view::Side& side, unsigned level_in, uint32_t bound, const uint8_t* tree_in,
+                uint64_t len_in, const uint8_t* zero_in, uint8_t* out, uint64_t len_out, uint32_t coop_max);
+// chain[l + 1] = hash2(node 0 of level l, its right sibling) for l in [from, to), from = side.top - 1: both through the
+// rule at level `from`, chain[l] and zero[l] above.  tv: the stored tree.  One quad.
+void view_top(hipStream_t s, const view::Side& side, TreeView tv, uint8_t* chain, unsigned from, unsigned to);
+// gather_proof with every sibling read as of the view's size
+void view_gather_proof(hipStream_t s, const view::Side& side, TreeView tv, const uint64_t* index, size_t n, unsigned depth,
+                       uint8_t* out, SibLayout lay, unsigned fmt_out);
 
 // ---- subtree placement: lift subtree-level witnesses to the depth of the enclosing tree ----
 // top[j] (device format, j < levels) = sibling of this subtree's ancestor at height sub_depth + j;

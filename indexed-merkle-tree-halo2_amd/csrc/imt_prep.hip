@@ -448,6 +448,8 @@ void rewind_refill(hipStream_t st, uint8_t* nodes, const uint64_t* off, const ui
     hipLaunchKernelGGL(k_rewind_refill, dim3(nblk(M - s), l0), dim3(BLOCK), 0, st, nodes, off, len, zero, s, M);
 }
 
+size_t apply_lists_tmp_bytes(size_t total) { return apply_scan_bytes(total) + 256; }
+
 hipError_t apply_lists(hipStream_t s, void* tmp, size_t tmp_bytes, const uint32_t* node, const uint32_t* time,
                        const uint32_t* re, uint32_t total, unsigned l0, unsigned depth, uint32_t* pos,
                        const apply::Lists& lists) {

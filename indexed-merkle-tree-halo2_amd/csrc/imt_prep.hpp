@@ -76,6 +76,8 @@ hipError_t index_only(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t
 // ---- witness-free insertion (imt_itree_apply_batch): the touched nodes of every level (imt_apply.hpp) ----
 // From the level-0 tables run() left ([total] each): lists.node rows 0 .. l0-1, lists.src and lists.count[0 .. depth].
 // pos = [l0][lists.stride] scratch for the scans; tmp as in the workspace (temp_bytes_needed covers it).
+// the temporary storage apply_lists needs for `total` events, for a caller without a Workspace (a view's build)
+size_t apply_lists_tmp_bytes(size_t total);
 hipError_t apply_lists(hipStream_t s, void* tmp, size_t tmp_bytes, const uint32_t* node, const uint32_t* time,
                        const uint32_t* re, uint32_t total, unsigned l0, unsigned depth, uint32_t* pos,
                        const apply::Lists& lists);
