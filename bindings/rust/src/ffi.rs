@@ -275,6 +275,7 @@ extern "C" {
     pub fn imt_itree_view_get_proof_batch(v: *mut imt_itree_view, index: *const u64, n: usize, sib: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_view_non_membership_witness(v: *mut imt_itree_view, vals: *const c_void, n: usize, low_index: *mut u64, low_leaf: *mut c_void, is_largest: *mut u8, low_sib: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_view_stats(v: *mut imt_itree_view, hashes: *mut u64, builds: *mut u64) -> c_int;
+    pub fn imt_itree_view_insert_witness(v: *mut imt_itree_view, n: usize, out: *const imt_insert_out, flags: c_uint) -> c_int;
     pub fn imt_itree_lookup_batch(t: *mut imt_itree, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, flags: c_uint) -> c_int;
     pub fn imt_itree_non_membership_witness(t: *mut imt_itree, vals: *const c_void, n: usize, low_index: *mut u64, low_leaf: *mut c_void, is_largest: *mut u8, low_sib: *mut c_void, flags: c_uint) -> c_int;
 

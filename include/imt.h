@@ -565,6 +565,26 @@ int imt_itree_view_non_membership_witness(imt_itree_view *v, const void *vals /*
                                           uint8_t *is_largest /*[n]*/, void *low_sib /*[depth][n][32]*/,
                                           unsigned flags);
 int imt_itree_view_stats(imt_itree_view *v, uint64_t *hashes /*[depth + 1] or NULL*/, uint64_t *builds /*or NULL*/);
+/* APPLY NOW, PROVE LATER: the insert_leaf witnesses of the n insertions that followed the view's size -- the values the
+ * tree holds at leaves [size, size + n), in that order, inserted into the tree as of `size`.  There is no `vals`: the tree
+ * has the values, however they went in (apply, witness, filtered, sliced, loaded).
+ * DEFINED BY THE SIZES ALONE.  Take a fresh tree fed the first size - 1 values and call imt_itree_insert_batch on it with
+ * the next n values and the same flags: this call writes into `out` what that call would write, byte for byte -- all nine
+ * fields, NULL fields skipped, placement, global indices and value partition, IMT_FMT_*, IMT_SIB_ITEM_MAJOR and
+ * IMT_DEVICE_PTRS, level-major stride n, rows [depth, global_depth) of a placed tree's sibling arrays left to the caller
+ * (imt_itree_lift_batch).  IMT_INPUTS_READY and IMT_HOST_PREP change nothing here: the call runs on the context's stream
+ * and prepares on the GPU.
+ * It is a view query otherwise: it never changes the tree (stored nodes, index buffers, plan sets, size, rows of the value
+ * array), it rebuilds a stale side table first, behind everything in flight, and it is refused where the other queries
+ * are.  Synchronous for host pointers; with IMT_DEVICE_PTRS it is enqueued on the context's stream.
+ * size + n above the tree's current size (so any n > 0 on a view at the current size, and any n while the tree is
+ * smaller than the view): IMT_ERR_RANGE.  out == NULL: IMT_ERR_ARG.  A misaligned device buffer: IMT_ERR_ARG, as for
+ * imt_itree_insert_batch.  n == 0: IMT_OK.  Nothing is written in any of these cases.  Never IMT_ERR_VALUE: stored values
+ * were valid when they went in.
+ * Memory: the view owns a plan set for 2n events (what one of the tree's own plan sets holds for a batch of n), grow-only
+ * and freed with the view; the merged index of size + n entries, 4 bytes each, is borrowed from the context for the time
+ * of the call, as a rebuild borrows its scratch. */
+int imt_itree_view_insert_witness(imt_itree_view *v, size_t n, const imt_insert_out *out, unsigned flags);
 /* Read-only query of the device-resident index for any mix of values (one kernel, k_lookup): status ZERO / FOREIGN /
  * PRESENT / NEW and leaf_index = the sentinel / UINT64_MAX / the stored leaf / the low leaf (what find_low returns).
  * Fails only for its arguments, a value >= p (IMT_ERR_NONCANONICAL) or a HIP error, never for a value's class.  With

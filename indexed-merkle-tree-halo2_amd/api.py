@@ -838,6 +838,27 @@ class IndexedTreeView:
         self._checked(lib.imt_itree_view_non_membership_witness(self.h, _p(v), n, _p(low), _p(leaves), _p(largest), _p(sib), 0))
         return low, leaves, sib, largest
 
+    def insert_witness(self, n, proofs=True, item_major=False):
+        """The witnesses of the n insertions that followed this view's size (imt_itree_view_insert_witness): the dict
+        IndexedTree.insert_batch returns on a fresh tree fed the first size - 1 values, for the next n values the tree
+        holds.  Nothing of the tree changes."""
+        tree = self.tree
+        d = tree.global_depth                     # a placed tree fills rows [0, depth); lift_batch() the rest
+        res = dict(low_index=np.empty(n, np.uint64), low_leaf=np.empty((n, 3, 32), np.uint8),
+                   is_largest=np.empty(n, np.uint8), old_root=np.empty((n, 32), np.uint8),
+                   interim_root=np.empty((n, 32), np.uint8), new_root=np.empty((n, 32), np.uint8),
+                   new_leaf=np.empty((n, 3, 32), np.uint8))
+        if proofs:
+            shape = (n, d, 32) if item_major else (d, n, 32)
+            res["low_sib"] = np.empty(shape, np.uint8)
+            res["new_sib"] = np.empty(shape, np.uint8)
+        out = _ffi.InsertOut(**{k: a.ctypes.data for k, a in res.items()})
+        self.ctx._check(lib.imt_itree_view_insert_witness(self.h, n, ctypes.byref(out),
+                                                          _ffi.SIB_ITEM_MAJOR if item_major else 0))
+        size = self.size
+        res["new_index"] = np.arange(size, size + n, dtype=np.uint64) + np.uint64(tree.index_base)
+        return res
+
     def stats(self):
         """(hashes per level of the last rebuild [depth + 1], rebuilds so far)."""
         hashes, builds = np.zeros(self.depth + 1, dtype=np.uint64), ctypes.c_uint64()

@@ -218,6 +218,7 @@ struct imt_itree_view {
     uint32_t* d_list = nullptr;              // [levels][rows]
     uint8_t* d_side = nullptr;               // [levels][rows][32]
     unsigned top = 0;                        // of the last build
+    PlanSet plan;                            // imt_itree_view_insert_witness: tables and versions of a replay (grow-only)
     view::Side side() const { return {d_list, d_count, rows_cap, top, size, d_side, d_chain}; }
 };
 
@@ -2076,6 +2077,19 @@ static int view_reserve(imt_itree_view* v, size_t rows, unsigned levels) {
     return IMT_OK;
 }
 
+// The context's stream behind everything in flight on the tree, with the device index current: what a view's build and
+// a replay read -- stored nodes, d_val, the index -- is then the tree's committed state.
+static int view_behind_tree(imt_itree* t) {
+    imt_ctx* c = t->ctx;
+    int rc;
+    if ((rc = ensure_device_index(t))) return rc;
+    if ((rc = join_top(t))) return rc;
+    for (const auto& pl : t->plan)                              // and behind whatever else a plan set still has in flight: the
+        if (pl.in_flight) IMT_HIP(c, hipStreamWaitEvent(c->stream, pl.done, 0));   // sets themselves stay as they are
+    IMT_HIP(c, hipStreamSynchronize(t->up_stream));             // the index is written on the side stream
+    return IMT_OK;
+}
+
 // The cache for (v->size, the tree as it is): the index of the earlier tree and the side table, on the context's stream
 // behind everything in flight on the tree.  imt_itree_rewind's sequence with two differences: every output goes to the
 // view's memory, and nothing is refilled or written back -- the hashes read their children through the rule instead.
@@ -2091,11 +2105,7 @@ static int view_build(imt_itree_view* v) {
         v->builds++;
         return IMT_OK;
     }
-    if ((rc = ensure_device_index(t))) return rc;
-    if ((rc = join_top(t))) return rc;
-    for (const auto& pl : t->plan)                              // and behind whatever else a plan set still has in flight: the
-        if (pl.in_flight) IMT_HIP(c, hipStreamWaitEvent(c->stream, pl.done, 0));   // sets themselves stay as they are
-    IMT_HIP(c, hipStreamSynchronize(t->up_stream));             // the index is written on the side stream
+    if ((rc = view_behind_tree(t))) return rc;
     hipStream_t s = c->stream;
     const unsigned L0 = std::min(ceil_log2(M), t->depth);
     const size_t max_rows = (size_t)std::min(M - S, S) + 1;
@@ -2199,6 +2209,7 @@ extern "C" void imt_itree_view_free(imt_itree_view* v) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     view_release_build(v);
+    plan_free(v->plan);
     for (void* q : {(void*)v->d_sorted, (void*)v->d_count, (void*)v->d_chain})
         if (q) hipFree(q);
     delete v;
@@ -2245,6 +2256,97 @@ extern "C" int imt_itree_view_non_membership_witness(imt_itree_view* v, const vo
                                                      void* low_leaf, uint8_t* is_largest, void* low_sib, unsigned flags) {
     int rc = view_enter(v, flags);
     return rc ? rc : non_membership_witness(v->t, view_source(v), vals, n, low_index, low_leaf, is_largest, low_sib, flags);
+}
+
+// The witnesses of the n insertions that followed the view's size (imt_replay.hpp), behind view_enter and the range
+// check: imt_itree_insert_batch's sequence on the context's stream with the view in the tree's place.  The preparation
+// runs against the view's index over the values where they are, the tables and versions live in the view's own plan
+// set, every base sibling is read as of the view's size, and there is no write-back, no stored root and no commit.
+static int view_replay(imt_itree_view* v, size_t n, const imt_insert_out* out, unsigned flags) {
+    imt_itree* t = v->t;
+    imt_ctx* c = t->ctx;
+    const bool dev = flags & IMT_DEVICE_PTRS, item_major = flags & IMT_SIB_ITEM_MAJOR;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    const uint64_t S = v->size;
+    const size_t E = 2 * n;
+    const unsigned L0 = std::min(ceil_log2(S + n), t->depth);       // of the tree the insertions were made into
+    int rc;
+    if ((rc = view_behind_tree(t))) return rc;
+    hipStream_t s = c->stream;
+    PlanSet& P = v->plan;
+    if (P.cap_events < E || P.cap_levels < t->depth) IMT_HIP(c, hipStreamSynchronize(s));   // an earlier replay may still use it
+    if ((rc = plan_reserve(c, P, E, t->depth, t->cap))) return rc;
+    struct Trim {           // the merged index is 4 bytes per leaf of the tree as of size + n: borrowed, like a build's scratch
+        imt_ctx* c;
+        ~Trim() { c->trim_scratch(3, (size_t)64 << 20); }
+    } trim{c};
+    uint32_t* merged = (uint32_t*)c->dev_scratch(3, (size_t)(S + n) * 4);
+    if (!merged) return IMT_ERR_HIP;
+    // ---- where each requested output is written: the caller's array, or scratch copied back at the end ----
+    size_t slot = 4;
+    imt_insert_out d = {};
+    const size_t sib_bytes = (size_t)t->global_depth * n * 32;
+    if (!stage_out(c, dev, slot, out->low_index, n * 8, d.low_index) || !stage_out(c, dev, slot, out->is_largest, n, d.is_largest) ||
+        !stage_out(c, dev, slot, out->low_leaf, n * 96, d.low_leaf) || !stage_out(c, dev, slot, out->new_leaf, n * 96, d.new_leaf) ||
+        !stage_out(c, dev, slot, out->old_root, n * 32, d.old_root) ||
+        !stage_out(c, dev, slot, out->interim_root, n * 32, d.interim_root) ||
+        !stage_out(c, dev, slot, out->new_root, n * 32, d.new_root) || !stage_out(c, dev, slot, out->low_sib, sib_bytes, d.low_sib) ||
+        !stage_out(c, dev, slot, out->new_sib, sib_bytes, d.new_sib))
+        return IMT_ERR_HIP;
+    // ---- hash-free part: the values are rows [S, S + n) of d_val, the index is the view's ----
+    IMT_HIP(c, hipMemsetAsync(P.ws.err, 0, sizeof(int), s));
+    P.ws.part_mod = t->part_mod;
+    P.ws.part_res = t->part_res;
+    IMT_HIP(c, prep::run(s, P.ws, nullptr, t->d_val, v->d_sorted, merged, (uint32_t)S, (uint32_t)n, t->index_base, P.d_pre,
+                         P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][2], P.d_tab[0][3], d.low_index, d.is_largest,
+                         (uint8_t*)d.low_leaf, (uint8_t*)d.new_leaf));
+    // ---- hashing: witness_hashes' stages, the levels below L0 against the view and none of them written back ----
+    const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->global_depth} : launch::SibLayout{n, 1};
+    const view::Side side = v->side();
+    sweep_leaf_hashes(t, P, s, E);
+    int pf = c->prof_begin(IMT_PROF_INDEX, s);
+    index_phase(P, s, E, L0, nullptr);
+    c->prof_end(pf, s);
+    for (unsigned l = 0; l < L0; l++) {
+        const PlanSet::Level row = P.level(l);
+        pf = c->prof_begin(IMT_PROF_LEVEL, s);
+        launch::sweep_view_level(s, side, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], row.from, row.sibsrc, row.nodeb, row.timen,
+                                 t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, (uint32_t)E, (uint8_t*)d.low_sib,
+                                 (uint8_t*)d.new_sib, lay, l, fmt, c->coop_max_events);
+        c->prof_end(pf, s);
+    }
+    for (unsigned l = L0; l < t->depth; l++) {
+        pf = c->prof_begin(IMT_PROF_TOP, s);
+        launch::sweep_upper(s, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], c->d_zero + (size_t)l * 32, 0, (uint32_t)E, 0xffffffffu, nullptr,
+                            nullptr, (uint8_t*)d.low_sib, (uint8_t*)d.new_sib, lay, l, fmt, c->coop_max_events);
+        c->prof_end(pf, s);
+    }
+    // old_root[0] is the view's root; the other roots are the events' top values
+    if (d.old_root) launch::convert(s, v->d_chain + (size_t)t->depth * 32, (uint8_t*)d.old_root, 1, IMT_FMT_DEVICE, fmt, c->d_err);
+    launch::emit_roots(s, P.d_val[t->depth & 1], 0, (uint32_t)E, (uint32_t)E, (uint8_t*)d.old_root, (uint8_t*)d.interim_root,
+                       (uint8_t*)d.new_root, fmt, nullptr, nullptr);
+    // ---- outputs ----
+    const HostPlan hp;
+    if ((rc = deliver_hashfree_outputs(t, s, n, out, d, hp, flags, slot))) return rc;
+    if (dev) return IMT_OK;
+    if ((rc = deliver_witness_outputs(t, s, n, out, d, item_major, n))) return rc;
+    IMT_HIP(c, hipStreamSynchronize(s));
+    return IMT_OK;
+}
+
+extern "C" int imt_itree_view_insert_witness(imt_itree_view* v, size_t n, const imt_insert_out* out, unsigned flags) {
+    if (!view_alive(v)) return IMT_ERR_ARG;
+    imt_itree* t = v->t;
+    imt_ctx* c = t->ctx;
+    if (!out) return c->fail(IMT_ERR_ARG, "null outputs");
+    int rc = view_enter(v, flags);
+    if (rc) return rc;
+    if (n == 0) return IMT_OK;
+    if (n > t->size - v->size)
+        return c->fail(IMT_ERR_RANGE, "the tree holds %llu leaves: no %zu insertions follow the view's %llu", (unsigned long long)t->size,
+                       n, (unsigned long long)v->size);
+    if ((rc = check_out_ptrs(c, flags & IMT_DEVICE_PTRS, out))) return rc;
+    return view_replay(v, n, out, flags & ~(unsigned)IMT_HOST_PREP);
 }
 
 extern "C" int imt_itree_view_stats(imt_itree_view* v, uint64_t* hashes, uint64_t* builds) {

@@ -1122,6 +1122,68 @@ __global__ void __launch_bounds__(BLOCK) k_view_gather_proof(view::Side sd, laun
     store_fe(g_pc, out + ((uint64_t)l * lay.level_stride + i * lay.item_stride) * 32, x, fmt_out);
 }
 
+// -----------------------------------------------------------------------------------------------
+// Witnesses of insertions already made (imt_replay.hpp): k_sweep's LEVEL launch below l0 against a view.  The tables are
+// required (the levels from l0 up are k_sweep's own launches: their sibling is the empty subtree in any tree), nothing
+// goes back to the stored tree, and a sibling no earlier event of the replay has written is the node as of the view's
+// size -- side table, stored node or empty subtree (replay::sibling_row) -- instead of the stored node.  The address is
+// resolved before the hash's registers are live: at most ~20 steps of 4-byte loads against one hash.  A replay runs
+// alone on the context's stream, so like k_apply_level and k_view_level this kernel owns its copy of the hash body.
+// -----------------------------------------------------------------------------------------------
+__global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_sweep_view(launch::SweepViewArgs v) {
+    const launch::SweepArgs& a = v.sweep;
+    const size_t t = gtid();
+    if (t >= a.count) return;
+    const uint32_t x = a.begin + (uint32_t)t;        // slot of level l + 1
+    const uint32_t k = a.from[x] & ~sweep::LAST_BIT, n = a.node_below[x], e = a.time_next[x];
+    const uint8_t* sp = replay::sibling_row(v.side, a.sibsrc[x], a.level, (uint64_t)(n ^ 1u), a.val_in, a.tree_l, a.len_l,
+                                            a.zero_l);
+    Fe A, B, o, cur, sv;
+    load_packed(cur, a.val_in + (size_t)k * 32);
+    load_packed(sv, sp);
+    const bool right = n & 1u;
+#pragma unroll
+    for (int i = 0; i < NL; i++) {
+        A.v[i] = right ? sv.v[i] : cur.v[i];
+        B.v[i] = right ? cur.v[i] : sv.v[i];
+    }
+    uint8_t* row = (e & 1u) ? a.new_sib : a.low_sib;
+    if (row) store_fe(g_pc, row + ((uint64_t)a.level * a.lay.level_stride + (uint64_t)(e >> 1) * a.lay.item_stride) * 32, sv, a.fmt_out);
+    hash23_stashed(g_pc, o, A, B, false, nullptr, 0);        // a 2-input hash never reads the stash
+    store_packed(a.val_out + (size_t)x * 32, o);
+}
+
+// a quad of lanes per event (k_sweep_coop)
+__global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_sweep_view_coop(launch::SweepViewArgs v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ uint32_t tab[coop::TAB_DWORDS];
+    coop::tab_fill(tab, g_pc);                       // before anyone leaves: it ends in a barrier
+    const launch::SweepArgs& a = v.sweep;
+    const size_t t = gtid();
+    const size_t q = t >> 2;
+    if (q >= a.count) return;                        // whole quads leave together
+    const unsigned role = (unsigned)t & 3u, ri = role == 3u ? 0u : role;
+    const uint32_t x = a.begin + (uint32_t)q;
+    const uint32_t k = a.from[x] & ~sweep::LAST_BIT, n = a.node_below[x], e = a.time_next[x];
+    const uint8_t* sp = replay::sibling_row(v.side, a.sibsrc[x], a.level, (uint64_t)(n ^ 1u), a.val_in, a.tree_l, a.len_l,
+                                            a.zero_l);
+    Fe X, C3, o, cur, sv;
+    C3 = g_pc.one;                                   // never read: a 2-input hash
+    load_packed(cur, a.val_in + (size_t)k * 32);
+    load_packed(sv, sp);
+    const bool right = n & 1u;
+    const bool take_sv = (ri == 2u) != right;        // lane 1 holds the left input of the hash, lane 2 the right one
+#pragma unroll
+    for (int i = 0; i < NL; i++) X.v[i] = take_sv ? sv.v[i] : cur.v[i];
+    if (role == 0u) {
+        uint8_t* row = (e & 1u) ? a.new_sib : a.low_sib;
+        if (row) store_fe(g_pc, row + ((uint64_t)a.level * a.lay.level_stride + (uint64_t)(e >> 1) * a.lay.item_stride) * 32, sv, a.fmt_out);
+    }
+    coop::hash23(tab, o, X, C3, false, ri);
+    if (role == 1u) store_packed(a.val_out + (size_t)x * 32, o);
+#endif
+}
+
 // ---- subtree placement (imt_itree_lift_batch) ---------------------------------------------------
 // A tree placed as subtree g of a deeper tree produces subtree-level roots; the enclosing tree's root
 // after the same event is `levels` more hash2 up a path whose siblings are the same for the whole batch.
@@ -1629,6 +1691,25 @@ void view_gather_proof(hipStream_t s, const view::Side& side, TreeView tv, const
     if (!n || !depth) return;
     hipLaunchKernelGGL(k_view_gather_proof, dim3(nblk(n * depth)), dim3(BLOCK), 0, s, side, tv, index, n, depth, out, lay,
                        fmt_out);
+}
+void sweep_view_level(hipStream_t s, const view::Side& side, const uint8_t* val_in, uint8_t* val_out, const uint32_t* from,
+                      const int32_t* sibsrc, const uint32_t* node_below, const uint32_t* time_next, const uint8_t* tree_l,
+                      uint64_t len_l, const uint8_t* zero_l, uint32_t k_count, uint8_t* low_sib, uint8_t* new_sib, SibLayout lay,
+                      unsigned level, unsigned fmt_out, uint32_t coop_max) {
+    if (!k_count) return;
+    SweepViewArgs v{};
+    SweepArgs& a = v.sweep;
+    a.mode = SWEEP_LEVEL;
+    a.begin = 0; a.count = k_count;
+    a.val_in = val_in; a.val_out = val_out; a.from = from; a.sibsrc = sibsrc; a.node_below = node_below;
+    a.time_next = time_next; a.tree_l = tree_l; a.len_l = len_l; a.zero_l = zero_l; a.level = level;
+    a.low_sib = low_sib; a.new_sib = new_sib; a.lay = lay; a.fmt_out = fmt_out;
+    a.last_event = 0xffffffffu;
+    v.side = side;
+    if (a.count <= coop_max)       // launch_sweep's choice
+        hipLaunchKernelGGL(k_sweep_view_coop, dim3(nblk((size_t)a.count * 4)), dim3(BLOCK), 0, s, v);
+    else
+        hipLaunchKernelGGL(k_sweep_view, dim3(nblk(a.count)), dim3(BLOCK), 0, s, v);
 }
 void emit_roots(hipStream_t s, const uint8_t* val, uint32_t e_begin, uint32_t e_count, uint32_t total, uint8_t* old_root,
                 uint8_t* interim_root, uint8_t* new_root, unsigned fmt_out, uint8_t* roots_dev, uint8_t* node_store) {

@@ -7,6 +7,7 @@
 #include "imt_consts.hpp"
 #include "imt_sweep.hpp"
 #include "imt_view.hpp"
+#include "imt_replay.hpp"
 
 namespace imt {
 namespace launch {
@@ -234,6 +235,19 @@ void view_top(hipStream_t s, const view::Side& side, TreeView tv, uint8_t* chain
 // gather_proof with every sibling read as of the view's size
 void view_gather_proof(hipStream_t s, const view::Side& side, TreeView tv, const uint64_t* index, size_t n, unsigned depth,
                        uint8_t* out, SibLayout lay, unsigned fmt_out);
+
+// ---- witnesses of insertions already made (imt_replay.hpp): the level sweep against a view, nothing written back ----
+// argument block of k_sweep_view: a LEVEL launch of k_sweep below l0 (from .. time_next required, no node_in / node_out)
+// and the view whose size the base siblings are read as of.  tree_l / len_l / zero_l: the stored level, as for k_sweep.
+struct SweepViewArgs {
+    SweepArgs sweep;
+    view::Side side;
+};
+// hashes slots [0, k_count) of level `level` + 1; coop_max as for the sweep
+void sweep_view_level(hipStream_t s, const view::Side& side, const uint8_t* val_in, uint8_t* val_out, const uint32_t* from,
+                      const int32_t* sibsrc, const uint32_t* node_below, const uint32_t* time_next, const uint8_t* tree_l,
+                      uint64_t len_l, const uint8_t* zero_l, uint32_t k_count, uint8_t* low_sib, uint8_t* new_sib, SibLayout lay,
+                      unsigned level, unsigned fmt_out, uint32_t coop_max);
 
 // ---- subtree placement: lift subtree-level witnesses to the depth of the enclosing tree ----
 // top[j] (device format, j < levels) = sibling of this subtree's ancestor at height sub_depth + j;

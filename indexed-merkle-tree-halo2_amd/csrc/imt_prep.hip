@@ -64,6 +64,12 @@ __global__ void __launch_bounds__(BLOCK) k_scatter(const uint8_t* __restrict__ v
     iota[i] = M + i;
 }
 
+// k_scatter for values that are rows [M, M + n) of d_val already (run() with vals == NULL): nothing of d_val is written
+__global__ void __launch_bounds__(BLOCK) k_iota(uint32_t M, uint32_t n, uint32_t* __restrict__ iota) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) iota[i] = M + i;
+}
+
 __global__ void __launch_bounds__(BLOCK) k_gap(const uint8_t* __restrict__ d_val, const uint32_t* __restrict__ sorted_old,
                                                uint32_t M, const uint32_t* __restrict__ bsorted, uint32_t n,
                                                uint32_t* __restrict__ gap, uint32_t* __restrict__ st0, int* err) {
@@ -488,8 +494,11 @@ hipError_t run(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t* d_val
     // the workspace was sized for (cap_n, tree capacity); a larger request must not run into it
     if (n > ws.cap_n || temp_bytes_needed(n, (size_t)M) > ws.tmp_bytes) return hipErrorInvalidValue;
     (void)hipGetLastError();       // the thread's sticky error may be a stale one from an unrelated earlier call
-    hipLaunchKernelGGL(k_scatter, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, d_val, M, n, ws.part_mod, ws.part_res, ws.iota,
-                       ws.err);
+    if (vals)
+        hipLaunchKernelGGL(k_scatter, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, d_val, M, n, ws.part_mod, ws.part_res, ws.iota,
+                           ws.err);
+    else
+        hipLaunchKernelGGL(k_iota, dim3(nblk(n)), dim3(BLOCK), 0, s, M, n, ws.iota);
     size_t tb = ws.tmp_bytes;
     if ((e = rocprim::merge_sort(ws.tmp, tb, ws.iota, ws.bsorted, (size_t)n, ValLess{d_val}, s)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_gap, dim3(nblk(n)), dim3(BLOCK), 0, s, d_val, sorted_old, M, ws.bsorted, n, ws.gap, ws.st,

@@ -62,6 +62,9 @@ size_t temp_bytes_needed(size_t n, size_t max_size);
 // workspace is written, so a failed batch leaves the tree untouched.  Returns the first failure of a
 // rocPRIM call or kernel launch (hipErrorInvalidValue if the workspace is too small for (n, M)).
 // All 32-byte rows (vals, d_val, pre, o_*_leaf) must be 16-byte aligned: they move as two 16-byte words.
+// vals == NULL: the values are rows [M, M + n) of d_val already (a replay of insertions the tree has made,
+// imt_itree_view_insert_witness).  Then no row of d_val is written, not even with the bytes it holds, and the checks of
+// the values themselves (non-canonical, zero, foreign) are skipped: stored values passed them when they went in.
 hipError_t run(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t* d_val, const uint32_t* sorted_old,
                uint32_t* sorted_new, uint32_t M, uint32_t n, uint64_t base, uint8_t* pre, uint32_t* node, uint32_t* time,
                uint32_t* rs, uint32_t* re, uint64_t* o_low_index, uint8_t* o_is_largest, uint8_t* o_low_leaf,
