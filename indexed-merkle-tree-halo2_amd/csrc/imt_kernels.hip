@@ -88,6 +88,25 @@ __device__ __forceinline__ void fe_from_u64(Fe& r, uint64_t x) {
 }
 
 // ---------------------------------------------------------------------------------
+// Stages the hash kernels below are built from.  Every kernel still inlines its own copy of the hash body (the comments
+// above chain_inline, k_sweep and k_apply_level say why); what it does around the hash is written once, here.
+// ---------------------------------------------------------------------------------
+// (left, right) inputs of a node's hash from the child `cur` and its sibling `sv`; right: cur is the right child
+__device__ __forceinline__ void order_pair(Fe& A, Fe& B, bool right, const Fe& cur, const Fe& sv) {
+#pragma unroll
+    for (int i = 0; i < NL; i++) {
+        A.v[i] = right ? sv.v[i] : cur.v[i];
+        B.v[i] = right ? cur.v[i] : sv.v[i];
+    }
+}
+// the sibling event e met at a.level is that event's proof element: row e >> 1 of low_sib (e even: the low leaf's path)
+// or new_sib (e odd: the new leaf's), when the caller asked for the rows
+__device__ __forceinline__ void store_proof_row(const launch::SweepArgs& a, uint32_t e, const Fe& sv) {
+    uint8_t* row = (e & 1u) ? a.new_sib : a.low_sib;
+    if (row) store_fe(g_pc, row + ((uint64_t)a.level * a.lay.level_stride + (uint64_t)(e >> 1) * a.lay.item_stride) * 32, sv, a.fmt_out);
+}
+
+// ---------------------------------------------------------------------------------
 // One hash chain with the hash INLINED, exactly once per kernel (round 4; what k_sweep got in round 2): one loop whose
 // iteration -1 is the 3-input leaf hash (when `with_leaf`, wave-uniform) and whose iterations 0 .. depth-1 climb the
 // path -- right child at level l <=> bit l of idx is 1 (src/utils.rs:93-101).  No call, hence no call ABI: rounds 1-3
@@ -101,6 +120,7 @@ __device__ __forceinline__ void fe_from_u64(Fe& r, uint64_t x) {
 // ---------------------------------------------------------------------------------
 struct NoLevelHook {
     __device__ __forceinline__ void operator()(unsigned, const Fe&, const Fe&) const {}
+    __device__ __forceinline__ void operator()(unsigned, const Fe&) const {}      // chain_quad: this lane's input
 };
 struct NoLeafHook {
     __device__ __forceinline__ void operator()(const Fe&) const {}
@@ -126,12 +146,7 @@ __device__ __forceinline__ void chain_inline(Fe& cur, bool with_leaf, LoadLeaf l
             const size_t item = gtid_again();
             Fe sv;
             ok &= load_fe(g_pc, sv, sib + ((uint64_t)it * lay.level_stride + item * lay.item_stride) * 32, fmt_in);
-            const bool right = ((index[item] ^ flip) >> it) & 1;
-#pragma unroll
-            for (int i = 0; i < NL; i++) {
-                A.v[i] = right ? sv.v[i] : cur.v[i];
-                B.v[i] = right ? cur.v[i] : sv.v[i];
-            }
+            order_pair(A, B, ((index[item] ^ flip) >> it) & 1, cur, sv);
             on_level((unsigned)it, A, B);
         }
         hash23_stashed(g_pc, cur, A, B, three, stash, BLOCK);
@@ -149,6 +164,53 @@ struct LeafAt {
         ok &= load_fe(g_pc, c, p + 64, fmt_in);
     }
 };
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// ---------------------------------------------------------------------------------
+// The same stages for a quad of lanes per hash (imt_coop_device.hpp).  Lane 1 holds the left input, lane 2 the right
+// one; ri is the lane's state lane (lane 3 shadows lane 0).
+// ---------------------------------------------------------------------------------
+// leaf prologue: lane 1 val, lane 2 next_val, C3 = next_idx (absorbed by lane 1).  Lane 1 reads next_val as well, so
+// that every element is validated once.
+__device__ __forceinline__ bool leaf_inputs_quad(Fe& X, Fe& C3, const uint8_t* p, unsigned fmt, unsigned ri) {
+    Fe seen;
+    bool ok = load_fe(g_pc, X, p + (ri == 2u ? 32 : 0), fmt);
+    ok &= load_fe(g_pc, C3, p + 64, fmt);
+    if (ri == 1u) ok &= load_fe(g_pc, seen, p + 32, fmt);
+    return ok;
+}
+// order_pair for a quad, this lane's input: lane 2 of a left child and lane 1 of a right child take the sibling
+__device__ __forceinline__ void pick_input(Fe& X, unsigned ri, bool right, const Fe& cur, const Fe& sv) {
+    coop::sel(X, (ri == 2u) != right, sv, cur);
+}
+// one link of a chain: lane 1 ends up with the hash and hands it to its neighbours for the next level
+__device__ __forceinline__ void hash_to_quad(const uint32_t* tab, Fe& cur, const Fe& X, const Fe& C3, bool three, unsigned ri) {
+    Fe o;
+    coop::hash23(tab, o, X, C3, three, ri);
+    coop::quad_bcast<1>(cur, o);
+}
+// a chain that starts from the hash of the leaf preimage at p
+__device__ __forceinline__ void leaf_start_quad(const uint32_t* tab, Fe& cur, const uint8_t* p, unsigned fmt, unsigned ri, bool& ok) {
+    Fe X, C3;
+    ok &= leaf_inputs_quad(X, C3, p, fmt, ri);
+    hash_to_quad(tab, cur, X, C3, true, ri);
+}
+// chain_inline's climb for a quad per item: bit l of idx = the node is a right child at level l; `on_level` sees this
+// lane's input of every level before it is hashed (k_path_pairs_coop stores it)
+template <class OnLevel = NoLevelHook>
+__device__ __forceinline__ void chain_quad(const uint32_t* tab, Fe& cur, uint64_t idx, const uint8_t* sib, launch::SibLayout lay,
+                                           size_t item, unsigned depth, unsigned fmt_in, unsigned ri, bool& ok,
+                                           OnLevel on_level = OnLevel()) {
+#pragma unroll 1
+    for (unsigned l = 0; l < depth; l++) {
+        Fe sv, X;
+        ok &= load_fe(g_pc, sv, sib + ((uint64_t)l * lay.level_stride + item * lay.item_stride) * 32, fmt_in);
+        pick_input(X, ri, (idx >> l) & 1, cur, sv);
+        on_level(l, X);
+        hash_to_quad(tab, cur, X, X, false, ri);         // a 2-input hash never reads the third
+    }
+}
+#endif
 
 // ---- a1 / a10 --------------------------------------------------------------------
 __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_hash_batch(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
@@ -288,30 +350,15 @@ __global__ IMT_COOP_WAVES void __launch_bounds__(BLOCK) k_path_pairs_coop(launch
     const launch::PathChains::Chain ch = a.c[blockIdx.y];
     const unsigned role = (unsigned)t & 3u, ri = role == 3u ? 0u : role;
     bool ok = true;
-    Fe cur, X, C3, o;
-    C3 = g_pc.one;
-    if (ch.leaf3) {
-        ok &= load_fe(g_pc, X, ch.leaf3 + i * 96 + (ri == 2u ? 32 : 0), a.fmt_in);
-        ok &= load_fe(g_pc, C3, ch.leaf3 + i * 96 + 64, a.fmt_in);
-        if (ri == 1u) ok &= load_fe(g_pc, o, ch.leaf3 + i * 96 + 32, a.fmt_in);
-        coop::hash23(tab, o, X, C3, true, ri);
-        coop::quad_bcast<1>(cur, o);
-    } else {
-        ok &= load_fe(g_pc, cur, ch.leaf + i * 32, a.fmt_in);
-    }
-    const uint64_t idx = ch.index[i];
-#pragma unroll 1
-    for (unsigned l = 0; l < a.depth; l++) {
-        Fe sv;
-        ok &= load_fe(g_pc, sv, ch.sib + ((uint64_t)l * a.lay.level_stride + i * a.lay.item_stride) * 32, a.fmt_in);
-        const bool right = (idx >> l) & 1;
-        const bool take_sv = (ri == 2u) != right;
-#pragma unroll
-        for (int q = 0; q < NL; q++) X.v[q] = take_sv ? sv.v[q] : cur.v[q];
-        if (role == 1u || role == 2u) store_packed(ch.pairs + ((size_t)l * a.n + i) * 64 + (role == 2u ? 32 : 0), X);
-        coop::hash23(tab, o, X, C3, false, ri);
-        coop::quad_bcast<1>(cur, o);
-    }
+    Fe cur;
+    if (ch.leaf3) leaf_start_quad(tab, cur, ch.leaf3 + i * 96, a.fmt_in, ri, ok);
+    else ok &= load_fe(g_pc, cur, ch.leaf + i * 32, a.fmt_in);
+    uint8_t* const pairs = ch.pairs;
+    const size_t n = a.n;
+    auto store_input = [pairs, n, i, role](unsigned l, const Fe& X) {
+        if (role == 1u || role == 2u) store_packed(pairs + ((size_t)l * n + i) * 64 + (role == 2u ? 32 : 0), X);
+    };
+    chain_quad(tab, cur, ch.index[i], ch.sib, a.lay, i, a.depth, a.fmt_in, ri, ok, store_input);
     if (role == 1u && ch.root_out) store_fe(g_pc, ch.root_out + i * 32, cur, a.fmt_out);
     flag_err(a.err, ok);
 #endif
@@ -377,30 +424,11 @@ k_path_root_coop(const uint8_t* __restrict__ leaf, const uint8_t* __restrict__ l
     if (i >= n) return;
     const unsigned role = (unsigned)t & 3u, ri = role == 3u ? 0u : role;
     bool ok = true;
-    Fe cur, X, C3, o;
-    C3 = g_pc.one;
-    if (leaf3) {
-        ok &= load_fe(g_pc, X, leaf3 + i * 96 + (ri == 2u ? 32 : 0), fmt_in);
-        ok &= load_fe(g_pc, C3, leaf3 + i * 96 + 64, fmt_in);
-        if (ri == 1u) ok &= load_fe(g_pc, o, leaf3 + i * 96 + 32, fmt_in);     // every element validated once
-        coop::hash23(tab, o, X, C3, true, ri);
-        coop::quad_bcast<1>(cur, o);
-    } else {
-        ok &= load_fe(g_pc, cur, leaf + i * 32, fmt_in);
-    }
-    uint64_t idx = index[i];
-    if (is_helper) idx = ~idx;
-#pragma unroll 1
-    for (unsigned l = 0; l < depth; l++) {
-        Fe sv;
-        ok &= load_fe(g_pc, sv, sib + ((uint64_t)l * lay.level_stride + i * lay.item_stride) * 32, fmt_in);
-        const bool right = (idx >> l) & 1;
-        const bool take_sv = (ri == 2u) != right;        // lane 1 holds the left input, lane 2 the right one
-#pragma unroll
-        for (int q = 0; q < NL; q++) X.v[q] = take_sv ? sv.v[q] : cur.v[q];
-        coop::hash23(tab, o, X, C3, false, ri);
-        coop::quad_bcast<1>(cur, o);
-    }
+    Fe cur;
+    if (leaf3) leaf_start_quad(tab, cur, leaf3 + i * 96, fmt_in, ri, ok);
+    else ok &= load_fe(g_pc, cur, leaf + i * 32, fmt_in);
+    // helper 1 = left child (src/utils.rs:79): the helper mask is the complement of the index
+    chain_quad(tab, cur, is_helper ? ~index[i] : index[i], sib, lay, i, depth, fmt_in, ri, ok);
     if (role == 1u) {
         if (root_out) store_fe(g_pc, root_out + i * 32, cur, fmt_out);
         if (ok_out) {
@@ -414,6 +442,19 @@ k_path_root_coop(const uint8_t* __restrict__ leaf, const uint8_t* __restrict__ l
 }
 
 // ---- a13: verify_non_inclusion (src/indexed_merkle_tree.rs:127-229) ---------------
+// its range predicates as fail bits: new_val lies strictly between low.val and low.next_val, or beyond low.val with no
+// next value when the low leaf is the largest.  The flag is read here, behind the three conversions, so that it is not
+// one more live register across them.
+__device__ __forceinline__ unsigned range_fail(const Fe& low_val, const Fe& low_next, const Fe& new_val, const uint8_t* is_largest) {
+    Fe nvi, lvi, lni;
+    to_int(nvi, new_val); to_int(lvi, low_val); to_int(lni, low_next);
+    const unsigned s = *is_largest;
+    unsigned fail = 0;
+    if (s > 1) fail |= 0x80;                                                             // assert_bit :41
+    if (!(s ? fe_is_zero(low_next) : int_lt(nvi, lni))) fail |= 0x01;                    // :143, :180-191
+    if (!int_lt(lvi, nvi)) fail |= 0x04;                                                 // :206-228
+    return fail;
+}
 __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK)
 k_non_membership(const uint8_t* __restrict__ root, unsigned root_stride, const uint8_t* __restrict__ low_leaf,
                  const uint64_t* __restrict__ low_index, const uint8_t* __restrict__ sib, launch::SibLayout lay,
@@ -447,20 +488,11 @@ k_non_membership_pred(const uint8_t* __restrict__ low_leaf, const uint8_t* __res
                       size_t n, uint8_t* __restrict__ fail_out, unsigned fmt_in, int* err) {
     const size_t i = gtid();
     if (i >= n) return;
-    bool ok = true;
-    unsigned fail = 0;
-    Fe v, nx, nv, nvi, lvi, lni;
-    ok &= load_fe(g_pc, v, low_leaf + (i * 3 + 0) * 32, fmt_in);
+    Fe v, nx, nv;
+    bool ok = load_fe(g_pc, v, low_leaf + (i * 3 + 0) * 32, fmt_in);
     ok &= load_fe(g_pc, nx, low_leaf + (i * 3 + 1) * 32, fmt_in);
     ok &= load_fe(g_pc, nv, new_val + i * 32, fmt_in);
-    to_int(nvi, nv); to_int(lvi, v); to_int(lni, nx);
-    const unsigned s = is_largest[i];
-    if (s > 1) fail |= 0x80;                                    // assert_bit :41
-    const bool is_zero = fe_is_zero(nx);                        // :143
-    const bool next_gr = int_lt(nvi, lni);                      // :180
-    if (!(s ? is_zero : next_gr)) fail |= 0x01;                 // :182-191
-    if (!int_lt(lvi, nvi)) fail |= 0x04;                        // :206-228
-    fail_out[i] |= (uint8_t)fail;
+    fail_out[i] |= (uint8_t)range_fail(v, nx, nv, is_largest + i);
     flag_err(err, ok);
 }
 
@@ -480,35 +512,17 @@ k_non_membership_coop(const uint8_t* __restrict__ root, unsigned root_stride, co
     if (i >= n) return;
     const unsigned role = (unsigned)t & 3u, ri = role == 3u ? 0u : role;
     bool ok = true;
-    unsigned fail = 0;
+    unsigned fail;
     {   // the range predicates, on every lane of the quad alike (lane 1 reports)
-        Fe v, nx, nv, nvi, lvi, lni;
+        Fe v, nx, nv;
         ok &= load_fe(g_pc, v, low_leaf + (i * 3 + 0) * 32, fmt_in);
         ok &= load_fe(g_pc, nx, low_leaf + (i * 3 + 1) * 32, fmt_in);
         ok &= load_fe(g_pc, nv, new_val + i * 32, fmt_in);
-        to_int(nvi, nv); to_int(lvi, v); to_int(lni, nx);
-        const unsigned s = is_largest[i];
-        if (s > 1) fail |= 0x80;
-        if (!(s ? fe_is_zero(nx) : int_lt(nvi, lni))) fail |= 0x01;
-        if (!int_lt(lvi, nvi)) fail |= 0x04;
+        fail = range_fail(v, nx, nv, is_largest + i);
     }
-    Fe cur, X, C3, o;
-    ok &= load_fe(g_pc, X, low_leaf + i * 96 + (ri == 2u ? 32 : 0), fmt_in);
-    ok &= load_fe(g_pc, C3, low_leaf + i * 96 + 64, fmt_in);
-    coop::hash23(tab, o, X, C3, true, ri);
-    coop::quad_bcast<1>(cur, o);
-    const uint64_t idx = low_index[i];
-#pragma unroll 1
-    for (unsigned l = 0; l < depth; l++) {
-        Fe sv;
-        ok &= load_fe(g_pc, sv, sib + ((uint64_t)l * lay.level_stride + i * lay.item_stride) * 32, fmt_in);
-        const bool right = (idx >> l) & 1;
-        const bool take_sv = (ri == 2u) != right;
-#pragma unroll
-        for (int q = 0; q < NL; q++) X.v[q] = take_sv ? sv.v[q] : cur.v[q];
-        coop::hash23(tab, o, X, C3, false, ri);
-        coop::quad_bcast<1>(cur, o);
-    }
+    Fe cur;
+    leaf_start_quad(tab, cur, low_leaf + i * 96, fmt_in, ri, ok);
+    chain_quad(tab, cur, low_index[i], sib, lay, i, depth, fmt_in, ri, ok);
     if (role == 1u) {
         Fe rt;
         ok &= load_fe(g_pc, rt, root + i * (size_t)root_stride, fmt_in);
@@ -604,13 +618,12 @@ k_insert_chains_coop(const uint8_t* __restrict__ low_leaf, const uint64_t* __res
     const uint64_t idx = chain < 2 ? low_index[i] : new_path_index[i];
     uint8_t* leaf_out = nullptr;
     uint8_t* root_out;
-    Fe cur, X, C3, o;
-    C3 = g_pc.one;
+    Fe cur;
     if (chain == 2) {            // the zero leaf at the new slot           :286-294
         cur = g_pc.zero_leaf;
         root_out = trace + (4 * n + i) * 32;
     } else {
-        // lane 1: first input, lane 2: second input, C3: third input (absorbed by lane 1)
+        Fe X, C3;
         if (chain == 1) {        // {low.val, new.val, new_leaf_index}      :265-284
             ok &= load_fe(g_pc, X, (ri == 2u ? new_leaf : low_leaf) + (i * 3 + 0) * 32, fmt_in);
             fe_from_u64(C3, new_index[i]);
@@ -618,27 +631,14 @@ k_insert_chains_coop(const uint8_t* __restrict__ low_leaf, const uint64_t* __res
             root_out = trace + (3 * n + i) * 32;
         } else {                 // a leaf as given: the low leaf :193-204, the new leaf :299-312
             const uint8_t* lf = chain == 0 ? low_leaf : new_leaf;
-            ok &= load_fe(g_pc, X, lf + i * 96 + (ri == 2u ? 32 : 0), fmt_in);
-            ok &= load_fe(g_pc, C3, lf + i * 96 + 64, fmt_in);
-            if (ri == 1u) ok &= load_fe(g_pc, o, lf + i * 96 + 32, fmt_in);       // (every element validated once)
+            ok &= leaf_inputs_quad(X, C3, lf + i * 96, fmt_in, ri);
             leaf_out = trace + ((chain == 0 ? 0 : 5) * n + i) * 32;
             root_out = trace + ((chain == 0 ? 1 : 6) * n + i) * 32;
         }
-        coop::hash23(tab, o, X, C3, true, ri);
-        coop::quad_bcast<1>(cur, o);
+        hash_to_quad(tab, cur, X, C3, true, ri);
         if (role == 1u) store_packed(leaf_out, cur);
     }
-#pragma unroll 1
-    for (unsigned l = 0; l < depth; l++) {
-        Fe sv;
-        ok &= load_fe(g_pc, sv, sib + ((uint64_t)l * lay.level_stride + i * lay.item_stride) * 32, fmt_in);
-        const bool right = (idx >> l) & 1;
-        const bool take_sv = (ri == 2u) != right;
-#pragma unroll
-        for (int q = 0; q < NL; q++) X.v[q] = take_sv ? sv.v[q] : cur.v[q];
-        coop::hash23(tab, o, X, C3, false, ri);
-        coop::quad_bcast<1>(cur, o);
-    }
+    chain_quad(tab, cur, idx, sib, lay, i, depth, fmt_in, ri, ok);
     if (role == 1u) store_packed(root_out, cur);
     flag_err(err, ok);
 #endif
@@ -660,13 +660,7 @@ k_insert_check(const uint8_t* __restrict__ old_root, const uint8_t* __restrict__
     }
     ok &= load_fe(g_pc, r0, old_root + i * 32, fmt_in);
     ok &= load_fe(g_pc, r1, new_root + i * 32, fmt_in);
-    unsigned fail = 0;
-    Fe nvi, lvi, lni;
-    to_int(nvi, nl[0]); to_int(lvi, low[0]); to_int(lni, low[1]);
-    const unsigned s = is_largest[i];
-    if (s > 1) fail |= 0x80;
-    if (!(s ? fe_is_zero(low[1]) : int_lt(nvi, lni))) fail |= 0x01;
-    if (!int_lt(lvi, nvi)) fail |= 0x04;
+    unsigned fail = range_fail(low[0], low[1], nl[0], is_largest + i);
     load_packed(t, trace + (1 * n + i) * 32);
     if (!fe_eq(t, r0)) fail |= 0x02;
     Fe interim, z;
@@ -793,6 +787,64 @@ k_writeback(const uint8_t* __restrict__ val_l, const uint32_t* __restrict__ from
     d[1] = s[1];
 }
 
+// ---- the sibling rules of the sweep kernels, and the body of their quad forms ----
+// Where an event finds its sibling sn of a.level is all that separates the inserting sweep from a replay: the newest
+// version an earlier event of the batch made (slot ss >= 0 one level down) or, when there is none, the node as it was
+// before the batch.  k_sweep_coop: the stored tree is the tree the batch started from.  (k_sweep keeps its own text,
+// rule included; docs/LAB_NOTES.md says why.)
+struct StoredSibling {
+    __device__ __forceinline__ const uint8_t* operator()(const launch::SweepArgs& a, int32_t ss, uint64_t sn) const {
+        return ss >= 0 ? a.val_in + (size_t)ss * 32 : (sn < a.len_l ? a.tree_l + sn * 32 : a.zero_l);
+    }
+};
+// k_sweep_view, k_sweep_view_coop: the stored tree has moved on, the sibling is the node as of the view's size (imt_replay.hpp)
+struct ViewSibling {
+    const view::Side& side;
+    __device__ __forceinline__ const uint8_t* operator()(const launch::SweepArgs& a, int32_t ss, uint64_t sn) const {
+        return replay::sibling_row(side, ss, a.level, sn, a.val_in, a.tree_l, a.len_l, a.zero_l);
+    }
+};
+#if defined(__HIP_DEVICE_COMPILE__)
+// A quad per slot; lane 0 stores what is not the hash, lane 1 the hash.  TABLES: the launch is a LEVEL launch below l0 by
+// construction (k_sweep_view_coop), so the instance has no LEAVES branch, no from == NULL branch and no last_event stores.
+template <bool TABLES, class Sibling>
+__device__ __forceinline__ void sweep_body_quad(const launch::SweepArgs& a, Sibling sibling, uint32_t* tab) {
+    coop::tab_fill(tab, g_pc);                       // before anyone leaves: it ends in a barrier
+    const size_t t = gtid();
+    const size_t q = t >> 2;
+    if (q >= a.count) return;                        // whole quads leave together
+    const unsigned role = (unsigned)t & 3u, ri = role == 3u ? 0u : role;
+    const uint32_t x = a.begin + (uint32_t)q;
+    const bool leaves = !TABLES && a.mode == launch::SWEEP_LEAVES;
+    Fe X, C3, o;
+    C3 = g_pc.one;                                   // any value: only read for LEAVES
+    if (leaves) {
+        flag_err(a.err, leaf_inputs_quad(X, C3, a.pre + (size_t)a.time0[x] * 96, a.fmt_in, ri));
+    } else {
+        uint32_t k = x, n = 0, e = x;
+        const uint8_t* sp = a.zero_l;
+        if (TABLES || a.from) {
+            k = a.from[x] & ~sweep::LAST_BIT;
+            n = a.node_below[x];
+            e = a.time_next[x];
+            sp = sibling(a, a.sibsrc[x], (uint64_t)(n ^ 1u));
+        }
+        Fe cur, sv;
+        load_packed(cur, a.val_in + (size_t)k * 32);
+        load_packed(sv, sp);
+        pick_input(X, ri, n & 1u, cur, sv);
+        if (role == 0u) {
+            if (!TABLES && x == a.last_event && a.node_in) store_packed(a.node_in, cur);
+            store_proof_row(a, e, sv);
+        }
+    }
+    coop::hash23(tab, o, X, C3, leaves, ri);
+    if (role == 1u) {
+        store_packed(a.val_out + (size_t)x * 32, o);
+        if (!TABLES && x == a.last_event && a.node_out) store_packed(a.node_out, o);
+    }
+}
+#endif
 // -----------------------------------------------------------------------------------------------
 // THE hash kernel of a batch insertion: one hash per thread, the hash inlined exactly once.
 //   LEAVES  slot k of level 0 = H(preimage of event time0[k])                                   (:662-671)
@@ -862,50 +914,7 @@ __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_sweep(launch::SweepArg
 __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_sweep_coop(launch::SweepArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ uint32_t tab[coop::TAB_DWORDS];
-    coop::tab_fill(tab, g_pc);                       // before anyone leaves: it ends in a barrier
-    const size_t t = gtid();
-    const size_t q = t >> 2;
-    if (q >= a.count) return;                        // whole quads leave together
-    const unsigned role = (unsigned)t & 3u, ri = role == 3u ? 0u : role;
-    const uint32_t x = a.begin + (uint32_t)q;
-    Fe X, C3, o;
-    C3 = g_pc.one;                                   // any value: only read for LEAVES
-    if (a.mode == launch::SWEEP_LEAVES) {
-        const uint8_t* p = a.pre + (size_t)a.time0[x] * 96;
-        bool ok = load_fe(g_pc, X, p + (ri == 2u ? 32 : 0), a.fmt_in);     // lane 1: val, lane 2: next_val
-        ok &= load_fe(g_pc, C3, p + 64, a.fmt_in);                         // next_idx, absorbed by lane 1
-        if (ri == 1u) ok &= load_fe(g_pc, o, p + 32, a.fmt_in);            // (every element validated once)
-        flag_err(a.err, ok);
-    } else {
-        uint32_t k = x, n = 0, e = x;
-        const uint8_t* sp = a.zero_l;
-        if (a.from) {
-            k = a.from[x] & ~sweep::LAST_BIT;
-            n = a.node_below[x];
-            e = a.time_next[x];
-            const int32_t ss = a.sibsrc[x];
-            const uint64_t sn = (uint64_t)(n ^ 1u);
-            sp = ss >= 0 ? a.val_in + (size_t)ss * 32 : (sn < a.len_l ? a.tree_l + sn * 32 : a.zero_l);
-        }
-        Fe cur, sv;
-        load_packed(cur, a.val_in + (size_t)k * 32);
-        load_packed(sv, sp);
-        const bool right = n & 1u;
-        // lane 1 holds the left input of the hash, lane 2 the right one
-        const bool take_sv = (ri == 2u) != right;    // lane 2 & left child, or lane 1 & right child: the sibling
-#pragma unroll
-        for (int i = 0; i < NL; i++) X.v[i] = take_sv ? sv.v[i] : cur.v[i];
-        if (role == 0u) {
-            if (x == a.last_event && a.node_in) store_packed(a.node_in, cur);
-            uint8_t* row = (e & 1u) ? a.new_sib : a.low_sib;
-            if (row) store_fe(g_pc, row + ((uint64_t)a.level * a.lay.level_stride + (uint64_t)(e >> 1) * a.lay.item_stride) * 32, sv, a.fmt_out);
-        }
-    }
-    coop::hash23(tab, o, X, C3, a.mode == launch::SWEEP_LEAVES, ri);
-    if (role == 1u) {
-        store_packed(a.val_out + (size_t)x * 32, o);
-        if (x == a.last_event && a.node_out) store_packed(a.node_out, o);
-    }
+    sweep_body_quad<false>(a, StoredSibling(), tab);
 #endif
 }
 
@@ -931,6 +940,53 @@ k_emit_roots(const uint8_t* __restrict__ val, uint32_t e_begin, uint32_t e_count
         if (interim_root) store_fe(g_pc, interim_root + (size_t)i * 32, cur, fmt_out);
     }
 }
+
+// -----------------------------------------------------------------------------------------------
+// One hash per LISTED node, a quad of lanes each: the body of k_apply_level_coop and k_view_level_coop.  The two differ
+// in `Rule` alone: child(c) is the row of child c of the level below, out(j, p) where the hash of place j of the list,
+// node p, goes.  (The thread forms keep their own text; docs/LAB_NOTES.md says why.)
+//   LEAVES  H(preimage of event src[j])
+//   LEVEL   hash2(children 2p, 2p + 1), p = list[j]
+// The guards: the launch is sized by a host-side bound, the count of the list is a device word (the call does not wait
+// for it), and a listed node the level cannot hold is not hashed -- never by construction, but a stray index must not
+// become a stray store.
+// -----------------------------------------------------------------------------------------------
+#if defined(__HIP_DEVICE_COMPILE__)
+template <class Rule, class Args>
+__device__ __forceinline__ void listed_body_quad(const Args& a, uint32_t* tab) {
+    coop::tab_fill(tab, g_pc);                       // before anyone leaves: it ends in a barrier
+    const size_t t = gtid();
+    const size_t j = t >> 2;
+    if (j >= a.bound || j >= *a.count) return;       // whole quads leave together
+    const unsigned role = (unsigned)t & 3u, ri = role == 3u ? 0u : role;
+    const uint64_t p = a.list[j];
+    if (p >= a.len_out) return;
+    const Rule rule{a};
+    Fe X, C3, o;
+    C3 = g_pc.one;                                   // any value: only read for LEAVES
+    if (a.mode == launch::APPLY_LEAVES) {
+        flag_err(a.err, leaf_inputs_quad(X, C3, a.pre + (size_t)a.src[j] * 96, a.fmt_in, ri));
+    } else {
+        load_packed(X, rule.child(2 * p + (ri == 2u ? 1u : 0u)));          // lane 1: left child, lane 2: right child
+    }
+    coop::hash23(tab, o, X, C3, a.mode == launch::APPLY_LEAVES, ri);
+    if (role == 1u) store_packed(rule.out(j, p), o);
+}
+#endif
+// k_apply_level_coop: the stored level below (a child outside its prefix is the empty subtree), into the stored tree
+struct StoredLevel {
+    const launch::ApplyArgs& a;
+    __device__ __forceinline__ const uint8_t* child(uint64_t c) const { return c < a.len_in ? a.tree_in + c * 32 : a.zero_in; }
+    __device__ __forceinline__ uint8_t* out(size_t, uint64_t p) const { return a.tree_out + p * 32; }
+};
+// k_view_level_coop: the level below as of the view's size, into the side table's row
+struct ViewLevel {
+    const launch::ViewArgs& a;
+    __device__ __forceinline__ const uint8_t* child(uint64_t c) const {
+        return view::node_row(a.side, a.level_in, c, a.tree_in, a.len_in, a.zero_in);
+    }
+    __device__ __forceinline__ uint8_t* out(size_t j, uint64_t) const { return a.out + j * 32; }
+};
 
 // -----------------------------------------------------------------------------------------------
 // Witness-free insertion (imt_apply.hpp): the hash kernel of imt_itree_apply_batch.  One hash per LISTED node, the
@@ -973,27 +1029,7 @@ __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_apply_level(launch::Ap
 __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_apply_level_coop(launch::ApplyArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ uint32_t tab[coop::TAB_DWORDS];
-    coop::tab_fill(tab, g_pc);                       // before anyone leaves: it ends in a barrier
-    const size_t t = gtid();
-    const size_t j = t >> 2;
-    if (j >= a.bound || j >= *a.count) return;       // whole quads leave together
-    const unsigned role = (unsigned)t & 3u, ri = role == 3u ? 0u : role;
-    const uint64_t p = a.list[j];
-    if (p >= a.len_out) return;
-    Fe X, C3, o;
-    C3 = g_pc.one;                                   // any value: only read for LEAVES
-    if (a.mode == launch::APPLY_LEAVES) {
-        const uint8_t* q = a.pre + (size_t)a.src[j] * 96;
-        bool ok = load_fe(g_pc, X, q + (ri == 2u ? 32 : 0), a.fmt_in);     // lane 1: val, lane 2: next_val
-        ok &= load_fe(g_pc, C3, q + 64, a.fmt_in);                         // next_idx, absorbed by lane 1
-        if (ri == 1u) ok &= load_fe(g_pc, o, q + 32, a.fmt_in);            // (every element validated once)
-        flag_err(a.err, ok);
-    } else {
-        const uint64_t ch = 2 * p + (ri == 2u ? 1u : 0u);                  // lane 1: left child, lane 2: right child
-        load_packed(X, ch < a.len_in ? a.tree_in + ch * 32 : a.zero_in);
-    }
-    coop::hash23(tab, o, X, C3, a.mode == launch::APPLY_LEAVES, ri);
-    if (role == 1u) store_packed(a.tree_out + p * 32, o);
+    listed_body_quad<StoredLevel>(a, tab);
 #endif
 }
 
@@ -1023,12 +1059,11 @@ __global__ IMT_HASH_WAVES void k_apply_top(uint8_t* nodes, const uint64_t* __res
 }
 
 // -----------------------------------------------------------------------------------------------
-// A view of the tree at an earlier size (imt_view.hpp): k_apply_level's hashes with another load and store address.
+// A view of the tree at an earlier size (imt_view.hpp): the listed nodes' hashes into the side table.
 //   LEAVES  side row 0, place j = H(preimage of event src[j]): the relinked leaves and the empty slot
 //   LEVEL   side row l + 1, place j = hash2(children 2p, 2p + 1 of level l as of the view's size), p = list[j]: each
 //           child is the side table's entry, the stored node or the empty subtree (view::node_row).
-// Nothing of the tree is written.  The guards are k_apply_level's: the launch bound (<= the side table's stride, so a
-// place is inside its row), the device count, and a listed node the level cannot hold is not hashed.
+// Nothing of the tree is written.  The launch bound is at most the side table's stride, so a place is inside its row.
 // -----------------------------------------------------------------------------------------------
 __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_view_level(launch::ViewArgs a) {
     __shared__ uint32_t stash[NL][BLOCK];
@@ -1054,31 +1089,11 @@ __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_view_level(launch::Vie
     store_packed(a.out + j * 32, o);
 }
 
-// a quad of lanes per listed node (k_apply_level_coop)
+// a quad of lanes per listed node
 __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_view_level_coop(launch::ViewArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ uint32_t tab[coop::TAB_DWORDS];
-    coop::tab_fill(tab, g_pc);                       // before anyone leaves: it ends in a barrier
-    const size_t t = gtid();
-    const size_t j = t >> 2;
-    if (j >= a.bound || j >= *a.count) return;       // whole quads leave together
-    const unsigned role = (unsigned)t & 3u, ri = role == 3u ? 0u : role;
-    const uint64_t p = a.list[j];
-    if (p >= a.len_out) return;
-    Fe X, C3, o;
-    C3 = g_pc.one;                                   // any value: only read for LEAVES
-    if (a.mode == launch::APPLY_LEAVES) {
-        const uint8_t* q = a.pre + (size_t)a.src[j] * 96;
-        bool ok = load_fe(g_pc, X, q + (ri == 2u ? 32 : 0), a.fmt_in);     // lane 1: val, lane 2: next_val
-        ok &= load_fe(g_pc, C3, q + 64, a.fmt_in);                         // next_idx, absorbed by lane 1
-        if (ri == 1u) ok &= load_fe(g_pc, o, q + 32, a.fmt_in);            // (every element validated once)
-        flag_err(a.err, ok);
-    } else {
-        const uint64_t ch = 2 * p + (ri == 2u ? 1u : 0u);                  // lane 1: left child, lane 2: right child
-        load_packed(X, view::node_row(a.side, a.level_in, ch, a.tree_in, a.len_in, a.zero_in));
-    }
-    coop::hash23(tab, o, X, C3, a.mode == launch::APPLY_LEAVES, ri);
-    if (role == 1u) store_packed(a.out + j * 32, o);
+    listed_body_quad<ViewLevel>(a, tab);
 #endif
 }
 
@@ -1136,51 +1151,21 @@ __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_sweep_view(launch::Swe
     if (t >= a.count) return;
     const uint32_t x = a.begin + (uint32_t)t;        // slot of level l + 1
     const uint32_t k = a.from[x] & ~sweep::LAST_BIT, n = a.node_below[x], e = a.time_next[x];
-    const uint8_t* sp = replay::sibling_row(v.side, a.sibsrc[x], a.level, (uint64_t)(n ^ 1u), a.val_in, a.tree_l, a.len_l,
-                                            a.zero_l);
+    const uint8_t* sp = ViewSibling{v.side}(a, a.sibsrc[x], (uint64_t)(n ^ 1u));
     Fe A, B, o, cur, sv;
     load_packed(cur, a.val_in + (size_t)k * 32);
     load_packed(sv, sp);
-    const bool right = n & 1u;
-#pragma unroll
-    for (int i = 0; i < NL; i++) {
-        A.v[i] = right ? sv.v[i] : cur.v[i];
-        B.v[i] = right ? cur.v[i] : sv.v[i];
-    }
-    uint8_t* row = (e & 1u) ? a.new_sib : a.low_sib;
-    if (row) store_fe(g_pc, row + ((uint64_t)a.level * a.lay.level_stride + (uint64_t)(e >> 1) * a.lay.item_stride) * 32, sv, a.fmt_out);
+    order_pair(A, B, n & 1u, cur, sv);
+    store_proof_row(a, e, sv);
     hash23_stashed(g_pc, o, A, B, false, nullptr, 0);        // a 2-input hash never reads the stash
     store_packed(a.val_out + (size_t)x * 32, o);
 }
 
-// a quad of lanes per event (k_sweep_coop)
+// a quad of lanes per event
 __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_sweep_view_coop(launch::SweepViewArgs v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ uint32_t tab[coop::TAB_DWORDS];
-    coop::tab_fill(tab, g_pc);                       // before anyone leaves: it ends in a barrier
-    const launch::SweepArgs& a = v.sweep;
-    const size_t t = gtid();
-    const size_t q = t >> 2;
-    if (q >= a.count) return;                        // whole quads leave together
-    const unsigned role = (unsigned)t & 3u, ri = role == 3u ? 0u : role;
-    const uint32_t x = a.begin + (uint32_t)q;
-    const uint32_t k = a.from[x] & ~sweep::LAST_BIT, n = a.node_below[x], e = a.time_next[x];
-    const uint8_t* sp = replay::sibling_row(v.side, a.sibsrc[x], a.level, (uint64_t)(n ^ 1u), a.val_in, a.tree_l, a.len_l,
-                                            a.zero_l);
-    Fe X, C3, o, cur, sv;
-    C3 = g_pc.one;                                   // never read: a 2-input hash
-    load_packed(cur, a.val_in + (size_t)k * 32);
-    load_packed(sv, sp);
-    const bool right = n & 1u;
-    const bool take_sv = (ri == 2u) != right;        // lane 1 holds the left input of the hash, lane 2 the right one
-#pragma unroll
-    for (int i = 0; i < NL; i++) X.v[i] = take_sv ? sv.v[i] : cur.v[i];
-    if (role == 0u) {
-        uint8_t* row = (e & 1u) ? a.new_sib : a.low_sib;
-        if (row) store_fe(g_pc, row + ((uint64_t)a.level * a.lay.level_stride + (uint64_t)(e >> 1) * a.lay.item_stride) * 32, sv, a.fmt_out);
-    }
-    coop::hash23(tab, o, X, C3, false, ri);
-    if (role == 1u) store_packed(a.val_out + (size_t)x * 32, o);
+    sweep_body_quad<true>(v.sweep, ViewSibling{v.side}, tab);
 #endif
 }
 
@@ -1213,12 +1198,7 @@ k_lift_roots(uint8_t* __restrict__ old_root, uint8_t* __restrict__ interim_root,
     for (unsigned j = 0; j < levels; j++) {
         Fe sv, a, b, o;
         load_packed(sv, top + (size_t)j * 32);
-        const bool right = (pos_bits >> j) & 1;
-#pragma unroll
-        for (int i = 0; i < NL; i++) {
-            a.v[i] = right ? sv.v[i] : cur.v[i];
-            b.v[i] = right ? cur.v[i] : sv.v[i];
-        }
+        order_pair(a, b, (pos_bits >> j) & 1, cur, sv);
         hash23_stashed(g_pc, o, a, b, false, nullptr, 0);
         cur = o;
     }
@@ -1602,11 +1582,11 @@ void merge_level(hipStream_t s, sweep::LevelTable in, sweep::LevelOut out, uint3
     if (!total) return;
     hipLaunchKernelGGL(k_merge_level, dim3(nblk(total)), dim3(BLOCK), 0, s, in, out, total);
 }
-void sweep_level(hipStream_t s, const uint8_t* val_in, uint8_t* val_out, const uint32_t* from, const int32_t* sibsrc,
-                 const uint32_t* node_below, const uint32_t* time_next, const uint8_t* tree_l, uint64_t len_l,
-                 const uint8_t* zero_l, uint32_t k_begin, uint32_t k_count, uint8_t* low_sib, uint8_t* new_sib,
-                 SibLayout lay, unsigned level, unsigned fmt_out, uint32_t coop_max) {
-    if (!k_count) return;
+// the arguments of a LEVEL launch below l0: slots [k_begin, k_begin + k_count) of level `level` + 1 from the tables
+static SweepArgs level_args(const uint8_t* val_in, uint8_t* val_out, const uint32_t* from, const int32_t* sibsrc,
+                            const uint32_t* node_below, const uint32_t* time_next, const uint8_t* tree_l, uint64_t len_l,
+                            const uint8_t* zero_l, uint32_t k_begin, uint32_t k_count, uint8_t* low_sib, uint8_t* new_sib,
+                            SibLayout lay, unsigned level, unsigned fmt_out) {
     SweepArgs a{};
     a.mode = SWEEP_LEVEL;
     a.begin = k_begin; a.count = k_count;
@@ -1614,7 +1594,15 @@ void sweep_level(hipStream_t s, const uint8_t* val_in, uint8_t* val_out, const u
     a.time_next = time_next; a.tree_l = tree_l; a.len_l = len_l; a.zero_l = zero_l; a.level = level;
     a.low_sib = low_sib; a.new_sib = new_sib; a.lay = lay; a.fmt_out = fmt_out;
     a.last_event = 0xffffffffu;
-    launch_sweep(s, a, coop_max);
+    return a;
+}
+void sweep_level(hipStream_t s, const uint8_t* val_in, uint8_t* val_out, const uint32_t* from, const int32_t* sibsrc,
+                 const uint32_t* node_below, const uint32_t* time_next, const uint8_t* tree_l, uint64_t len_l,
+                 const uint8_t* zero_l, uint32_t k_begin, uint32_t k_count, uint8_t* low_sib, uint8_t* new_sib,
+                 SibLayout lay, unsigned level, unsigned fmt_out, uint32_t coop_max) {
+    if (!k_count) return;
+    launch_sweep(s, level_args(val_in, val_out, from, sibsrc, node_below, time_next, tree_l, len_l, zero_l, k_begin, k_count,
+                               low_sib, new_sib, lay, level, fmt_out), coop_max);
 }
 void sweep_upper(hipStream_t s, const uint8_t* val_in, uint8_t* val_out, const uint8_t* zero_l, uint32_t e_begin,
                  uint32_t e_count, uint32_t last_event, uint8_t* node_in, uint8_t* node_out, uint8_t* low_sib,
@@ -1697,19 +1685,12 @@ void sweep_view_level(hipStream_t s, const view::Side& side, const uint8_t* val_
                       uint64_t len_l, const uint8_t* zero_l, uint32_t k_count, uint8_t* low_sib, uint8_t* new_sib, SibLayout lay,
                       unsigned level, unsigned fmt_out, uint32_t coop_max) {
     if (!k_count) return;
-    SweepViewArgs v{};
-    SweepArgs& a = v.sweep;
-    a.mode = SWEEP_LEVEL;
-    a.begin = 0; a.count = k_count;
-    a.val_in = val_in; a.val_out = val_out; a.from = from; a.sibsrc = sibsrc; a.node_below = node_below;
-    a.time_next = time_next; a.tree_l = tree_l; a.len_l = len_l; a.zero_l = zero_l; a.level = level;
-    a.low_sib = low_sib; a.new_sib = new_sib; a.lay = lay; a.fmt_out = fmt_out;
-    a.last_event = 0xffffffffu;
-    v.side = side;
-    if (a.count <= coop_max)       // launch_sweep's choice
-        hipLaunchKernelGGL(k_sweep_view_coop, dim3(nblk((size_t)a.count * 4)), dim3(BLOCK), 0, s, v);
+    const SweepViewArgs v{level_args(val_in, val_out, from, sibsrc, node_below, time_next, tree_l, len_l, zero_l, 0, k_count,
+                                     low_sib, new_sib, lay, level, fmt_out), side};
+    if (k_count <= coop_max)       // launch_sweep's choice
+        hipLaunchKernelGGL(k_sweep_view_coop, dim3(nblk((size_t)k_count * 4)), dim3(BLOCK), 0, s, v);
     else
-        hipLaunchKernelGGL(k_sweep_view, dim3(nblk(a.count)), dim3(BLOCK), 0, s, v);
+        hipLaunchKernelGGL(k_sweep_view, dim3(nblk(k_count)), dim3(BLOCK), 0, s, v);
 }
 void emit_roots(hipStream_t s, const uint8_t* val, uint32_t e_begin, uint32_t e_count, uint32_t total, uint8_t* old_root,
                 uint8_t* interim_root, uint8_t* new_root, unsigned fmt_out, uint8_t* roots_dev, uint8_t* node_store) {

@@ -977,9 +977,13 @@ def test_hash_trace_vs_oracle_formats_and_layouts(imt, ctx, oracle):
         ctx.hash_trace(bad)
 
 
-def test_path_trace_is_the_trace_of_every_hash_on_the_path(imt, ctx, oracle):
+@pytest.mark.parametrize("form", ["quad", "thread"])
+def test_path_trace_is_the_trace_of_every_hash_on_the_path(imt, ctx, ctx_thread_per_hash, oracle, form):
     """imt_path_trace_batch = leaf-hash trace + one hash2 trace per level with the (left, right) inputs dual_mux
-    selects (src/indexed_merkle_tree.rs:47-63,78-96); checked against the oracle hash by hash."""
+    selects (src/indexed_merkle_tree.rs:47-63,78-96); checked against the oracle hash by hash.  Both forms of the kernel
+    that finds the inputs: these few paths run a quad of lanes per path (k_path_pairs_coop) by default, one thread per
+    path (k_path_pairs) with the quad form switched off, and the two give the same bytes."""
+    ctx, other = (ctx, ctx_thread_per_hash) if form == "quad" else (ctx_thread_per_hash, ctx)
     depth, n = 5, 9
     rng = random.Random(11)
     leaf3 = [[rng.randrange(P) for _ in range(3)] for _ in range(n)]
@@ -1006,11 +1010,17 @@ def test_path_trace_is_the_trace_of_every_hash_on_the_path(imt, ctx, oracle):
     tr2, roots2 = ctx.path_trace(index, imt.to_bytes(sib), depth, leaf=imt.to_bytes(leaf))
     assert tr2.shape == (depth * 1208, n, 32)
     assert ints(roots2) == [oracle.path_root(leaf[i], index[i], imt.to_bytes([sib[l][i] for l in range(depth)])) for i in range(n)]
+    for kw, (want_tr, want_roots) in (({"leaf3": imt.to_bytes(leaf3)}, (tr, roots)), ({"leaf": imt.to_bytes(leaf)}, (tr2, roots2))):
+        otr, oroots = other.path_trace(index, imt.to_bytes(sib), depth, **kw)
+        assert (otr == want_tr).all() and (oroots == want_roots).all()
 
 
-def test_insert_trace_is_what_the_circuit_would_assign(imt, ctx, oracle):
+@pytest.mark.parametrize("form", ["quad", "thread"])
+def test_insert_trace_is_what_the_circuit_would_assign(imt, ctx, ctx_thread_per_hash, oracle, form):
     """imt_insert_trace_batch on real insertion witnesses: the 3 + 4 d traces per insertion, in insert_leaf's call
-    order, each equal to the oracle's trace of the hash the circuit computes there; the chains end in the roots."""
+    order, each equal to the oracle's trace of the hash the circuit computes there; the chains end in the roots.  The
+    four chains' inputs come from k_path_pairs_coop (quad) or k_path_pairs (thread): the same bytes from both."""
+    ctx, other = (ctx, ctx_thread_per_hash) if form == "quad" else (ctx_thread_per_hash, ctx)
     depth, n = 4, 6
     t = imt.IndexedTree(ctx, depth, 16)
     t.insert_batch([77, 5])
@@ -1044,6 +1054,8 @@ def test_insert_trace_is_what_the_circuit_would_assign(imt, ctx, oracle):
     tim = ctx.insert_trace(r["low_leaf"], r["low_index"], r["low_sib"].transpose(1, 0, 2).copy(), r["new_leaf"],
                            r["new_index"], r["new_sib"].transpose(1, 0, 2).copy(), depth, item_major=True)
     assert (tim.transpose(1, 0, 2) == tr).all()
+    assert (other.insert_trace(r["low_leaf"], r["low_index"], r["low_sib"], r["new_leaf"], r["new_index"], r["new_sib"], depth)
+            == tr).all()
     t.close()
 
 
