@@ -10,6 +10,11 @@ step scripts that tests/test_gpu_tree_sequences.py plays on the GPU.
   test_model_load_refusals         the breakages of test_oracle_golden's sparse_load cases, and a few more.
   test_script_coverage             the pair coverage of scripts(), asserted.
   test_scripts_are_self_consistent every accepted step accepted by the model, every refused one refused with its code.
+  test_view_schedule               view_schedule() and view_rounds(): the rules of the schedule and of the expected rebuilds.
+  test_view_coverage               what tests/test_gpu_view_sequences.py sees with that schedule on the committed scripts:
+                                   every writer kind makes a view stale, every transition of a view's state, histories
+                                   that change beneath a view, replays of leaves of every origin, rounds that must not
+                                   rebuild.  It fails for a schedule that keeps the view at size 1 alone.
 """
 import os
 import sys
@@ -286,3 +291,112 @@ def test_scripts_reach_the_states_of_the_two_copies():
             ("full check", True, True), ("refused call, then a reader", True, False),
             ("refused call, then a reader", False, True)}
     assert want <= seen, f"states the scripts never reach: {sorted(map(str, want - seen))}"
+
+
+# ---------------------------------------------------------------- the views kept alive beside the scripts
+def test_view_schedule():
+    """the schedule is a pure function of the script, and view_rounds() restates imt.h's rules of a view's cache"""
+    for s in tmod.scripts():
+        sched, rounds, tr = tmod.view_schedule(s), tmod.view_rounds(s), tmod.trace(s)
+        assert sched == tmod.view_schedule(s) and len(sched) == len(rounds) == len(s.steps)
+        live, builds_due = [1], {1: True}
+        for i, ((st, before, after, res), (closed, created), rnd) in enumerate(zip(tr, sched, rounds)):
+            tag = f"{s.name} step {i}"
+            assert not (closed or created) or (i % tmod.VIEW_EVERY == 0 and not isinstance(res, Refused)), tag
+            assert 1 not in closed and all(c in live for c in closed), tag
+            live = [x for x in live if x not in closed]
+            for c in created:
+                assert c not in live and 1 <= c <= len(after), f"{tag}: a view is created at a size the tree has reached"
+                live.append(c)
+            assert len(live) <= tmod.MAX_VIEWS and [r.size for r in rnd] == live, tag
+            if tmod.changes_content(st, before, after, res):
+                assert after != before or st.kind == 10, tag
+                builds_due = dict.fromkeys(builds_due, True)
+            else:
+                assert after == before, tag
+            builds_due = {x: builds_due.get(x, True) for x in live}
+            for r in rnd:
+                M = len(after)
+                assert r.state == (tmod.SMALLER if M < r.size else tmod.HEAD if M == r.size else tmod.BEHIND), tag
+                if r.state == tmod.SMALLER:
+                    assert (r.prefix, r.build, r.n_replay) == (None, False, 0), tag
+                else:
+                    assert r.prefix == after[:r.size] and r.build == builds_due[r.size], tag
+                    assert r.n_replay == min(M - r.size, tmod.REPLAY_MAX), tag
+                    builds_due[r.size] = False
+
+
+def view_coverage(scripts, rounds_of):
+    """what the rounds of `rounds_of(script)` cover, as a dict of counters and sets"""
+    from collections import Counter, defaultdict
+    cov = dict(stale_by=defaultdict(Counter), transitions=Counter(), history=Counter(), origins=Counter(), crossings=0,
+               quiet=Counter())
+    for s in scripts:
+        origin, state, answered = [0], {}, {}                     # who wrote leaf i; per view its last state and prefix
+        for (st, before, after, res), rnd in zip(tmod.trace(s), rounds_of(s)):
+            k = tmod.writer_kind(st)
+            if not isinstance(res, Refused):
+                origin = origin + [st.kind] * len(res["acc"]) if st.kind <= 8 else origin[:st.arg] if st.kind == 9 else \
+                    [0] + [10] * (len(after) - 1)
+            assert len(origin) == len(after)
+            live = {r.size for r in rnd}
+            state = {x: v for x, v in state.items() if x in live}
+            answered = {x: v for x, v in answered.items() if x in live}
+            for r in rnd:
+                if r.build and r.since == (k, ):                  # the view was answering, this step made it stale
+                    cov["stale_by"][s.shape.name][k] += 1
+                if state.get(r.size, r.state) != r.state:
+                    cov["transitions"][state[r.size], r.state] += 1
+                state[r.size] = r.state
+                if r.prefix is None:
+                    continue
+                if answered.get(r.size, r.prefix) != r.prefix:
+                    cov["history"][s.shape.name] += 1
+                answered[r.size] = r.prefix
+                cov["origins"].update(origin[r.size:r.size + r.n_replay])
+                if r.size > 2 and (r.size - 1).bit_length() != (r.size + r.n_replay - 1).bit_length():
+                    cov["crossings"] += 1                         # ceil_log2 of the size changes inside the replayed range
+                if not r.build and not tmod.changes_content(st, before, after, res) and st.kind != 9:
+                    cov["quiet"]["refused" if st.refusal else "accepted nothing"] += 1
+    return cov
+
+
+def test_view_coverage():
+    scripts = tmod.scripts()
+    cov = view_coverage(scripts, tmod.view_rounds)
+    shapes = {s.shape.name for s in scripts}
+    # (a) every writer kind makes a live answering view stale and is followed by a round, within each shape
+    for name in shapes:
+        missing = [k for k in KINDS if not cov["stale_by"][name][k]]
+        assert not missing, f"{name}: writer kinds that never make a view stale: {missing}"
+    # (b) the six transitions between the three states of a view
+    states = (tmod.HEAD, tmod.BEHIND, tmod.SMALLER)
+    missing = [(a, b) for a in states for b in states if a != b and not cov["transitions"][a, b]]
+    assert not missing, f"transitions of a view's state that never occur: {missing}"
+    # (c) per shape the history changes beneath a view: it answers for another prefix than at its last answered round
+    assert all(cov["history"][name] for name in shapes), cov["history"]
+    # (d) replayed ranges hold leaves written by every inserting kind and by a load
+    assert all(cov["origins"][k] for k in (1, 2, 3, 4, 5, 6, 7, 8, 10)), cov["origins"]
+    # (e) a replayed range crosses a power of two in size
+    assert cov["crossings"]
+    # (f) a refused step and a filtered batch that accepted nothing are followed by a round that must not rebuild
+    assert cov["quiet"]["refused"] and cov["quiet"]["accepted nothing"], cov["quiet"]
+    total = sum((c for c in cov["stale_by"].values()), start=type(cov["transitions"])())
+    print(f"stale by kind {dict(sorted(total.items()))}, transitions {dict(cov['transitions'])}, history changes "
+          f"{dict(cov['history'])}, replayed origins {dict(sorted(cov['origins'].items()))}, crossings {cov['crossings']}, "
+          f"quiet rounds {dict(cov['quiet'])}")
+    # the scripts replayed on the other two forms of the hash kernels, a round after every second step: every writer kind
+    # is still among what a rebuilt view is stale by, every state of a view occurs, and no expectation is lost -- what a
+    # skipped round would have rebuilt for, the next one does
+    for name in ("d32", "part3"):
+        s = next(x for x in scripts if x.shape.name == name)
+        thin, full = tmod.view_rounds(s, tmod.VIEW_ROUNDS_OTHER_FORMS), tmod.view_rounds(s)
+        assert all(not rnd for rnd in thin[1::2]) and all(len(a) == len(b) for a, b in zip(thin[::2], full[::2])), s.name
+        assert all((a.size, a.state, a.prefix, a.n_replay) == (b.size, b.state, b.prefix, b.n_replay)
+                   for x, y in zip(thin[::2], full[::2]) for a, b in zip(x, y)), s.name
+        by = {k for rnd in thin for r in rnd if r.build for k in r.since}
+        assert by == set(KINDS), f"{s.name}: writer kinds no rebuilt view is stale by: {sorted(set(KINDS) - by)}"
+        assert {r.state for rnd in thin for r in rnd} == set(states), s.name
+    # the view at size 1 alone is not enough: the tree is never smaller than it, and it never sees another history
+    alone = view_coverage(scripts, lambda s: [[r for r in rnd if r.size == 1] for rnd in tmod.view_rounds(s)])
+    assert not any(tmod.SMALLER in pair for pair in alone["transitions"]) and not alone["history"]

@@ -16,6 +16,9 @@ writer kinds is adjacent somewhere with a light check between the two and somewh
      left in flight                                  9 rewind(s)
    4 insert_filtered, GPU prepare                   10 load of a snapshot taken from the model
    5 insert_filtered, IMT_HOST_PREP                 11 a refused call of one of the kinds above
+
+view_schedule() and view_rounds() say which views (imt_itree_view_*) tests/test_gpu_view_sequences.py keeps alive beside a
+script, what each answers after every step and when its cache must be rebuilt; the scripts themselves do not change.
 """
 import bisect
 import random
@@ -262,6 +265,79 @@ def trace(script):
         except Refused as e:
             res = e
         out.append((st, before, tuple(m.vals), res))
+    return out
+
+
+# ---------------------------------------------------------------- views beside a script
+# What tests/test_gpu_view_sequences.py keeps alive while it plays a script, and what every view must then answer.  A view
+# at size s of a tree that holds `vals` is a model reset to vals[:s]; while len(vals) < s it answers nothing (IMT_ERR_RANGE).
+HEAD, BEHIND, SMALLER = "at the head", "behind the head", "tree smaller than the view"
+MAX_VIEWS = 4                        # live at once, the one at size 1 included
+VIEW_EVERY = 4                       # a new view after every accepted step whose index is a multiple of this
+REPLAY_MAX = 16                      # insertions replayed per view and round
+VIEW_ROUNDS_OTHER_FORMS = 2          # the scripts replayed on the thread and quad forms: a round after every second step
+ViewRound = namedtuple("ViewRound", "size state prefix build since n_replay")
+
+
+def changes_content(st, before, after, res):
+    """Does the step change the tree's contents as include/imt.h counts them (A VIEW FOLLOWS THE TREE): an insertion of
+    any kind that accepted something, a load, a rewind below the current size.  A refused call, a filtered batch that
+    accepted nothing and a rewind to the current size do not."""
+    if isinstance(res, Refused):
+        return False
+    if st.kind <= 8:
+        return bool(res["acc"])
+    return st.arg < len(before) if st.kind == 9 else True
+
+
+def view_schedule(script):
+    """[(sizes closed, sizes created)] per step, both after the step and before its round of queries; the view at size 1
+    exists before step 0 and is never closed.  Views are told apart by their size: there is at most one of a size.  After
+    every accepted step whose index is a multiple of VIEW_EVERY a view is created unless one of its size exists: at the
+    size M the tree then has and below it, at 1 + (M - 1) // 2, in turn.  With MAX_VIEWS alive the oldest one that is not
+    the view at size 1 is closed first."""
+    live, out, made = [1], [], 0
+    for i, (st, before, after, res) in enumerate(trace(script)):
+        closed, created = (), ()
+        if i % VIEW_EVERY == 0 and not isinstance(res, Refused):
+            M = len(after)
+            s = M if made % 2 == 0 else 1 + (M - 1) // 2
+            if s not in live:
+                made += 1
+                if len(live) == MAX_VIEWS:
+                    closed = (live.pop(1), )
+                live.append(s)
+                created = (s, )
+        out.append((closed, created))
+    return out
+
+
+def view_rounds(script, every=1):
+    """Per step the round of queries that follows it: [ViewRound] of the live views, oldest first; with every = 2 only the
+    steps of even index are followed by a round ([] for the others: what they changed shows in the next round).
+         state      HEAD, BEHIND or SMALLER
+         prefix     the values the view answers for (vals[:size] of the tree after the step); None while SMALLER
+         build      the round rebuilds the view's cache (imt_itree_view_stats' count goes up by one): its first answered
+                    round, and every answered round with a content-changing step since the last answered one
+         since      the writer kinds of those content-changing steps, oldest first
+         n_replay   min(insertions that follow the view's size, REPLAY_MAX)"""
+    stale, since, out = {1: True}, {1: ()}, []
+    for i, ((st, before, after, res), (closed, created)) in enumerate(zip(trace(script), view_schedule(script))):
+        if changes_content(st, before, after, res):
+            for s in stale:
+                stale[s], since[s] = True, since[s] + (writer_kind(st), )
+        for s in closed:
+            del stale[s], since[s]
+        for s in created:
+            stale[s], since[s] = True, ()
+        M, rnd = len(after), []
+        for s in stale if i % every == 0 else ():
+            if M < s:                                             # answers nothing, builds nothing, stays as stale as it is
+                rnd.append(ViewRound(s, SMALLER, None, False, since[s], 0))
+                continue
+            rnd.append(ViewRound(s, HEAD if s == M else BEHIND, after[:s], stale[s], since[s], min(M - s, REPLAY_MAX)))
+            stale[s], since[s] = False, ()
+        out.append(rnd)
     return out
 
 
