@@ -38,6 +38,17 @@ pub struct imt_insert_out {
     pub new_sib: *mut c_void,
 }
 
+/// `imt_read_out`: rows of the READs of `imt_itree_mixed_batch`; every pointer may be null.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct imt_read_out {
+    pub low_index: *mut u64,
+    pub low_leaf: *mut c_void,
+    pub is_largest: *mut u8,
+    pub root: *mut c_void,
+    pub low_sib: *mut c_void,
+}
+
 #[repr(C)]
 pub struct imt_sliced {
     _opaque: [u8; 0],
@@ -136,6 +147,10 @@ pub const IMT_F_NEXT_VAL: u8 = 0x10;
 pub const IMT_F_NEXT_IDX: u8 = 0x20;
 pub const IMT_F_NEW_ROOT: u8 = 0x40;
 pub const IMT_F_BAD_BIT: u8 = 0x80;
+
+// kind of an operation (imt_itree_mixed_batch)
+pub const IMT_OP_INSERT: u8 = 0;
+pub const IMT_OP_READ: u8 = 1;
 
 // status of a value (imt_itree_insert_filtered / imt_itree_lookup_batch)
 pub const IMT_VAL_NEW: u8 = 0;
@@ -276,6 +291,7 @@ extern "C" {
     pub fn imt_itree_view_non_membership_witness(v: *mut imt_itree_view, vals: *const c_void, n: usize, low_index: *mut u64, low_leaf: *mut c_void, is_largest: *mut u8, low_sib: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_view_stats(v: *mut imt_itree_view, hashes: *mut u64, builds: *mut u64) -> c_int;
     pub fn imt_itree_view_insert_witness(v: *mut imt_itree_view, n: usize, out: *const imt_insert_out, flags: c_uint) -> c_int;
+    pub fn imt_itree_mixed_batch(t: *mut imt_itree, vals: *const c_void, op: *const u8, n: usize, ins: *const imt_insert_out, rd: *const imt_read_out, n_inserted: *mut u64, bad_op: *mut u64, flags: c_uint) -> c_int;
     pub fn imt_itree_lookup_batch(t: *mut imt_itree, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, flags: c_uint) -> c_int;
     pub fn imt_itree_non_membership_witness(t: *mut imt_itree, vals: *const c_void, n: usize, low_index: *mut u64, low_leaf: *mut c_void, is_largest: *mut u8, low_sib: *mut c_void, flags: c_uint) -> c_int;
 

@@ -605,6 +605,50 @@ int imt_itree_non_membership_witness(imt_itree *t, const void *vals /*[n][32]*/,
                                      uint8_t *is_largest /*[n]*/, void *low_sib /*[depth][n][32]*/,
                                      unsigned flags);
 
+/* A BLOCK AS IT IS: insertions and non-inclusion checks in one ordered list, for the prover of a block whose transactions
+ * either insert a nullifier (insert_leaf) or only assert that a value is absent (verify_non_inclusion) against the tree as
+ * it stands at that point of the block.
+ * DEFINED BY THE SEQUENCE ALONE.  Walk the n operations in order on the tree: op[p] == IMT_OP_INSERT is
+ * imt_itree_insert_batch of the one value vals[p]; op[p] == IMT_OP_READ is imt_itree_non_membership_witness of that one
+ * value against the tree at that moment, plus imt_itree_root.  The call writes, byte for byte, what that walk writes, and
+ * leaves the tree the walk leaves.  Row r of every `ins` array belongs to the r-th INSERT, row q of every `rd` array to the
+ * q-th READ; sibling arrays of both keep the caller's dimensions (level-major [depth][n][32] with level stride n, the
+ * number of operations; or item-major), imt_itree_insert_filtered's convention.  *n_inserted = the number of INSERTs.
+ * What follows from the definition:
+ *  - a batch of INSERTs only is imt_itree_insert_batch(t, vals, n, ins, flags);
+ *  - a batch of READs only is imt_itree_non_membership_witness plus the current root in every row: it changes nothing,
+ *    it is not counted as a change of the tree (views stay fresh) and imt_itree_root_lagged does not see it;
+ *  - a READ of a value that a LATER operation of the batch inserts is legal, and so are two READs of one value -- their
+ *    rows differ if an insertion between them changed the low leaf;
+ *  - the root of a READ is new_root of the last INSERT before it, the tree's root before the call if there is none.
+ * One level sweep serves both kinds: an INSERT costs 2 + 2*depth hashes, a READ 1 + depth.
+ * REFUSALS, the tree untouched and no output written in every one of them.  IMT_ERR_VALUE: an INSERT
+ * imt_itree_insert_batch would refuse at that point of the walk (0, stored, inserted earlier in the batch), or a READ of
+ * 0, of a stored value or of a value an EARLIER operation of the batch inserts; *bad_op is then the smallest offending
+ * position (written in this case only; *n_inserted with IMT_OK only).  IMT_ERR_NONCANONICAL and IMT_ERR_FULL as for
+ * imt_itree_insert_batch, the latter counting INSERTs only.  IMT_ERR_ARG: an op byte above 1; NULL vals or op with
+ * n > 0; a misaligned device buffer; IMT_PIPELINE, IMT_HOST_PREP or IMT_INPUTS_READY in flags; a placed or partitioned
+ * tree (so a value of another subtree's residue cannot occur); a replica of a sliced world with steps in flight; an open
+ * slice; a call between imt_itree_batch_begin and _end.  n == 0: IMT_OK.
+ * NOT IN THIS CALL: pipelining against other batches and placed / partitioned trees.
+ * IMT_FMT_*, IMT_SIB_ITEM_MAJOR and IMT_DEVICE_PTRS mean what they mean to imt_itree_insert_batch; with IMT_DEVICE_PTRS
+ * `op` is a device pointer too, n_inserted and bad_op are host memory always.  The call orders itself behind batches in
+ * flight (pipelined ones included), later calls are ordered behind it, and like imt_itree_insert_batch it returns once the
+ * values have been checked on the GPU: n_inserted and bad_op are complete at return. */
+#define IMT_OP_INSERT 0
+#define IMT_OP_READ 1
+typedef struct imt_read_out {   /* rows of the q-th READ; every pointer may be NULL; host or device per flags */
+    uint64_t *low_index;     /* [n]        the low leaf of the value as of the READ */
+    void *low_leaf;          /* [n][3][32] its preimage then */
+    uint8_t *is_largest;     /* [n]        low_leaf.next_val == 0 */
+    void *root;              /* [n][32]    the root the witness verifies against */
+    void *low_sib;           /* [depth][n][32] the low leaf's proof against it (layout per flags) */
+} imt_read_out;
+int imt_itree_mixed_batch(imt_itree *t, const void *vals /*[n][32]*/, const uint8_t *op /*[n]*/, size_t n,
+                          const imt_insert_out *ins /*may be NULL*/, const imt_read_out *rd /*may be NULL*/,
+                          uint64_t *n_inserted /*host, may be NULL*/, uint64_t *bad_op /*host, may be NULL*/,
+                          unsigned flags);
+
 /* ---- e: the tree as ONE SUBTREE of a deeper tree (sharding by leaf-index range) -----------------
  * north_star's multi-GPU layout: GPU g owns leaf indices [g << depth, (g + 1) << depth) of a tree of depth
  * global_depth as an indexed tree of its own (own {0,0,0} sentinel at its first leaf, own sorted list; the

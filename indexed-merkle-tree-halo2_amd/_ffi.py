@@ -78,6 +78,10 @@ class InsertOut(ctypes.Structure):
                                         "new_root", "new_leaf", "low_sib", "new_sib")]
 
 
+class ReadOut(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("low_index", "low_leaf", "is_largest", "root", "low_sib")]
+
+
 # every symbol include/imt.h declares, with its signature
 SIGNATURES = {
     "imt_version": (ctypes.c_char_p, []),
@@ -148,6 +152,8 @@ SIGNATURES = {
     "imt_itree_get_leaves": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
     "imt_itree_non_membership_witness": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                                  c_uint]),
+    "imt_itree_mixed_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, P(InsertOut), P(ReadOut), P(c_u64), P(c_u64),
+                                      c_uint]),
     "imt_itree_load": (c_int, [c_void_p, c_void_p, c_u64, c_uint]),
     "imt_itree_find_low_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
     "imt_itree_insert_filtered": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, P(c_u64), P(InsertOut), c_uint]),
@@ -226,6 +232,7 @@ ERR = dict(NO_LEAVES=-1, ODD_LEAVES=-2, NOT_POW2=-3, RANGE=-4, NONCANONICAL=-5, 
            ARG=-9, VALUE=-10, FULL=-11, INTERNAL=-12, TIMEOUT=-13)
 FMT_CANONICAL, FMT_MONT256, FMT_DEVICE = 0, 1, 2
 DEVICE_PTRS, SIB_ITEM_MAJOR, ROOT_PER_ITEM, PIPELINE, HOST_PREP, INPUTS_READY = 0x10, 0x20, 0x40, 0x80, 0x100, 0x200
+OP_INSERT, OP_READ = 0, 1     # imt_itree_mixed_batch
 VAL_NEW, VAL_ZERO, VAL_PRESENT, VAL_REPEATED, VAL_FOREIGN = 0, 1, 2, 3, 4     # imt_itree_insert_filtered / lookup_batch
 F_RANGE_PRED, F_LOW_IN_ROOT, F_LOW_LT_NEW, F_ZERO_SLOT, F_NEXT_VAL, F_NEXT_IDX, F_NEW_ROOT, F_BAD_BIT = (
     0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80)

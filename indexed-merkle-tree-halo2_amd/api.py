@@ -634,6 +634,43 @@ class IndexedTree:
         res.update(status=status, leaf_index=leaf, n_inserted=m)
         return res
 
+    def mixed_batch(self, vals, ops, proofs=True, item_major=False):
+        """A block of interleaved operations (imt_itree_mixed_batch): ops[p] = OP_INSERT / OP_READ for vals[p], each
+        answered against the tree as it stands at that point of the list.  Returns (ins, rd): ins is the insert_batch()
+        dict of the INSERTs in their order, rd the rows of the READs -- low_index, low_leaf, is_largest, root and (proofs)
+        low_sib, what non_membership_witness() and root() would answer there.  Sibling arrays keep stride len(vals) in
+        memory and are cut to their rows.  A refused value raises ValueError with .bad_op = the first offending
+        position; the tree is unchanged."""
+        v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
+        op = np.ascontiguousarray(ops, dtype=np.uint8)
+        n, d = v.shape[0], self.depth
+        if op.shape != (n,):
+            raise ValueError("mixed_batch: one op per value")
+        ins = dict(low_index=np.empty(n, np.uint64), low_leaf=np.empty((n, 3, 32), np.uint8),
+                   is_largest=np.empty(n, np.uint8), old_root=np.empty((n, 32), np.uint8),
+                   interim_root=np.empty((n, 32), np.uint8), new_root=np.empty((n, 32), np.uint8),
+                   new_leaf=np.empty((n, 3, 32), np.uint8))
+        rd = dict(low_index=np.empty(n, np.uint64), low_leaf=np.empty((n, 3, 32), np.uint8),
+                  is_largest=np.empty(n, np.uint8), root=np.empty((n, 32), np.uint8))
+        if proofs:
+            shape = (n, d, 32) if item_major else (d, n, 32)
+            ins["low_sib"], ins["new_sib"], rd["low_sib"] = (np.empty(shape, np.uint8) for _ in range(3))
+        out = _ffi.InsertOut(**{k: a.ctypes.data for k, a in ins.items()})
+        rout = _ffi.ReadOut(**{k: a.ctypes.data for k, a in rd.items()})
+        n_ins, bad = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = lib.imt_itree_mixed_batch(self.h, _p(v), _p(op), n, ctypes.byref(out), ctypes.byref(rout), ctypes.byref(n_ins),
+                                       ctypes.byref(bad), _ffi.SIB_ITEM_MAJOR if item_major else 0)
+        if rc == _ffi.ERR["VALUE"]:
+            e = ValueError(lib.imt_last_error(self.ctx.h).decode())
+            e.bad_op = bad.value
+            raise e
+        self.ctx._check(rc)
+        for res, m in ((ins, n_ins.value), (rd, n - n_ins.value)):
+            for k in list(res):
+                res[k] = res[k][:, :m] if k.endswith("_sib") and not item_major else res[k][:m]
+        ins["new_index"] = np.arange(self.size - n_ins.value, self.size, dtype=np.uint64)
+        return ins, rd
+
     def apply_batch(self, vals, host_prep=False):
         """insert_batch() without witnesses (imt_itree_apply_batch): the same tree afterwards, every touched node hashed
         once; returns the root after the batch."""

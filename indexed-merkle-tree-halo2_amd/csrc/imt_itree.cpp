@@ -1721,6 +1721,211 @@ extern "C" int imt_itree_apply_stats(imt_itree* t, uint64_t* hashes) {
 }
 
 // ------------------------------------------------------------------------------------
+// mixed batches: non-inclusion READs between the INSERTs of one call
+// ------------------------------------------------------------------------------------
+// The hashing of imt_itree_mixed_batch on stream s, behind the preparation: witness_hashes' sequence for a batch that runs
+// alone on the context's stream, with the LEVEL launches and the roots routed through erow (an event's id no longer says
+// whose rows it fills).  Leaf hashes, index phase and write-back are the stages witness_hashes uses; a READ's versions go
+// back to the stored tree like any other -- they are the bytes already there.
+static int mixed_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, size_t n_ins, const imt_insert_out& d,
+                        const launch::MixedRoute& route, uint8_t* read_root, launch::SibLayout lay, unsigned fmt) {
+    imt_ctx* c = t->ctx;
+    read_old_root(t, s, d, fmt);        // nothing on this stream has touched the stored root yet
+    sweep_leaf_hashes(t, P, s, E);
+    int pf = c->prof_begin(IMT_PROF_INDEX, s);
+    index_phase(P, s, E, L0, nullptr);
+    c->prof_end(pf, s);
+    for (unsigned l = 0; l < L0; l++) {
+        const PlanSet::Level row = P.level(l);
+        pf = c->prof_begin(IMT_PROF_LEVEL, s);
+        launch::sweep_level_mixed(s, route, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], row.from, row.sibsrc, row.nodeb, row.timen,
+                                  t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, (uint32_t)E, (uint8_t*)d.low_sib,
+                                  (uint8_t*)d.new_sib, lay, l, fmt, c->coop_max_events);
+        c->prof_end(pf, s);
+        pf = c->prof_begin(IMT_PROF_WRITEBACK, s);
+        launch::writeback(s, P.d_val[l & 1], row.from, row.nodeb, t->nodes(l), (uint32_t)E);
+        c->prof_end(pf, s);
+    }
+    for (unsigned l = L0; l < t->depth; l++) {
+        pf = c->prof_begin(IMT_PROF_TOP, s);
+        launch::sweep_upper_mixed(s, route, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], c->d_zero + (size_t)l * 32, (uint32_t)E,
+                                  l == L0 ? t->nodes(l) : nullptr, t->nodes(l + 1), (uint8_t*)d.low_sib, (uint8_t*)d.new_sib,
+                                  lay, l, fmt, c->coop_max_events);
+        c->prof_end(pf, s);
+    }
+    launch::emit_roots_mixed(s, route, P.d_val[t->depth & 1], (uint32_t)E, (uint32_t)n_ins, (uint8_t*)d.old_root,
+                             (uint8_t*)d.interim_root, (uint8_t*)d.new_root, read_root, fmt,
+                             L0 == t->depth ? t->nodes(t->depth) : nullptr);
+    return IMT_OK;
+}
+
+// rows [0, rows) of a staged sibling array to the caller's: item-major they are one block, level-major they are the
+// first `rows` of every level's n
+static int copy_sib_rows(imt_itree* t, hipStream_t s, void* user, const void* dev_buf, size_t rows, size_t n, bool item_major) {
+    imt_ctx* c = t->ctx;
+    if (!user || !rows) return IMT_OK;
+    if (item_major || rows == n)
+        IMT_HIP(c, hipMemcpyAsync(user, dev_buf, (size_t)t->depth * rows * 32, hipMemcpyDeviceToHost, s));
+    else
+        IMT_HIP(c, hipMemcpy2DAsync(user, n * 32, dev_buf, n * 32, rows * 32, t->depth, hipMemcpyDeviceToHost, s));
+    return IMT_OK;
+}
+
+extern "C" int imt_itree_mixed_batch(imt_itree* t, const void* vals, const uint8_t* op, size_t n, const imt_insert_out* ins,
+                                     const imt_read_out* rd, uint64_t* n_inserted, uint64_t* bad_op, unsigned flags) {
+    if (!t) return IMT_ERR_ARG;
+    imt_ctx* c = t->ctx;
+    IMT_NOT_SLICED(t);
+    if (n == 0) {
+        if (n_inserted) *n_inserted = 0;
+        return IMT_OK;
+    }
+    if (!vals || !op) return c->fail(IMT_ERR_ARG, "null vals / op");
+    if (flags & (IMT_PIPELINE | IMT_HOST_PREP | IMT_INPUTS_READY))
+        return c->fail(IMT_ERR_ARG, "mixed batches take neither IMT_PIPELINE, IMT_HOST_PREP nor IMT_INPUTS_READY");
+    if (t->index_base || t->global_depth != t->depth || t->part_mod > 1)
+        return c->fail(IMT_ERR_ARG, "mixed batches are not available on a placed or partitioned tree");
+    int rc = check_batch_call(t, n, flags);
+    if (rc) return rc;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    if ((rc = check_fe_ptrs(c, dev, {vals})) || (rc = check_out_ptrs(c, dev, ins))) return rc;
+    if (rd && (rc = check_fe_ptrs(c, dev, {rd->low_leaf, rd->root, rd->low_sib}))) return rc;
+    if (dev && ((ins && ((uintptr_t)ins->low_index & 7u)) || (rd && ((uintptr_t)rd->low_index & 7u))))
+        return c->fail(IMT_ERR_ARG, "device low_index array is not 8-byte aligned");
+    if (!dev)
+        for (size_t p = 0; p < n; p++)
+            if (op[p] > IMT_OP_READ) return c->fail(IMT_ERR_ARG, "op[%zu] = %u is neither IMT_OP_INSERT nor IMT_OP_READ", p, op[p]);
+    if ((rc = ensure_device_index(t))) return rc;
+    const uint64_t M = t->size;
+    double waited_ms = 0;
+
+    // ---- plan buffers: 2n events hold any mix; the per-operation scratch is the filter's and the slot table's, idle here ----
+    PlanSet& P = t->plan[t->cur];
+    if ((rc = acquire_plan(t, 2 * n, 0, waited_ms))) return rc;
+    const prep::MixedWs mx{P.fw.flag, P.fw.rank, P.fw.idx, P.fw.aux, P.d_slot};
+
+    // ---- ranks, then the checks: nothing of the caller's is written before the batch is accepted ----
+    hipStream_t ps = t->up_stream;
+    if ((rc = order_behind_caller(t, ps, flags))) return rc;
+    size_t slot = 2;
+    const uint8_t* d_vals = nullptr;
+    uint8_t* up = dev ? nullptr : (uint8_t*)c->dev_scratch(slot++, n * 32);
+    if ((rc = stage_canonical(c, ps, vals, n, flags, up, P.d_canon, P.ws.err, &d_vals))) return rc;
+    const uint8_t* d_op = op;
+    if (!dev) {
+        uint8_t* o = (uint8_t*)c->dev_scratch(slot++, n);
+        if (!o) return IMT_ERR_HIP;
+        IMT_HIP(c, hipMemcpyAsync(o, op, n, hipMemcpyHostToDevice, ps));
+        d_op = o;
+    }
+    IMT_HIP(c, prep::mixed_ranks(ps, P.ws, mx, d_op, (uint32_t)n));
+    IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, mx.word, sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
+    IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, ps));
+    IMT_HIP(c, hipStreamSynchronize(ps));
+    if (*t->h_err_pin & prep::ERR_OP) return c->fail(IMT_ERR_ARG, "an op byte is neither IMT_OP_INSERT nor IMT_OP_READ");
+    const size_t n_ins = *t->h_cnt_pin, n_rd = n - n_ins;
+    if ((rc = check_room(t, n_ins))) return rc;
+    P.ws.part_mod = t->part_mod;
+    P.ws.part_res = t->part_res;
+    IMT_HIP(c, prep::mixed_check(ps, P.ws, mx, d_vals, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)M, (uint32_t)n,
+                                 (uint32_t)n_ins));
+    IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, mx.word + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
+    IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, ps));
+    IMT_HIP(c, hipStreamSynchronize(ps));
+    if ((rc = insertion_verdict(t, *t->h_err_pin, "batch"))) {
+        if (rc == IMT_ERR_VALUE) {
+            if (bad_op) *bad_op = *t->h_cnt_pin;
+            std::string why = c->last_error;
+            return c->fail(rc, "operation %u: %s (a READ: 0, stored, or inserted earlier in the batch)", *t->h_cnt_pin, why.c_str());
+        }
+        return rc;
+    }
+
+    // ---- accepted: events, tables, merged index, hash-free outputs (side stream) ----
+    const size_t E = n + n_ins;
+    const unsigned L0 = std::min(ceil_log2(M + n_ins), t->depth);
+    const bool item_major = flags & IMT_SIB_ITEM_MAJOR;
+    const size_t sib_bytes = (size_t)t->depth * n * 32;      // the caller's dimensions, whichever kind the rows are
+    imt_insert_out d = {};
+    imt_read_out r = {};
+    if (ins && n_ins &&
+        (!stage_out(c, dev, slot, ins->low_index, n_ins * 8, d.low_index) ||
+         !stage_out(c, dev, slot, ins->is_largest, n_ins, d.is_largest) ||
+         !stage_out(c, dev, slot, ins->low_leaf, n_ins * 96, d.low_leaf) ||
+         !stage_out(c, dev, slot, ins->new_leaf, n_ins * 96, d.new_leaf) ||
+         !stage_out(c, dev, slot, ins->old_root, n_ins * 32, d.old_root) ||
+         !stage_out(c, dev, slot, ins->interim_root, n_ins * 32, d.interim_root) ||
+         !stage_out(c, dev, slot, ins->new_root, n_ins * 32, d.new_root) ||
+         !stage_out(c, dev, slot, ins->low_sib, sib_bytes, d.low_sib) || !stage_out(c, dev, slot, ins->new_sib, sib_bytes, d.new_sib)))
+        return IMT_ERR_HIP;
+    if (rd && n_rd &&
+        (!stage_out(c, dev, slot, rd->low_index, n_rd * 8, r.low_index) ||
+         !stage_out(c, dev, slot, rd->is_largest, n_rd, r.is_largest) ||
+         !stage_out(c, dev, slot, rd->low_leaf, n_rd * 96, r.low_leaf) || !stage_out(c, dev, slot, rd->root, n_rd * 32, r.root) ||
+         !stage_out(c, dev, slot, rd->low_sib, sib_bytes, r.low_sib)))
+        return IMT_ERR_HIP;
+    IMT_HIP(c, prep::mixed_events(ps, P.ws, mx, t->d_val, t->d_sorted[t->sorted_cur], t->d_sorted[t->sorted_cur ^ 1], (uint32_t)M,
+                                  (uint32_t)n, (uint32_t)n_ins, t->index_base, P.d_pre, P.d_tab[0][0], P.d_tab[0][1],
+                                  P.d_tab[0][2], P.d_tab[0][3], d.low_index, d.is_largest, (uint8_t*)d.low_leaf,
+                                  (uint8_t*)d.new_leaf, prep::ReadOut{r.low_index, r.is_largest, (uint8_t*)r.low_leaf}));
+    IMT_HIP(c, hipEventRecord(t->up_done, ps));
+
+    // ---- hashing on the context's stream, behind every batch in flight ----
+    hipStream_t s = c->stream;
+    if ((rc = join_top(t))) return rc;
+    IMT_HIP(c, hipStreamWaitEvent(s, t->up_done, 0));
+    const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->depth} : launch::SibLayout{n, 1};
+    if ((rc = mixed_hashes(t, P, s, E, L0, n_ins, d, launch::MixedRoute{mx.erow, (uint8_t*)r.low_sib}, (uint8_t*)r.root, lay, fmt)))
+        return rc;
+    P.pipelined = false;
+    if (n_ins) {    // the tree has changed: from here the call is a batch like any other
+        IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
+        P.has_root = true;
+        P.sliced = false;
+        P.l0 = L0;
+    }
+    IMT_HIP(c, hipEventRecord(P.done, s));
+    P.in_flight = true;
+    if (n_ins) {
+        t->cur = (t->cur + 1) % imt_itree::NSETS;
+        t->batch_no++;
+        t->sorted_cur ^= 1;
+        t->size = M + n_ins;
+        t->mirror_valid = false;
+        t->gen++;
+    }
+
+    // ---- outputs ----
+    if (fmt != IMT_FMT_CANONICAL) {
+        if (d.low_leaf) launch::convert(s, (uint8_t*)d.low_leaf, (uint8_t*)d.low_leaf, n_ins * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
+        if (d.new_leaf) launch::convert(s, (uint8_t*)d.new_leaf, (uint8_t*)d.new_leaf, n_ins * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
+        if (r.low_leaf) launch::convert(s, (uint8_t*)r.low_leaf, (uint8_t*)r.low_leaf, n_rd * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
+    }
+    if (n_inserted) *n_inserted = n_ins;
+    if (dev) return IMT_OK;
+    auto back = [&](void* user, const void* from, size_t bytes) -> int {
+        if (user && from) IMT_HIP(c, hipMemcpyAsync(user, from, bytes, hipMemcpyDeviceToHost, s));
+        return IMT_OK;
+    };
+    if (ins && n_ins &&
+        ((rc = back(ins->low_index, d.low_index, n_ins * 8)) || (rc = back(ins->is_largest, d.is_largest, n_ins)) ||
+         (rc = back(ins->low_leaf, d.low_leaf, n_ins * 96)) || (rc = back(ins->new_leaf, d.new_leaf, n_ins * 96)) ||
+         (rc = back(ins->old_root, d.old_root, n_ins * 32)) || (rc = back(ins->interim_root, d.interim_root, n_ins * 32)) ||
+         (rc = back(ins->new_root, d.new_root, n_ins * 32)) ||
+         (rc = copy_sib_rows(t, s, ins->low_sib, d.low_sib, n_ins, n, item_major)) ||
+         (rc = copy_sib_rows(t, s, ins->new_sib, d.new_sib, n_ins, n, item_major))))
+        return rc;
+    if (rd && n_rd &&
+        ((rc = back(rd->low_index, r.low_index, n_rd * 8)) || (rc = back(rd->is_largest, r.is_largest, n_rd)) ||
+         (rc = back(rd->low_leaf, r.low_leaf, n_rd * 96)) || (rc = back(rd->root, r.root, n_rd * 32)) ||
+         (rc = copy_sib_rows(t, s, rd->low_sib, r.low_sib, n_rd, n, item_major))))
+        return rc;
+    IMT_HIP(c, hipStreamSynchronize(s));
+    return IMT_OK;
+}
+
+// ------------------------------------------------------------------------------------
 // going back (imt_rewind.hpp)
 // ------------------------------------------------------------------------------------
 extern "C" int imt_itree_rewind(imt_itree* t, uint64_t new_size, void* root_out, uint64_t* hashes, unsigned flags) {

@@ -105,6 +105,22 @@ __device__ __forceinline__ void store_proof_row(const launch::SweepArgs& a, uint
     uint8_t* row = (e & 1u) ? a.new_sib : a.low_sib;
     if (row) store_fe(g_pc, row + ((uint64_t)a.level * a.lay.level_stride + (uint64_t)(e >> 1) * a.lay.item_stride) * 32, sv, a.fmt_out);
 }
+// Whose proof row the sibling of event e is.  A batch of insertions alone: the rule above, from e itself.
+struct InsertRows {
+    __device__ __forceinline__ void operator()(const launch::SweepArgs& a, uint32_t e, const Fe& sv) const { store_proof_row(a, e, sv); }
+};
+// A mixed batch (imt_itree_mixed_batch): e says nothing, erow[e] = (row << 2) | kind does -- the low-leaf or new-leaf path
+// of the row-th INSERT, or the low-leaf path of the row-th READ (prep::ROW_LOW / ROW_NEW / ROW_READ).  All three arrays
+// have the caller's dimensions, a.lay.
+struct MixedRows {
+    const uint32_t* erow;
+    uint8_t* read_sib;
+    __device__ __forceinline__ void operator()(const launch::SweepArgs& a, uint32_t e, const Fe& sv) const {
+        const uint32_t w = erow[e], kind = w & 3u;
+        uint8_t* row = kind == 0u ? a.low_sib : (kind == 1u ? a.new_sib : read_sib);
+        if (row) store_fe(g_pc, row + ((uint64_t)a.level * a.lay.level_stride + (uint64_t)(w >> 2) * a.lay.item_stride) * 32, sv, a.fmt_out);
+    }
+};
 
 // ---------------------------------------------------------------------------------
 // One hash chain with the hash INLINED, exactly once per kernel (round 4; what k_sweep got in round 2): one loop whose
@@ -805,10 +821,10 @@ struct ViewSibling {
     }
 };
 #if defined(__HIP_DEVICE_COMPILE__)
-// A quad per slot; lane 0 stores what is not the hash, lane 1 the hash.  TABLES: the launch is a LEVEL launch below l0 by
+// A quad per slot; lane 0 stores what is not the hash, lane 1 the hash.  Rows: whose proof row the sibling is.  TABLES: the launch is a LEVEL launch below l0 by
 // construction (k_sweep_view_coop), so the instance has no LEAVES branch, no from == NULL branch and no last_event stores.
-template <bool TABLES, class Sibling>
-__device__ __forceinline__ void sweep_body_quad(const launch::SweepArgs& a, Sibling sibling, uint32_t* tab) {
+template <bool TABLES, class Sibling, class Rows = InsertRows>
+__device__ __forceinline__ void sweep_body_quad(const launch::SweepArgs& a, Sibling sibling, uint32_t* tab, Rows rows = Rows()) {
     coop::tab_fill(tab, g_pc);                       // before anyone leaves: it ends in a barrier
     const size_t t = gtid();
     const size_t q = t >> 2;
@@ -835,7 +851,7 @@ __device__ __forceinline__ void sweep_body_quad(const launch::SweepArgs& a, Sibl
         pick_input(X, ri, n & 1u, cur, sv);
         if (role == 0u) {
             if (!TABLES && x == a.last_event && a.node_in) store_packed(a.node_in, cur);
-            store_proof_row(a, e, sv);
+            rows(a, e, sv);
         }
     }
     coop::hash23(tab, o, X, C3, leaves, ri);
@@ -916,6 +932,71 @@ __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_sweep_coop(launch::Swe
     __shared__ uint32_t tab[coop::TAB_DWORDS];
     sweep_body_quad<false>(a, StoredSibling(), tab);
 #endif
+}
+
+// -----------------------------------------------------------------------------------------------
+// The LEVEL launches of a mixed batch (imt_itree_mixed_batch): k_sweep's, below l0 and above, with the proof row of an
+// event looked up (MixedRows) instead of derived from its id.  A READ is an event like any other here: it rewrites its
+// low leaf with the preimage that leaf has at that moment, so its versions are the bytes of the versions they supersede
+// and the siblings it meets on the way up are its witness.  The leaf hashes of a mixed batch are k_sweep's own LEAVES
+// launch (rows play no part in it), so this kernel has no LEAVES branch and no stash.  A mixed batch runs alone on the
+// context's stream, so like k_sweep_view this kernel owns its copy of the hash body.
+// -----------------------------------------------------------------------------------------------
+__global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_sweep_mixed(launch::SweepMixedArgs m) {
+    const launch::SweepArgs& a = m.sweep;
+    const size_t t = gtid();
+    if (t >= a.count) return;
+    const uint32_t x = a.begin + (uint32_t)t;        // slot (= event id at and above l0)
+    uint32_t k = x, n = 0, e = x;
+    const uint8_t* sp = a.zero_l;
+    if (a.from) {
+        k = a.from[x] & ~sweep::LAST_BIT;
+        n = a.node_below[x];
+        e = a.time_next[x];
+        sp = StoredSibling()(a, a.sibsrc[x], (uint64_t)(n ^ 1u));
+    }
+    Fe A, B, o, cur, sv;
+    load_packed(cur, a.val_in + (size_t)k * 32);
+    load_packed(sv, sp);
+    if (x == a.last_event && a.node_in) store_packed(a.node_in, cur);
+    order_pair(A, B, n & 1u, cur, sv);
+    MixedRows{m.erow, m.read_sib}(a, e, sv);
+    hash23_stashed(g_pc, o, A, B, false, nullptr, 0);        // a 2-input hash never reads the stash
+    store_packed(a.val_out + (size_t)x * 32, o);
+    if (x == a.last_event && a.node_out) store_packed(a.node_out, o);
+}
+
+// a quad of lanes per event
+__global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_sweep_mixed_coop(launch::SweepMixedArgs m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ uint32_t tab[coop::TAB_DWORDS];
+    sweep_body_quad<false>(m.sweep, StoredSibling(), tab, MixedRows{m.erow, m.read_sib});
+#endif
+}
+
+// k_emit_roots for a mixed batch: the top value of an INSERT's first event is its interim root, of its second its new root
+// (= the old root of the INSERT after it, whatever READs lie between), of a READ's event the root its witness verifies
+// against
+__global__ void __launch_bounds__(BLOCK)
+k_emit_roots_mixed(const uint8_t* __restrict__ val, uint32_t total, const uint32_t* __restrict__ erow, uint32_t n_ins,
+                   uint8_t* __restrict__ old_root, uint8_t* __restrict__ interim_root, uint8_t* __restrict__ new_root,
+                   uint8_t* __restrict__ read_root, unsigned fmt_out, uint8_t* __restrict__ node_store) {
+    const size_t t = gtid();
+    if (t >= total) return;
+    const uint32_t e = (uint32_t)t;
+    Fe cur;
+    load_packed(cur, val + (size_t)e * 32);
+    if (e == total - 1 && node_store) store_packed(node_store, cur);
+    const uint32_t w = erow[e], kind = w & 3u;
+    const size_t i = w >> 2;
+    if (kind == 1u) {
+        if (new_root) store_fe(g_pc, new_root + i * 32, cur, fmt_out);
+        if (old_root && i + 1 < (size_t)n_ins) store_fe(g_pc, old_root + (i + 1) * 32, cur, fmt_out);
+    } else if (kind == 0u) {
+        if (interim_root) store_fe(g_pc, interim_root + i * 32, cur, fmt_out);
+    } else {
+        if (read_root) store_fe(g_pc, read_root + i * 32, cur, fmt_out);
+    }
 }
 
 // Roots of events [e_begin, e_begin + e_count) from the top values (indexed by event id), no hashing: event 2i is
@@ -1615,6 +1696,40 @@ void sweep_upper(hipStream_t s, const uint8_t* val_in, uint8_t* val_out, const u
     a.low_sib = low_sib; a.new_sib = new_sib; a.lay = lay; a.fmt_out = fmt_out;
     a.last_event = last_event; a.node_in = node_in; a.node_out = node_out;
     launch_sweep(s, a, coop_max);
+}
+// the LEVEL launches of a mixed batch: launch_sweep's choice between the two forms
+static void launch_sweep_mixed(hipStream_t s, const SweepArgs& a, const MixedRoute& r, uint32_t coop_max) {
+    const SweepMixedArgs m{a, r.erow, r.read_sib};
+    if (a.count <= coop_max)
+        hipLaunchKernelGGL(k_sweep_mixed_coop, dim3(nblk((size_t)a.count * 4)), dim3(BLOCK), 0, s, m);
+    else
+        hipLaunchKernelGGL(k_sweep_mixed, dim3(nblk(a.count)), dim3(BLOCK), 0, s, m);
+}
+void sweep_level_mixed(hipStream_t s, const MixedRoute& r, const uint8_t* val_in, uint8_t* val_out, const uint32_t* from,
+                       const int32_t* sibsrc, const uint32_t* node_below, const uint32_t* time_next, const uint8_t* tree_l,
+                       uint64_t len_l, const uint8_t* zero_l, uint32_t k_count, uint8_t* low_sib, uint8_t* new_sib, SibLayout lay,
+                       unsigned level, unsigned fmt_out, uint32_t coop_max) {
+    if (!k_count) return;
+    launch_sweep_mixed(s, level_args(val_in, val_out, from, sibsrc, node_below, time_next, tree_l, len_l, zero_l, 0, k_count,
+                                     low_sib, new_sib, lay, level, fmt_out), r, coop_max);
+}
+void sweep_upper_mixed(hipStream_t s, const MixedRoute& r, const uint8_t* val_in, uint8_t* val_out, const uint8_t* zero_l,
+                       uint32_t e_count, uint8_t* node_in, uint8_t* node_out, uint8_t* low_sib, uint8_t* new_sib, SibLayout lay,
+                       unsigned level, unsigned fmt_out, uint32_t coop_max) {
+    if (!e_count) return;
+    SweepArgs a{};
+    a.mode = SWEEP_LEVEL;
+    a.begin = 0; a.count = e_count;
+    a.val_in = val_in; a.val_out = val_out; a.zero_l = zero_l; a.level = level;
+    a.low_sib = low_sib; a.new_sib = new_sib; a.lay = lay; a.fmt_out = fmt_out;
+    a.last_event = e_count - 1; a.node_in = node_in; a.node_out = node_out;
+    launch_sweep_mixed(s, a, r, coop_max);
+}
+void emit_roots_mixed(hipStream_t s, const MixedRoute& r, const uint8_t* val, uint32_t total, uint32_t n_ins, uint8_t* old_root,
+                      uint8_t* interim_root, uint8_t* new_root, uint8_t* read_root, unsigned fmt_out, uint8_t* node_store) {
+    if (!total) return;
+    hipLaunchKernelGGL(k_emit_roots_mixed, dim3(nblk(total)), dim3(BLOCK), 0, s, val, total, r.erow, n_ins, old_root,
+                       interim_root, new_root, read_root, fmt_out, node_store);
 }
 // one thread per listed node, or -- while the launch is small enough to leave most SIMDs idle -- one quad per node
 static void launch_apply(hipStream_t s, const ApplyArgs& a, uint32_t coop_max) {

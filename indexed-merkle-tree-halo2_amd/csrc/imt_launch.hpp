@@ -249,6 +249,30 @@ void sweep_view_level(hipStream_t s, const view::Side& side, const uint8_t* val_
                       uint64_t len_l, const uint8_t* zero_l, uint32_t k_count, uint8_t* low_sib, uint8_t* new_sib, SibLayout lay,
                       unsigned level, unsigned fmt_out, uint32_t coop_max);
 
+// ---- mixed batches (imt_itree_mixed_batch): the sweep with READ events among the INSERTs' ----
+// erow[e] = (row << 2) | kind for every event (prep::ROW_*): whose proof rows and root event e's are.  read_sib: the READs'
+// low_sib (NULL: not wanted), dimensioned like the INSERTs' sibling arrays.  The leaf hashes and the index phase of a
+// mixed batch are the ordinary ones; these are its LEVEL launches (below l0: all slots; above: all events, the last
+// event's nodes to node_in / node_out) and its roots.  coop_max as for the sweep.
+struct MixedRoute {
+    const uint32_t* erow;
+    uint8_t* read_sib;
+};
+struct SweepMixedArgs {                   // argument block of k_sweep_mixed: a LEVEL launch of k_sweep and the route
+    SweepArgs sweep;
+    const uint32_t* erow;
+    uint8_t* read_sib;
+};
+void sweep_level_mixed(hipStream_t s, const MixedRoute& r, const uint8_t* val_in, uint8_t* val_out, const uint32_t* from,
+                       const int32_t* sibsrc, const uint32_t* node_below, const uint32_t* time_next, const uint8_t* tree_l,
+                       uint64_t len_l, const uint8_t* zero_l, uint32_t k_count, uint8_t* low_sib, uint8_t* new_sib, SibLayout lay,
+                       unsigned level, unsigned fmt_out, uint32_t coop_max);
+void sweep_upper_mixed(hipStream_t s, const MixedRoute& r, const uint8_t* val_in, uint8_t* val_out, const uint8_t* zero_l,
+                       uint32_t e_count, uint8_t* node_in, uint8_t* node_out, uint8_t* low_sib, uint8_t* new_sib, SibLayout lay,
+                       unsigned level, unsigned fmt_out, uint32_t coop_max);
+void emit_roots_mixed(hipStream_t s, const MixedRoute& r, const uint8_t* val, uint32_t total, uint32_t n_ins, uint8_t* old_root,
+                      uint8_t* interim_root, uint8_t* new_root, uint8_t* read_root, unsigned fmt_out, uint8_t* node_store);
+
 // ---- subtree placement: lift subtree-level witnesses to the depth of the enclosing tree ----
 // top[j] (device format, j < levels) = sibling of this subtree's ancestor at height sub_depth + j;
 // bit j of pos_bits = that ancestor is a RIGHT child.  Roots are lifted in place (format fmt):

@@ -165,6 +165,128 @@ __global__ void __launch_bounds__(BLOCK) k_runs(const uint64_t* __restrict__ key
     re[k] = lo;
 }
 
+// ---- mixed batches (imt_itree_mixed_batch; the rules are in imt_prep_logic.hpp) ----
+static_assert(OP_ZERO == ERR_ZERO && OP_DUPLICATE == ERR_DUPLICATE && OP_FOREIGN == ERR_FOREIGN, "one set of error bits");
+struct ValRankLess {                   // ValLess with equal values ordered by leaf index, i.e. by rank
+    const uint8_t* val;
+    __device__ bool operator()(uint32_t a, uint32_t b) const {
+        const uint8_t *x = val + (uint64_t)a * 32, *y = val + (uint64_t)b * 32;
+        return lt256(x, y) || (a < b && !lt256(y, x));
+    }
+};
+
+__global__ void __launch_bounds__(BLOCK) k_mixed_flag(const uint8_t* __restrict__ op, uint32_t n, uint32_t* __restrict__ flag,
+                                                      int* err) {
+    const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const uint8_t o = op[p];
+    if (o > 1) atomicOr(err, ERR_OP);
+    flag[p] = o == 0 ? 1u : 0u;
+}
+__global__ void k_mixed_count(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ rank, uint32_t n,
+                              uint32_t* __restrict__ word) {
+    word[0] = rank[n - 1] + flag[n - 1];
+    word[1] = OP_NONE;
+}
+// every operation's value on its own; an INSERT's value goes to its row of d_val
+__global__ void __launch_bounds__(BLOCK)
+k_mixed_scatter(const uint8_t* __restrict__ vals, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ rank,
+                uint8_t* __restrict__ d_val, uint32_t M, uint32_t n, uint32_t part_mod, uint32_t part_res,
+                uint32_t* __restrict__ iota, uint32_t* __restrict__ ipos, int* err, uint32_t* bad) {
+    const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const uint8_t* v = vals + (uint64_t)p * 32;
+    if (geq_p(v)) atomicOr(err, ERR_NONCANONICAL);
+    const int e = op_value_class(v, part_mod, part_res);
+    if (e) { atomicOr(err, e); atomicMin(bad, p); }
+    if (!flag[p]) return;
+    const uint32_t r = rank[p];
+    copy32(d_val + (uint64_t)(M + r) * 32, v);
+    iota[r] = M + r;
+    ipos[r] = p;
+}
+// k_gap for the INSERTs of a mixed batch: the duplicate is named
+__global__ void __launch_bounds__(BLOCK)
+k_mixed_gap(const uint8_t* __restrict__ d_val, const uint32_t* __restrict__ sorted_old, uint32_t M,
+            const uint32_t* __restrict__ bsorted, uint32_t n_ins, const uint32_t* __restrict__ ipos,
+            uint32_t* __restrict__ gap, uint32_t* __restrict__ st0, int* err, uint32_t* bad) {
+    const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n_ins) return;
+    const uint32_t g = count_below(d_val, sorted_old, M, d_val + (uint64_t)bsorted[j] * 32);
+    gap[j] = g;
+    st0[j] = bsorted[j] - M;
+    if (insert_is_duplicate(d_val, sorted_old, M, bsorted, j, g)) { atomicOr(err, ERR_DUPLICATE); atomicMin(bad, ipos[bsorted[j] - M]); }
+}
+// low leaf and successor of every READ, as of its place in the batch: behind the INSERTs' in low / succ
+__global__ void __launch_bounds__(BLOCK)
+k_mixed_reads(const uint8_t* __restrict__ vals, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ rank,
+              const uint8_t* __restrict__ d_val, const uint32_t* __restrict__ sorted_old, uint32_t M,
+              const uint32_t* __restrict__ bsorted, const uint32_t* __restrict__ gap, const uint32_t* __restrict__ st,
+              uint32_t n, uint32_t n_ins, int levels, uint32_t part_mod, uint32_t part_res, uint32_t* __restrict__ low,
+              uint32_t* __restrict__ succ, int* err, uint32_t* bad) {
+    const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n || flag[p]) return;
+    const uint32_t R = rank[p], q = p - R;
+    const ReadAnswer a = read_neighbours(vals + (uint64_t)p * 32, R, d_val, sorted_old, M, bsorted, gap, st, n_ins, levels,
+                                         part_mod, part_res);
+    if (a.err) { atomicOr(err, a.err); atomicMin(bad, p); }
+    low[n_ins + q] = a.low;
+    succ[n_ins + q] = a.succ;
+}
+// k_events over the operations: an INSERT's two events as there, a READ's one -- the low leaf's preimage as of the READ,
+// which is what that leaf holds then, so hashing it rewrites the leaf with its own bytes
+__global__ void __launch_bounds__(BLOCK)
+k_mixed_events(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ rank, const uint8_t* __restrict__ d_val,
+               uint32_t M, uint32_t n, uint32_t n_ins, uint64_t base, const uint32_t* __restrict__ low,
+               const uint32_t* __restrict__ succ, uint8_t* __restrict__ pre, uint64_t* __restrict__ keys,
+               uint32_t* __restrict__ erow, uint64_t* __restrict__ o_low_index, uint8_t* __restrict__ o_is_largest,
+               uint8_t* __restrict__ o_low_leaf, uint8_t* __restrict__ o_new_leaf, ReadOut rd) {
+    const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t r = rank[p], e = p + r;
+    const bool ins = flag[p];
+    const uint32_t row = ins ? r : p - r, at = ins ? r : n_ins + row;
+    const uint32_t lo = low[at], su = succ[at];
+    const uint8_t* lv = d_val + (uint64_t)lo * 32;
+    uint8_t* e0 = pre + (uint64_t)e * 96;
+    copy32(e0, lv);
+    keys[e] = ((uint64_t)lo << 32) | (uint64_t)e;
+    // {succ.val, succ.idx}, what the low leaf points at before the operation: a READ's event keeps it, an INSERT's new leaf
+    // inherits it
+    uint8_t* nxt = ins ? e0 + 96 + 32 : e0 + 32;
+    if (su != NONE) { copy32(nxt, d_val + (uint64_t)su * 32); put_u64(nxt + 32, base + su); }
+    else { zero32(nxt); zero32(nxt + 32); }
+    if (ins) {
+        const uint8_t* v = d_val + (uint64_t)(M + r) * 32;
+        uint8_t* e1 = e0 + 96;
+        copy32(e0 + 32, v);
+        put_u64(e0 + 64, base + M + r);
+        copy32(e1, v);
+        keys[e + 1] = ((uint64_t)(M + r) << 32) | (uint64_t)(e + 1);
+        erow[e] = (r << 2) | ROW_LOW;
+        erow[e + 1] = (r << 2) | ROW_NEW;
+        if (o_new_leaf) {
+            uint8_t* o = o_new_leaf + (uint64_t)r * 96;
+            copy32(o, e1);
+            copy32(o + 32, e1 + 32);
+            copy32(o + 64, e1 + 64);
+        }
+    } else {
+        erow[e] = (row << 2) | ROW_READ;
+    }
+    uint64_t* oi = ins ? o_low_index : rd.low_index;
+    uint8_t* og = ins ? o_is_largest : rd.is_largest;
+    uint8_t* ol = ins ? o_low_leaf : rd.low_leaf;
+    if (oi) oi[row] = base + lo;
+    if (og) og[row] = su == NONE ? 1 : 0;
+    if (ol) {                            // the low leaf before the operation: {low.val, succ.val, succ.idx}
+        uint8_t* o = ol + (uint64_t)row * 96;
+        copy32(o, lv);
+        copy32(o + 32, nxt);
+        copy32(o + 64, nxt + 32);
+    }
+}
+
 __global__ void __launch_bounds__(BLOCK) k_find_low(const uint8_t* __restrict__ vals, const uint8_t* __restrict__ d_val,
                                                     const uint32_t* __restrict__ sorted, uint32_t M, uint32_t n,
                                                     uint64_t base, uint32_t part_mod, uint32_t part_res,
@@ -534,6 +656,69 @@ hipError_t index_only(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t
     if ((e = rocprim::merge(ws.tmp, tb, sorted_old, ws.bsorted, sorted_new, (size_t)M, (size_t)n, ValLess{d_val}, s)) !=
         hipSuccess)
         return e;
+    return hipGetLastError();
+}
+
+hipError_t mixed_ranks(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* op, uint32_t n) {
+    hipError_t e;
+    size_t need = 0;
+    (void)rocprim::exclusive_scan(nullptr, need, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n, rocprim::plus<uint32_t>(),
+                                  nullptr);
+    if (n == 0 || n > ws.cap_n || need > ws.tmp_bytes) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_mixed_flag, dim3(nblk(n)), dim3(BLOCK), 0, s, op, n, mx.flag, ws.err);
+    size_t tb = ws.tmp_bytes;
+    if ((e = rocprim::exclusive_scan(ws.tmp, tb, mx.flag, mx.rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), s)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_mixed_count, dim3(1), dim3(1), 0, s, mx.flag, mx.rank, n, mx.word);
+    return hipGetLastError();
+}
+
+hipError_t mixed_check(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, uint8_t* d_val,
+                       const uint32_t* sorted_old, uint32_t M, uint32_t n, uint32_t n_ins) {
+    const int levels = levels_for(n_ins);
+    hipError_t e;
+    if (n == 0 || n > ws.cap_n || n_ins > n || temp_bytes_needed(n_ins, (size_t)M) > ws.tmp_bytes) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_mixed_scatter, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, mx.flag, mx.rank, d_val, M, n, ws.part_mod,
+                       ws.part_res, ws.iota, mx.ipos, ws.err, mx.word + 1);
+    if (n_ins) {
+        size_t tb = ws.tmp_bytes;
+        if ((e = rocprim::merge_sort(ws.tmp, tb, ws.iota, ws.bsorted, (size_t)n_ins, ValRankLess{d_val}, s)) != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(k_mixed_gap, dim3(nblk(n_ins)), dim3(BLOCK), 0, s, d_val, sorted_old, M, ws.bsorted, n_ins, mx.ipos,
+                           ws.gap, ws.st, ws.err, mx.word + 1);
+        for (int k = 1; k < levels; k++)
+            hipLaunchKernelGGL(k_sparse_level, dim3(nblk(n_ins)), dim3(BLOCK), 0, s, ws.st, n_ins, k);
+        hipLaunchKernelGGL(k_neighbours, dim3(nblk(n_ins)), dim3(BLOCK), 0, s, ws.st, levels, ws.bsorted, ws.gap, sorted_old, M,
+                           n_ins, ws.low, ws.succ);
+    }
+    if (n_ins < n)
+        hipLaunchKernelGGL(k_mixed_reads, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, mx.flag, mx.rank, d_val, sorted_old, M,
+                           ws.bsorted, ws.gap, ws.st, n, n_ins, levels, ws.part_mod, ws.part_res, ws.low, ws.succ, ws.err,
+                           mx.word + 1);
+    return hipGetLastError();
+}
+
+hipError_t mixed_events(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* d_val, const uint32_t* sorted_old,
+                        uint32_t* sorted_new, uint32_t M, uint32_t n, uint32_t n_ins, uint64_t base, uint8_t* pre,
+                        uint32_t* node, uint32_t* time, uint32_t* rs, uint32_t* re, uint64_t* o_low_index,
+                        uint8_t* o_is_largest, uint8_t* o_low_leaf, uint8_t* o_new_leaf, const ReadOut& rd) {
+    hipError_t e;
+    if (n == 0 || n > ws.cap_n || n_ins > n) return hipErrorInvalidValue;
+    const uint32_t E = n + n_ins;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_mixed_events, dim3(nblk(n)), dim3(BLOCK), 0, s, mx.flag, mx.rank, d_val, M, n, n_ins, base, ws.low,
+                       ws.succ, pre, ws.keys, mx.erow, o_low_index, o_is_largest, o_low_leaf, o_new_leaf, rd);
+    size_t tb = ws.tmp_bytes;
+    if ((e = rocprim::radix_sort_keys(ws.tmp, tb, ws.keys, ws.keys_sorted, (size_t)E, 0, 64, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_runs, dim3(nblk(E)), dim3(BLOCK), 0, s, ws.keys_sorted, E, node, time, rs, re);
+    if (n_ins) {
+        tb = ws.tmp_bytes;
+        if ((e = rocprim::merge(ws.tmp, tb, sorted_old, ws.bsorted, sorted_new, (size_t)M, (size_t)n_ins, ValLess{d_val}, s)) !=
+            hipSuccess)
+            return e;
+    }
     return hipGetLastError();
 }
 

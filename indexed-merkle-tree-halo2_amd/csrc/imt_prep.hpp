@@ -76,6 +76,38 @@ hipError_t run(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t* d_val
 hipError_t index_only(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t* d_val, const uint32_t* sorted_old,
                       uint32_t* sorted_new, uint32_t M, uint32_t n);
 
+// ---- mixed batches (imt_itree_mixed_batch): INSERTs and READs in one ordered list (imt_prep_logic.hpp) ----
+// An operation at position p that R INSERTs precede has the events p + R (the low leaf: rewritten by an INSERT, rewritten
+// with the bytes it holds by a READ) and, an INSERT, p + R + 1 (the new leaf): E = 2 n_ins + n_reads events whose ids keep
+// the order of the operations.  erow[e] says whose rows event e's proof elements and root are.
+constexpr int ERR_OP = 512;                  // an op byte that is neither INSERT (0) nor READ (1)
+constexpr uint32_t ROW_LOW = 0, ROW_NEW = 1, ROW_READ = 2;      // erow[e] = (row << 2) | one of these
+struct MixedWs {              // scratch of one mixed batch of n operations, beside the Workspace
+    uint32_t* flag = nullptr;      // [n]   1 = INSERT
+    uint32_t* rank = nullptr;      // [n]   INSERTs before the operation
+    uint32_t* ipos = nullptr;      // [n]   position of the r-th INSERT
+    uint32_t* word = nullptr;      // [2]   number of INSERTs, smallest offending position (0xffffffff: none)
+    uint32_t* erow = nullptr;      // [2n]  indexed by event
+};
+struct ReadOut {              // device pointers, any may be NULL: row q belongs to the q-th READ
+    uint64_t* low_index;
+    uint8_t* is_largest;
+    uint8_t* low_leaf;             // [..][3][32] canonical
+};
+// 1. ranks and the number of INSERTs (mx.word[0]); ERR_OP into ws.err.  op: [n] device.
+hipError_t mixed_ranks(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* op, uint32_t n);
+// 2. behind it, n_ins read back and M + n_ins within the capacity: the INSERT values into rows [M, M + n_ins) of d_val,
+// every check of the values (ERR_* into ws.err, the smallest offending position into mx.word[1]) and the neighbours of
+// every operation (ws.low / ws.succ: INSERTs by rank, then READs by rank).  Writes nothing else of the tree, no output.
+hipError_t mixed_check(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, uint8_t* d_val,
+                       const uint32_t* sorted_old, uint32_t M, uint32_t n, uint32_t n_ins);
+// 3. behind it, the batch accepted: what run() leaves -- preimages pre[E][96] by event, the level-0 tables [E],
+// sorted_new[M + n_ins] (untouched if n_ins == 0), the hash-free outputs of both kinds -- and mx.erow.
+hipError_t mixed_events(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* d_val, const uint32_t* sorted_old,
+                        uint32_t* sorted_new, uint32_t M, uint32_t n, uint32_t n_ins, uint64_t base, uint8_t* pre,
+                        uint32_t* node, uint32_t* time, uint32_t* rs, uint32_t* re, uint64_t* o_low_index,
+                        uint8_t* o_is_largest, uint8_t* o_low_leaf, uint8_t* o_new_leaf, const ReadOut& rd);
+
 // ---- witness-free insertion (imt_itree_apply_batch): the touched nodes of every level (imt_apply.hpp) ----
 // From the level-0 tables run() left ([total] each): lists.node rows 0 .. l0-1, lists.src and lists.count[0 .. depth].
 // pos = [l0][lists.stride] scratch for the scans; tmp as in the workspace (temp_bytes_needed covers it).

@@ -65,6 +65,82 @@ IMT_PL_HD uint32_t nearest_smaller_right(const uint32_t* st, uint32_t n, int lev
     return p < n ? p : n;
 }
 
+// ---- mixed batches (imt_itree_mixed_batch): READs between the INSERTs of one batch -------------------------------
+// The INSERTs of the batch in value order, equal values by rank: bsorted[j] = M + rank of the j-th smallest (its row of
+// val), gap[j] = stored values below it, st = the sparse min-table over their ranks (row 0 = bsorted[j] - M, row stride
+// n_ins).  An operation's rank R is the number of INSERTs before it, so "an INSERT with a smaller position" is "an INSERT
+// of rank < R" for an INSERT and a READ alike.  A READ is a query point of that table and nothing else: it is in none of
+// these arrays, so it is nobody's neighbour.
+// Nearest position left of j0 (right: at or right of j0) whose rank is < thr; n if there is none.
+IMT_PL_HD uint32_t nearest_below_left(const uint32_t* st, uint32_t n, int levels, uint32_t j0, uint32_t thr) {
+    uint32_t p = j0;                      // invariant: every entry in [p, j0) is >= thr
+    for (int k = levels - 1; k >= 0; k--) {
+        const uint32_t w = 1u << k;
+        if (p >= w && st[(uint64_t)k * n + (p - w)] >= thr) p -= w;
+    }
+    return p > 0 ? p - 1 : n;
+}
+IMT_PL_HD uint32_t nearest_below_right(const uint32_t* st, uint32_t n, int levels, uint32_t j0, uint32_t thr) {
+    uint32_t p = j0;                      // invariant: every entry in [j0, p) is >= thr
+    for (int k = levels - 1; k >= 0; k--) {
+        const uint32_t w = 1u << k;
+        if (p + w <= n && st[(uint64_t)k * n + p] >= thr) p += w;
+    }
+    return p < n ? p : n;
+}
+// number of the batch's INSERT values strictly below x
+IMT_PL_HD uint32_t batch_below(const uint8_t* val, const uint32_t* bsorted, uint32_t n_ins, const uint8_t* x) {
+    uint32_t lo = 0, hi = n_ins;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (lt256(val + (uint64_t)bsorted[mid] * 32, x)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// What is wrong with an operation's value (the bits of prep::ERR_ZERO / ERR_DUPLICATE / ERR_FOREIGN): each refuses the
+// batch with IMT_ERR_VALUE, and the smallest position that has one is *bad_op.
+constexpr int OP_ZERO = 2, OP_DUPLICATE = 4, OP_FOREIGN = 8;
+constexpr uint32_t OP_NONE = 0xffffffffu;
+IMT_PL_HD int op_value_class(const uint8_t* x, uint32_t part_mod, uint32_t part_res) {
+    const uint64_t* w = reinterpret_cast<const uint64_t*>(x);
+    int e = 0;
+    if ((w[0] | w[1] | w[2] | w[3]) == 0) e |= OP_ZERO;
+    if (part_mod > 1 && mod_small(x, part_mod) != part_res) e |= OP_FOREIGN;
+    return e;
+}
+// The INSERT at place j of the value order is a duplicate iff its value is stored or the INSERT before it in that order
+// has the same value -- that one has the smaller rank, so the walk would have refused THIS one.
+IMT_PL_HD bool insert_is_duplicate(const uint8_t* val, const uint32_t* sorted_old, uint32_t M, const uint32_t* bsorted,
+                                   uint32_t j, uint32_t g) {
+    const uint8_t* x = val + (uint64_t)bsorted[j] * 32;
+    if (g < M && eq256(val + (uint64_t)sorted_old[g] * 32, x)) return true;
+    return j > 0 && eq256(val + (uint64_t)bsorted[j - 1] * 32, x);
+}
+// A READ of x behind R INSERTs.  Duplicate iff x is stored or an INSERT of rank < R has the same value (the first of an
+// equal run has the smallest rank); an equal INSERT of rank >= R comes later and is none of its business.  Its low leaf
+// is the nearest INSERT to the left with rank < R if no stored value lies between (same gap), else the stored
+// predecessor; its successor likewise to the right, OP_NONE if x is above everything.  Always in bounds, also for the
+// refused value 0 (g == 0).
+struct ReadAnswer {
+    uint32_t low, succ;     // rows of val
+    int err;                // OP_* bits
+};
+IMT_PL_HD ReadAnswer read_neighbours(const uint8_t* x, uint32_t R, const uint8_t* val, const uint32_t* sorted_old, uint32_t M,
+                                     const uint32_t* bsorted, const uint32_t* gap, const uint32_t* st, uint32_t n_ins,
+                                     int levels, uint32_t part_mod, uint32_t part_res) {
+    ReadAnswer a;
+    a.err = op_value_class(x, part_mod, part_res);
+    const uint32_t g = count_below(val, sorted_old, M, x);
+    if (g < M && eq256(val + (uint64_t)sorted_old[g] * 32, x) && g > 0) a.err |= OP_DUPLICATE;
+    const uint32_t j0 = batch_below(val, bsorted, n_ins, x);
+    if (j0 < n_ins && st[j0] < R && eq256(val + (uint64_t)bsorted[j0] * 32, x)) a.err |= OP_DUPLICATE;
+    const uint32_t jl = nearest_below_left(st, n_ins, levels, j0, R);
+    const uint32_t jr = nearest_below_right(st, n_ins, levels, j0, R);
+    a.low = (jl < n_ins && gap[jl] == g) ? bsorted[jl] : sorted_old[g > 0 ? g - 1 : 0];
+    a.succ = (jr < n_ins && gap[jr] == g) ? bsorted[jr] : (g < M ? sorted_old[g] : OP_NONE);
+    return a;
+}
+
 // ---- snapshot check (imt_itree_load): the leaves, visited in value order, must be ONE linked list ----------------
 // pre = [n][3][32] canonical {val, next_val, next_idx}; idx[r] = leaf index of the r-th smallest val (candidate order:
 // sorted by the top 64 bits at least).  Rank r checks leaf idx[r] against its successor idx[r + 1]: strictly larger
