@@ -4,7 +4,7 @@ imt_itree keeps its sorted list twice -- the host mirror and the device index --
 every call that changes the tree leaves another combination of mirror_valid / dev_index_valid / sorted_cur / batches in
 flight behind, and every call that reads the list picks its path from those and from the pointer mode.  The other GPU
 tests follow one writer each; this one walks the transitions.  test_sequence plays the committed scripts of
-tests/tree_model.py (every ordered pair of the ten writer kinds adjacent with a light and with a full check between
+tests/tree_model.py (every ordered pair of the twelve writer kinds adjacent with a light and with a full check between
 them, every kind right after a refused call; tests/test_tree_model.py asserts that coverage) on an IndexedTree beside
 the plain-Python model.  Expected lists come from the model, expected roots, proofs and witness rows from the CPU oracle
 loaded with the model's preimages; every comparison is bit-exact.
@@ -12,7 +12,14 @@ loaded with the model's preimages; every comparison is bit-exact.
   after an accepted step   the call's own outputs (root_out, rewind's root, status / leaf_index / n_inserted, the witness
                            rows, new_index); a pipelined device-pointer batch is left in flight, its rows are compared at
                            the next full check
-  after a refused step     the error code; size, root() and the whole snapshot unchanged
+  after a mixed batch      (kinds 12 and 13; host pointers through IndexedTree.mixed_batch, device pointers through
+                           test_gpu_mixed.Raw with every buffer pre-filled) n_inserted, new_index, the INSERT rows = the
+                           oracle's rows of inserting the INSERTs alone, every field of every READ row = one walk of the
+                           oracle over the operations (tree_model.oracle_read_rows), rows beyond the counts untouched;
+                           imt_itree_root_lagged(0) is the new root after kind 12; after kind 13 it returns what it returned
+                           right before (code and bytes) and size, root() and snapshot() are what they were
+  after a refused step     the error code; size, root() and the whole snapshot unchanged; of a mixed batch also *bad_op and,
+                           with device pointers, that no output byte was written
   light check              size and root(): neither touches the two copies of the list
   full check               size, root(), get_leaves of every slot (host and device pointers), snapshot(), the proof of
                            every slot, find_low of the probe set (host and device pointers) and its refusals, lookup,
@@ -27,6 +34,7 @@ import numpy as np
 import pytest
 
 import test_gpu_insert_matrix as tm
+import test_gpu_mixed as tgm
 import tree_model as tmod
 from oracle_lib import arr_ints, ints_to_arr
 from test_gpu_rewind import DeviceBatches, compare_rows
@@ -36,7 +44,7 @@ pytestmark = pytest.mark.gpu
 SCRIPTS = {s.name: s for s in tmod.scripts()}
 KIND_NAMES = {1: "insert_batch", 2: "insert_batch host_prep", 3: "insert_batch device pipelined", 4: "insert_filtered",
               5: "insert_filtered host_prep", 6: "apply_batch", 7: "apply_batch host_prep", 8: "apply_filtered", 9: "rewind",
-              10: "load"}
+              10: "load", 12: "mixed_batch", 13: "mixed_batch READs only"}
 N_PROBES = 24
 FOREIGN_PROBES = (5, 6, 8, 9)          # of another residue on the partitioned tree (v % 3 != 1)
 
@@ -86,6 +94,7 @@ class Player:
         self.base = tmod.index_base(sh)
         self.dv = DeviceBatches(imt, c, t, t.global_depth)
         self.in_flight = []                       # (device buffers, the oracle's rows, tag) of pipelined batches
+        self.last_mixed = None                    # (size before, the INSERT rows, level-major) of the last kind-12 step
         self.err_name = {v: k for k, v in imt._ffi.ERR.items()}
 
     def close(self):
@@ -127,6 +136,62 @@ class Player:
             return t.load_device(d.data_ptr(), pre.shape[0], st.arg["fmt"])
         return t.load(pre, st.arg["fmt"])
 
+    # ---- the mixed batch ----
+    def root_lagged(self):
+        """(return code, the 32 bytes) of imt_itree_root_lagged(t, 0), host pointers"""
+        out = np.zeros(32, np.uint8)
+        rc = self.imt.lib.imt_itree_root_lagged(self.t.h, 0, out.ctypes.data_as(ctypes.c_void_p), 0)
+        return rc, out.tobytes()
+
+    def mixed_call(self, st):
+        """(IMT_ERR_* name or None, bad_op or None, n_inserted, ins, rd, untouched): ins / rd cut to their rows, siblings
+        item-major [rows, depth, 32]; untouched: on the device-pointer path, whether no output byte was written"""
+        t, f, depth = self.t, self.imt._ffi, self.shape.depth
+        arr, ops, im = ints_to_arr(st.vals), list(st.arg["ops"]), st.arg["item_major"]
+        n = len(ops)
+        rows_first = lambda a: a if im else a.transpose(1, 0, 2)
+        if not st.arg["device"]:
+            try:
+                ins, rd = t.mixed_batch(arr, ops, item_major=im)
+            except ValueError as e:
+                return "VALUE", e.bad_op, None, None, None, None
+            except self.imt.ImtError as e:
+                return self.err_name[e.code], None, None, None, None, None
+            n_ins = ins["low_index"].shape[0]
+        else:
+            r = tgm.Raw(self.imt, depth, n, im, dev=True)
+            rc = r.call(t, arr, ops, f.SIB_ITEM_MAJOR if im else 0)          # returns behind a synchronisation of both streams
+            if rc:
+                assert r.n_ins.value == 0xDEAD, "n_inserted written by a refused call"
+                bad = None if r.bad.value == 0xDEAD else r.bad.value
+                return self.err_name[rc], bad, None, None, None, r.untouched()
+            assert r.bad.value == 0xDEAD, "bad_op written by an accepted call"
+            n_ins = r.n_ins.value
+            assert n_ins <= n, f"n_inserted {n_ins} of {n} operations"
+            ins, rd = tgm.cut(r.host(r.ins), n_ins, n, im), tgm.cut(r.host(r.rd), n - n_ins, n, im)      # beyond: the sentinel
+            ins["new_index"] = np.arange(t.size - n_ins, t.size, dtype=np.uint64)
+        for d in (ins, rd):
+            for k in d:
+                if k.endswith("_sib"):
+                    d[k] = rows_first(d[k])
+        return None, None, n_ins, ins, rd, None
+
+    def check_mixed(self, st, before, out, n_ins, ins, rd, tag):
+        sh, ops = self.shape, st.arg["ops"]
+        acc, n_rd = out["acc"], ops.count(tmod.OP_READ)
+        assert n_ins == len(acc), f"{tag}: n_inserted {n_ins}"
+        assert all(a.shape[0] == n_ins for a in ins.values()) and all(a.shape[0] == n_rd for a in rd.values()), f"{tag}: row counts"
+        ins = {k: (a.transpose(1, 0, 2) if k.endswith("_sib") else a) for k, a in ins.items()}      # compare_rows: level-major
+        self.check_rows(ins, before, acc, tag)
+        self.last_mixed = (len(before), ins)      # for tests/test_gpu_view_sequences.py: a replay across this step gives these rows
+        want = tmod.oracle_read_rows(sh, before, st)
+        assert [int(x) for x in want["low_index"]] == [r[1] for r in out["reads"]]
+        assert set(rd) == set(tgm.RD_FIELDS)
+        for k in tgm.RD_FIELDS:
+            bad = np.nonzero((np.asarray(rd[k]) != want[k]).reshape(n_rd, -1).any(axis=1))[0]
+            first = out["reads"][bad[0]] if bad.size else None
+            assert bad.size == 0, f"{tag}: READ row {bad[:1]} (operation {first[0]}, {first[4]} INSERTs before it): {k}"
+
     def check_rows(self, got, before, acc, tag):
         n = len(acc)
         if n == 0:                                # a filtered batch that accepted nothing wrote no row
@@ -143,9 +208,21 @@ class Player:
         came = f" after kind {tmod.writer_kind(prev)} and a {prev.check} check" if prev else ""
         tag = f"{self.script.name} step {i} kind {tmod.writer_kind(st)} ({what}, size {m.size}){came}"
         before = tuple(m.vals)
-        code, res = self.code_of(lambda: self.call(st))
+        mixed = st.kind in (tmod.MIXED, tmod.MIXED_READS)
+        if mixed:
+            if st.kind == tmod.MIXED_READS:
+                lagged = self.root_lagged()
+            code, bad_op, n_ins, ins, rd, untouched = self.mixed_call(st)
+            tag += f", {'device' if st.arg['device'] else 'host'} pointers, {'item' if st.arg['item_major'] else 'level'}-major"
+        else:
+            code, res = self.code_of(lambda: self.call(st))
         if st.refusal:
             assert code == tmod.REFUSAL_CODE[st.refusal], f"{tag}: returned {code}"
+            if mixed:
+                with pytest.raises(tmod.Refused) as e:
+                    tmod.play(m, st)
+                assert bad_op == e.value.bad_op, f"{tag}: bad_op {bad_op}, the walk is refused at {e.value.bad_op}"
+                assert untouched in (None, True), f"{tag}: a refused call wrote into an output buffer"
             assert t.size == len(before) and t.root() == tmod.oracle_root(sh, before), f"{tag}: size or root changed"
             assert (t.snapshot() == tmod.pre_arr(m.preimages(range(m.size)))).all(), f"{tag}: snapshot changed"
         else:
@@ -170,6 +247,16 @@ class Player:
                 assert root == tmod.oracle_root(sh, after), f"{tag}: root_out"
             elif k == 9:
                 assert res == tmod.oracle_root(sh, after), f"{tag}: rewind's root"
+            elif mixed:
+                self.check_mixed(st, before, out, n_ins, ins, rd, tag)
+                if k == tmod.MIXED:
+                    rc, root = self.root_lagged()
+                    assert rc == 0 and arr_ints(np.frombuffer(root, np.uint8)) == [tmod.oracle_root(sh, after)], \
+                        f"{tag}: imt_itree_root_lagged(0) returned {rc}, not the root after the batch"
+                else:                                     # READs only: a writer that changes nothing
+                    assert self.root_lagged() == lagged, f"{tag}: imt_itree_root_lagged(0) sees a batch of READs only"
+                    assert t.size == len(before) and t.root() == tmod.oracle_root(sh, before), f"{tag}: size or root changed"
+                    assert (t.snapshot() == tmod.pre_arr(m.preimages(range(m.size)))).all(), f"{tag}: snapshot changed"
         if st.check == tmod.FULL:
             self.full_check(tag)
         else:

@@ -4,8 +4,9 @@ A view (imt_itree_view_*) is a cache keyed by (size, the tree's count of content
 (imt_itree_view_insert_witness) reads the values and the index where the writers left them.  Every writer has to bump
 that count, nothing else may, and a build has to read the copy of the list the last writer left current -- a mistake in
 either raises no error, it serves wrong proofs against a finalized root.  test_gpu_view.py and test_gpu_replay.py grow
-their trees with apply and witness batches; this file plays the committed scripts of tests/tree_model.py (the ten ways
-into the tree in every adjacent order, refused calls between them) exactly as test_gpu_tree_sequences.Player plays them,
+their trees with apply and witness batches; this file plays the committed scripts of tests/tree_model.py (the twelve ways
+into the tree in every adjacent order, refused calls between them; a mixed batch with an INSERT makes every view stale,
+one of READs only and a refused one make none stale) exactly as test_gpu_tree_sequences.Player plays them,
 the tree's own checks included, with views alive beside the tree (tree_model.view_schedule; tests/test_tree_model.py
 asserts what that schedule covers).  Expected answers are the plain-Python model's and the CPU oracle's for the prefix
 vals[:size] of whatever the model then holds; every comparison is bit-exact.
@@ -16,7 +17,8 @@ vals[:size] of whatever the model then holds; every comparison is bit-exact.
       non_membership_witness of the prefix's probes, the witness accepted by imt_non_membership_batch against the view's
       root, a stored value and 0 refused
       insert_witness of the next min(size of the tree - size of the view, 16) insertions: all nine fields and new_index;
-      sibling rows [depth, global_depth) keep the caller's pattern; one insertion more than the tree holds is refused
+      sibling rows [depth, global_depth) keep the caller's pattern; one insertion more than the tree holds is refused;
+      where the replayed range holds a whole mixed batch that has just run, its rows there are that batch's INSERT rows
       stats: the hashes per level by imt_itree_rewind's definition, and one rebuild exactly where tree_model.view_rounds
       says: the first answered round, and every answered round behind a step that changed the contents
       while the tree is smaller than the view: every query IMT_ERR_RANGE, no rebuild
@@ -202,6 +204,7 @@ class ViewPlayer(Player):
         self.schedule, self.rounds = tmod.view_schedule(script), tmod.view_rounds(script, every)
         self.every, self.n_rounds = every, 0
         self.views = {}                                           # size -> [view, rebuilds expected so far]
+        self.n_whole_mixed = 0                                    # replays compared with a mixed batch's own INSERT rows
         self.open(1)
 
     def open(self, s):
@@ -232,13 +235,25 @@ class ViewPlayer(Player):
             tag = (f"{self.script.name} step {i} kind {tmod.writer_kind(st)} ({what}), view at {r.size} of {self.m.size} "
                    f"({r.state}), {'device' if device else 'host'} pointers, content changed by kinds {list(r.since)} since it "
                    f"last answered")
-            hashes = check_view(self.imt, self.c, ent[0], self.shape, self.m.vals, device, tag)
+            try:
+                hashes = check_view(self.imt, self.c, ent[0], self.shape, self.m.vals, device, tag)
+            except AssertionError as e:                           # a wrong answer: say whether the view had rebuilt for it
+                raise AssertionError(f"{e}\n{tag}: {ent[0].stats()[1]} rebuilds so far, {ent[1] + r.build} expected") from None
             assert (hashes is None) == (r.state == tmod.SMALLER), tag
             ent[1] += r.build
             got_hashes, builds = ent[0].stats()
             assert builds == ent[1], f"{tag}: {builds} rebuilds so far, {ent[1]} expected ({'one' if r.build else 'none'} in this round)"
             if hashes is not None:
                 assert got_hashes.tolist() == hashes, f"{tag}: hashes per level {got_hashes.tolist()}, by the definition {hashes}"
+            if st.kind == tmod.MIXED and not st.refusal and r.size <= self.last_mixed[0] and r.size + r.n_replay >= self.m.size:
+                # the replay reaches across the whole mixed batch: its rows there are the batch's own INSERT rows
+                M0, ins = self.last_mixed
+                res = ent[0].insert_witness(r.n_replay)
+                a, b = M0 - r.size, self.m.size - r.size
+                for k in trp.FIELDS + ("new_index", ):
+                    got = res[k][:, a:b] if k.endswith("_sib") else res[k][a:b]
+                    assert got.shape == ins[k].shape and (got == ins[k]).all(), f"{tag}: the replay of the mixed batch's INSERTs: {k}"
+                self.n_whole_mixed += 1
 
 
 @pytest.mark.parametrize("name,form", _cases())

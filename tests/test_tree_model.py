@@ -8,13 +8,20 @@ step scripts that tests/test_gpu_tree_sequences.py plays on the GPU.
                                    middle one).
   test_model_filter_and_readers    classify / lookup / find_low / nm_witness against a brute-force statement.
   test_model_load_refusals         the breakages of test_oracle_golden's sparse_load cases, and a few more.
-  test_script_coverage             the pair coverage of scripts(), asserted.
+  test_model_mixed_against_the_walk TreeModel.mixed (written from include/imt.h) against test_mixed_logic.walk over that
+                                   file's adversarial and random scripts: rows, refusals and bad_op.
+  test_first_pass_scripts_are_unchanged  the digest of the nine scripts that ran before the mixed batch existed.
+  test_script_coverage             the pair coverage of scripts(), asserted: the ten older kinds over the first pass, all
+                                   twelve over everything, and what the second pass owes by itself (the triples with a
+                                   mixed batch in them, its refusals with bad_op, pointer modes and layouts, READs on a
+                                   full tree, more operations than room, reads at size 1, READs whose rows change
+                                   inside one batch, where the READ values come from).
   test_scripts_are_self_consistent every accepted step accepted by the model, every refused one refused with its code.
   test_view_schedule               view_schedule() and view_rounds(): the rules of the schedule and of the expected rebuilds.
   test_view_coverage               what tests/test_gpu_view_sequences.py sees with that schedule on the committed scripts:
                                    every writer kind makes a view stale, every transition of a view's state, histories
                                    that change beneath a view, replays of leaves of every origin, rounds that must not
-                                   rebuild.  It fails for a schedule that keeps the view at size 1 alone.
+                                   rebuild (behind a mixed batch of READs only and a refused one among them).  It fails for a schedule that keeps the view at size 1 alone.
 """
 import os
 import sys
@@ -172,13 +179,68 @@ def test_model_load_refusals(oracle):
     assert part.vals == [0, 4]
 
 
+# ---------------------------------------------------------------- TreeModel.mixed against the walk of test_mixed_logic
+def test_model_mixed_against_the_walk():
+    """Two independent statements of one definition: TreeModel.mixed (from include/imt.h) and test_mixed_logic.walk (the
+    expectation of the rules the kernels run), over that file's adversarial and random scripts."""
+    import test_mixed_logic as tml
+    cases = tml.all_cases()
+    assert len(cases) >= 900 and all(c in cases for c in tml.ADVERSARIAL.values())
+    n_refused = 0
+    beyond = [c for c in cases if max(v for _, v in c[1]) >= P]   # the walk knows no modulus: "limbs" reads 2^255
+    assert len(beyond) == 1
+    for ci, (stored, script) in enumerate(c for c in cases if c not in beyond):
+        m = TreeModel(8, 256)
+        m._reset(stored)
+        vals, ops = [v for _, v in script], [op for op, _ in script]
+        assert (tml.INSERT, tml.READ) == (tmod.OP_INSERT, tmod.OP_READ)
+        rows, bad = tml.walk(stored, script)
+        if bad >= 0:
+            with pytest.raises(Refused) as e:
+                m.mixed(vals, ops)
+            assert (e.value.code, e.value.bad_op) == ("VALUE", bad) and m.vals == stored, (ci, stored, script)
+            assert m.order == sorted(stored) and m.where == {v: i for i, v in enumerate(stored)}, ci
+            n_refused += 1
+            continue
+        acc, reads = m.mixed(vals, ops)
+        assert acc == [v for op, v in script if op == tml.INSERT] and m.vals == stored + acc, (ci, stored, script)
+        assert [r[0] for r in reads] == [p for p, op in enumerate(ops) if op == tml.READ], ci
+        for p, low, leaf, largest, n_before in reads:
+            succ = rows[p][1]
+            assert low == rows[p][0] and largest == int(succ < 0) and n_before == ops[:p].count(tml.INSERT), (ci, p, stored, script)
+            assert leaf == (m.vals[low], 0 if succ < 0 else m.vals[succ], max(succ, 0)), (ci, p, stored, script)
+    assert n_refused >= 50
+    full = TreeModel(3, 8)
+    full.insert([10, 20, 30, 40, 50, 60])
+    with pytest.raises(Refused) as e:                              # FULL counts the INSERTs only
+        full.mixed([70, 80, 15], [0, 0, 1])
+    assert e.value.code == "FULL" and full.size == 7
+    assert full.mixed([70, 5, 15, 70, 25], [1, 1, 1, 0, 1])[0] == [70] and full.size == 8
+    assert len(full.mixed([5, 75], [1, 1])[1]) == 2                # READs only on a full tree
+    with pytest.raises(Refused) as e:
+        full.mixed([5, P], [1, 1])
+    assert e.value.code == "NONCANONICAL"
+    for m in (TreeModel(8, 64, 5 << 8), TreeModel(8, 64, 0, 3, 1)):
+        with pytest.raises(Refused) as e:
+            m.mixed([4], [1])
+        assert e.value.code == "ARG"
+
+
 # ---------------------------------------------------------------- the committed scripts
-def test_script_coverage():
-    scripts = tmod.scripts()
-    assert scripts is tmod.scripts() and len({s.name for s in scripts}) == len(scripts)
-    pairs, after_refusal, refusals, refused_kinds = set(), set(), set(), set()
-    rewinds, loads, shapes = set(), set(), {s.shape for s in scripts}
-    d3_story = False
+FIRST_PASS_DIGEST = "93cad3ee244feb5f5b33d7922700a6ac88035175a865acc3290861467724f726"
+
+
+def test_first_pass_scripts_are_unchanged():
+    """the nine scripts of the first pass are the record of what has passed on the GPU: byte for byte what they were"""
+    import hashlib
+    assert tmod.N_FIRST_PASS == 9
+    assert hashlib.sha256(repr(tmod.scripts()[:9]).encode()).hexdigest() == FIRST_PASS_DIGEST
+
+
+def survey(scripts):
+    """what a set of scripts covers"""
+    cov = dict(pairs=set(), after_refusal=set(), refusals=set(), refused_kinds=set(), rewinds=set(), loads=set(),
+               shapes={s.shape for s in scripts}, d3_story=False)
     for s in scripts:
         assert s.steps[-1].check == FULL, s.name
         assert all(st.check in (LIGHT, FULL) for st in s.steps)
@@ -187,45 +249,132 @@ def test_script_coverage():
             assert len(after) <= tmod.SIZE_LIMIT and (st.vals is None or 1 <= len(st.vals) <= 16), s.name
             if nxt is not None and not nxt[0].refusal:
                 if st.refusal:
-                    after_refusal.add(nxt[0].kind)
+                    cov["after_refusal"].add(nxt[0].kind)
                 else:
-                    pairs.add((st.kind, nxt[0].kind, st.check))
+                    cov["pairs"].add((st.kind, nxt[0].kind, st.check))
             if st.refusal:
-                refusals.add(st.refusal)
-                refused_kinds.add(st.kind)
+                cov["refusals"].add(st.refusal)
+                cov["refused_kinds"].add(st.kind)
             elif st.kind == 9:
                 M = len(before)
-                rewinds.add("noop" if st.arg == M else "one" if st.arg == 1 else "size-1" if st.arg == M - 1 else "interior")
+                cov["rewinds"].add("noop" if st.arg == M else "one" if st.arg == 1 else "size-1" if st.arg == M - 1 else "interior")
             elif st.kind == 10:
                 n = len(st.arg["pre"])
-                loads |= {("fmt", st.arg["fmt"]), ("device", st.arg["device"]), st.arg["source"],
-                          "shorter" if n < len(before) else "longer" if n > len(before) else "same"}
+                cov["loads"] |= {("fmt", st.arg["fmt"]), ("device", st.arg["device"]), st.arg["source"],
+                                 "shorter" if n < len(before) else "longer" if n > len(before) else "same"}
         if s.shape.cap == 8:                     # the tree fills, FULL is reached, and a rewind makes room again
             sizes = [(st, len(before), len(after)) for st, before, after, _ in tr]
             for i, (st, M, _) in enumerate(sizes):
-                if st.refusal == "full" and M == 8:
+                if st.refusal in ("full", "mixed_full") and M == 8:
                     back = [j for j in range(i + 1, len(sizes)) if sizes[j][0].kind == 9 and sizes[j][2] < sizes[j][1]]
-                    d3_story = d3_story or any(b > a for _, a, b in sizes[back[0] + 1:]) if back else d3_story
+                    if back and any(b > a for _, a, b in sizes[back[0] + 1:]):
+                        cov["d3_story"] = True
+    return cov
+
+
+def test_script_coverage():
+    scripts = tmod.scripts()
+    assert scripts is tmod.scripts() and len({s.name for s in scripts}) == len(scripts)
+    first, second = scripts[:tmod.N_FIRST_PASS], scripts[tmod.N_FIRST_PASS:]
+    # ---- the first pass: the ten older kinds, as before the mixed batch existed
+    cov = survey(first)
+    pairs, shapes = cov["pairs"], cov["shapes"]
     missing = [(a, b, lv) for lv in (LIGHT, FULL) for a in KINDS for b in KINDS if (a, b, lv) not in pairs]
     assert not missing, f"pairs of writer kinds never adjacent: {missing}"
-    assert after_refusal == set(KINDS), f"never right after a refused call: {sorted(set(KINDS) - after_refusal)}"
-    assert refusals == set(tmod.REFUSALS)
-    assert rewinds == set(tmod.REWIND_VARIANTS)
-    assert loads >= {("fmt", 0), ("fmt", 1), ("fmt", 2), ("device", False), ("device", True), "earlier", "unrelated",
-                     "shorter", "longer"}
-    assert shapes == set(tmod.SHAPES) and d3_story
+    assert cov["after_refusal"] == set(KINDS), f"never right after a refused call: {sorted(set(KINDS) - cov['after_refusal'])}"
+    assert cov["refusals"] == set(tmod.REFUSALS)
+    assert cov["rewinds"] == set(tmod.REWIND_VARIANTS)
+    assert cov["loads"] >= {("fmt", 0), ("fmt", 1), ("fmt", 2), ("device", False), ("device", True), "earlier", "unrelated",
+                            "shorter", "longer"}
+    assert shapes == set(tmod.SHAPES) and cov["d3_story"]
     g5 = ic.BY_NAME["placed_g5"]
     assert any(sh.placement == tuple(g5.placement) and (sh.depth, sh.cap) == (g5.depth, g5.cap) for sh in shapes)
     assert any(sh.partition == (3, 1) for sh in shapes)
     assert {(sh.depth, sh.cap) for sh in shapes} >= {(3, 8), (8, 64), (32, 256)}
     # the values: 1, p - 1, neighbours of stored values, groups that share their top 64 bits
-    stored = [v for s in scripts for st in s.steps if st.vals and not st.refusal for v in st.vals]
+    stored = [v for s in first for st in s.steps if st.vals and not st.refusal for v in st.vals]
     assert 1 in stored and P - 1 in stored
     every = set(stored)
     assert sum(v + 1 in every or v - 1 in every for v in every) >= 20
     tops = [v >> 192 for v in every]
     assert max(tops.count(t) for t in tmod.TOPS) >= 20
-    print(f"{len(scripts)} scripts, {sum(len(s.steps) for s in scripts)} steps, refused base kinds {sorted(refused_kinds)}")
+    print(f"{len(first)} scripts, {sum(len(s.steps) for s in first)} steps, refused base kinds {sorted(cov['refused_kinds'])}")
+    # ---- everything: all twelve kinds in every adjacent order at both check levels, each right after a refused call
+    A = tmod.ALL_KINDS
+    cov = survey(scripts)
+    missing = [(a, b, lv) for lv in (LIGHT, FULL) for a in A for b in A if (a, b, lv) not in cov["pairs"]]
+    assert not missing, f"pairs of writer kinds never adjacent: {missing}"
+    assert cov["after_refusal"] == set(A), f"never right after a refused call: {sorted(set(A) - cov['after_refusal'])}"
+    assert cov["refusals"] == set(tmod.REFUSALS) | set(tmod.MIXED_REFUSALS)
+    assert cov["shapes"] == set(tmod.SHAPES) and cov["d3_story"]
+    # ---- the second pass by itself: whatever a mixed batch takes part in
+    new = (tmod.MIXED, tmod.MIXED_READS)
+    cov = survey(second)
+    missing = [(a, b, lv) for lv in (LIGHT, FULL) for a in A for b in A if (a in new or b in new) and (a, b, lv) not in cov["pairs"]]
+    assert not missing, f"the second pass: pairs never adjacent: {missing}"
+    assert cov["after_refusal"] >= set(new) and cov["refusals"] >= set(tmod.MIXED_REFUSALS)
+    assert cov["shapes"] == set(tmod.MIXED_SHAPES) and cov["d3_story"] and len(second) <= 6
+    seen, modes, sources = set(), set(), dict.fromkeys(("neighbour", "top 64 bits", "read twice", "1 or p - 1", "other"), 0)
+    for s in second:
+        tr = tmod.trace(s)
+        for i, (st, before, after, res) in enumerate(tr):
+            if st.kind not in new:
+                continue
+            vals, ops, room = st.vals, st.arg["ops"], s.shape.cap - len(before)
+            assert len(vals) == len(ops) and set(ops) <= {0, 1} and set(st.arg) == {"ops", "device", "item_major"}, s.name
+            assert (st.kind == tmod.MIXED) == (0 in ops), f"{s.name} step {i}: kind 12 has an INSERT, kind 13 has none"
+            if st.refusal:
+                assert st.refusal in tmod.MIXED_REFUSALS and isinstance(res, Refused), s.name
+                modes.add(("refused", st.arg["device"]))
+                b = res.bad_op
+                if st.refusal == "mixed_read_stored":
+                    assert ops[b] == 1 and vals[b] in before[1:] and vals[b] not in vals[:b], (s.name, i)
+                elif st.refusal == "mixed_read_inserted_earlier":
+                    assert ops[b] == 1 and any(o == 0 and v == vals[b] for o, v in zip(ops[:b], vals[:b])), (s.name, i)
+                elif st.refusal == "mixed_insert_repeat":
+                    assert ops[b] == 0 and any(o == 0 and v == vals[b] for o, v in zip(ops[:b], vals[:b])), (s.name, i)
+                    assert ops.count(0) <= room, (s.name, i)
+                elif st.refusal == "mixed_full":
+                    assert b is None and ops.count(0) == room + 1 and all(0 < v < P for v in vals), (s.name, i)
+                else:
+                    assert b is None and any(o == 1 and v >= P for o, v in zip(ops, vals)) and ops.count(0) <= room, (s.name, i)
+                continue
+            assert 1 in ops, f"{s.name} step {i}: a mixed batch of the scripts has a READ"
+            modes.add((st.kind, st.arg["device"], st.arg["item_major"]))
+            reads, n_ins = res["reads"], ops.count(0)
+            assert res["acc"] == [v for v, o in zip(vals, ops) if o == 0] and after == before + tuple(res["acc"]), (s.name, i)
+            if st.kind == tmod.MIXED_READS and s.shape.cap == 8 and len(before) == 8:
+                seen.add("READs only on a full tree")
+            if st.kind == tmod.MIXED and len(ops) > room >= n_ins:
+                seen.add("more operations than room")
+            if i == 0:
+                seen.add("reads at size 1")
+                assert reads[0][1:4] == (0, (0, 0, 0), 1) or ops[0] == 0, s.name
+            stored_now = set(before)
+            for q, (p, low, leaf, largest, n_before) in enumerate(reads):
+                v = vals[p]
+                if v in [x for x, o in zip(vals[p + 1:], ops[p + 1:]) if o == 0]:
+                    seen.add("a READ of a value a later INSERT inserts")
+                for p2, low2, leaf2, largest2, n2 in reads[q + 1:]:
+                    if vals[p2] == v and n2 > n_before and (low2, leaf2, largest2) != (low, leaf, largest):
+                        seen.add("two READs of one value, rows differ")
+                        if low2 != low:
+                            seen.add("two READs of one value, another low leaf")
+                    if largest == 1 and largest2 == 0:
+                        seen.add("is_largest 1, later 0")
+                known = stored_now | set(res["acc"][:n_before])
+                src = "read twice" if v in [vals[r[0]] for r in reads[:q]] else "1 or p - 1" if v in (1, P - 1) else \
+                    "neighbour" if v - 1 in known or v + 1 in known else \
+                    "top 64 bits" if any(v >> 192 == x >> 192 for x in known if x) else "other"
+                sources[src] += 1
+    want = {"READs only on a full tree", "more operations than room", "reads at size 1", "a READ of a value a later INSERT inserts",
+            "two READs of one value, rows differ", "two READs of one value, another low leaf", "is_largest 1, later 0"}
+    assert seen == want, f"the second pass never has: {sorted(want - seen)}"
+    want = {(tmod.MIXED, d, im) for d in (False, True) for im in (False, True)} | {("refused", False), ("refused", True)}
+    assert modes >= want | {(tmod.MIXED_READS, d, im) for d in (False, True) for im in (False, True)}, \
+        f"pointer modes and layouts never played: {sorted(map(str, want - modes))}"
+    assert all(n >= 5 for n in sources.values()), f"where the values of the READs come from: {sources}"
+    print(f"{len(second)} scripts of the second pass, {sum(len(s.steps) for s in second)} steps, READ values {sources}")
 
 
 @pytest.mark.parametrize("script", tmod.scripts(), ids=lambda s: s.name)
@@ -242,6 +391,10 @@ def test_scripts_are_self_consistent(script):
                 assert after == before + tuple(res["acc"]) and len(res["status"]) == len(st.vals), tag
             elif st.kind == 9:
                 assert after == before[:st.arg], tag
+            elif st.kind in (tmod.MIXED, tmod.MIXED_READS):
+                ops = st.arg["ops"]
+                assert after == before + tuple(v for v, o in zip(st.vals, ops) if o == tmod.OP_INSERT), tag
+                assert len(res["reads"]) == ops.count(tmod.OP_READ) and (after == before) == (st.kind == tmod.MIXED_READS), tag
             else:
                 assert after == tuple(p[0] for p in st.arg["pre"]), tag
 
@@ -259,7 +412,14 @@ def test_scripts_reach_the_states_of_the_two_copies():
             k = st.kind
             host_prep = k in (2, 5, 7) or (k == 8 and bool(st.arg))
             changed = after != before
-            if k in (1, 2, 3, 4, 5, 6, 7, 8):
+            if k in (1, 2, 3, 4, 5, 6, 7, 8, tmod.MIXED, tmod.MIXED_READS):
+                if k >= tmod.MIXED and not dev:                  # a mixed batch is GPU-prepared: it needs the device index
+                    behind = tr[i - 1][0]
+                    seen.add(("mixed batch, device index stale", k, "refused" if st.refusal else "accepted"))
+                    if behind.refusal and behind.kind in (2, 5, 7):
+                        seen.add(("mixed batch right behind a refused host-prepared call, device index stale", k))
+                if k == tmod.MIXED_READS and not st.refusal and mirror:
+                    seen.add(("READs only with the mirror valid: it stays valid", ))
                 seen.add(("host-prepared call, mirror dropped", ) if host_prep and not mirror else
                          ("GPU-prepared call, device index stale", ) if not host_prep and not dev else ("batch", ))
                 if host_prep:
@@ -289,7 +449,11 @@ def test_scripts_reach_the_states_of_the_two_copies():
             ("rewind with the mirror valid, then a reader of the mirror", ), ("rewind, device index stale", ),
             ("load, device index stale", "accepted"), ("full check", True, False), ("full check", False, True),
             ("full check", True, True), ("refused call, then a reader", True, False),
-            ("refused call, then a reader", False, True)}
+            ("refused call, then a reader", False, True),
+            ("mixed batch, device index stale", tmod.MIXED, "accepted"), ("mixed batch, device index stale", tmod.MIXED_READS, "accepted"),
+            ("mixed batch right behind a refused host-prepared call, device index stale", tmod.MIXED),
+            ("mixed batch right behind a refused host-prepared call, device index stale", tmod.MIXED_READS),
+            ("READs only with the mirror valid: it stays valid", )}
     assert want <= seen, f"states the scripts never reach: {sorted(map(str, want - seen))}"
 
 
@@ -330,13 +494,14 @@ def view_coverage(scripts, rounds_of):
     """what the rounds of `rounds_of(script)` cover, as a dict of counters and sets"""
     from collections import Counter, defaultdict
     cov = dict(stale_by=defaultdict(Counter), transitions=Counter(), history=Counter(), origins=Counter(), crossings=0,
-               quiet=Counter())
+               quiet=Counter(), whole_mixed=0)
     for s in scripts:
         origin, state, answered = [0], {}, {}                     # who wrote leaf i; per view its last state and prefix
+        just_answered = set()                                     # the views that answered in the round before
         for (st, before, after, res), rnd in zip(tmod.trace(s), rounds_of(s)):
             k = tmod.writer_kind(st)
             if not isinstance(res, Refused):
-                origin = origin + [st.kind] * len(res["acc"]) if st.kind <= 8 else origin[:st.arg] if st.kind == 9 else \
+                origin = origin + [st.kind] * len(res["acc"]) if st.kind <= 8 or st.kind >= tmod.MIXED else origin[:st.arg] if st.kind == 9 else \
                     [0] + [10] * (len(after) - 1)
             assert len(origin) == len(after)
             live = {r.size for r in rnd}
@@ -358,6 +523,11 @@ def view_coverage(scripts, rounds_of):
                     cov["crossings"] += 1                         # ceil_log2 of the size changes inside the replayed range
                 if not r.build and not tmod.changes_content(st, before, after, res) and st.kind != 9:
                     cov["quiet"]["refused" if st.refusal else "accepted nothing"] += 1
+                    if st.kind >= tmod.MIXED and r.size in just_answered:      # fresh one round ago, and fresh still
+                        cov["quiet"]["refused mixed batch" if st.refusal else "READs only"] += 1
+                if k == tmod.MIXED and r.size <= len(before) and r.size + r.n_replay >= len(after):
+                    cov["whole_mixed"] += 1                       # the replay covers every INSERT of the mixed batch
+            just_answered = {r.size for r in rnd if r.prefix is not None}
     return cov
 
 
@@ -381,6 +551,14 @@ def test_view_coverage():
     assert cov["crossings"]
     # (f) a refused step and a filtered batch that accepted nothing are followed by a round that must not rebuild
     assert cov["quiet"]["refused"] and cov["quiet"]["accepted nothing"], cov["quiet"]
+    # (g) the mixed batch: with an INSERT it makes views stale on every plain shape; READs only and a refused one right
+    # behind an answered round are followed by a round that must not rebuild; replays cover leaves a mixed batch wrote,
+    # and the whole of one (the replayed rows are then that step's INSERT rows: both are the oracle's)
+    for name in ("d3", "d8", "d32"):
+        assert cov["stale_by"][name][tmod.MIXED], f"{name}: a mixed batch never makes a view stale"
+        assert not cov["stale_by"][name][tmod.MIXED_READS], f"{name}: READs only make nothing stale"
+    assert cov["quiet"]["READs only"] >= 10 and cov["quiet"]["refused mixed batch"], cov["quiet"]
+    assert cov["origins"][tmod.MIXED] >= 20 and cov["whole_mixed"] >= 10, (cov["origins"], cov["whole_mixed"])
     total = sum((c for c in cov["stale_by"].values()), start=type(cov["transitions"])())
     print(f"stale by kind {dict(sorted(total.items()))}, transitions {dict(cov['transitions'])}, history changes "
           f"{dict(cov['history'])}, replayed origins {dict(sorted(cov['origins'].items()))}, crossings {cov['crossings']}, "

@@ -6,16 +6,22 @@ restatements (imt_prep_logic.hpp, imt_filter_logic.hpp, host_filter).  It knows 
 witness rows of a state come from the CPU oracle, which is loaded with the model's preimages (oracle_root,
 oracle_proofs, oracle_rows; cached per state).
 
-scripts() returns the committed step scripts of tests/test_gpu_tree_sequences.py: sequences of the ten ways into the
+scripts() returns the committed step scripts of tests/test_gpu_tree_sequences.py: sequences of the twelve ways into the
 tree and of refused calls, generated coverage-directed from the literal seeds below so that every ordered pair of
 writer kinds is adjacent somewhere with a light check between the two and somewhere with a full one
-(tests/test_tree_model.py asserts that).  The writer kinds:
+(tests/test_tree_model.py asserts that).  The first nine scripts are the first pass: the ten older kinds on every shape,
+byte for byte what they were before the mixed batch existed (their digest is asserted).  A second pass with seeds of its
+own appends scripts on the plain shapes (the mixed batch refuses placed and partitioned trees) for exactly the pairs in
+which a mixed batch takes part.  The writer kinds:
    1 insert_batch, host pointers, GPU prepare        6 apply_batch, GPU prepare
    2 insert_batch, IMT_HOST_PREP                     7 apply_batch, IMT_HOST_PREP
    3 insert_batch, device pointers + IMT_PIPELINE,   8 apply_filtered, prepare mode alternating
      left in flight                                  9 rewind(s)
    4 insert_filtered, GPU prepare                   10 load of a snapshot taken from the model
-   5 insert_filtered, IMT_HOST_PREP                 11 a refused call of one of the kinds above
+   5 insert_filtered, IMT_HOST_PREP                 11 a refused call of one of the other kinds
+  12 mixed_batch with INSERTs and READs, host and   13 mixed_batch of READs only, a writer that must change nothing;
+     device pointers in turn, the sibling layout       host and device pointers in turn
+     changing at half that rate
 
 view_schedule() and view_rounds() say which views (imt_itree_view_*) tests/test_gpu_view_sequences.py keeps alive beside a
 script, what each answers after every step and when its cache must be rebuilt; the scripts themselves do not change.
@@ -33,11 +39,16 @@ from oracle_lib import P, ints_to_arr
 NEW, ZERO, PRESENT, REPEATED, FOREIGN = 0, 1, 2, 3, 4        # IMT_VAL_*
 NONE = (1 << 64) - 1
 LIGHT, FULL = "light", "full"
-KINDS = tuple(range(1, 11))
+KINDS = tuple(range(1, 11))          # the ten older writer kinds: what the first pass of scripts() plays
 REFUSED = 11
+MIXED, MIXED_READS = 12, 13
+ALL_KINDS = KINDS + (MIXED, MIXED_READS)
+OP_INSERT, OP_READ = 0, 1            # IMT_OP_*
 REFUSALS = ("stored", "repeat", "zero", "full", "ge_p", "broken_link", "rewind_past")
 REFUSAL_CODE = dict(stored="VALUE", repeat="VALUE", zero="VALUE", full="FULL", ge_p="NONCANONICAL", broken_link="VALUE",
-                    rewind_past="RANGE")
+                    rewind_past="RANGE", mixed_read_stored="VALUE", mixed_read_inserted_earlier="VALUE",
+                    mixed_insert_repeat="VALUE", mixed_full="FULL", mixed_ge_p="NONCANONICAL")
+MIXED_REFUSALS = ("mixed_read_stored", "mixed_read_inserted_earlier", "mixed_insert_repeat", "mixed_full", "mixed_ge_p")
 REWIND_VARIANTS = ("interior", "size-1", "noop", "one")
 REWIND_ORDER = ("interior", "size-1", "interior", "noop", "interior", "one")
 SIZE_LIMIT = 150                     # no script grows a tree past this many leaves
@@ -45,11 +56,11 @@ TOPS = (0x1234_5678_9ABC_DEF0, 0x2FFF_0000_0000_0001)      # top 64 bits shared 
 
 
 class Refused(Exception):
-    """the call is refused with IMT_ERR_<code> and changes nothing"""
+    """the call is refused with IMT_ERR_<code> and changes nothing; bad_op: *bad_op of a mixed batch refused for a value"""
 
-    def __init__(self, code):
+    def __init__(self, code, bad_op=None):
         super().__init__(code)
-        self.code = code
+        self.code, self.bad_op = code, bad_op
 
 
 class TreeModel:
@@ -124,6 +135,33 @@ class TreeModel:
         status, leaf, acc = self.classify(list(vals))
         self.insert(acc)
         return status, leaf, acc
+
+    def mixed(self, vals, ops):
+        """imt_itree_mixed_batch, from include/imt.h (DEFINED BY THE SEQUENCE ALONE): walk the operations in order, an
+        INSERT is insert() of the one value, a READ is nm_witness() of it against the list at that moment.  Returns
+        (the values inserted, [(position, low index, low-leaf preimage, is_largest, INSERTs before it)] of the READs).
+        Refused as insert_batch refuses -- FULL counts the INSERTs only -- or with VALUE and the smallest offending
+        position: an INSERT insert() refuses there, a READ of 0, of a stored value or of one inserted earlier in the
+        batch.  A refusal leaves the model as it was."""
+        vals, ops = list(vals), list(ops)
+        if self.index_base or self.part_mod > 1:
+            raise Refused("ARG")
+        if self.size + ops.count(OP_INSERT) > self.cap:
+            raise Refused("FULL")
+        if any(v >= P for v in vals):
+            raise Refused("NONCANONICAL")
+        start, acc, reads = self.size, [], []
+        try:
+            for p, (v, op) in enumerate(zip(vals, ops)):
+                if op == OP_INSERT:
+                    self.insert([v])
+                    acc.append(v)
+                else:
+                    reads.append((p, ) + self.nm_witness(v) + (len(acc), ))
+        except Refused:
+            self.rewind(start)
+            raise Refused("VALUE", p)
+        return acc, reads
 
     def rewind(self, s):
         if s == 0 or s > self.size:
@@ -239,8 +277,8 @@ def writer_kind(step):
 
 
 def play(m, step):
-    """One step on model m.  Accepted: dict(acc=the values inserted, status, leaf) (what applies).  A refused step
-    raises Refused and leaves m as it was."""
+    """One step on model m.  Accepted: dict(acc=the values inserted, status, leaf, reads) (what applies; reads: the READ
+    rows of a mixed batch as TreeModel.mixed returns them).  A refused step raises Refused and leaves m as it was."""
     k = step.kind
     if k in (1, 2, 3, 6, 7):
         m.insert(step.vals)
@@ -251,6 +289,9 @@ def play(m, step):
     if k == 9:
         m.rewind(step.arg)
         return {}
+    if k in (MIXED, MIXED_READS):
+        acc, reads = m.mixed(step.vals, step.arg["ops"])
+        return dict(acc=acc, reads=reads)
     m.load(step.arg["pre"])
     return {}
 
@@ -281,11 +322,12 @@ ViewRound = namedtuple("ViewRound", "size state prefix build since n_replay")
 
 def changes_content(st, before, after, res):
     """Does the step change the tree's contents as include/imt.h counts them (A VIEW FOLLOWS THE TREE): an insertion of
-    any kind that accepted something, a load, a rewind below the current size.  A refused call, a filtered batch that
-    accepted nothing and a rewind to the current size do not."""
+    any kind that accepted something (a mixed batch with an INSERT among them), a load, a rewind below the current size.
+    A refused call, a filtered batch that accepted nothing, a mixed batch of READs only and a rewind to the current size
+    do not."""
     if isinstance(res, Refused):
         return False
-    if st.kind <= 8:
+    if st.kind <= 8 or st.kind in (MIXED, MIXED_READS):
         return bool(res["acc"])
     return st.arg < len(before) if st.kind == 9 else True
 
@@ -451,6 +493,9 @@ class _Generator:
         a, b = self.out_degree(k, (LIGHT,)), self.out_degree(k, (FULL,))
         return LIGHT if a > b else FULL if b > a else self.rng.choice((LIGHT, FULL))
 
+    def refusal_level(self):
+        return (LIGHT, FULL)[self.n_refused & 1]
+
     # -- the steps --
     def snapshot_of(self, vals):
         return tuple(new_model(self.shape, vals).preimages(range(len(vals))))
@@ -539,7 +584,7 @@ class _Generator:
             kind, refusal = self.choose(prev, len(steps))
             st = self.make(kind, refusal)
             if st.refusal:
-                check = (LIGHT, FULL)[self.n_refused & 1]
+                check = self.refusal_level()
                 self.refusals = [r for r in self.refusals if r != st.refusal]
             else:
                 check = self.level(st.kind)
@@ -556,23 +601,238 @@ class _Generator:
         return Script(f"{shape.name}_{number:02d}", shape, tuple(steps))
 
 
+MIXED_SHAPES = SHAPES[:3]            # d3, d8, d32: imt_itree_mixed_batch refuses placed and partitioned trees
+MIXED_SEEDS = (0x4D530001, 0x4D530002, 0x4D530003, 0x4D530004, 0x4D530005, 0x4D530006, 0x4D530007, 0x4D530008, 0x4D530009,
+               0x4D53000A, 0x4D53000B, 0x4D53000C)
+MIXED_MAX_OPS = {3: 16, 8: 16, 32: 12}     # operations per mixed batch at a depth: every READ is an oracle proof of that depth
+
+
+class _MixedGenerator(_Generator):
+    """The second pass: the (a, b, level) triples in which a or b is a mixed batch (kinds 12 and 13), both of them right
+    after a refused call, the refusals of the mixed batch.  A generator of its own, with seeds of its own, so that the
+    scripts of the first pass stay what they are."""
+
+    def __init__(self):
+        super().__init__()
+        new = (MIXED, MIXED_READS)
+        self.need = {(a, b, lv) for a in ALL_KINDS for b in ALL_KINDS for lv in (LIGHT, FULL) if a in new or b in new}
+        self.need11 = set(new)
+        self.refusals = list(MIXED_REFUSALS)
+        self.n_mixed = {MIXED: 0, MIXED_READS: 0}
+        self.n_mixed_refused = 0
+        self.d3_reads_full = False
+        self.n_behind_stale = 0
+        self.stories = ["is_largest flips", "low leaf moves", "more operations than room"]
+
+    def done(self):
+        return not (self.need or self.need11 or self.refusals or self.stories) and self.d3_reads_full
+
+    def out_degree(self, k, levels=(LIGHT, FULL)):
+        return sum((k, b, lv) in self.need for b in ALL_KINDS for lv in levels)
+
+    def refusal_level(self):
+        return LIGHT if self.host_side else super().refusal_level()   # no reader between the refusal and the mixed batch
+
+    def fresh(self, k, exclude=()):
+        self.specials = []                                 # 1 and p - 1 are asked for by READs here (read_value)
+        return super().fresh(k, exclude)
+
+    def feasible(self, k):
+        return self.room() >= 1 if k in (1, 2, 3, 6, 7, MIXED) else True
+
+    def refusal_feasible(self, name):
+        m, room = self.m, self.m.cap - self.m.size
+        if name == "mixed_read_stored":
+            return m.size > 1
+        if name == "mixed_read_inserted_earlier":
+            return room >= 1
+        if name == "mixed_insert_repeat":
+            return room >= 2
+        if name == "mixed_full":
+            return room + 1 <= 8
+        if name == "mixed_ge_p":
+            return True
+        return super().refusal_feasible(name)
+
+    def choose(self, prev, pos):
+        rng, m = self.rng, self.m
+        d3, after_refusal = self.shape.cap == 8, prev is not None and bool(prev.refusal)
+        if d3 and m.size == m.cap and not after_refusal:
+            if not self.d3_reads_full:                     # READs only on a full tree: legal
+                self.d3_reads_full = True
+                return MIXED_READS, None
+            if "mixed_full" in self.refusals:
+                self.host_side = False
+                return None, "mixed_full"
+        feas = [k for k in ALL_KINDS if self.feasible(k)]
+        if prev is None:
+            cands = []
+        elif after_refusal:
+            cands = [k for k in feas if k in self.need11]
+        else:
+            cands = [k for k in feas if (prev.kind, k, prev.check) in self.need]
+        # once per script a refused host-prepared call right behind a host-prepared batch, a mixed batch behind it: the
+        # device index that the mixed batch needs is stale through both
+        stale = prev is not None and not after_refusal and prev.kind in (2, 5, 7) and prev.check == LIGHT and \
+            not self.stale_refusal and pos >= 3 and self.room() >= 2
+        if stale:
+            self.stale_refusal = True
+            self.host_side = True
+            names = [r for r in ("ge_p", "stored", "full") if self.refusal_feasible(r)]
+            return None, names[self.n_refused % len(names)]
+        if prev is not None and not after_refusal and (self.refusals or self.need11) and (not cands or pos % 6 == 4):
+            names = [r for r in self.refusals if self.refusal_feasible(r)] or \
+                    [r for r in MIXED_REFUSALS[self.n_mixed_refused % 5:] + MIXED_REFUSALS[:self.n_mixed_refused % 5]
+                     if self.refusal_feasible(r)]
+            self.host_side = False
+            return None, names[0]
+        if after_refusal and prev.kind in (2, 5, 7):       # behind the refused host-prepared call: kind 12 and 13 in turn
+            cands = [k for k in ((MIXED, MIXED_READS), (MIXED_READS, MIXED))[self.n_behind_stale & 1] if k in feas][:1]
+            self.n_behind_stale += 1
+        if after_refusal and not cands:                    # nothing owed behind a refusal: on to a mixed batch
+            cands = [k for k in (MIXED, MIXED_READS) if k in feas]
+        pool = cands or ([9, 10] if self.room() == 0 else feas)
+        best = max(self.out_degree(k) for k in pool)
+        return rng.choice([k for k in pool if self.out_degree(k) == best]), None
+
+    # -- the values of the READs --
+    def read_value(self, inserted, later, read):
+        """a value a READ may ask for: not 0, below p, neither stored nor among `inserted` (the batch's INSERTs so far)"""
+        m, rng = self.m, self.rng
+        known = m.vals[1:] + inserted
+        while True:
+            r = rng.random()
+            if r < 0.2 and later:
+                v = rng.choice(later)                      # a later INSERT of this batch inserts it
+            elif r < 0.35 and read:
+                v = rng.choice(read)                       # already read in this batch
+            elif r < 0.6 and known:
+                v = rng.choice(known) + rng.choice((-1, 1))
+            elif r < 0.8 and known:
+                v = (rng.choice(known) >> 192 << 192) | rng.getrandbits(192)       # shares its top 64 bits with a stored one
+            elif r < 0.85:
+                v = rng.choice((1, P - 1))
+            else:
+                v = self.pool.pop()
+            if 0 < v < P and v not in m.where and v not in inserted:
+                return v
+
+    def make_ops(self, kind, n_ins, n):
+        """(vals, ops) of an accepted mixed batch of n operations, n_ins of them INSERTs"""
+        m, rng = self.m, self.rng
+        new = self.fresh(n_ins)
+        ops = [OP_INSERT] * n_ins + [OP_READ] * (n - n_ins)
+        rng.shuffle(ops)
+        vals, inserted, read, later = [], [], [], list(new)
+        for op in ops:
+            if op == OP_INSERT:
+                v = later.pop(0)
+                inserted.append(v)
+            else:
+                v = self.read_value(inserted, later, read)
+                read.append(v)
+            vals.append(v)
+        return vals, ops
+
+    def story(self, name, room):
+        """(vals, ops) of a kind-12 batch written for one of the cases tests/test_tree_model.py asks for, or None"""
+        m, rng = self.m, self.rng
+        top = m.order[-1]
+        if name == "is_largest flips" and top + 4 < P and room >= 2:
+            x = top + 2                                    # above every stored value: the READ's low leaf is the largest one
+            return [x, x + 2, x, x - 1, x + 1, x + 1], [OP_READ, OP_INSERT, OP_READ, OP_READ, OP_READ, OP_INSERT]
+        if name == "low leaf moves" and room >= 3:
+            x, y = self.fresh(2)
+            if x - 2 > 0 and x - 1 not in m.where and x - 2 not in m.where and y not in (x - 1, x - 2):
+                return [x, x - 2, x, x - 1, y, x, y], [OP_READ, OP_INSERT, OP_READ, OP_INSERT, OP_READ, OP_READ, OP_INSERT]
+        left = m.cap - m.size                              # FULL counts the INSERTs only: n > room >= INSERTs is accepted
+        if name == "more operations than room" and 1 <= left < MIXED_MAX_OPS[self.shape.depth]:
+            return self.make_ops(MIXED, rng.randint(1, min(left, 3)), rng.randint(left + 1, MIXED_MAX_OPS[self.shape.depth]))
+        return None
+
+    def mixed_arg(self, kind, ops):
+        c = self.n_mixed[kind]
+        self.n_mixed[kind] += 1
+        return dict(ops=tuple(ops), device=bool(c & 1), item_major=bool((c >> 1) & 1))
+
+    def make(self, kind, refusal):
+        if kind not in (MIXED, MIXED_READS) or refusal:
+            return super().make(kind, refusal)
+        rng, room, top = self.rng, self.room(), MIXED_MAX_OPS[self.shape.depth]
+        if kind == MIXED_READS:
+            vals, ops = self.make_ops(kind, 0, rng.randint(1, top))
+        else:
+            got = None
+            for name in list(self.stories):
+                got = self.story(name, room)
+                if got:
+                    self.stories.remove(name)
+                    break
+            if not got:
+                n = rng.randint(2, top)
+                got = self.make_ops(kind, rng.randint(1, min(room, n - 1, 8)), n)
+            vals, ops = got
+        return Step(kind, None, tuple(vals), self.mixed_arg(kind, ops), None)
+
+    def make_refusal(self, name):
+        if name not in MIXED_REFUSALS:
+            return super().make_refusal(name)
+        m, rng = self.m, self.rng
+        self.n_refused += 1
+        self.n_mixed_refused += 1
+        room = m.cap - m.size
+        if name == "mixed_full":
+            n_ins = room + 1
+        elif name == "mixed_insert_repeat":
+            n_ins = rng.randint(1, min(room - 1, 4))       # the repeated INSERT still fits: the refusal is VALUE, not FULL
+        elif name == "mixed_read_inserted_earlier":
+            n_ins = rng.randint(1, min(room, 4))
+        else:
+            n_ins = rng.randint(0, min(room, 4))
+        vals, ops = self.make_ops(MIXED, n_ins, n_ins + rng.randint(1, 4))
+        ins_at = [p for p, op in enumerate(ops) if op == OP_INSERT]
+        if name == "mixed_read_stored":
+            at, bad = rng.randint(0, len(ops)), (OP_READ, rng.choice(m.vals[1:]))
+        elif name == "mixed_ge_p":
+            at, bad = rng.randint(0, len(ops)), (OP_READ, P + rng.randrange(3))
+        elif name == "mixed_full":
+            at, bad = None, None
+        else:
+            src = rng.choice(ins_at)
+            at = rng.randint(src + 1, len(ops))
+            bad = (OP_READ if name == "mixed_read_inserted_earlier" else OP_INSERT, vals[src])
+        if bad:
+            ops.insert(at, bad[0])
+            vals.insert(at, bad[1])
+        kind = MIXED if OP_INSERT in ops else MIXED_READS
+        c = self.n_mixed_refused
+        return Step(kind, name, tuple(vals), dict(ops=tuple(ops), device=bool(c & 1), item_major=bool((c >> 1) & 1)), None)
+
+
+N_FIRST_PASS = 9                     # scripts of the first pass: the record of what ran before the mixed batch existed
 _SCRIPTS = None
 
 
 def scripts():
-    """the committed scripts: as many as the coverage condition needs, every shape at least once"""
+    """the committed scripts: as many as the coverage conditions need, every shape at least once; the first pass first"""
     global _SCRIPTS
     if _SCRIPTS is None:
         g, out = _Generator(), []
         while not g.done() or len(out) < len(SHAPES):
             assert len(out) < len(SEEDS), "the generator does not reach its coverage"
             out.append(g.script(len(out), SHAPES[len(out) % len(SHAPES)], SEEDS[len(out)]))
+        assert len(out) == N_FIRST_PASS
+        g = _MixedGenerator()
+        while not g.done():
+            k = len(out) - N_FIRST_PASS
+            assert k < len(MIXED_SEEDS), "the second pass does not reach its coverage"
+            out.append(g.script(len(out), MIXED_SHAPES[k % len(MIXED_SHAPES)], MIXED_SEEDS[k]))
         _SCRIPTS = tuple(out)
     return _SCRIPTS
 
 
 # ---------------------------------------------------------------- the oracle's tree of a model state
-_ROOTS, _PROOFS, _ROWS = {}, {}, {}
+_ROOTS, _PROOFS, _ROWS, _READ_ROWS = {}, {}, {}, {}
 
 
 def pre_arr(pre):
@@ -646,4 +906,36 @@ def oracle_rows(shape, before, acc):
     finally:
         orc.sparse_free(h)
     _ROWS[key] = rec
+    return rec
+
+
+def oracle_read_rows(shape, before, step):
+    """the imt_read_out rows of the READs of mixed-batch `step` on the oracle's tree of state `before`: one walk on one
+    handle, sparse_insert at every INSERT, and at every READ sparse_root and sparse_proof of the low leaf the model names
+    (siblings item-major [n_reads, depth, 32], low_index global); the oracle's preimage of that leaf must be the model's"""
+    key = (shape, tuple(before), step.vals, step.arg["ops"])
+    if key in _READ_ROWS:
+        return _READ_ROWS[key]
+    orc, depth, base = oracle_lib.load(), shape.depth, index_base(shape)
+    m = new_model(shape, before)
+    n = step.arg["ops"].count(OP_READ)
+    rec = dict(low_index=np.empty(n, np.uint64), is_largest=np.empty(n, np.uint8), low_leaf=np.empty((n, 3, 32), np.uint8),
+               root=np.empty((n, 32), np.uint8), low_sib=np.empty((n, depth, 32), np.uint8))
+    h, q = _handle(orc, shape, before), 0
+    try:
+        for p, (v, op) in enumerate(zip(step.vals, step.arg["ops"])):
+            if op == OP_INSERT:
+                m.insert([v])
+                assert orc.sparse_insert(h, depth, v)["rc"] == 0, (shape.name, p)
+                continue
+            low, leaf, largest = m.nm_witness(v)
+            pre = orc.sparse_preimage(h, low - base)
+            assert (pre == pre_arr([leaf])[0]).all(), f"{shape.name}: the oracle's leaf {low} at operation {p} is not the model's"
+            rec["low_index"][q], rec["is_largest"][q], rec["low_leaf"][q] = low, largest, pre
+            rec["root"][q] = ints_to_arr([orc.sparse_root(h)])[0]
+            rec["low_sib"][q] = orc.sparse_proof(h, depth, low - base)
+            q += 1
+    finally:
+        orc.sparse_free(h)
+    _READ_ROWS[key] = rec
     return rec
