@@ -648,6 +648,49 @@ int imt_itree_mixed_batch(imt_itree *t, const void *vals /*[n][32]*/, const uint
                           const imt_insert_out *ins /*may be NULL*/, const imt_read_out *rd /*may be NULL*/,
                           uint64_t *n_inserted /*host, may be NULL*/, uint64_t *bad_op /*host, may be NULL*/,
                           unsigned flags);
+/* THE SAME BLOCK WHEN IT MAY HOLD INVALID TRANSACTIONS (a sequencer's): imt_itree_mixed_batch with the operations it
+ * would refuse skipped, each with a status, in one call.
+ * DEFINED BY THE SEQUENCE ALONE.  Walk the n operations in order as imt_itree_mixed_batch does; an operation the walk
+ * would refuse at that point is skipped, every other one is carried out.  status[p] of the operation at position p with
+ * value v is the first that applies of (whether the operation is an INSERT or a READ makes no difference):
+ *   IMT_VAL_ZERO      v == 0;
+ *   IMT_VAL_PRESENT   v was stored before the call;
+ *   IMT_VAL_REPEATED  p > f(v), with f(v) the smallest position whose operation is an INSERT of v: an earlier INSERT of
+ *                     this block put v in -- a double spend inside the block, or a READ of a value present by then;
+ *   IMT_VAL_NEW       otherwise (p <= f(v), or no INSERT of v at all): carried out.  A READ of a value a later operation
+ *                     inserts is NEW, as in imt_itree_mixed_batch; two READs of one value before its INSERT are both NEW.
+ * IMT_VAL_FOREIGN does not occur: placed and partitioned trees are refused as there.
+ * Let A be the positions with status NEW, in order: the call IS imt_itree_mixed_batch(t, vals[A], op[A], |A|, ins, rd, ..)
+ * -- the same tree, byte for byte the same rows, row r of the `ins` arrays the r-th accepted INSERT, row q of the `rd`
+ * arrays the q-th accepted READ -- except that sibling arrays keep the caller's dimensions: level-major [depth][n][32]
+ * with level stride n, the operations passed in, not |A| (item-major arrays are unchanged); imt_itree_insert_filtered's
+ * convention.  *n_inserted / *n_read = the accepted INSERTs / READs; rows at or beyond them are not written.
+ * leaf_index[p]: INSERT, NEW -> the leaf it was written to; READ, NEW -> the low leaf as of the READ (its rd->low_index
+ * row, what imt_itree_lookup_batch would report there); PRESENT -> the stored leaf; REPEATED -> the leaf the INSERT at
+ * f(v) was written to; ZERO -> the sentinel.
+ * status, leaf_index, *n_inserted and *n_read are complete when the call returns; status / leaf_index are host or device
+ * memory per IMT_DEVICE_PTRS (then `op` is a device pointer too), the two counts host memory always.
+ * What follows from the definition:
+ *  - a block in which nothing is refused is imt_itree_mixed_batch of it;
+ *  - a block of INSERTs only is imt_itree_insert_filtered of its values: the same status, leaf_index, *n_inserted and
+ *    `ins` rows;
+ *  - a block in which nothing is accepted, or only READs are, returns IMT_OK and changes nothing: it is not counted as a
+ *    change of the tree (views stay fresh) and imt_itree_root_lagged does not see it.
+ * ERRORS, the tree and every ins / rd buffer untouched, both counts 0.  IMT_ERR_ARG, nothing else written at all: NULL
+ * status, n_inserted or n_read; NULL vals or op with n > 0; an op byte above 1; a misaligned device buffer;
+ * IMT_PIPELINE, IMT_HOST_PREP or IMT_INPUTS_READY; a placed or partitioned tree; a replica of a sliced world with steps
+ * in flight; an open slice; a call between imt_itree_batch_begin and _end.  IMT_ERR_NONCANONICAL for a value >= p
+ * (malformed input, not a rejection); IMT_ERR_FULL if size + the accepted INSERTs exceeds the capacity (skipped INSERTs
+ * do not count): on these two status holds the classification and leaf_index is unspecified.  Never IMT_ERR_VALUE; should
+ * the checks of imt_itree_mixed_batch refuse what the filter accepted, that is a bug and IMT_ERR_INTERNAL.
+ * n == 0: IMT_OK, both counts 0.
+ * IMT_FMT_*, IMT_SIB_ITEM_MAJOR and IMT_DEVICE_PTRS mean what they mean to imt_itree_mixed_batch, and the call is ordered
+ * as that one: behind batches in flight, later calls behind it.  The classification costs one more host
+ * wait, a sort of the positions, two scans and four short kernels. */
+int imt_itree_mixed_filtered(imt_itree *t, const void *vals /*[n][32]*/, const uint8_t *op /*[n]*/, size_t n,
+                             uint8_t *status /*[n]*/, uint64_t *leaf_index /*[n] or NULL*/,
+                             const imt_insert_out *ins /*may be NULL*/, const imt_read_out *rd /*may be NULL*/,
+                             uint64_t *n_inserted /*host*/, uint64_t *n_read /*host*/, unsigned flags);
 
 /* ---- e: the tree as ONE SUBTREE of a deeper tree (sharding by leaf-index range) -----------------
  * north_star's multi-GPU layout: GPU g owns leaf indices [g << depth, (g + 1) << depth) of a tree of depth

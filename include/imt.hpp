@@ -491,6 +491,64 @@ public:
         }
         return m;
     }
+    // The same block when it may hold invalid transactions (imt_itree_mixed_filtered): an operation whose value is 0,
+    // stored, or put in by an earlier INSERT of the block is skipped with a status, whichever kind it is.  rows: what
+    // mixed_batch returns for the accepted operations; status[p] (IMT_VAL_*) and leaf_index[p] per operation passed in.
+    struct MixedFiltered {
+        Mixed rows;
+        std::vector<uint8_t> status;
+        std::vector<uint64_t> leaf_index;
+    };
+    MixedFiltered mixed_filtered(const std::vector<Fr>& vals, const std::vector<uint8_t>& op) {
+        const size_t n = vals.size(), d = depth_;
+        MixedFiltered f;
+        if (!n) return f;
+        if (op.size() != n) throw Error(IMT_ERR_ARG, "mixed_filtered: one op per value");
+        const uint64_t first = size();
+        Mixed& m = f.rows;
+        Insertions& r = m.inserted;
+        r.low_index.resize(n);
+        r.low_leaf.resize(n);
+        r.new_leaf.resize(n);
+        r.is_largest.resize(n);
+        r.old_root.resize(n);
+        r.interim_root.resize(n);
+        r.new_root.resize(n);
+        std::vector<Fr> ls(n * d), ns(n * d), rs(n * d);
+        std::vector<uint64_t> q_low(n);
+        std::vector<IndexedMerkleTreeLeaf> q_leaf(n);
+        std::vector<uint8_t> q_largest(n);
+        m.read_root.resize(n);
+        f.status.resize(n);
+        f.leaf_index.resize(n);
+        imt_insert_out out{r.low_index.data(), r.low_leaf.data(), r.is_largest.data(), r.old_root.data(),
+                           r.interim_root.data(), r.new_root.data(), r.new_leaf.data(), ls.data(), ns.data()};
+        imt_read_out rd{q_low.data(), q_leaf.data(), q_largest.data(), m.read_root.data(), rs.data()};
+        uint64_t k = 0, nr = 0;
+        c_->check(imt_itree_mixed_filtered(t_, vals.data(), op.data(), n, f.status.data(), f.leaf_index.data(), &out, &rd, &k, &nr,
+                                           IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR));
+        for (auto* v : {&r.low_leaf, &r.new_leaf}) v->resize(k);
+        for (auto* v : {&r.old_root, &r.interim_root, &r.new_root}) v->resize(k);
+        r.low_index.resize(k);
+        r.is_largest.resize(k);
+        r.low_leaf_proof.resize(k);
+        r.new_leaf_proof.resize(k);
+        r.new_index.resize(k);
+        for (size_t i = 0; i < k; i++) {
+            r.low_leaf_proof[i].assign(ls.begin() + i * d, ls.begin() + (i + 1) * d);
+            r.new_leaf_proof[i].assign(ns.begin() + i * d, ns.begin() + (i + 1) * d);
+            r.new_index[i] = first + i;
+        }
+        m.reads.resize(nr);
+        m.read_root.resize(nr);
+        for (size_t q = 0; q < nr; q++) {
+            m.reads[q].low_index = q_low[q];
+            m.reads[q].low_leaf = q_leaf[q];
+            m.reads[q].is_largest = q_largest[q];
+            m.reads[q].low_leaf_proof.assign(rs.begin() + q * d, rs.begin() + (q + 1) * d);
+        }
+        return f;
+    }
     imt_itree* get() const { return t_; }
     Context& context() const { return *c_; }
 

@@ -154,6 +154,8 @@ SIGNATURES = {
                                                  c_uint]),
     "imt_itree_mixed_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, P(InsertOut), P(ReadOut), P(c_u64), P(c_u64),
                                       c_uint]),
+    "imt_itree_mixed_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, P(InsertOut), P(ReadOut),
+                                         P(c_u64), P(c_u64), c_uint]),
     "imt_itree_load": (c_int, [c_void_p, c_void_p, c_u64, c_uint]),
     "imt_itree_find_low_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
     "imt_itree_insert_filtered": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, P(c_u64), P(InsertOut), c_uint]),

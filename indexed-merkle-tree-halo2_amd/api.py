@@ -671,6 +671,39 @@ class IndexedTree:
         ins["new_index"] = np.arange(self.size - n_ins.value, self.size, dtype=np.uint64)
         return ins, rd
 
+    def mixed_filtered(self, vals, ops, proofs=True, item_major=False):
+        """mixed_batch() of the operations that block would not be refused for (imt_itree_mixed_filtered): an operation
+        whose value is 0 (VAL_ZERO), stored (VAL_PRESENT) or put in by an earlier INSERT of the block (VAL_REPEATED) is
+        skipped, whichever kind it is.  Returns (ins, rd, status, leaf_index): ins / rd as mixed_batch() returns them
+        for the accepted operations, cut to their rows (sibling arrays keep stride len(vals) in memory); status and
+        leaf_index per operation passed in."""
+        v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
+        op = np.ascontiguousarray(ops, dtype=np.uint8)
+        n, d = v.shape[0], self.depth
+        if op.shape != (n,):
+            raise ValueError("mixed_filtered: one op per value")
+        ins = dict(low_index=np.empty(n, np.uint64), low_leaf=np.empty((n, 3, 32), np.uint8),
+                   is_largest=np.empty(n, np.uint8), old_root=np.empty((n, 32), np.uint8),
+                   interim_root=np.empty((n, 32), np.uint8), new_root=np.empty((n, 32), np.uint8),
+                   new_leaf=np.empty((n, 3, 32), np.uint8))
+        rd = dict(low_index=np.empty(n, np.uint64), low_leaf=np.empty((n, 3, 32), np.uint8),
+                  is_largest=np.empty(n, np.uint8), root=np.empty((n, 32), np.uint8))
+        if proofs:
+            shape = (n, d, 32) if item_major else (d, n, 32)
+            ins["low_sib"], ins["new_sib"], rd["low_sib"] = (np.empty(shape, np.uint8) for _ in range(3))
+        out = _ffi.InsertOut(**{k: a.ctypes.data for k, a in ins.items()})
+        rout = _ffi.ReadOut(**{k: a.ctypes.data for k, a in rd.items()})
+        status, leaf = np.empty(n, np.uint8), np.empty(n, np.uint64)
+        n_ins, n_rd = ctypes.c_uint64(), ctypes.c_uint64()
+        self.ctx._check(lib.imt_itree_mixed_filtered(self.h, _p(v), _p(op), n, _p(status), _p(leaf), ctypes.byref(out),
+                                                     ctypes.byref(rout), ctypes.byref(n_ins), ctypes.byref(n_rd),
+                                                     _ffi.SIB_ITEM_MAJOR if item_major else 0))
+        for res, m in ((ins, n_ins.value), (rd, n_rd.value)):
+            for k in list(res):
+                res[k] = res[k][:, :m] if k.endswith("_sib") and not item_major else res[k][:m]
+        ins["new_index"] = np.arange(self.size - n_ins.value, self.size, dtype=np.uint64)
+        return ins, rd, status, leaf
+
     def apply_batch(self, vals, host_prep=False):
         """insert_batch() without witnesses (imt_itree_apply_batch): the same tree afterwards, every touched node hashed
         once; returns the root after the batch."""

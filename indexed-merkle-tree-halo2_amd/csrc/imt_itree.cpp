@@ -152,7 +152,7 @@ struct imt_itree {
     int sorted_cur = 0;
     bool mirror_valid = true, dev_index_valid = true;
     int* h_err_pin = nullptr;        // pinned word for the prepare kernels' error bits
-    uint32_t* h_cnt_pin = nullptr;   // pinned word for the accepted count of imt_itree_insert_filtered
+    uint32_t* h_cnt_pin = nullptr;   // two pinned words: the accepted count of imt_itree_insert_filtered, the two of _mixed_filtered
     // a sharded batch between imt_itree_batch_begin and _end
     struct Pending { bool active = false; size_t n = 0; unsigned l0 = 0; int set = 0; } pending;
     static constexpr int NPIPE = IMT_NPIPE;     // batches in flight on the GPU under IMT_PIPELINE
@@ -244,7 +244,8 @@ static void plan_free(PlanSet& p) {
                     (void*)p.ws.succ, (void*)p.ws.keys, (void*)p.ws.keys_sorted, p.ws.tmp, (void*)p.ws.err})
         if (q) hipFree(q);
     for (void* q : {(void*)p.fw.idx, (void*)p.fw.ord, (void*)p.fw.st, (void*)p.fw.aux, (void*)p.fw.flag, (void*)p.fw.rank,
-                    (void*)p.fw.count, (void*)p.fw.acc, (void*)p.fw.status, (void*)p.fw.leaf, p.fw.tmp})
+                    (void*)p.fw.count, (void*)p.fw.acc, (void*)p.fw.aop, (void*)p.fw.apos, (void*)p.fw.status, (void*)p.fw.leaf,
+                    p.fw.tmp})
         if (q) hipFree(q);
     PlanSet keep;
     keep.done = p.done;
@@ -301,8 +302,10 @@ static int plan_reserve(imt_ctx* c, PlanSet& p, size_t events, unsigned levels, 
         A((void**)&p.fw.aux, N * 4);
         A((void**)&p.fw.flag, N * 4);
         A((void**)&p.fw.rank, N * 4);
-        A((void**)&p.fw.count, sizeof(uint32_t));
+        A((void**)&p.fw.count, 2 * sizeof(uint32_t));
         A((void**)&p.fw.acc, N * 32);
+        A((void**)&p.fw.aop, N);
+        A((void**)&p.fw.apos, N * 4);
         A((void**)&p.fw.status, N);
         A((void**)&p.fw.leaf, N * 8);
         p.fw.tmp_bytes = prep::filter_temp_bytes(N);
@@ -400,7 +403,7 @@ extern "C" int imt_itree_new(imt_ctx* c, unsigned depth, uint64_t capacity, imt_
         (e = hipMalloc((void**)&t->d_sorted[0], capacity * 4)) != hipSuccess ||
         (e = hipMalloc((void**)&t->d_sorted[1], capacity * 4)) != hipSuccess ||
         (e = hipHostMalloc((void**)&t->h_err_pin, sizeof(int), hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void**)&t->h_cnt_pin, sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess ||
+        (e = hipHostMalloc((void**)&t->h_cnt_pin, 2 * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess ||
         (e = hipMalloc((void**)&t->d_nodes, off * 32)) != hipSuccess ||
         (e = hipMalloc((void**)&t->d_off, (depth + 1) * 8)) != hipSuccess ||
         (e = hipMalloc((void**)&t->d_len, (depth + 1) * 8)) != hipSuccess ||
@@ -1771,54 +1774,29 @@ static int copy_sib_rows(imt_itree* t, hipStream_t s, void* user, const void* de
     return IMT_OK;
 }
 
-extern "C" int imt_itree_mixed_batch(imt_itree* t, const void* vals, const uint8_t* op, size_t n, const imt_insert_out* ins,
-                                     const imt_read_out* rd, uint64_t* n_inserted, uint64_t* bad_op, unsigned flags) {
-    if (!t) return IMT_ERR_ARG;
+// What imt_itree_mixed_filtered asks of the body below on top of a mixed batch: the low leaves of the accepted READs
+// into its leaf_index once mixed_check has found them, and a refusal of what the filter accepted reported as a bug.
+struct MixedFiltered {
+    uint64_t* d_leaf;       // leaf_index on the device (the caller's array or its staging), NULL: not asked for
+    uint64_t* h_leaf;       // a host-pointer caller's array, d_leaf is copied to; NULL otherwise
+    size_t n_all;           // its length: the operations passed in
+};
+
+// The body of imt_itree_mixed_batch behind the staging of its inputs: n operations (d_vals canonical, d_op, both device
+// memory that stream t->up_stream may read), on plan set P, acquired for >= 2 * stride events, with the error word clear.
+// stride >= n is the level stride of level-major sibling arrays -- the caller's dimensions, imt_itree_insert_filtered's
+// convention; slot: the first context scratch slot the staged outputs may take.
+static int mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, const uint8_t* d_op, size_t n, size_t stride, size_t slot,
+                      const imt_insert_out* ins, const imt_read_out* rd, uint64_t* n_inserted, uint64_t* bad_op, unsigned flags,
+                      const MixedFiltered* filtered) {
     imt_ctx* c = t->ctx;
-    IMT_NOT_SLICED(t);
-    if (n == 0) {
-        if (n_inserted) *n_inserted = 0;
-        return IMT_OK;
-    }
-    if (!vals || !op) return c->fail(IMT_ERR_ARG, "null vals / op");
-    if (flags & (IMT_PIPELINE | IMT_HOST_PREP | IMT_INPUTS_READY))
-        return c->fail(IMT_ERR_ARG, "mixed batches take neither IMT_PIPELINE, IMT_HOST_PREP nor IMT_INPUTS_READY");
-    if (t->index_base || t->global_depth != t->depth || t->part_mod > 1)
-        return c->fail(IMT_ERR_ARG, "mixed batches are not available on a placed or partitioned tree");
-    int rc = check_batch_call(t, n, flags);
-    if (rc) return rc;
+    int rc;
     const bool dev = flags & IMT_DEVICE_PTRS;
     const unsigned fmt = flags & IMT_FMT_MASK;
-    if ((rc = check_fe_ptrs(c, dev, {vals})) || (rc = check_out_ptrs(c, dev, ins))) return rc;
-    if (rd && (rc = check_fe_ptrs(c, dev, {rd->low_leaf, rd->root, rd->low_sib}))) return rc;
-    if (dev && ((ins && ((uintptr_t)ins->low_index & 7u)) || (rd && ((uintptr_t)rd->low_index & 7u))))
-        return c->fail(IMT_ERR_ARG, "device low_index array is not 8-byte aligned");
-    if (!dev)
-        for (size_t p = 0; p < n; p++)
-            if (op[p] > IMT_OP_READ) return c->fail(IMT_ERR_ARG, "op[%zu] = %u is neither IMT_OP_INSERT nor IMT_OP_READ", p, op[p]);
-    if ((rc = ensure_device_index(t))) return rc;
     const uint64_t M = t->size;
-    double waited_ms = 0;
-
-    // ---- plan buffers: 2n events hold any mix; the per-operation scratch is the filter's and the slot table's, idle here ----
-    PlanSet& P = t->plan[t->cur];
-    if ((rc = acquire_plan(t, 2 * n, 0, waited_ms))) return rc;
-    const prep::MixedWs mx{P.fw.flag, P.fw.rank, P.fw.idx, P.fw.aux, P.d_slot};
-
-    // ---- ranks, then the checks: nothing of the caller's is written before the batch is accepted ----
     hipStream_t ps = t->up_stream;
-    if ((rc = order_behind_caller(t, ps, flags))) return rc;
-    size_t slot = 2;
-    const uint8_t* d_vals = nullptr;
-    uint8_t* up = dev ? nullptr : (uint8_t*)c->dev_scratch(slot++, n * 32);
-    if ((rc = stage_canonical(c, ps, vals, n, flags, up, P.d_canon, P.ws.err, &d_vals))) return rc;
-    const uint8_t* d_op = op;
-    if (!dev) {
-        uint8_t* o = (uint8_t*)c->dev_scratch(slot++, n);
-        if (!o) return IMT_ERR_HIP;
-        IMT_HIP(c, hipMemcpyAsync(o, op, n, hipMemcpyHostToDevice, ps));
-        d_op = o;
-    }
+    // the per-operation scratch is the filter's and the slot table's, idle here
+    const prep::MixedWs mx{P.fw.flag, P.fw.rank, P.fw.idx, P.fw.aux, P.d_slot};
     IMT_HIP(c, prep::mixed_ranks(ps, P.ws, mx, d_op, (uint32_t)n));
     IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, mx.word, sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
     IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, ps));
@@ -1830,10 +1808,20 @@ extern "C" int imt_itree_mixed_batch(imt_itree* t, const void* vals, const uint8
     P.ws.part_res = t->part_res;
     IMT_HIP(c, prep::mixed_check(ps, P.ws, mx, d_vals, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)M, (uint32_t)n,
                                  (uint32_t)n_ins));
+    if (filtered && filtered->d_leaf && n_rd) {
+        IMT_HIP(c, prep::mixed_filter_reads(ps, P.fw, P.ws, mx, (uint32_t)n, (uint32_t)n_ins, t->index_base, filtered->d_leaf));
+    }
+    if (filtered && filtered->h_leaf)
+        IMT_HIP(c, hipMemcpyAsync(filtered->h_leaf, filtered->d_leaf, filtered->n_all * 8, hipMemcpyDeviceToHost, ps));
     IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, mx.word + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
     IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, ps));
     IMT_HIP(c, hipStreamSynchronize(ps));
     if ((rc = insertion_verdict(t, *t->h_err_pin, "batch"))) {
+        if (filtered) {
+            std::string why = c->last_error;
+            return c->fail(IMT_ERR_INTERNAL, "the mixed checks refuse operation %u of those the filter accepted: %s", *t->h_cnt_pin,
+                           why.c_str());
+        }
         if (rc == IMT_ERR_VALUE) {
             if (bad_op) *bad_op = *t->h_cnt_pin;
             std::string why = c->last_error;
@@ -1846,7 +1834,7 @@ extern "C" int imt_itree_mixed_batch(imt_itree* t, const void* vals, const uint8
     const size_t E = n + n_ins;
     const unsigned L0 = std::min(ceil_log2(M + n_ins), t->depth);
     const bool item_major = flags & IMT_SIB_ITEM_MAJOR;
-    const size_t sib_bytes = (size_t)t->depth * n * 32;      // the caller's dimensions, whichever kind the rows are
+    const size_t sib_bytes = (size_t)t->depth * stride * 32;      // the caller's dimensions, whichever kind the rows are
     imt_insert_out d = {};
     imt_read_out r = {};
     if (ins && n_ins &&
@@ -1875,7 +1863,7 @@ extern "C" int imt_itree_mixed_batch(imt_itree* t, const void* vals, const uint8
     hipStream_t s = c->stream;
     if ((rc = join_top(t))) return rc;
     IMT_HIP(c, hipStreamWaitEvent(s, t->up_done, 0));
-    const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->depth} : launch::SibLayout{n, 1};
+    const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->depth} : launch::SibLayout{stride, 1};
     if ((rc = mixed_hashes(t, P, s, E, L0, n_ins, d, launch::MixedRoute{mx.erow, (uint8_t*)r.low_sib}, (uint8_t*)r.root, lay, fmt)))
         return rc;
     P.pipelined = false;
@@ -1913,15 +1901,149 @@ extern "C" int imt_itree_mixed_batch(imt_itree* t, const void* vals, const uint8
          (rc = back(ins->low_leaf, d.low_leaf, n_ins * 96)) || (rc = back(ins->new_leaf, d.new_leaf, n_ins * 96)) ||
          (rc = back(ins->old_root, d.old_root, n_ins * 32)) || (rc = back(ins->interim_root, d.interim_root, n_ins * 32)) ||
          (rc = back(ins->new_root, d.new_root, n_ins * 32)) ||
-         (rc = copy_sib_rows(t, s, ins->low_sib, d.low_sib, n_ins, n, item_major)) ||
-         (rc = copy_sib_rows(t, s, ins->new_sib, d.new_sib, n_ins, n, item_major))))
+         (rc = copy_sib_rows(t, s, ins->low_sib, d.low_sib, n_ins, stride, item_major)) ||
+         (rc = copy_sib_rows(t, s, ins->new_sib, d.new_sib, n_ins, stride, item_major))))
         return rc;
     if (rd && n_rd &&
         ((rc = back(rd->low_index, r.low_index, n_rd * 8)) || (rc = back(rd->is_largest, r.is_largest, n_rd)) ||
          (rc = back(rd->low_leaf, r.low_leaf, n_rd * 96)) || (rc = back(rd->root, r.root, n_rd * 32)) ||
-         (rc = copy_sib_rows(t, s, rd->low_sib, r.low_sib, n_rd, n, item_major))))
+         (rc = copy_sib_rows(t, s, rd->low_sib, r.low_sib, n_rd, stride, item_major))))
         return rc;
     IMT_HIP(c, hipStreamSynchronize(s));
+    return IMT_OK;
+}
+
+extern "C" int imt_itree_mixed_batch(imt_itree* t, const void* vals, const uint8_t* op, size_t n, const imt_insert_out* ins,
+                                     const imt_read_out* rd, uint64_t* n_inserted, uint64_t* bad_op, unsigned flags) {
+    if (!t) return IMT_ERR_ARG;
+    imt_ctx* c = t->ctx;
+    IMT_NOT_SLICED(t);
+    if (n == 0) {
+        if (n_inserted) *n_inserted = 0;
+        return IMT_OK;
+    }
+    if (!vals || !op) return c->fail(IMT_ERR_ARG, "null vals / op");
+    if (flags & (IMT_PIPELINE | IMT_HOST_PREP | IMT_INPUTS_READY))
+        return c->fail(IMT_ERR_ARG, "mixed batches take neither IMT_PIPELINE, IMT_HOST_PREP nor IMT_INPUTS_READY");
+    if (t->index_base || t->global_depth != t->depth || t->part_mod > 1)
+        return c->fail(IMT_ERR_ARG, "mixed batches are not available on a placed or partitioned tree");
+    int rc = check_batch_call(t, n, flags);
+    if (rc) return rc;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    if ((rc = check_fe_ptrs(c, dev, {vals})) || (rc = check_out_ptrs(c, dev, ins))) return rc;
+    if (rd && (rc = check_fe_ptrs(c, dev, {rd->low_leaf, rd->root, rd->low_sib}))) return rc;
+    if (dev && ((ins && ((uintptr_t)ins->low_index & 7u)) || (rd && ((uintptr_t)rd->low_index & 7u))))
+        return c->fail(IMT_ERR_ARG, "device low_index array is not 8-byte aligned");
+    if (!dev)
+        for (size_t p = 0; p < n; p++)
+            if (op[p] > IMT_OP_READ) return c->fail(IMT_ERR_ARG, "op[%zu] = %u is neither IMT_OP_INSERT nor IMT_OP_READ", p, op[p]);
+    if ((rc = ensure_device_index(t))) return rc;
+    double waited_ms = 0;
+
+    // ---- plan buffers: 2n events hold any mix ----
+    PlanSet& P = t->plan[t->cur];
+    if ((rc = acquire_plan(t, 2 * n, 0, waited_ms))) return rc;
+
+    // ---- ranks, then the checks: nothing of the caller's is written before the batch is accepted ----
+    hipStream_t ps = t->up_stream;
+    if ((rc = order_behind_caller(t, ps, flags))) return rc;
+    size_t slot = 2;
+    const uint8_t* d_vals = nullptr;
+    uint8_t* up = dev ? nullptr : (uint8_t*)c->dev_scratch(slot++, n * 32);
+    if ((rc = stage_canonical(c, ps, vals, n, flags, up, P.d_canon, P.ws.err, &d_vals))) return rc;
+    const uint8_t* d_op = op;
+    if (!dev) {
+        uint8_t* o = (uint8_t*)c->dev_scratch(slot++, n);
+        if (!o) return IMT_ERR_HIP;
+        IMT_HIP(c, hipMemcpyAsync(o, op, n, hipMemcpyHostToDevice, ps));
+        d_op = o;
+    }
+    return mixed_core(t, P, d_vals, d_op, n, n, slot, ins, rd, n_inserted, bad_op, flags, nullptr);
+}
+
+// The filtered twin: prep::mixed_filter classifies the operations on the side stream, one wait brings back
+// the two counts and the error bits, and the accepted operations -- compacted into the plan set, P.fw.acc / aop -- are a
+// mixed batch of their own with the caller's level stride.  status / leaf_index are classified into the plan set's
+// staging whatever the pointers are: a device-pointer caller's op bytes are checked by the class kernel, and a bad one
+// must leave the caller's arrays as they were.
+extern "C" int imt_itree_mixed_filtered(imt_itree* t, const void* vals, const uint8_t* op, size_t n, uint8_t* status,
+                                        uint64_t* leaf_index, const imt_insert_out* ins, const imt_read_out* rd,
+                                        uint64_t* n_inserted, uint64_t* n_read, unsigned flags) {
+    if (!t) return IMT_ERR_ARG;
+    imt_ctx* c = t->ctx;
+    if (n_inserted) *n_inserted = 0;        // the counts are 0 on every error
+    if (n_read) *n_read = 0;
+    IMT_NOT_SLICED(t);
+    if (!status || !n_inserted || !n_read) return c->fail(IMT_ERR_ARG, "null status / n_inserted / n_read");
+    if (n == 0) return IMT_OK;
+    if (!vals || !op) return c->fail(IMT_ERR_ARG, "null vals / op");
+    if (flags & (IMT_PIPELINE | IMT_HOST_PREP | IMT_INPUTS_READY))
+        return c->fail(IMT_ERR_ARG, "mixed batches take neither IMT_PIPELINE, IMT_HOST_PREP nor IMT_INPUTS_READY");
+    if (t->index_base || t->global_depth != t->depth || t->part_mod > 1)
+        return c->fail(IMT_ERR_ARG, "mixed batches are not available on a placed or partitioned tree");
+    int rc = check_batch_call(t, n, flags);
+    if (rc) return rc;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    if ((rc = check_fe_ptrs(c, dev, {vals})) || (rc = check_out_ptrs(c, dev, ins))) return rc;
+    if (rd && (rc = check_fe_ptrs(c, dev, {rd->low_leaf, rd->root, rd->low_sib}))) return rc;
+    if (dev && ((ins && ((uintptr_t)ins->low_index & 7u)) || (rd && ((uintptr_t)rd->low_index & 7u))))
+        return c->fail(IMT_ERR_ARG, "device low_index array is not 8-byte aligned");
+    if (dev && ((uintptr_t)leaf_index & 7u)) return c->fail(IMT_ERR_ARG, "device leaf_index array is not 8-byte aligned");
+    if (!dev)
+        for (size_t p = 0; p < n; p++)
+            if (op[p] > IMT_OP_READ) return c->fail(IMT_ERR_ARG, "op[%zu] = %u is neither IMT_OP_INSERT nor IMT_OP_READ", p, op[p]);
+    if ((rc = ensure_device_index(t))) return rc;
+    double waited_ms = 0;
+    PlanSet& P = t->plan[t->cur];
+    if ((rc = acquire_plan(t, 2 * n, 0, waited_ms))) return rc;
+
+    // ---- the classification: nothing of the caller's is written before the op bytes are known to be good ----
+    hipStream_t ps = t->up_stream;
+    if ((rc = order_behind_caller(t, ps, flags))) return rc;
+    size_t slot = 2;
+    const uint8_t* d_vals = nullptr;
+    // the plan's own buffer for the upload as well, as gpu_filter has it
+    if ((rc = stage_canonical(c, ps, vals, n, flags, P.d_canon, P.d_canon, P.ws.err, &d_vals))) return rc;
+    const uint8_t* d_op = op;
+    if (!dev) {
+        uint8_t* o = (uint8_t*)c->dev_scratch(slot++, n);
+        if (!o) return IMT_ERR_HIP;
+        IMT_HIP(c, hipMemcpyAsync(o, op, n, hipMemcpyHostToDevice, ps));
+        d_op = o;
+    }
+    uint64_t* d_leaf = leaf_index ? P.fw.leaf : nullptr;
+    IMT_HIP(c, prep::mixed_filter(ps, P.fw, d_vals, d_op, (uint32_t)n, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)t->size,
+                                  t->index_base, P.fw.status, d_leaf, P.ws.err));
+    IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, P.fw.count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
+    IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, ps));
+    if (!dev) IMT_HIP(c, hipMemcpyAsync(status, P.fw.status, n, hipMemcpyDeviceToHost, ps));     // its op bytes were checked above
+    IMT_HIP(c, hipStreamSynchronize(ps));
+    if (*t->h_err_pin & prep::ERR_OP) return c->fail(IMT_ERR_ARG, "an op byte is neither IMT_OP_INSERT nor IMT_OP_READ");
+    if (dev) IMT_HIP(c, hipMemcpyAsync(status, P.fw.status, n, hipMemcpyDeviceToDevice, ps));
+    const size_t n_ins = t->h_cnt_pin[0], n_rd = t->h_cnt_pin[1], n_acc = n_ins + n_rd;
+    if (*t->h_err_pin & prep::ERR_NONCANONICAL) rc = c->fail(IMT_ERR_NONCANONICAL, "a value is not reduced (>= p)");
+    else rc = check_room(t, n_ins);
+    const hipMemcpyKind to_user = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (rc || !n_acc) {       // refused, or nothing to carry out: the classification is the whole answer
+        if (leaf_index) IMT_HIP(c, hipMemcpyAsync(leaf_index, d_leaf, n * 8, to_user, ps));
+        IMT_HIP(c, hipStreamSynchronize(ps));
+        return rc;
+    }
+
+    // ---- the accepted operations: a mixed batch with the caller's dimensions ----
+    MixedFiltered fl{nullptr, nullptr, n};
+    if (leaf_index) {
+        if (dev) {      // the rest of the classification now, the low leaves of the READs straight into the caller's array
+            IMT_HIP(c, hipMemcpyAsync(leaf_index, d_leaf, n * 8, to_user, ps));
+            fl.d_leaf = leaf_index;
+        } else {
+            fl.d_leaf = d_leaf;
+            fl.h_leaf = leaf_index;
+        }
+    }
+    if ((rc = mixed_core(t, P, P.fw.acc, P.fw.aop, n_acc, n, slot, ins, rd, nullptr, nullptr, flags, &fl))) return rc;
+    *n_inserted = n_ins;
+    *n_read = n_rd;
     return IMT_OK;
 }
 

@@ -1,6 +1,7 @@
 // imt_prep.hip -- device kernels of the GPU batch preparation (see imt_prep.hpp).  Index and byte
 // work only (no field arithmetic): bound by HBM latency, a few hundred microseconds per 2^16 batch.
 // Sorting and merging use rocPRIM (AMD's device primitives) with a 256-bit comparator.
+#include <algorithm>
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
@@ -374,6 +375,76 @@ __global__ void __launch_bounds__(BLOCK) k_filter_compact(const uint8_t* __restr
     if (i + 1 == n) *count = rank[i] + flag[i];
 }
 
+// ---- filtered mixed batches (imt_itree_mixed_filtered; the rule is in imt_filter_logic.hpp) ----
+struct MixedPosLess {                  // order positions by value, INSERT before READ, then position
+    const uint8_t* vals;
+    const uint8_t* op;
+    __device__ bool operator()(uint32_t a, uint32_t b) const { return mixed_pos_less(vals, op, a, b); }
+};
+
+__global__ void __launch_bounds__(BLOCK) k_mixed_filter_class(const uint8_t* __restrict__ vals, const uint8_t* __restrict__ op,
+                                                              uint32_t n, uint32_t* __restrict__ idx, uint8_t* __restrict__ st,
+                                                              int* err) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t* v = vals + (uint64_t)i * 32;
+    if (geq_p(v)) atomicOr(err, ERR_NONCANONICAL);
+    if (op[i] > 1) atomicOr(err, ERR_OP);
+    st[i] = filter_class(v, 0, 0);
+    idx[i] = i;
+}
+
+// over the batch order: PRESENT against the stored index, REPEATED against the head of the run; the accepted flags by kind
+__global__ void __launch_bounds__(BLOCK)
+k_mixed_filter_rank(const uint8_t* __restrict__ vals, const uint8_t* __restrict__ op, const uint32_t* __restrict__ ord, uint32_t n,
+                    const uint8_t* __restrict__ d_val, const uint32_t* __restrict__ sorted, uint32_t M, uint8_t* __restrict__ st,
+                    uint32_t* __restrict__ aux, uint32_t* __restrict__ flag_ins, uint32_t* __restrict__ flag_rd) {
+    const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t i = ord[j];
+    uint32_t a = 0;
+    const uint8_t s = mixed_filter_rank(vals, op, ord, j, st[i], d_val, sorted, M, &a);
+    const bool ins = op[i] == 0;
+    st[i] = s;
+    aux[i] = a;
+    flag_ins[i] = (s == VAL_NEW && ins) ? 1u : 0u;
+    flag_rd[i] = (s == VAL_NEW && !ins) ? 1u : 0u;
+}
+
+// input order: status, the leaf of everything but an accepted READ, the accepted operations side by side, the counts
+__global__ void __launch_bounds__(BLOCK)
+k_mixed_filter_compact(const uint8_t* __restrict__ vals, const uint8_t* __restrict__ op, uint32_t n, const uint8_t* __restrict__ st,
+                       const uint32_t* __restrict__ aux, const uint32_t* __restrict__ flag_ins,
+                       const uint32_t* __restrict__ rank_ins, const uint32_t* __restrict__ flag_rd,
+                       const uint32_t* __restrict__ rank_rd, uint64_t base, uint32_t M, uint8_t* __restrict__ acc,
+                       uint8_t* __restrict__ aop, uint32_t* __restrict__ apos, uint8_t* __restrict__ status,
+                       uint64_t* __restrict__ leaf, uint32_t* __restrict__ count) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t s = st[i], o = op[i];
+    if (s == VAL_NEW) {
+        const uint32_t k = rank_ins[i] + rank_rd[i];
+        copy32(acc + (uint64_t)k * 32, vals + (uint64_t)i * 32);
+        aop[k] = o;
+        apos[k] = i;
+    }
+    status[i] = s;
+    if (leaf && !(s == VAL_NEW && o != 0)) leaf[i] = mixed_filter_leaf(s, aux[i], rank_ins, i, base, M);
+    if (i + 1 == n) {
+        count[0] = rank_ins[i] + flag_ins[i];
+        count[1] = rank_rd[i] + flag_rd[i];
+    }
+}
+
+// behind mixed_check of the accepted operations: an accepted READ reports its low leaf (rank: INSERTs before operation k)
+__global__ void __launch_bounds__(BLOCK)
+k_mixed_filter_reads(const uint8_t* __restrict__ aop, const uint32_t* __restrict__ apos, const uint32_t* __restrict__ rank,
+                     const uint32_t* __restrict__ low, uint32_t n_acc, uint32_t n_ins, uint64_t base, uint64_t* __restrict__ leaf) {
+    const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= n_acc || aop[k] == 0) return;
+    leaf[apos[k]] = base + low[n_ins + (k - rank[k])];
+}
+
 __global__ void __launch_bounds__(BLOCK) k_lookup(const uint8_t* __restrict__ vals, const uint8_t* __restrict__ d_val,
                                                   const uint32_t* __restrict__ sorted, uint32_t M, uint32_t n, uint64_t base,
                                                   uint32_t part_mod, uint32_t part_res, uint8_t* __restrict__ status,
@@ -722,12 +793,13 @@ hipError_t mixed_events(hipStream_t s, Workspace& ws, const MixedWs& mx, const u
     return hipGetLastError();
 }
 
+static size_t mixed_filter_temp_bytes(size_t n);
 size_t filter_temp_bytes(size_t n) {
     size_t a = 0, b = 0;
     (void)rocprim::merge_sort(nullptr, a, (uint32_t*)nullptr, (uint32_t*)nullptr, n, PosLess{nullptr}, nullptr);
     (void)rocprim::exclusive_scan(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n, rocprim::plus<uint32_t>(),
                                   nullptr);
-    return (a > b ? a : b) + 256;
+    return std::max(std::max(a, b) + 256, mixed_filter_temp_bytes(n));      // one allocation serves both filters
 }
 
 hipError_t filter(hipStream_t s, FilterWs& ws, const uint8_t* vals, uint32_t n, const uint8_t* d_val,
@@ -747,6 +819,46 @@ hipError_t filter(hipStream_t s, FilterWs& ws, const uint8_t* vals, uint32_t n, 
         return e;
     hipLaunchKernelGGL(k_filter_compact, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, n, ws.st, ws.aux, ws.flag, ws.rank, base,
                        M, ws.acc, status, leaf, ws.count);
+    return hipGetLastError();
+}
+
+static size_t mixed_filter_temp_bytes(size_t n) {
+    size_t a = 0;
+    (void)rocprim::merge_sort(nullptr, a, (uint32_t*)nullptr, (uint32_t*)nullptr, n, MixedPosLess{nullptr, nullptr}, nullptr);
+    return a + 256;
+}
+
+hipError_t mixed_filter(hipStream_t s, FilterWs& ws, const uint8_t* vals, const uint8_t* op, uint32_t n, const uint8_t* d_val,
+                        const uint32_t* sorted, uint32_t M, uint64_t base, uint8_t* status, uint64_t* leaf, int* err) {
+    hipError_t e;
+    if (n == 0 || n > ws.cap_n || filter_temp_bytes(n) > ws.tmp_bytes || mixed_filter_temp_bytes(n) > ws.tmp_bytes)
+        return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_mixed_filter_class, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, op, n, ws.idx, ws.st, err);
+    size_t tb = ws.tmp_bytes;
+    if ((e = rocprim::merge_sort(ws.tmp, tb, ws.idx, ws.ord, (size_t)n, MixedPosLess{vals, op}, s)) != hipSuccess) return e;
+    // ws.idx has been sorted from and is free: it holds the accepted-READ flags, and ws.ord, read for the last time by the
+    // rank kernel, their scan
+    uint32_t *flag_rd = ws.idx, *rank_rd = ws.ord;
+    hipLaunchKernelGGL(k_mixed_filter_rank, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, op, ws.ord, n, d_val, sorted, M, ws.st, ws.aux,
+                       ws.flag, flag_rd);
+    tb = ws.tmp_bytes;
+    if ((e = rocprim::exclusive_scan(ws.tmp, tb, ws.flag, ws.rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), s)) != hipSuccess)
+        return e;
+    tb = ws.tmp_bytes;
+    if ((e = rocprim::exclusive_scan(ws.tmp, tb, flag_rd, rank_rd, 0u, (size_t)n, rocprim::plus<uint32_t>(), s)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(k_mixed_filter_compact, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, op, n, ws.st, ws.aux, ws.flag, ws.rank,
+                       flag_rd, rank_rd, base, M, ws.acc, ws.aop, ws.apos, status, leaf, ws.count);
+    return hipGetLastError();
+}
+
+hipError_t mixed_filter_reads(hipStream_t s, const FilterWs& ws, const Workspace& prep_ws, const MixedWs& mx, uint32_t n_acc,
+                              uint32_t n_ins, uint64_t base, uint64_t* leaf) {
+    if (n_acc == 0 || n_acc > ws.cap_n || n_ins > n_acc || !leaf) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_mixed_filter_reads, dim3(nblk(n_acc)), dim3(BLOCK), 0, s, ws.aop, ws.apos, mx.rank, prep_ws.low, n_acc,
+                       n_ins, base, leaf);
     return hipGetLastError();
 }
 

@@ -145,8 +145,10 @@ struct FilterWs {             // per plan set, sized for `cap_n` values
     uint32_t* aux = nullptr;       // [n]   stored leaf (PRESENT) / first occurrence (REPEATED)
     uint32_t* flag = nullptr;      // [n]   1 = accepted
     uint32_t* rank = nullptr;      // [n]   exclusive scan of flag
-    uint32_t* count = nullptr;     // [1]   accepted values
+    uint32_t* count = nullptr;     // [2]   accepted values; mixed_filter: accepted INSERTs, accepted READs
     uint8_t* acc = nullptr;        // [n][32] accepted values in input order (canonical)
+    uint8_t* aop = nullptr;        // [n]   mixed_filter: op bytes of the accepted operations, beside acc
+    uint32_t* apos = nullptr;      // [n]   mixed_filter: input position of the k-th accepted operation
     uint8_t* status = nullptr;     // [n]   staging of the status for host-pointer callers
     uint64_t* leaf = nullptr;      // [n]   ... and of the leaf indices
     void* tmp = nullptr;           // rocPRIM temporary storage
@@ -160,6 +162,20 @@ size_t filter_temp_bytes(size_t n);
 hipError_t filter(hipStream_t s, FilterWs& ws, const uint8_t* vals, uint32_t n, const uint8_t* d_val,
                   const uint32_t* sorted, uint32_t M, uint64_t base, uint32_t part_mod, uint32_t part_res,
                   uint8_t* status, uint64_t* leaf, int* err);
+
+// ---- filtered mixed batches (imt_itree_mixed_filtered): which operations of a block are carried out ----
+// Classifies the operations (vals [n][32] canonical, op [n], both device) against the stored index of a tree that is
+// neither placed nor partitioned (mixed_filter_rank, imt_filter_logic.hpp): status[i]; leaf[i] (may be NULL) for every
+// operation but an accepted READ; the accepted operations compacted in input order -- values into ws.acc, op bytes into
+// ws.aop, positions into ws.apos -- and their numbers into ws.count[0] (INSERTs) and ws.count[1] (READs).
+// ERR_NONCANONICAL / ERR_OP are OR-ed into *err.  Writes nothing but ws, status, leaf and err.  ws.flag / rank / idx / ord /
+// aux are scratch: MixedWs may be laid over them afterwards, ws.acc / aop / apos stay.
+hipError_t mixed_filter(hipStream_t s, FilterWs& ws, const uint8_t* vals, const uint8_t* op, uint32_t n, const uint8_t* d_val,
+                        const uint32_t* sorted, uint32_t M, uint64_t base, uint8_t* status, uint64_t* leaf, int* err);
+// Behind mixed_ranks + mixed_check of (ws.acc, ws.aop, n_acc): leaf[ws.apos[k]] = base + the low leaf of the k-th accepted
+// operation, for the READs among them.
+hipError_t mixed_filter_reads(hipStream_t s, const FilterWs& ws, const Workspace& prep_ws, const MixedWs& mx, uint32_t n_acc,
+                              uint32_t n_ins, uint64_t base, uint64_t* leaf);
 
 // imt_itree_lookup_batch: status and leaf index (may be NULL) of every candidate (lookup_one, imt_filter_logic.hpp)
 void lookup(hipStream_t s, const uint8_t* vals, const uint8_t* d_val, const uint32_t* sorted, uint32_t M, uint32_t n,
