@@ -585,6 +585,8 @@ int imt_itree_view_stats(imt_itree_view *v, uint64_t *hashes /*[depth + 1] or NU
  * and freed with the view; the merged index of size + n entries, 4 bytes each, is borrowed from the context for the time
  * of the call, as a rebuild borrows its scratch. */
 int imt_itree_view_insert_witness(imt_itree_view *v, size_t n, const imt_insert_out *out, unsigned flags);
+/* Its twin for a block that also held READs, imt_itree_view_mixed_witness, takes an imt_read_out and is declared with
+ * the mixed batches below, behind imt_itree_mixed_filtered. */
 /* Read-only query of the device-resident index for any mix of values (one kernel, k_lookup): status ZERO / FOREIGN /
  * PRESENT / NEW and leaf_index = the sentinel / UINT64_MAX / the stored leaf / the low leaf (what find_low returns).
  * Fails only for its arguments, a value >= p (IMT_ERR_NONCANONICAL) or a HIP error, never for a value's class.  With
@@ -691,6 +693,44 @@ int imt_itree_mixed_filtered(imt_itree *t, const void *vals /*[n][32]*/, const u
                              uint8_t *status /*[n]*/, uint64_t *leaf_index /*[n] or NULL*/,
                              const imt_insert_out *ins /*may be NULL*/, const imt_read_out *rd /*may be NULL*/,
                              uint64_t *n_inserted /*host*/, uint64_t *n_read /*host*/, unsigned flags);
+/* APPLY A MIXED BLOCK NOW, PROVE IT LATER (beside imt_itree_view_insert_witness; declared here for imt_read_out): the
+ * witnesses of a block of INSERTs and READs whose insertions the tree has already made, witness-free or otherwise, and may
+ * since have built upon -- every READ's witness against the tree as it stood at that point of the block.
+ * DEFINED BY THE SIZE AND THE LIST ALONE.  Take a fresh tree fed the first size - 1 values this tree holds and call
+ * imt_itree_mixed_batch(fresh, vals, op, n, ins, rd, n_inserted, bad_op, flags) on it: this call writes what that call
+ * writes, byte for byte -- every `ins` and `rd` field, NULL fields skipped, row r of `ins` the r-th INSERT, row q of `rd` the
+ * q-th READ, sibling arrays level-major with level stride n or item-major, IMT_FMT_*, IMT_SIB_ITEM_MAJOR and
+ * IMT_DEVICE_PTRS as there (`op` a device pointer too), *n_inserted = the number of INSERTs.
+ * ONE CONDITION MAKES IT A REPLAY: the INSERTs of the list must be the values the tree holds at leaves
+ * [size, size + n_ins), in that order.  The caller passes the block as it was, and the call checks that it was this block.
+ * What follows from the definition:
+ *  - a list of INSERTs only is imt_itree_view_insert_witness(v, n, ins, flags);
+ *  - a list of READs only is imt_itree_view_non_membership_witness of those values with imt_itree_view_root in every
+ *    rd->root row (on a view at the tree's current size too);
+ *  - the root of a READ with no INSERT before it, and old_root of the first INSERT, are the VIEW's root, not the tree's;
+ *  - a READ of a value that a later operation of the list inserts is legal, so is a READ of a value the tree received
+ *    after size + n_ins, and so are two READs of one value.
+ * It is a view query otherwise: it never changes the tree (stored nodes, index buffers, plan sets, size, lagged roots,
+ * rows of the value array -- an INSERT's value is compared with its row, never written there), it rebuilds a stale side
+ * table first, behind everything in flight, pipelined batches included, and it is refused where the other view queries
+ * are.  Synchronous for host pointers; with IMT_DEVICE_PTRS it is enqueued on the context's stream.  n_inserted and
+ * bad_op are host memory and complete at return.
+ * REFUSALS, nothing written to `ins` or `rd`, tree and view untouched.  IMT_ERR_VALUE with *bad_op = the smallest position
+ * p at which either the walk on the fresh tree refuses the operation (a READ of 0, of a value stored as of the view's
+ * size, or of a value an earlier INSERT of the list put in) or the operation is an INSERT of rank r whose value is not the
+ * one the tree holds at leaf size + r.  IMT_ERR_RANGE: more INSERTs in the list than imt_itree_size(t) - size, or a tree
+ * smaller than the view.  IMT_ERR_NONCANONICAL for a value >= p.  IMT_ERR_ARG: a handle that is not a live view; NULL
+ * vals or op with n > 0; an op byte above 1; a misaligned device buffer; IMT_PIPELINE, IMT_HOST_PREP or
+ * IMT_INPUTS_READY in flags; a placed or partitioned tree; a replica of a sliced world with steps in flight; an open
+ * slice; a call between imt_itree_batch_begin and _end.  n == 0: IMT_OK, *n_inserted = 0.  Never IMT_ERR_FULL.
+ * NOT IN THIS CALL: a filtered form (the caller kept the statuses from when the block went in and passes the accepted
+ * operations), placed and partitioned trees.
+ * Memory as for imt_itree_view_insert_witness: the view's plan set grows to 2n events, the merged index of size + n_ins
+ * entries is borrowed from the context for the time of the call. */
+int imt_itree_view_mixed_witness(imt_itree_view *v, const void *vals /*[n][32]*/, const uint8_t *op /*[n]*/, size_t n,
+                                 const imt_insert_out *ins /*may be NULL*/, const imt_read_out *rd /*may be NULL*/,
+                                 uint64_t *n_inserted /*host, may be NULL*/, uint64_t *bad_op /*host, may be NULL*/,
+                                 unsigned flags);
 
 /* ---- e: the tree as ONE SUBTREE of a deeper tree (sharding by leaf-index range) -----------------
  * north_star's multi-GPU layout: GPU g owns leaf indices [g << depth, (g + 1) << depth) of a tree of depth

@@ -594,6 +594,57 @@ public:
                                                         w.low_leaf_proof.data(), IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR));
         return w;
     }
+    // The witnesses of a mixed block the tree applied at this view's size (imt_itree_view_mixed_witness): what
+    // IndexedTree::mixed_batch returns on a fresh tree fed the first size - 1 values.  The INSERTs of the list must be the
+    // values the tree holds from the view's size on.  A refused operation or an INSERT that is not the stored value:
+    // Error(IMT_ERR_VALUE), *bad_op (if given) = the first offending position.  Nothing of the tree changes.
+    IndexedTree::Mixed mixed_witness(const std::vector<Fr>& vals, const std::vector<uint8_t>& op, uint64_t* bad_op = nullptr) {
+        const size_t n = vals.size(), d = depth_;
+        IndexedTree::Mixed m;
+        if (!n) return m;
+        if (op.size() != n) throw Error(IMT_ERR_ARG, "mixed_witness: one op per value");
+        const uint64_t first = size();
+        IndexedTree::Insertions& r = m.inserted;
+        r.low_index.resize(n);
+        r.low_leaf.resize(n);
+        r.new_leaf.resize(n);
+        r.is_largest.resize(n);
+        r.old_root.resize(n);
+        r.interim_root.resize(n);
+        r.new_root.resize(n);
+        std::vector<Fr> ls(n * d), ns(n * d), rs(n * d);
+        std::vector<uint64_t> q_low(n);
+        std::vector<IndexedMerkleTreeLeaf> q_leaf(n);
+        std::vector<uint8_t> q_largest(n);
+        m.read_root.resize(n);
+        imt_insert_out out{r.low_index.data(), r.low_leaf.data(), r.is_largest.data(), r.old_root.data(),
+                           r.interim_root.data(), r.new_root.data(), r.new_leaf.data(), ls.data(), ns.data()};
+        imt_read_out rd{q_low.data(), q_leaf.data(), q_largest.data(), m.read_root.data(), rs.data()};
+        uint64_t k = 0;
+        c_->check(imt_itree_view_mixed_witness(v_, vals.data(), op.data(), n, &out, &rd, &k, bad_op,
+                                               IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR));
+        for (auto* v : {&r.low_leaf, &r.new_leaf}) v->resize(k);
+        for (auto* v : {&r.old_root, &r.interim_root, &r.new_root}) v->resize(k);
+        r.low_index.resize(k);
+        r.is_largest.resize(k);
+        r.low_leaf_proof.resize(k);
+        r.new_leaf_proof.resize(k);
+        r.new_index.resize(k);
+        for (size_t i = 0; i < k; i++) {
+            r.low_leaf_proof[i].assign(ls.begin() + i * d, ls.begin() + (i + 1) * d);
+            r.new_leaf_proof[i].assign(ns.begin() + i * d, ns.begin() + (i + 1) * d);
+            r.new_index[i] = first + i;
+        }
+        m.reads.resize(n - k);
+        m.read_root.resize(n - k);
+        for (size_t q = 0; q < n - k; q++) {
+            m.reads[q].low_index = q_low[q];
+            m.reads[q].low_leaf = q_leaf[q];
+            m.reads[q].is_largest = q_largest[q];
+            m.reads[q].low_leaf_proof.assign(rs.begin() + q * d, rs.begin() + (q + 1) * d);
+        }
+        return m;
+    }
     // hashes per level of the last rebuild ([depth + 1]); builds, if given: rebuilds so far
     std::vector<uint64_t> stats(uint64_t* builds = nullptr) {
         std::vector<uint64_t> h(depth_ + 1);

@@ -929,6 +929,43 @@ class IndexedTreeView:
         res["new_index"] = np.arange(size, size + n, dtype=np.uint64) + np.uint64(tree.index_base)
         return res
 
+    def mixed_witness(self, vals, ops, proofs=True, item_major=False):
+        """The witnesses of a mixed block the tree applied at this view's size (imt_itree_view_mixed_witness): the
+        (ins, rd) dicts IndexedTree.mixed_batch returns on a fresh tree fed the first size - 1 values.  The INSERTs of
+        the list must be the values the tree holds from the view's size on, in that order.  A refused operation, or an
+        INSERT that is not the stored value, raises ValueError with .bad_op = the first offending position.  Nothing of
+        the tree changes."""
+        v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
+        op = np.ascontiguousarray(ops, dtype=np.uint8)
+        n, d = v.shape[0], self.depth
+        if op.shape != (n,):
+            raise ValueError("mixed_witness: one op per value")
+        ins = dict(low_index=np.empty(n, np.uint64), low_leaf=np.empty((n, 3, 32), np.uint8),
+                   is_largest=np.empty(n, np.uint8), old_root=np.empty((n, 32), np.uint8),
+                   interim_root=np.empty((n, 32), np.uint8), new_root=np.empty((n, 32), np.uint8),
+                   new_leaf=np.empty((n, 3, 32), np.uint8))
+        rd = dict(low_index=np.empty(n, np.uint64), low_leaf=np.empty((n, 3, 32), np.uint8),
+                  is_largest=np.empty(n, np.uint8), root=np.empty((n, 32), np.uint8))
+        if proofs:
+            shape = (n, d, 32) if item_major else (d, n, 32)
+            ins["low_sib"], ins["new_sib"], rd["low_sib"] = (np.empty(shape, np.uint8) for _ in range(3))
+        out = _ffi.InsertOut(**{k: a.ctypes.data for k, a in ins.items()})
+        rout = _ffi.ReadOut(**{k: a.ctypes.data for k, a in rd.items()})
+        n_ins, bad = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = lib.imt_itree_view_mixed_witness(self.h, _p(v), _p(op), n, ctypes.byref(out), ctypes.byref(rout),
+                                              ctypes.byref(n_ins), ctypes.byref(bad), _ffi.SIB_ITEM_MAJOR if item_major else 0)
+        if rc == _ffi.ERR["VALUE"]:
+            e = ValueError(lib.imt_last_error(self.ctx.h).decode())
+            e.bad_op = bad.value
+            raise e
+        self.ctx._check(rc)
+        for res, m in ((ins, n_ins.value), (rd, n - n_ins.value)):
+            for k in list(res):
+                res[k] = res[k][:, :m] if k.endswith("_sib") and not item_major else res[k][:m]
+        size = self.size
+        ins["new_index"] = np.arange(size, size + n_ins.value, dtype=np.uint64)
+        return ins, rd
+
     def stats(self):
         """(hashes per level of the last rebuild [depth + 1], rebuilds so far)."""
         hashes, builds = np.zeros(self.depth + 1, dtype=np.uint64), ctypes.c_uint64()

@@ -1774,6 +1774,66 @@ static int copy_sib_rows(imt_itree* t, hipStream_t s, void* user, const void* de
     return IMT_OK;
 }
 
+// Where the kernels of a mixed batch write the outputs the caller asked for (stage_out, row r of `ins` the r-th INSERT, row
+// q of `rd` the q-th READ; sib_bytes: a sibling array of the caller's dimensions).  False: scratch could not be had.
+static bool mixed_stage_outputs(imt_ctx* c, bool dev, size_t& slot, const imt_insert_out* ins, const imt_read_out* rd, size_t n_ins,
+                                size_t n_rd, size_t sib_bytes, imt_insert_out& d, imt_read_out& r) {
+    if (ins && n_ins &&
+        (!stage_out(c, dev, slot, ins->low_index, n_ins * 8, d.low_index) ||
+         !stage_out(c, dev, slot, ins->is_largest, n_ins, d.is_largest) ||
+         !stage_out(c, dev, slot, ins->low_leaf, n_ins * 96, d.low_leaf) ||
+         !stage_out(c, dev, slot, ins->new_leaf, n_ins * 96, d.new_leaf) ||
+         !stage_out(c, dev, slot, ins->old_root, n_ins * 32, d.old_root) ||
+         !stage_out(c, dev, slot, ins->interim_root, n_ins * 32, d.interim_root) ||
+         !stage_out(c, dev, slot, ins->new_root, n_ins * 32, d.new_root) ||
+         !stage_out(c, dev, slot, ins->low_sib, sib_bytes, d.low_sib) || !stage_out(c, dev, slot, ins->new_sib, sib_bytes, d.new_sib)))
+        return false;
+    if (rd && n_rd &&
+        (!stage_out(c, dev, slot, rd->low_index, n_rd * 8, r.low_index) ||
+         !stage_out(c, dev, slot, rd->is_largest, n_rd, r.is_largest) ||
+         !stage_out(c, dev, slot, rd->low_leaf, n_rd * 96, r.low_leaf) || !stage_out(c, dev, slot, rd->root, n_rd * 32, r.root) ||
+         !stage_out(c, dev, slot, rd->low_sib, sib_bytes, r.low_sib)))
+        return false;
+    return true;
+}
+
+// The end of a mixed call on stream s, behind its hashing: the preimages into the caller's format, and for a host-pointer
+// caller every staged array copied to the caller's and the stream waited for.  stride: the level stride of the sibling
+// arrays.
+static int mixed_deliver_outputs(imt_itree* t, hipStream_t s, const imt_insert_out* ins, const imt_read_out* rd,
+                                 const imt_insert_out& d, const imt_read_out& r, size_t n_ins, size_t n_rd, size_t stride,
+                                 unsigned flags) {
+    imt_ctx* c = t->ctx;
+    int rc;
+    const bool dev = flags & IMT_DEVICE_PTRS, item_major = flags & IMT_SIB_ITEM_MAJOR;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    if (fmt != IMT_FMT_CANONICAL) {
+        if (d.low_leaf) launch::convert(s, (uint8_t*)d.low_leaf, (uint8_t*)d.low_leaf, n_ins * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
+        if (d.new_leaf) launch::convert(s, (uint8_t*)d.new_leaf, (uint8_t*)d.new_leaf, n_ins * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
+        if (r.low_leaf) launch::convert(s, (uint8_t*)r.low_leaf, (uint8_t*)r.low_leaf, n_rd * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
+    }
+    if (dev) return IMT_OK;
+    auto back = [&](void* user, const void* from, size_t bytes) -> int {
+        if (user && from) IMT_HIP(c, hipMemcpyAsync(user, from, bytes, hipMemcpyDeviceToHost, s));
+        return IMT_OK;
+    };
+    if (ins && n_ins &&
+        ((rc = back(ins->low_index, d.low_index, n_ins * 8)) || (rc = back(ins->is_largest, d.is_largest, n_ins)) ||
+         (rc = back(ins->low_leaf, d.low_leaf, n_ins * 96)) || (rc = back(ins->new_leaf, d.new_leaf, n_ins * 96)) ||
+         (rc = back(ins->old_root, d.old_root, n_ins * 32)) || (rc = back(ins->interim_root, d.interim_root, n_ins * 32)) ||
+         (rc = back(ins->new_root, d.new_root, n_ins * 32)) ||
+         (rc = copy_sib_rows(t, s, ins->low_sib, d.low_sib, n_ins, stride, item_major)) ||
+         (rc = copy_sib_rows(t, s, ins->new_sib, d.new_sib, n_ins, stride, item_major))))
+        return rc;
+    if (rd && n_rd &&
+        ((rc = back(rd->low_index, r.low_index, n_rd * 8)) || (rc = back(rd->is_largest, r.is_largest, n_rd)) ||
+         (rc = back(rd->low_leaf, r.low_leaf, n_rd * 96)) || (rc = back(rd->root, r.root, n_rd * 32)) ||
+         (rc = copy_sib_rows(t, s, rd->low_sib, r.low_sib, n_rd, stride, item_major))))
+        return rc;
+    IMT_HIP(c, hipStreamSynchronize(s));
+    return IMT_OK;
+}
+
 // What imt_itree_mixed_filtered asks of the body below on top of a mixed batch: the low leaves of the accepted READs
 // into its leaf_index once mixed_check has found them, and a refusal of what the filter accepted reported as a bug.
 struct MixedFiltered {
@@ -1837,22 +1897,7 @@ static int mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, const uin
     const size_t sib_bytes = (size_t)t->depth * stride * 32;      // the caller's dimensions, whichever kind the rows are
     imt_insert_out d = {};
     imt_read_out r = {};
-    if (ins && n_ins &&
-        (!stage_out(c, dev, slot, ins->low_index, n_ins * 8, d.low_index) ||
-         !stage_out(c, dev, slot, ins->is_largest, n_ins, d.is_largest) ||
-         !stage_out(c, dev, slot, ins->low_leaf, n_ins * 96, d.low_leaf) ||
-         !stage_out(c, dev, slot, ins->new_leaf, n_ins * 96, d.new_leaf) ||
-         !stage_out(c, dev, slot, ins->old_root, n_ins * 32, d.old_root) ||
-         !stage_out(c, dev, slot, ins->interim_root, n_ins * 32, d.interim_root) ||
-         !stage_out(c, dev, slot, ins->new_root, n_ins * 32, d.new_root) ||
-         !stage_out(c, dev, slot, ins->low_sib, sib_bytes, d.low_sib) || !stage_out(c, dev, slot, ins->new_sib, sib_bytes, d.new_sib)))
-        return IMT_ERR_HIP;
-    if (rd && n_rd &&
-        (!stage_out(c, dev, slot, rd->low_index, n_rd * 8, r.low_index) ||
-         !stage_out(c, dev, slot, rd->is_largest, n_rd, r.is_largest) ||
-         !stage_out(c, dev, slot, rd->low_leaf, n_rd * 96, r.low_leaf) || !stage_out(c, dev, slot, rd->root, n_rd * 32, r.root) ||
-         !stage_out(c, dev, slot, rd->low_sib, sib_bytes, r.low_sib)))
-        return IMT_ERR_HIP;
+    if (!mixed_stage_outputs(c, dev, slot, ins, rd, n_ins, n_rd, sib_bytes, d, r)) return IMT_ERR_HIP;
     IMT_HIP(c, prep::mixed_events(ps, P.ws, mx, t->d_val, t->d_sorted[t->sorted_cur], t->d_sorted[t->sorted_cur ^ 1], (uint32_t)M,
                                   (uint32_t)n, (uint32_t)n_ins, t->index_base, P.d_pre, P.d_tab[0][0], P.d_tab[0][1],
                                   P.d_tab[0][2], P.d_tab[0][3], d.low_index, d.is_largest, (uint8_t*)d.low_leaf,
@@ -1885,32 +1930,8 @@ static int mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, const uin
     }
 
     // ---- outputs ----
-    if (fmt != IMT_FMT_CANONICAL) {
-        if (d.low_leaf) launch::convert(s, (uint8_t*)d.low_leaf, (uint8_t*)d.low_leaf, n_ins * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
-        if (d.new_leaf) launch::convert(s, (uint8_t*)d.new_leaf, (uint8_t*)d.new_leaf, n_ins * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
-        if (r.low_leaf) launch::convert(s, (uint8_t*)r.low_leaf, (uint8_t*)r.low_leaf, n_rd * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
-    }
     if (n_inserted) *n_inserted = n_ins;
-    if (dev) return IMT_OK;
-    auto back = [&](void* user, const void* from, size_t bytes) -> int {
-        if (user && from) IMT_HIP(c, hipMemcpyAsync(user, from, bytes, hipMemcpyDeviceToHost, s));
-        return IMT_OK;
-    };
-    if (ins && n_ins &&
-        ((rc = back(ins->low_index, d.low_index, n_ins * 8)) || (rc = back(ins->is_largest, d.is_largest, n_ins)) ||
-         (rc = back(ins->low_leaf, d.low_leaf, n_ins * 96)) || (rc = back(ins->new_leaf, d.new_leaf, n_ins * 96)) ||
-         (rc = back(ins->old_root, d.old_root, n_ins * 32)) || (rc = back(ins->interim_root, d.interim_root, n_ins * 32)) ||
-         (rc = back(ins->new_root, d.new_root, n_ins * 32)) ||
-         (rc = copy_sib_rows(t, s, ins->low_sib, d.low_sib, n_ins, stride, item_major)) ||
-         (rc = copy_sib_rows(t, s, ins->new_sib, d.new_sib, n_ins, stride, item_major))))
-        return rc;
-    if (rd && n_rd &&
-        ((rc = back(rd->low_index, r.low_index, n_rd * 8)) || (rc = back(rd->is_largest, r.is_largest, n_rd)) ||
-         (rc = back(rd->low_leaf, r.low_leaf, n_rd * 96)) || (rc = back(rd->root, r.root, n_rd * 32)) ||
-         (rc = copy_sib_rows(t, s, rd->low_sib, r.low_sib, n_rd, stride, item_major))))
-        return rc;
-    IMT_HIP(c, hipStreamSynchronize(s));
-    return IMT_OK;
+    return mixed_deliver_outputs(t, s, ins, rd, d, r, n_ins, n_rd, stride, flags);
 }
 
 extern "C" int imt_itree_mixed_batch(imt_itree* t, const void* vals, const uint8_t* op, size_t n, const imt_insert_out* ins,
@@ -2674,6 +2695,161 @@ extern "C" int imt_itree_view_insert_witness(imt_itree_view* v, size_t n, const 
                        n, (unsigned long long)v->size);
     if ((rc = check_out_ptrs(c, flags & IMT_DEVICE_PTRS, out))) return rc;
     return view_replay(v, n, out, flags & ~(unsigned)IMT_HOST_PREP);
+}
+
+// The witnesses of a mixed block the tree has already applied at the view's size, behind view_enter and the
+// argument checks: mixed_core's sequence with view_replay's differences.  Everything runs on the context's stream behind
+// the tree, in the view's own plan set; the INSERT values are compared with the rows they went to instead of written
+// there, the neighbours are searched in the view's index, the base siblings below L0 are read as of the view's size, and
+// there is no write-back, no stored root, no rotation of plan sets and no commit.  A view at the tree's current size has
+// no side table: the stored tree is the tree as of that size, the list can hold no INSERT, and the live LEVEL launch reads
+// the siblings where they are -- still without the write-back.
+static int view_replay_mixed(imt_itree_view* v, const void* vals, const uint8_t* op, size_t n, const imt_insert_out* ins,
+                             const imt_read_out* rd, uint64_t* n_inserted, uint64_t* bad_op, unsigned flags) {
+    imt_itree* t = v->t;
+    imt_ctx* c = t->ctx;
+    const bool dev = flags & IMT_DEVICE_PTRS, item_major = flags & IMT_SIB_ITEM_MAJOR;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    const uint64_t S = v->size;
+    int rc;
+    if ((rc = view_behind_tree(t))) return rc;
+    hipStream_t s = c->stream;
+    PlanSet& P = v->plan;
+    if (P.cap_events < 2 * n || P.cap_levels < t->depth) IMT_HIP(c, hipStreamSynchronize(s));   // an earlier replay may still use it
+    if ((rc = plan_reserve(c, P, 2 * n, t->depth, t->cap))) return rc;      // 2n events hold any mix
+
+    // ---- ranks, the range, then the checks: nothing of the caller's is written before the list is accepted ----
+    size_t slot = 4;
+    const uint8_t* d_vals = nullptr;
+    uint8_t* up = dev ? nullptr : (uint8_t*)c->dev_scratch(slot++, n * 32);
+    if ((rc = stage_canonical(c, s, vals, n, flags, up, P.d_canon, P.ws.err, &d_vals))) return rc;
+    const uint8_t* d_op = op;
+    if (!dev) {
+        uint8_t* o = (uint8_t*)c->dev_scratch(slot++, n);
+        if (!o) return IMT_ERR_HIP;
+        IMT_HIP(c, hipMemcpyAsync(o, op, n, hipMemcpyHostToDevice, s));
+        d_op = o;
+    }
+    const prep::MixedWs mx{P.fw.flag, P.fw.rank, P.fw.idx, P.fw.aux, P.d_slot};
+    IMT_HIP(c, prep::mixed_ranks(s, P.ws, mx, d_op, (uint32_t)n));
+    IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, mx.word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, s));
+    IMT_HIP(c, hipStreamSynchronize(s));
+    if (*t->h_err_pin & prep::ERR_OP) return c->fail(IMT_ERR_ARG, "an op byte is neither IMT_OP_INSERT nor IMT_OP_READ");
+    const size_t n_ins = *t->h_cnt_pin, n_rd = n - n_ins;
+    if (n_ins > t->size - S)
+        return c->fail(IMT_ERR_RANGE, "the tree holds %llu leaves: no %zu insertions follow the view's %llu", (unsigned long long)t->size,
+                       n_ins, (unsigned long long)S);
+    const uint32_t* index = v->current ? t->d_sorted[t->sorted_cur] : v->d_sorted;
+    P.ws.part_mod = t->part_mod;
+    P.ws.part_res = t->part_res;
+    IMT_HIP(c, prep::mixed_check_view(s, P.ws, mx, d_vals, t->d_val, index, (uint32_t)S, (uint32_t)n, (uint32_t)n_ins));
+    IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, mx.word + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, s));
+    IMT_HIP(c, hipStreamSynchronize(s));
+    const int perr = *t->h_err_pin;
+    if (perr & prep::ERR_NONCANONICAL) return c->fail(IMT_ERR_NONCANONICAL, "a value is not reduced (>= p)");
+    if (perr & (prep::ERR_ZERO | prep::ERR_FOREIGN | prep::ERR_DUPLICATE | prep::ERR_MISMATCH)) {
+        const uint32_t bad = *t->h_cnt_pin;
+        if (bad_op && bad < n) *bad_op = bad;
+        // which of the two it is at that position: an INSERT that matches its row has nothing else wrong with it
+        uint32_t is_ins = 0, rank = 0;
+        uint8_t given[32], held[32];
+        if (bad >= n) return c->fail(IMT_ERR_INTERNAL, "the checks refuse the list (bits %#x) and name no position", perr);
+        IMT_HIP(c, hipMemcpyAsync(&is_ins, mx.flag + bad, 4, hipMemcpyDeviceToHost, s));
+        IMT_HIP(c, hipMemcpyAsync(&rank, mx.rank + bad, 4, hipMemcpyDeviceToHost, s));
+        IMT_HIP(c, hipStreamSynchronize(s));
+        if (is_ins) {
+            IMT_HIP(c, hipMemcpyAsync(given, d_vals + (size_t)bad * 32, 32, hipMemcpyDeviceToHost, s));
+            IMT_HIP(c, hipMemcpyAsync(held, t->d_val + (size_t)(S + rank) * 32, 32, hipMemcpyDeviceToHost, s));
+            IMT_HIP(c, hipStreamSynchronize(s));
+            if (std::memcmp(given, held, 32) != 0)
+                return c->fail(IMT_ERR_VALUE, "operation %u: INSERT %u of the list is not the value stored at leaf %llu", bad, rank,
+                               (unsigned long long)(S + rank));
+        }
+        return c->fail(IMT_ERR_VALUE, "operation %u: refused as of its place in the list (0, stored at the view's size, or inserted "
+                       "earlier in the list)", bad);
+    }
+
+    // ---- accepted: events, tables, hash-free outputs ----
+    const size_t E = n + n_ins;
+    const unsigned L0 = std::min(ceil_log2(S + n_ins), t->depth);       // of the tree the block was applied to
+    struct Trim {           // the merged index is computed and dropped: borrowed, like a build's scratch
+        imt_ctx* c;
+        ~Trim() { c->trim_scratch(3, (size_t)64 << 20); }
+    } trim{c};
+    uint32_t* merged = (uint32_t*)c->dev_scratch(3, (size_t)(S + n_ins) * 4);
+    if (!merged) return IMT_ERR_HIP;
+    imt_insert_out d = {};
+    imt_read_out r = {};
+    if (!mixed_stage_outputs(c, dev, slot, ins, rd, n_ins, n_rd, (size_t)t->depth * n * 32, d, r)) return IMT_ERR_HIP;
+    IMT_HIP(c, prep::mixed_events(s, P.ws, mx, t->d_val, index, merged, (uint32_t)S, (uint32_t)n, (uint32_t)n_ins, t->index_base,
+                                  P.d_pre, P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][2], P.d_tab[0][3], d.low_index, d.is_largest,
+                                  (uint8_t*)d.low_leaf, (uint8_t*)d.new_leaf,
+                                  prep::ReadOut{r.low_index, r.is_largest, (uint8_t*)r.low_leaf}));
+
+    // ---- hashing: mixed_hashes' stages, the levels below L0 against the view and none of them written back ----
+    const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->depth} : launch::SibLayout{n, 1};
+    const launch::MixedRoute route{mx.erow, (uint8_t*)r.low_sib};
+    sweep_leaf_hashes(t, P, s, E);
+    int pf = c->prof_begin(IMT_PROF_INDEX, s);
+    index_phase(P, s, E, L0, nullptr);
+    c->prof_end(pf, s);
+    for (unsigned l = 0; l < L0; l++) {
+        const PlanSet::Level row = P.level(l);
+        pf = c->prof_begin(IMT_PROF_LEVEL, s);
+        if (v->current)
+            launch::sweep_level_mixed(s, route, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], row.from, row.sibsrc, row.nodeb, row.timen,
+                                      t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, (uint32_t)E, (uint8_t*)d.low_sib,
+                                      (uint8_t*)d.new_sib, lay, l, fmt, c->coop_max_events);
+        else
+            launch::sweep_view_level_mixed(s, v->side(), route, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], row.from, row.sibsrc,
+                                           row.nodeb, row.timen, t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, (uint32_t)E,
+                                           (uint8_t*)d.low_sib, (uint8_t*)d.new_sib, lay, l, fmt, c->coop_max_events);
+        c->prof_end(pf, s);
+    }
+    for (unsigned l = L0; l < t->depth; l++) {
+        pf = c->prof_begin(IMT_PROF_TOP, s);
+        launch::sweep_upper_mixed(s, route, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], c->d_zero + (size_t)l * 32, (uint32_t)E, nullptr,
+                                  nullptr, (uint8_t*)d.low_sib, (uint8_t*)d.new_sib, lay, l, fmt, c->coop_max_events);
+        c->prof_end(pf, s);
+    }
+    // old_root[0] is the view's root (an INSERT means the view is not at the tree's size: the chain exists); the other
+    // roots, a READ's before the first INSERT included, are the events' top values
+    if (d.old_root) launch::convert(s, v->d_chain + (size_t)t->depth * 32, (uint8_t*)d.old_root, 1, IMT_FMT_DEVICE, fmt, c->d_err);
+    launch::emit_roots_mixed(s, route, P.d_val[t->depth & 1], (uint32_t)E, (uint32_t)n_ins, (uint8_t*)d.old_root,
+                             (uint8_t*)d.interim_root, (uint8_t*)d.new_root, (uint8_t*)r.root, fmt, nullptr);
+    if (n_inserted) *n_inserted = n_ins;
+    return mixed_deliver_outputs(t, s, ins, rd, d, r, n_ins, n_rd, n, flags);
+}
+
+extern "C" int imt_itree_view_mixed_witness(imt_itree_view* v, const void* vals, const uint8_t* op, size_t n,
+                                            const imt_insert_out* ins, const imt_read_out* rd, uint64_t* n_inserted,
+                                            uint64_t* bad_op, unsigned flags) {
+    if (!view_alive(v)) return IMT_ERR_ARG;
+    imt_itree* t = v->t;
+    imt_ctx* c = t->ctx;
+    if (n && (!vals || !op)) return c->fail(IMT_ERR_ARG, "null vals / op");
+    if (flags & (IMT_PIPELINE | IMT_HOST_PREP | IMT_INPUTS_READY))
+        return c->fail(IMT_ERR_ARG, "a mixed replay takes neither IMT_PIPELINE, IMT_HOST_PREP nor IMT_INPUTS_READY");
+    if (t->index_base || t->global_depth != t->depth || t->part_mod > 1)
+        return c->fail(IMT_ERR_ARG, "mixed replays are not available on a placed or partitioned tree");
+    if (n > ((size_t)1 << 30)) return c->fail(IMT_ERR_RANGE, "list too large");
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    int rc;
+    if ((rc = check_fe_ptrs(c, dev, {vals})) || (rc = check_out_ptrs(c, dev, ins))) return rc;
+    if (rd && (rc = check_fe_ptrs(c, dev, {rd->low_leaf, rd->root, rd->low_sib}))) return rc;
+    if (dev && ((ins && ((uintptr_t)ins->low_index & 7u)) || (rd && ((uintptr_t)rd->low_index & 7u))))
+        return c->fail(IMT_ERR_ARG, "device low_index array is not 8-byte aligned");
+    if (!dev)
+        for (size_t p = 0; p < n; p++)
+            if (op[p] > IMT_OP_READ) return c->fail(IMT_ERR_ARG, "op[%zu] = %u is neither IMT_OP_INSERT nor IMT_OP_READ", p, op[p]);
+    if ((rc = view_enter(v, flags))) return rc;
+    if (n == 0) {
+        if (n_inserted) *n_inserted = 0;
+        return IMT_OK;
+    }
+    return view_replay_mixed(v, vals, op, n, ins, rd, n_inserted, bad_op, flags);
 }
 
 extern "C" int imt_itree_view_stats(imt_itree_view* v, uint64_t* hashes, uint64_t* builds) {

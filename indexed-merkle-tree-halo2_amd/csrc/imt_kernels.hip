@@ -1250,6 +1250,36 @@ __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_sweep_view_coop(launch
 #endif
 }
 
+// -----------------------------------------------------------------------------------------------
+// Witnesses of a mixed block already applied (imt_itree_view_mixed_witness): k_sweep_view's launch with the proof row of
+// an event looked up as k_sweep_mixed looks it up.  A READ's event meets the same siblings an INSERT's low-leaf event
+// would -- BATCH, SIDE, STORED or EMPTY (imt_replay.hpp) -- and they are its witness as of its place in the block.  Below
+// l0 only: the levels from l0 up are k_sweep_mixed's launches with no node stores.  Nothing goes back to the stored tree.
+// -----------------------------------------------------------------------------------------------
+__global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_sweep_view_mixed(launch::SweepViewMixedArgs v) {
+    const launch::SweepArgs& a = v.sweep;
+    const size_t t = gtid();
+    if (t >= a.count) return;
+    const uint32_t x = a.begin + (uint32_t)t;        // slot of level l + 1
+    const uint32_t k = a.from[x] & ~sweep::LAST_BIT, n = a.node_below[x], e = a.time_next[x];
+    const uint8_t* sp = ViewSibling{v.side}(a, a.sibsrc[x], (uint64_t)(n ^ 1u));
+    Fe A, B, o, cur, sv;
+    load_packed(cur, a.val_in + (size_t)k * 32);
+    load_packed(sv, sp);
+    order_pair(A, B, n & 1u, cur, sv);
+    MixedRows{v.erow, v.read_sib}(a, e, sv);
+    hash23_stashed(g_pc, o, A, B, false, nullptr, 0);        // a 2-input hash never reads the stash
+    store_packed(a.val_out + (size_t)x * 32, o);
+}
+
+// a quad of lanes per event
+__global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_sweep_view_mixed_coop(launch::SweepViewMixedArgs v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ uint32_t tab[coop::TAB_DWORDS];
+    sweep_body_quad<true>(v.sweep, ViewSibling{v.side}, tab, MixedRows{v.erow, v.read_sib});
+#endif
+}
+
 // ---- subtree placement (imt_itree_lift_batch) ---------------------------------------------------
 // A tree placed as subtree g of a deeper tree produces subtree-level roots; the enclosing tree's root
 // after the same event is `levels` more hash2 up a path whose siblings are the same for the whole batch.
@@ -1806,6 +1836,18 @@ void sweep_view_level(hipStream_t s, const view::Side& side, const uint8_t* val_
         hipLaunchKernelGGL(k_sweep_view_coop, dim3(nblk((size_t)k_count * 4)), dim3(BLOCK), 0, s, v);
     else
         hipLaunchKernelGGL(k_sweep_view, dim3(nblk(k_count)), dim3(BLOCK), 0, s, v);
+}
+void sweep_view_level_mixed(hipStream_t s, const view::Side& side, const MixedRoute& r, const uint8_t* val_in, uint8_t* val_out,
+                            const uint32_t* from, const int32_t* sibsrc, const uint32_t* node_below, const uint32_t* time_next,
+                            const uint8_t* tree_l, uint64_t len_l, const uint8_t* zero_l, uint32_t k_count, uint8_t* low_sib,
+                            uint8_t* new_sib, SibLayout lay, unsigned level, unsigned fmt_out, uint32_t coop_max) {
+    if (!k_count) return;
+    const SweepViewMixedArgs v{level_args(val_in, val_out, from, sibsrc, node_below, time_next, tree_l, len_l, zero_l, 0, k_count,
+                                          low_sib, new_sib, lay, level, fmt_out), side, r.erow, r.read_sib};
+    if (k_count <= coop_max)       // launch_sweep's choice
+        hipLaunchKernelGGL(k_sweep_view_mixed_coop, dim3(nblk((size_t)k_count * 4)), dim3(BLOCK), 0, s, v);
+    else
+        hipLaunchKernelGGL(k_sweep_view_mixed, dim3(nblk(k_count)), dim3(BLOCK), 0, s, v);
 }
 void emit_roots(hipStream_t s, const uint8_t* val, uint32_t e_begin, uint32_t e_count, uint32_t total, uint8_t* old_root,
                 uint8_t* interim_root, uint8_t* new_root, unsigned fmt_out, uint8_t* roots_dev, uint8_t* node_store) {

@@ -273,6 +273,22 @@ void sweep_upper_mixed(hipStream_t s, const MixedRoute& r, const uint8_t* val_in
 void emit_roots_mixed(hipStream_t s, const MixedRoute& r, const uint8_t* val, uint32_t total, uint32_t n_ins, uint8_t* old_root,
                       uint8_t* interim_root, uint8_t* new_root, uint8_t* read_root, unsigned fmt_out, uint8_t* node_store);
 
+// ---- witnesses of a mixed block already applied (imt_itree_view_mixed_witness): both of the above at once ----
+// argument block of k_sweep_view_mixed: k_sweep_view's (a LEVEL launch below l0 and the view the base siblings are read as
+// of) with k_sweep_mixed's route.  The levels from l0 up are sweep_upper_mixed with both node stores NULL, the roots
+// emit_roots_mixed with node_store NULL: nothing goes back to the stored tree.
+struct SweepViewMixedArgs {
+    SweepArgs sweep;
+    view::Side side;
+    const uint32_t* erow;
+    uint8_t* read_sib;
+};
+// hashes slots [0, k_count) of level `level` + 1; coop_max as for the sweep
+void sweep_view_level_mixed(hipStream_t s, const view::Side& side, const MixedRoute& r, const uint8_t* val_in, uint8_t* val_out,
+                            const uint32_t* from, const int32_t* sibsrc, const uint32_t* node_below, const uint32_t* time_next,
+                            const uint8_t* tree_l, uint64_t len_l, const uint8_t* zero_l, uint32_t k_count, uint8_t* low_sib,
+                            uint8_t* new_sib, SibLayout lay, unsigned level, unsigned fmt_out, uint32_t coop_max);
+
 // ---- subtree placement: lift subtree-level witnesses to the depth of the enclosing tree ----
 // top[j] (device format, j < levels) = sibling of this subtree's ancestor at height sub_depth + j;
 // bit j of pos_bits = that ancestor is a RIGHT child.  Roots are lifted in place (format fmt):

@@ -206,6 +206,24 @@ k_mixed_scatter(const uint8_t* __restrict__ vals, const uint32_t* __restrict__ f
     iota[r] = M + r;
     ipos[r] = p;
 }
+// k_mixed_scatter for a list replayed against the tree (imt_itree_view_mixed_witness): no row of d_val is written, not
+// even with the bytes it holds -- an INSERT's value is compared with the row it went to instead (replay_op_class)
+__global__ void __launch_bounds__(BLOCK)
+k_mixed_match(const uint8_t* __restrict__ vals, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ rank,
+              const uint8_t* __restrict__ d_val, uint32_t S, uint32_t n, uint32_t part_mod, uint32_t part_res,
+              uint32_t* __restrict__ iota, uint32_t* __restrict__ ipos, int* err, uint32_t* bad) {
+    const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= n) return;
+    const uint8_t* v = vals + (uint64_t)p * 32;
+    if (geq_p(v)) atomicOr(err, ERR_NONCANONICAL);
+    const bool ins = flag[p];
+    const uint32_t r = rank[p];
+    const int e = replay_op_class(v, ins, r, d_val, S, part_mod, part_res);
+    if (e) { atomicOr(err, e); atomicMin(bad, p); }
+    if (!ins) return;
+    iota[r] = S + r;
+    ipos[r] = p;
+}
 // k_gap for the INSERTs of a mixed batch: the duplicate is named
 __global__ void __launch_bounds__(BLOCK)
 k_mixed_gap(const uint8_t* __restrict__ d_val, const uint32_t* __restrict__ sorted_old, uint32_t M,
@@ -745,14 +763,33 @@ hipError_t mixed_ranks(hipStream_t s, Workspace& ws, const MixedWs& mx, const ui
     return hipGetLastError();
 }
 
+// the checks behind the first kernel of mixed_check / mixed_check_view: the INSERT values are rows [M, M + n_ins) of d_val
+static hipError_t mixed_neighbours(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, const uint8_t* d_val,
+                                   const uint32_t* sorted_old, uint32_t M, uint32_t n, uint32_t n_ins);
+
 hipError_t mixed_check(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, uint8_t* d_val,
                        const uint32_t* sorted_old, uint32_t M, uint32_t n, uint32_t n_ins) {
-    const int levels = levels_for(n_ins);
-    hipError_t e;
     if (n == 0 || n > ws.cap_n || n_ins > n || temp_bytes_needed(n_ins, (size_t)M) > ws.tmp_bytes) return hipErrorInvalidValue;
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_mixed_scatter, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, mx.flag, mx.rank, d_val, M, n, ws.part_mod,
                        ws.part_res, ws.iota, mx.ipos, ws.err, mx.word + 1);
+    return mixed_neighbours(s, ws, mx, vals, d_val, sorted_old, M, n, n_ins);
+}
+
+hipError_t mixed_check_view(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, const uint8_t* d_val,
+                            const uint32_t* sorted_view, uint32_t S, uint32_t n, uint32_t n_ins) {
+    static_assert(OP_MISMATCH == ERR_MISMATCH, "one set of error bits");
+    if (n == 0 || n > ws.cap_n || n_ins > n || temp_bytes_needed(n_ins, (size_t)S) > ws.tmp_bytes) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_mixed_match, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, mx.flag, mx.rank, d_val, S, n, ws.part_mod,
+                       ws.part_res, ws.iota, mx.ipos, ws.err, mx.word + 1);
+    return mixed_neighbours(s, ws, mx, vals, d_val, sorted_view, S, n, n_ins);
+}
+
+static hipError_t mixed_neighbours(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, const uint8_t* d_val,
+                                   const uint32_t* sorted_old, uint32_t M, uint32_t n, uint32_t n_ins) {
+    const int levels = levels_for(n_ins);
+    hipError_t e;
     if (n_ins) {
         size_t tb = ws.tmp_bytes;
         if ((e = rocprim::merge_sort(ws.tmp, tb, ws.iota, ws.bsorted, (size_t)n_ins, ValRankLess{d_val}, s)) != hipSuccess)

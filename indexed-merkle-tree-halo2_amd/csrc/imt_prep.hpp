@@ -101,6 +101,13 @@ hipError_t mixed_ranks(hipStream_t s, Workspace& ws, const MixedWs& mx, const ui
 // every operation (ws.low / ws.succ: INSERTs by rank, then READs by rank).  Writes nothing else of the tree, no output.
 hipError_t mixed_check(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, uint8_t* d_val,
                        const uint32_t* sorted_old, uint32_t M, uint32_t n, uint32_t n_ins);
+// 2'. the same for a list replayed against a view (imt_itree_view_mixed_witness): sorted_view[S] is the view's index, and
+// the INSERT of rank r must be the value row S + r of d_val holds (S + n_ins <= the tree's size: the caller has checked).
+// Writes NO row of d_val: the value is compared instead, ERR_MISMATCH into ws.err and the position into mx.word[1] like
+// every other offender (replay_op_class, imt_prep_logic.hpp); the remaining checks run over the stored rows.
+constexpr int ERR_MISMATCH = 1024;
+hipError_t mixed_check_view(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, const uint8_t* d_val,
+                            const uint32_t* sorted_view, uint32_t S, uint32_t n, uint32_t n_ins);
 // 3. behind it, the batch accepted: what run() leaves -- preimages pre[E][96] by event, the level-0 tables [E],
 // sorted_new[M + n_ins] (untouched if n_ins == 0), the hash-free outputs of both kinds -- and mx.erow.
 hipError_t mixed_events(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* d_val, const uint32_t* sorted_old,

@@ -141,6 +141,21 @@ IMT_PL_HD ReadAnswer read_neighbours(const uint8_t* x, uint32_t R, const uint8_t
     return a;
 }
 
+// ---- a mixed list replayed against the rows the tree stores (imt_itree_view_mixed_witness) ---------------------------
+// The list is the block as it went in at size S: its INSERT of rank r must be the value the tree holds at leaf S + r.
+// What is wrong with the operation at one position on its own: the op_value_class bits of its value and, for an INSERT,
+// OP_MISMATCH unless its value is row S + r of val.  Everything else that can refuse an operation (a READ of a stored value
+// or of one an earlier INSERT put in) is judged by read_neighbours / insert_is_duplicate over the STORED rows [S, S + n_ins),
+// which are the list's own INSERTs at every position before the first mismatch -- so the smallest offending position
+// over all of these bits is the smallest position at which the walk refuses or the list differs from the tree.
+constexpr int OP_MISMATCH = 1024;
+IMT_PL_HD int replay_op_class(const uint8_t* x, bool insert, uint32_t r, const uint8_t* val, uint32_t S, uint32_t part_mod,
+                              uint32_t part_res) {
+    int e = op_value_class(x, part_mod, part_res);
+    if (insert && !eq256(val + (uint64_t)(S + r) * 32, x)) e |= OP_MISMATCH;
+    return e;
+}
+
 // ---- snapshot check (imt_itree_load): the leaves, visited in value order, must be ONE linked list ----------------
 // pre = [n][3][32] canonical {val, next_val, next_idx}; idx[r] = leaf index of the r-th smallest val (candidate order:
 // sorted by the top 64 bits at least).  Rank r checks leaf idx[r] against its successor idx[r + 1]: strictly larger
