@@ -275,6 +275,8 @@ extern "C" {
     pub fn imt_itree_get_proof_batch(t: *mut imt_itree, index: *const u64, n: usize, sib: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_get_leaves(t: *mut imt_itree, index: *const u64, n: usize, preimage: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_load(t: *mut imt_itree, preimages: *const c_void, n: u64, flags: c_uint) -> c_int;
+    pub fn imt_itree_load_values(t: *mut imt_itree, vals: *const c_void, n: u64, bad_pos: *mut u64, flags: c_uint) -> c_int;
+    pub fn imt_itree_get_values(t: *mut imt_itree, first: u64, n: usize, vals: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_find_low_batch(t: *mut imt_itree, vals: *const c_void, n: usize, low_index: *mut u64, flags: c_uint) -> c_int;
     pub fn imt_itree_insert_filtered(t: *mut imt_itree, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, n_inserted: *mut u64, out: *const imt_insert_out, flags: c_uint) -> c_int;
     pub fn imt_itree_apply_batch(t: *mut imt_itree, vals: *const c_void, n: usize, root_out: *mut c_void, flags: c_uint) -> c_int;
@@ -287,6 +289,7 @@ extern "C" {
     pub fn imt_itree_view_root(v: *mut imt_itree_view, root: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_view_lookup_batch(v: *mut imt_itree_view, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, flags: c_uint) -> c_int;
     pub fn imt_itree_view_get_leaves(v: *mut imt_itree_view, index: *const u64, n: usize, preimage: *mut c_void, flags: c_uint) -> c_int;
+    pub fn imt_itree_view_get_values(v: *mut imt_itree_view, first: u64, n: usize, vals: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_view_get_proof_batch(v: *mut imt_itree_view, index: *const u64, n: usize, sib: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_view_non_membership_witness(v: *mut imt_itree_view, vals: *const c_void, n: usize, low_index: *mut u64, low_leaf: *mut c_void, is_largest: *mut u8, low_sib: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_view_stats(v: *mut imt_itree_view, hashes: *mut u64, builds: *mut u64) -> c_int;

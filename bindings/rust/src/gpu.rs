@@ -292,6 +292,26 @@ impl IndexedTree {
         }
         check(&g, unsafe { imt_itree_load(self.handle, pre.as_ptr() as *const c_void, leaves.len() as u64, IMT_FMT_CANONICAL) })
     }
+    /// The value log: the values of leaves `first .. first + n` in global leaf indices (`imt_itree_get_values`); every
+    /// inserted value of a tree that is not placed is `values(1, size - 1)`.
+    pub fn values<F: ScalarField>(&self, first: u64, n: usize) -> Result<Vec<F>, ImtError> {
+        let g = context().lock().unwrap();
+        let mut v = vec![0u8; n * 32];
+        check(&g, unsafe { imt_itree_get_values(self.handle, first, n, v.as_mut_ptr() as *mut c_void, IMT_FMT_CANONICAL) })?;
+        Ok(from_bytes(&v))
+    }
+    /// Cold start: replace the contents with the tree a fresh one holds after inserting `vals` in order
+    /// (`imt_itree_load_values`).  A log one-by-one insertion would not get through is refused with the tree as it was;
+    /// the second field of the error is the position it would stop at.
+    pub fn load_values<F: ScalarField>(&mut self, vals: &[F]) -> Result<(), (ImtError, Option<u64>)> {
+        let g = context().lock().unwrap();
+        let v = to_bytes(vals);
+        let mut bad = u64::MAX;
+        check(&g, unsafe {
+            imt_itree_load_values(self.handle, v.as_ptr() as *const c_void, vals.len() as u64, &mut bad, IMT_FMT_CANONICAL)
+        })
+        .map_err(|e| (e, if bad == u64::MAX { None } else { Some(bad) }))
+    }
 }
 
 /// The tree as it was when it held `size` leaves, read-only, while the [`IndexedTree`] stays where it is and keeps
@@ -323,6 +343,13 @@ impl IndexedTreeView {
         let mut r = [0u8; 32];
         check(&g, unsafe { imt_itree_view_root(self.handle, r.as_mut_ptr() as *mut c_void, IMT_FMT_CANONICAL) })?;
         Ok(F::from_bytes_le(&r))
+    }
+    /// [`IndexedTree::values`] below the view's size (`imt_itree_view_get_values`); never rebuilds the view.
+    pub fn values<F: ScalarField>(&self, first: u64, n: usize) -> Result<Vec<F>, ImtError> {
+        let g = context().lock().unwrap();
+        let mut v = vec![0u8; n * 32];
+        check(&g, unsafe { imt_itree_view_get_values(self.handle, first, n, v.as_mut_ptr() as *mut c_void, IMT_FMT_CANONICAL) })?;
+        Ok(from_bytes(&v))
     }
     /// (hashes per level of the last rebuild, rebuilds so far)
     pub fn stats(&self) -> Result<(Vec<u64>, u64), ImtError> {

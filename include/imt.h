@@ -437,6 +437,24 @@ int imt_itree_get_leaves(imt_itree *t, const uint64_t *index /*[n] or NULL*/, si
  * rebuilds every stored level (n leaf hashes + one pass of k_tree_level per level: about 2 hashes per leaf, the "final
  * root only" build of SURVEY.md 8d).  Host memory needed: none beyond the caller's own buffer. */
 int imt_itree_load(imt_itree *t, const void *preimages /*[n][3][32]*/, uint64_t n, unsigned flags);
+/* The same from the value log alone: a tree is a function of its values in leaf order.  imt_itree_load_values replaces
+ * the tree's contents by what a fresh tree of the same depth, capacity, placement and value partition holds after
+ * imt_itree_apply_batch(vals, n) -- every stored node, the index, the size n + 1 and every answer afterwards are the
+ * same bytes.  vals: the inserted values in insertion order (leaves 1 .. n; the sentinel is not passed), host memory or
+ * device memory with IMT_DEVICE_PTRS, any IMT_FMT_*.  32 bytes per leaf instead of imt_itree_load's 96, no links to
+ * check, and the leaf hashes read each successor through the sorted order: the preimages are never written anywhere.
+ * Refused like imt_itree_load where the values do not matter (IMT_ERR_FULL if n + 1 exceeds the capacity, IMT_ERR_ARG
+ * for NULL / n == 0 / an unknown format / an open slice), and with imt_itree_apply_batch's code where they do:
+ * IMT_ERR_NONCANONICAL, else IMT_ERR_VALUE for a 0, a repeated value or a foreign residue.  On those two *bad_pos (may be
+ * NULL) is the smallest position of vals that is >= p, 0, foreign or equal to a value at a smaller position: where
+ * inserting one by one would stop.  A refused call has written nothing of the tree.  Synchronous; afterwards as after
+ * imt_itree_load (no lagged root, views rebuild on their next query). */
+int imt_itree_load_values(imt_itree *t, const void *vals /*[n][32]*/, uint64_t n, uint64_t *bad_pos /*or NULL*/,
+                          unsigned flags);
+/* the values of leaves [first, first + n), global leaf indices as imt_itree_get_leaves counts them (leaf 0 gives 0): a
+ * copy of the device index, any format, host or device memory.  IMT_ERR_RANGE unless all of them are below the size.
+ * imt_itree_load_values(imt_itree_get_values(first leaf + 1, size - 1)) reproduces the tree. */
+int imt_itree_get_values(imt_itree *t, uint64_t first, size_t n, void *vals /*[n][32]*/, unsigned flags);
 /* low leaf (greatest val < v) for n candidate values: a binary search per value in the device-resident index
  * (k_find_low; with IMT_DEVICE_PTRS `vals` and `low_index` are device pointers); IMT_ERR_VALUE if some v is 0, present,
  * or (with a value partition set) of another subtree's residue */
@@ -558,6 +576,8 @@ int imt_itree_view_lookup_batch(imt_itree_view *v, const void *vals /*[n][32]*/,
                                 uint64_t *leaf_index /*[n] or NULL*/, unsigned flags);
 int imt_itree_view_get_leaves(imt_itree_view *v, const uint64_t *index /*[n] or NULL*/, size_t n,
                               void *preimage /*[n][3][32]*/, unsigned flags);
+/* imt_itree_get_values below the view's size: reads stored values only, so it never builds the view */
+int imt_itree_view_get_values(imt_itree_view *v, uint64_t first, size_t n, void *vals /*[n][32]*/, unsigned flags);
 int imt_itree_view_get_proof_batch(imt_itree_view *v, const uint64_t *index /*[n]*/, size_t n,
                                    void *sib /*[depth][n][32]*/, unsigned flags);
 int imt_itree_view_non_membership_witness(imt_itree_view *v, const void *vals /*[n][32]*/, size_t n,

@@ -417,6 +417,17 @@ public:
     void load(const std::vector<IndexedMerkleTreeLeaf>& leaves) {
         c_->check(imt_itree_load(t_, leaves.data(), leaves.size(), IMT_FMT_CANONICAL));
     }
+    // the value log: the values of leaves [first, first + n) in global leaf indices (n = 0: up to the size of a tree that
+    // is not placed); load_values() makes the tree a fresh one holds after apply_batch of them, and throws, leaving the
+    // tree as it was and *bad_pos at the position one-by-one insertion would stop at, if that would refuse one
+    std::vector<Fr> values(uint64_t first = 1, size_t n = 0) {
+        std::vector<Fr> out(n ? n : (size_t)(size() > first ? size() - first : 0));
+        if (!out.empty()) c_->check(imt_itree_get_values(t_, first, out.size(), out.data(), IMT_FMT_CANONICAL));
+        return out;
+    }
+    void load_values(const std::vector<Fr>& vals, uint64_t* bad_pos = nullptr) {
+        c_->check(imt_itree_load_values(t_, vals.data(), vals.size(), bad_pos, IMT_FMT_CANONICAL));
+    }
     std::vector<Fr> get_proof(uint64_t index) {
         std::vector<Fr> sib(depth_);
         if (depth_) c_->check(imt_itree_get_proof_batch(t_, &index, 1, sib.data(), IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR));
@@ -579,6 +590,11 @@ public:
     std::vector<IndexedMerkleTreeLeaf> get_leaves(const std::vector<uint64_t>& index) {
         std::vector<IndexedMerkleTreeLeaf> out(index.size());
         if (!index.empty()) c_->check(imt_itree_view_get_leaves(v_, index.data(), index.size(), out.data(), IMT_FMT_CANONICAL));
+        return out;
+    }
+    std::vector<Fr> values(uint64_t first, size_t n) {
+        std::vector<Fr> out(n);
+        if (n) c_->check(imt_itree_view_get_values(v_, first, n, out.data(), IMT_FMT_CANONICAL));
         return out;
     }
     std::vector<Fr> get_proof(uint64_t index) {

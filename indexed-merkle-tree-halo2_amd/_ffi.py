@@ -157,6 +157,8 @@ SIGNATURES = {
     "imt_itree_mixed_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, P(InsertOut), P(ReadOut),
                                          P(c_u64), P(c_u64), c_uint]),
     "imt_itree_load": (c_int, [c_void_p, c_void_p, c_u64, c_uint]),
+    "imt_itree_load_values": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_uint]),
+    "imt_itree_get_values": (c_int, [c_void_p, c_u64, c_size_t, c_void_p, c_uint]),
     "imt_itree_find_low_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
     "imt_itree_insert_filtered": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, P(c_u64), P(InsertOut), c_uint]),
     "imt_itree_apply_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
@@ -169,6 +171,7 @@ SIGNATURES = {
     "imt_itree_view_root": (c_int, [c_void_p, c_void_p, c_uint]),
     "imt_itree_view_lookup_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_uint]),
     "imt_itree_view_get_leaves": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
+    "imt_itree_view_get_values": (c_int, [c_void_p, c_u64, c_size_t, c_void_p, c_uint]),
     "imt_itree_view_get_proof_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
     "imt_itree_view_non_membership_witness": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
                                                       c_uint]),

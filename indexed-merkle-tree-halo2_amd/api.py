@@ -792,6 +792,44 @@ class IndexedTree:
             raise ValueError(lib.imt_last_error(self.ctx.h).decode())
         self.ctx._check(rc)
 
+    def values(self, first=1, n=None, fmt=0):
+        """The values [n, 32] of leaves first .. first + n - 1 (imt_itree_get_values), counted from this tree's first
+        leaf: the default is every inserted value in insertion order, the tree's value log."""
+        n = self.size - first if n is None else n
+        out = np.empty((n, 32), dtype=np.uint8)
+        self.ctx._check(lib.imt_itree_get_values(self.h, self.index_base + first, n, _p(out), fmt))
+        return out
+
+    def values_into(self, device_ptr, first=1, n=None, fmt=0):
+        """The same into device memory the caller owns ([n][32] bytes, 16-byte aligned): nothing crosses PCIe."""
+        n = self.size - first if n is None else n
+        self.ctx._check(lib.imt_itree_get_values(self.h, self.index_base + first, n, ctypes.c_void_p(device_ptr),
+                                                 fmt | _ffi.DEVICE_PTRS))
+
+    def load_values(self, vals, fmt=0):
+        """Replace the contents with the tree of a value log (imt_itree_load_values): what a fresh tree holds after
+        apply_batch(vals).  A log that one-by-one insertion would not get through raises ValueError with the position it
+        would stop at as `bad_pos` (ImtError for a value >= p); the tree is then as it was."""
+        a = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
+        self._load_values(_p(a), a.shape[0], fmt)
+
+    def load_values_device(self, device_ptr, n, fmt=0):
+        """load_values() of n values already in device memory (16-byte aligned)."""
+        self._load_values(ctypes.c_void_p(device_ptr), n, fmt | _ffi.DEVICE_PTRS)
+
+    def _load_values(self, ptr, n, flags):
+        bad = ctypes.c_uint64(2 ** 64 - 1)
+        rc = lib.imt_itree_load_values(self.h, ptr, n, ctypes.byref(bad), flags)
+        if rc == _ffi.ERR["VALUE"]:
+            e = ValueError(lib.imt_last_error(self.ctx.h).decode())
+            e.bad_pos = bad.value
+            raise e
+        try:
+            self.ctx._check(rc)
+        except ImtError as e:
+            e.bad_pos = bad.value if bad.value != 2 ** 64 - 1 else None
+            raise
+
     def find_low(self, vals):
         v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
         out = np.empty(v.shape[0], dtype=np.uint64)
@@ -890,6 +928,13 @@ class IndexedTreeView:
         idx = np.ascontiguousarray(index, dtype=np.uint64)
         out = np.empty((idx.size, 3, 32), dtype=np.uint8)
         self.ctx._check(lib.imt_itree_view_get_leaves(self.h, _p(idx), idx.size, _p(out), 0))
+        return out
+
+    def values(self, first=1, n=None, fmt=0):
+        """IndexedTree.values below the view's size (imt_itree_view_get_values); it never rebuilds the view."""
+        n = self.size - first if n is None else n
+        out = np.empty((n, 32), dtype=np.uint8)
+        self.ctx._check(lib.imt_itree_view_get_values(self.h, self.tree.index_base + first, n, _p(out), fmt))
         return out
 
     def get_proof_batch(self, index, item_major=False):

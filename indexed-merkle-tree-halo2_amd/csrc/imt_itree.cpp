@@ -1144,6 +1144,157 @@ extern "C" int imt_itree_load(imt_itree* t, const void* preimages, uint64_t n, u
     return IMT_OK;
 }
 
+// The tree of a value log: what a fresh tree holds after imt_itree_apply_batch(vals, n).  imt_itree_load's sequence with
+// the values in the preimages' place: the same sort, a check that asks what the walk would refuse instead of whether the
+// links close, and leaf hashes that read the successor through the order (launch::index_leaves) instead of from a
+// [n][3][32] array nobody has.
+extern "C" int imt_itree_load_values(imt_itree* t, const void* vals, uint64_t n, uint64_t* bad_pos, unsigned flags) {
+    if (!t) return IMT_ERR_ARG;
+    imt_ctx* c = t->ctx;
+    IMT_NOT_SLICED(t);
+    if (!vals || n == 0) return c->fail(IMT_ERR_ARG, "null / empty value log");
+    if ((flags & IMT_FMT_MASK) == 3) return c->fail(IMT_ERR_ARG, "unknown field-element format");
+    if (n >= t->cap) return c->fail(IMT_ERR_FULL, "%llu values and the sentinel make %llu leaves, capacity is %llu",
+                                    (unsigned long long)n, (unsigned long long)n + 1, (unsigned long long)t->cap);
+    if (slice_open(t)) return c->fail(IMT_ERR_ARG, "a slice is open (issue its remaining units first)");
+    int rc = c->set_device();
+    if (rc) return rc;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    if ((rc = check_fe_ptrs(c, dev, {vals}))) return rc;
+    if ((rc = join_top(t))) return rc;
+    for (auto& pl : t->plan)
+        if (pl.in_flight) { IMT_HIP(c, hipEventSynchronize(pl.done)); pl.in_flight = false; pl.pipelined = false; }
+    IMT_HIP(c, hipStreamSynchronize(t->up_stream));
+    hipStream_t s = c->stream;
+    struct Trim {
+        imt_ctx* c;
+        ~Trim() { c->trim_scratch(2, (size_t)64 << 20); c->trim_scratch(3, (size_t)64 << 20); }
+    } trim{c};
+    const size_t ws_bytes = prep::load_values_ws_bytes((size_t)n);
+    uint8_t* ws = (uint8_t*)c->dev_scratch(3, ws_bytes + 256);      // [error word, offending position | 256-byte aligned workspace]
+    if (!ws) return IMT_ERR_HIP;
+    int* d_perr = (int*)ws;
+    uint32_t* d_bad = (uint32_t*)(ws + 4);
+    // ---- the canonical values on the device: the caller's own memory if that is what it holds ----
+    const uint8_t* d_can = (const uint8_t*)vals;
+    int raw_err = 0;
+    uint32_t raw_bad = 0xffffffffu;
+    if (!dev || fmt != IMT_FMT_CANONICAL) {
+        uint8_t* buf = (uint8_t*)c->dev_scratch(2, (size_t)n * 32);
+        if (!buf) return IMT_ERR_HIP;
+        if (!dev) IMT_HIP(c, hipMemcpyAsync(buf, vals, (size_t)n * 32, hipMemcpyHostToDevice, s));
+        if (fmt != IMT_FMT_CANONICAL) {
+            // every format refuses an encoding >= p, and the conversion reduces it: found here, on the bytes as they came
+            IMT_HIP(c, hipMemsetAsync(d_perr, 0, sizeof(int), s));
+            IMT_HIP(c, hipMemsetAsync(d_bad, 0xff, sizeof(uint32_t), s));
+            prep::first_noncanonical(s, dev ? d_can : buf, (uint32_t)n, d_perr, d_bad);
+            IMT_HIP(c, hipMemcpyAsync(&raw_err, d_perr, sizeof(int), hipMemcpyDeviceToHost, s));
+            IMT_HIP(c, hipMemcpyAsync(&raw_bad, d_bad, sizeof(raw_bad), hipMemcpyDeviceToHost, s));
+            if ((rc = c->clear_err())) return rc;
+            launch::convert(s, dev ? d_can : buf, buf, (size_t)n, fmt, IMT_FMT_CANONICAL, c->d_err);
+        }
+        d_can = buf;
+    }
+    // ---- the check: ordered by (value, position), every rank against its predecessor ----
+    const uint32_t* d_order = nullptr;
+    int perr = 0;
+    uint32_t bad = 0;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        IMT_HIP(c, hipMemsetAsync(d_perr, 0, sizeof(int), s));
+        IMT_HIP(c, hipMemsetAsync(d_bad, 0xff, sizeof(uint32_t), s));
+        IMT_HIP(c, prep::load_values_check(s, d_can, (uint32_t)n, t->part_mod, t->part_res, ws + 256, ws_bytes, attempt == 1,
+                                           d_perr, d_bad, &d_order));
+        IMT_HIP(c, hipMemcpyAsync(&perr, d_perr, sizeof(int), hipMemcpyDeviceToHost, s));
+        IMT_HIP(c, hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, s));
+        IMT_HIP(c, hipStreamSynchronize(s));
+        // values that agree in their top 64 bits and came out of the radix sort in the wrong order: sort with the full
+        // comparator and check again (the other bits of a first attempt that tied mean nothing)
+        if (!(perr & prep::LOAD_TIE)) break;
+    }
+    perr |= raw_err;
+    bad = std::min(bad, raw_bad);
+    if (perr & (prep::ERR_NONCANONICAL | prep::ERR_ZERO | prep::ERR_FOREIGN | prep::ERR_DUPLICATE)) {
+        if (bad_pos && bad < n) *bad_pos = bad;
+        return insertion_verdict(t, perr, "log");
+    }
+    if (perr) return c->fail(IMT_ERR_INTERNAL, "value log check: unexpected error bits %d", perr);
+    // ---- device rebuild: nothing of the tree has been written up to here ----
+    if ((rc = c->clear_err())) return rc;
+    const uint64_t M = n + 1;
+    prep::load_values_commit(s, d_can, d_order, (uint32_t)n, t->d_val, t->d_sorted[t->sorted_cur]);
+    for (unsigned l = 0; l <= t->depth; l++)
+        launch::fill_level(s, t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32);
+    launch::index_leaves(s, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)M, t->index_base, t->d_nodes, c->d_err);
+    uint64_t filled = M;
+    for (unsigned l = 0; l < t->depth; l++) {
+        const uint64_t parents = (filled + 1) / 2;
+        if (t->h_len[l] >= 2) {
+            launch::tree_level(s, t->nodes(l), t->nodes(l + 1), parents);
+        } else {   // a single stored node: its sibling is the empty subtree of this height
+            IMT_HIP(c, hipMemcpyAsync(t->nodes(l + 1), t->nodes(l), 32, hipMemcpyDeviceToDevice, s));
+            launch::extend_root(s, t->nodes(l + 1), c->d_zero, l, l + 1);
+        }
+        filled = parents;
+    }
+    rc = c->sync_and_check();
+    if (rc) return rc;
+    t->pre.clear();
+    t->pre.shrink_to_fit();
+    t->sorted.clear();
+    t->sorted.shrink_to_fit();
+    t->size = M;
+    t->mirror_valid = false;
+    t->dev_index_valid = true;
+    t->pending.active = false;
+    t->gen++;
+    for (auto& pl : t->plan) pl.has_root = false;
+    return IMT_OK;
+}
+
+// values of leaves [first, first + n) (global indices) of the tree, or of the tree as of a view's size: rows of d_val
+static int get_values(imt_itree* t, uint64_t size, uint64_t first, size_t n, void* vals, unsigned flags) {
+    imt_ctx* c = t->ctx;
+    if (n == 0) return IMT_OK;
+    if (!vals) return c->fail(IMT_ERR_ARG, "null buffer");
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    int rc;
+    if ((rc = check_fe_ptrs(c, dev, {vals}))) return rc;
+    const uint64_t lo = first - t->index_base;                    // wraps below the base: out of range
+    if (lo >= size || n > size - lo)
+        return c->fail(IMT_ERR_RANGE, "leaves [%llu, %llu) are not all below the size %llu", (unsigned long long)first,
+                       (unsigned long long)(first + n), (unsigned long long)(t->index_base + size));
+    if ((rc = ensure_device_index(t))) return rc;
+    if ((rc = join_top(t))) return rc;
+    hipStream_t s = c->stream;
+    IMT_HIP(c, hipStreamSynchronize(t->up_stream));     // the index may have been written on the side stream
+    const uint8_t* src = t->d_val + lo * 32;
+    if (dev) {
+        if (fmt == IMT_FMT_CANONICAL) IMT_HIP(c, hipMemcpyAsync(vals, src, n * 32, hipMemcpyDeviceToDevice, s));
+        else launch::convert(s, src, (uint8_t*)vals, n, IMT_FMT_CANONICAL, fmt, c->d_err);
+        return IMT_OK;
+    }
+    if (fmt != IMT_FMT_CANONICAL) {
+        uint8_t* d_out = (uint8_t*)c->dev_scratch(1, n * 32);
+        if (!d_out) return IMT_ERR_HIP;
+        launch::convert(s, src, d_out, n, IMT_FMT_CANONICAL, fmt, c->d_err);
+        src = d_out;
+    }
+    IMT_HIP(c, hipMemcpyAsync(vals, src, n * 32, hipMemcpyDeviceToHost, s));
+    IMT_HIP(c, hipStreamSynchronize(s));
+    c->trim_scratch(1, (size_t)64 << 20);
+    return IMT_OK;
+}
+extern "C" int imt_itree_get_values(imt_itree* t, uint64_t first, size_t n, void* vals, unsigned flags) {
+    if (!t) return IMT_ERR_ARG;
+    imt_ctx* c = t->ctx;
+    IMT_NOT_SLICED(t);
+    if ((flags & IMT_FMT_MASK) == 3) return c->fail(IMT_ERR_ARG, "unknown field-element format");
+    int rc = c->set_device();
+    return rc ? rc : get_values(t, t->size, first, n, vals, flags);
+}
+
 // ------------------------------------------------------------------------------------
 // batch insertion
 // ------------------------------------------------------------------------------------
@@ -2593,6 +2744,18 @@ extern "C" int imt_itree_view_lookup_batch(imt_itree_view* v, const void* vals, 
 extern "C" int imt_itree_view_get_leaves(imt_itree_view* v, const uint64_t* index, size_t n, void* preimage, unsigned flags) {
     int rc = view_enter(v, flags);
     return rc ? rc : get_leaves(v->t, view_source(v), index, n, preimage, flags);
+}
+
+// the refusals of view_enter without its build: the values of the earlier tree are the first rows of d_val as they are
+extern "C" int imt_itree_view_get_values(imt_itree_view* v, uint64_t first, size_t n, void* vals, unsigned flags) {
+    if (!view_alive(v)) return IMT_ERR_ARG;
+    imt_itree* t = v->t;
+    int rc = check_view_call(t, flags);
+    if (rc) return rc;
+    if (t->size < v->size)
+        return t->ctx->fail(IMT_ERR_RANGE, "the tree holds %llu leaves, fewer than the view's %llu", (unsigned long long)t->size,
+                            (unsigned long long)v->size);
+    return get_values(t, v->size, first, n, vals, flags);
 }
 
 extern "C" int imt_itree_view_get_proof_batch(imt_itree_view* v, const uint64_t* index, size_t n, void* sib, unsigned flags) {

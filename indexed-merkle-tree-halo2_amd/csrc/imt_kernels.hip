@@ -703,6 +703,34 @@ __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_tree_level(const uint8
     store_packed(next + i * 32, o);
 }
 
+// ---- the leaf hashes of a tree from its device index (imt_itree_load_values) ----------
+// Rank r of the value order is leaf sorted[r]; its successor is the next rank, so its preimage is
+// {val[sorted[r]], val[sorted[r + 1]], base + sorted[r + 1]} ({val, 0, 0} for the last rank: k_leaves of imt_prep.hip has
+// the same rule) and is hashed from the two value rows where they lie: the [M][3][32] preimages k_hash_batch would read
+// never exist.  Node sorted[r] of stored level 0 is written; sorted is a permutation of [0, M), M <= the level's length.
+__global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_index_leaves(const uint8_t* __restrict__ val,
+                                                        const uint32_t* __restrict__ sorted, uint32_t M, uint64_t base,
+                                                        uint8_t* __restrict__ tree0, int* err) {
+    const size_t r = gtid();
+    if (r >= M) return;
+    __shared__ uint32_t stash[NL][BLOCK];
+    Fe a, b, o;
+    bool ok;
+    {   // the successor: row 0 of val is the sentinel's 0, which is the next_val of the last rank as well
+        const bool last = r + 1 == M;
+        const uint32_t su = last ? 0u : sorted[r + 1];
+        Fe c;
+        fe_from_u64(c, last ? 0 : base + su);
+#pragma unroll
+        for (int q = 0; q < NL; q++) stash[q][threadIdx.x] = c.v[q];
+        ok = load_fe(g_pc, b, val + (size_t)su * 32, FMT_CANONICAL);
+    }
+    ok &= load_fe(g_pc, a, val + (size_t)sorted[r] * 32, FMT_CANONICAL);
+    hash23_stashed(g_pc, o, a, b, true, &stash[0][threadIdx.x], BLOCK);
+    store_packed(tree0 + (size_t)sorted[gtid_again()] * 32, o);     // re-read behind the hash: a cached load, no register kept
+    flag_err(err, ok);
+}
+
 // keeps a wave-uniform chain on the vector ALU: hipcc otherwise runs an all-constant chain on the
 // scalar unit, where one hash takes ~1.6 ms (64 of them made context creation take 100 ms)
 __device__ __forceinline__ void force_vector(Fe& x) {
@@ -1646,6 +1674,11 @@ void tree_level(hipStream_t s, const uint8_t* prev, uint8_t* next, size_t n_pare
                            (unsigned)FMT_DEVICE, (unsigned)FMT_DEVICE, (int*)nullptr);
     else
         hipLaunchKernelGGL(k_tree_level, dim3(nblk(n_parents)), dim3(BLOCK), 0, s, prev, next, n_parents);
+}
+void index_leaves(hipStream_t s, const uint8_t* val, const uint32_t* sorted, uint32_t M, uint64_t base, uint8_t* tree0,
+                  int* err) {
+    if (!M) return;
+    hipLaunchKernelGGL(k_index_leaves, dim3(nblk(M)), dim3(BLOCK), 0, s, val, sorted, M, base, tree0, err);
 }
 void zero_chain(hipStream_t s, uint8_t* out, unsigned depth) {
     hipLaunchKernelGGL(k_zero_chain, dim3(1), dim3(64), 0, s, out, depth);

@@ -110,6 +110,10 @@ void insert_witness(hipStream_t s, const uint8_t* old_root, const uint8_t* low_l
 
 // next[i] = hash2(prev[2i], prev[2i+1]), device format
 void tree_level(hipStream_t s, const uint8_t* prev, uint8_t* next, size_t n_parents, uint32_t coop_max = 0);
+// stored level 0 from the device index (val[M][32] canonical, sorted[M]): node sorted[r] = H(val[sorted[r]],
+// val[sorted[r + 1]], base + sorted[r + 1]), the last rank H(val, 0, 0); tree0 in device format.  A value >= p sets *err.
+void index_leaves(hipStream_t s, const uint8_t* val, const uint32_t* sorted, uint32_t M, uint64_t base, uint8_t* tree0,
+                  int* err);
 // chain: out[l+1] = hash2(out[l], out[l]) for l < depth, out[0] = H(0,0,0); one thread
 void zero_chain(hipStream_t s, uint8_t* out, unsigned depth);
 // cur = hash2(cur, zero[l]) for l in [from, to): extends a subtree root up the left spine

@@ -532,6 +532,52 @@ __global__ void __launch_bounds__(BLOCK) k_leaves(const uint64_t* __restrict__ i
     else { zero32(o + 32); zero32(o + 64); }
 }
 
+// ---- value log: imt_itree_load_values' check and commit (the rule is in imt_prep_logic.hpp) ----
+struct LvPosLess {                     // order positions by value, then position
+    const uint8_t* vals;
+    __device__ bool operator()(uint32_t a, uint32_t b) const { return lv_pos_less(vals, a, b); }
+};
+
+__global__ void __launch_bounds__(BLOCK) k_lv_keys(const uint8_t* __restrict__ vals, uint32_t n, uint64_t* __restrict__ keys,
+                                                   uint32_t* __restrict__ idx) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    keys[i] = reinterpret_cast<const uint64_t*>(vals + (uint64_t)i * 32)[3];
+    idx[i] = i;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_lv_check(const uint8_t* __restrict__ vals, uint32_t n, uint32_t part_mod,
+                                                    uint32_t part_res, const uint32_t* __restrict__ ord, int* err,
+                                                    uint32_t* bad) {
+    const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= n) return;
+    const int e = load_values_rank(vals, ord, r, part_mod, part_res);
+    if (e) {
+        atomicOr(err, e);
+        if (e & ~LOAD_TIE) atomicMin(bad, ord[r]);
+    }
+}
+
+__global__ void __launch_bounds__(BLOCK) k_first_noncanonical(const uint8_t* __restrict__ raw, uint32_t n, int* err,
+                                                              uint32_t* bad) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    if (geq_p(raw + (uint64_t)i * 32)) {
+        atomicOr(err, ERR_NONCANONICAL);
+        atomicMin(bad, i);
+    }
+}
+
+// thread i writes row i of d_val and entry i of the index, i = 0 .. n: both have n + 1 entries
+__global__ void __launch_bounds__(BLOCK) k_lv_commit(const uint8_t* __restrict__ vals, const uint32_t* __restrict__ ord,
+                                                     uint32_t n, uint8_t* __restrict__ d_val, uint32_t* __restrict__ sorted) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i > n) return;
+    if (i == 0) { zero32(d_val); sorted[0] = 0; return; }
+    copy32(d_val + (uint64_t)i * 32, vals + (uint64_t)(i - 1) * 32);
+    sorted[i] = ord[i - 1] + 1;
+}
+
 int levels_for(uint32_t n) {
     int k = 1;
     while ((1u << k) <= n) k++;
@@ -963,6 +1009,46 @@ void leaves(hipStream_t s, const uint64_t* index, uint64_t first, uint32_t n, co
             uint32_t M, uint64_t cap, uint64_t base, uint8_t* out, int* err) {
     if (!n) return;
     hipLaunchKernelGGL(k_leaves, dim3(nblk(n)), dim3(BLOCK), 0, s, index, first, n, d_val, sorted, M, cap, base, out, err);
+}
+
+size_t load_values_ws_bytes(size_t n) {
+    size_t a = 0, b = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, a, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr,
+                                    (uint32_t*)nullptr, n, 0, 64, nullptr);
+    (void)rocprim::merge_sort(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, n, LvPosLess{nullptr}, nullptr);
+    const size_t r = (n + 63) / 64 * 64;
+    return 2 * r * 8 + 2 * r * 4 + (a > b ? a : b) + 256;
+}
+
+hipError_t load_values_check(hipStream_t s, const uint8_t* vals, uint32_t n, uint32_t part_mod, uint32_t part_res, void* ws,
+                             size_t ws_bytes, bool full_sort, int* err, uint32_t* bad, const uint32_t** order) {
+    if (!n || load_values_ws_bytes(n) > ws_bytes) return hipErrorInvalidValue;
+    const size_t r = ((size_t)n + 63) / 64 * 64;
+    uint8_t* w = (uint8_t*)ws;
+    uint64_t* keys = (uint64_t*)w;
+    uint64_t* keys2 = keys + r;
+    uint32_t* idx = (uint32_t*)(keys2 + r);
+    uint32_t* idx2 = idx + r;
+    void* tmp = idx2 + r;
+    size_t tb = ws_bytes - (size_t)((uint8_t*)tmp - w);
+    hipError_t e;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_lv_keys, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, n, keys, idx);
+    if (full_sort) e = rocprim::merge_sort(tmp, tb, idx, idx2, (size_t)n, LvPosLess{vals}, s);
+    else e = rocprim::radix_sort_pairs(tmp, tb, keys, keys2, idx, idx2, (size_t)n, 0, 64, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_lv_check, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, n, part_mod, part_res, idx2, err, bad);
+    *order = idx2;
+    return hipGetLastError();
+}
+
+void first_noncanonical(hipStream_t s, const uint8_t* raw, uint32_t n, int* err, uint32_t* bad) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_first_noncanonical, dim3(nblk(n)), dim3(BLOCK), 0, s, raw, n, err, bad);
+}
+
+void load_values_commit(hipStream_t s, const uint8_t* vals, const uint32_t* order, uint32_t n, uint8_t* d_val, uint32_t* sorted) {
+    hipLaunchKernelGGL(k_lv_commit, dim3(nblk((size_t)n + 1)), dim3(BLOCK), 0, s, vals, order, n, d_val, sorted);
 }
 
 }  // namespace prep

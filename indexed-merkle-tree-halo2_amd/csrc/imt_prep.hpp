@@ -215,5 +215,21 @@ void load_commit(hipStream_t s, const uint8_t* pre, uint32_t n, uint8_t* d_val);
 void leaves(hipStream_t s, const uint64_t* index, uint64_t first, uint32_t n, const uint8_t* d_val, const uint32_t* sorted,
             uint32_t M, uint64_t cap, uint64_t base, uint8_t* out, int* err);
 
+
+// ---- value log (imt_itree_load_values, imt_itree_get_values): a tree from its values in leaf order ----
+// load_values_check: vals = [n][32] canonical, position q = the value of leaf q + 1 (the sentinel is not passed).  Orders
+// the positions by value, equal values by position (radix sort on the top 64 bits; full_sort: merge sort with
+// lv_pos_less -- the caller's second attempt after LOAD_TIE) and judges every rank (load_values_rank, imt_prep_logic.hpp):
+// error bits are OR-ed into *err, the smallest offending position into *bad (atomicMin: the caller sets it to 0xffffffff).  *order = the positions
+// in that order, inside `ws` (load_values_ws_bytes(n) bytes of device memory).  Writes nothing but ws / err.
+size_t load_values_ws_bytes(size_t n);
+hipError_t load_values_check(hipStream_t s, const uint8_t* vals, uint32_t n, uint32_t part_mod, uint32_t part_res, void* ws,
+                             size_t ws_bytes, bool full_sort, int* err, uint32_t* bad, const uint32_t** order);
+// raw = [n][32] in ANY format, before it is converted: every format refuses the encodings >= p.  ERR_NONCANONICAL into
+// *err and the smallest such position into *bad, which the caller has set (atomicMin).
+void first_noncanonical(hipStream_t s, const uint8_t* raw, uint32_t n, int* err, uint32_t* bad);
+// d_val rows [0, n] = {0, vals}; sorted[0 .. n] = {0, order + 1}: the index of the tree that holds exactly these values
+void load_values_commit(hipStream_t s, const uint8_t* vals, const uint32_t* order, uint32_t n, uint8_t* d_val, uint32_t* sorted);
+
 }  // namespace prep
 }  // namespace imt

@@ -184,5 +184,54 @@ IMT_PL_HD int load_check_rank(const uint8_t* pre, uint32_t n, uint64_t base, con
     return e;
 }
 
+// ---- value log check (imt_itree_load_values): which position would one-by-one insertion stop at ---------------------
+// vals = [n][32] the inserted values in insertion order: position q becomes leaf q + 1.  The sentinel's 0 of leaf 0 is not
+// among them: it is the smallest value at the smallest leaf, so it is rank 0 of the tree's order whatever the values are,
+// and "equal to the sentinel" is "is 0".  ord[r] = the position of the r-th smallest value, equal values by position (the
+// candidate order of the radix sort: by the top 64 bits, equal keys in input order).  Rank r judges position ord[r]
+// against its predecessor ord[r - 1]: a smaller value, or an equal one at a larger position, says the candidate order
+// is not the order (LOAD_TIE: the caller re-sorts with lv_pos_less and the other bits of this attempt mean nothing); an
+// equal value at a smaller position was inserted earlier, so the walk refuses THIS one.  Together with what is wrong
+// with the value alone (>= p, 0, a foreign residue) these are all the refusals of the walk, and the smallest position
+// that has one is where it stops.
+constexpr int LV_NONCANONICAL = 1;      // the other bits: OP_ZERO / OP_DUPLICATE / OP_FOREIGN, LOAD_TIE
+// three-way comparison, the most significant differing limb decides (the form of cmp256, imt_filter_logic.hpp)
+IMT_PL_HD int lv_cmp256(const uint8_t* a, const uint8_t* b) {
+    const uint64_t* x = reinterpret_cast<const uint64_t*>(a);
+    const uint64_t* y = reinterpret_cast<const uint64_t*>(b);
+    int c = 0;
+    for (int i = 0; i < 4; i++) {
+        const int d = (int)(x[i] > y[i]) - (int)(x[i] < y[i]);
+        c = d ? d : c;
+    }
+    return c;
+}
+// the order of the fallback sort: by value, then by position -- total, and written without a branch
+IMT_PL_HD bool lv_pos_less(const uint8_t* vals, uint32_t a, uint32_t b) {
+    const int c = lv_cmp256(vals + (uint64_t)a * 32, vals + (uint64_t)b * 32);
+    return c < 0 || (c == 0 && a < b);
+}
+IMT_PL_HD bool lv_geq_p(const uint8_t* v) {
+    const uint64_t P[4] = {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};
+    const uint64_t* x = reinterpret_cast<const uint64_t*>(v);
+    for (int i = 3; i >= 0; i--)
+        if (x[i] != P[i]) return x[i] > P[i];
+    return true;
+}
+// the error bits of position ord[r]; 0 = the walk inserts it (if it gets that far)
+IMT_PL_HD int load_values_rank(const uint8_t* vals, const uint32_t* ord, uint32_t r, uint32_t part_mod, uint32_t part_res) {
+    const uint32_t q = ord[r];
+    const uint8_t* x = vals + (uint64_t)q * 32;
+    int e = op_value_class(x, part_mod, part_res);
+    if (lv_geq_p(x)) e |= LV_NONCANONICAL;
+    if (r > 0) {
+        const uint32_t pq = ord[r - 1];
+        const int c = lv_cmp256(vals + (uint64_t)pq * 32, x);
+        if (c > 0 || (c == 0 && pq > q)) e |= LOAD_TIE;
+        else if (c == 0) e |= OP_DUPLICATE;
+    }
+    return e;
+}
+
 }  // namespace prep
 }  // namespace imt
