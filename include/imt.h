@@ -505,9 +505,10 @@ int imt_itree_apply_batch(imt_itree *t, const void *vals /*[n][32]*/, size_t n, 
 int imt_itree_apply_filtered(imt_itree *t, const void *vals /*[n][32]*/, size_t n, uint8_t *status /*[n]*/,
                              uint64_t *leaf_index /*[n] or NULL*/, uint64_t *n_inserted /*host*/,
                              void *root_out /*[32] or NULL*/, unsigned flags);
-/* What the last apply call that inserted something hashed: hashes[0] = leaf hashes, hashes[l] = hash2 calls that
- * produced level-l nodes, l = 1 .. depth -- the number of distinct nodes the batch touched at every level.  Host memory;
- * waits for that call.  IMT_ERR_ARG if there has been none. */
+/* What the last apply call that inserted something hashed (imt_itree_apply_batch, _apply_filtered, _apply_mixed or
+ * _apply_mixed_filtered; a call that inserted nothing, a block of READs only included, hashed nothing and is not it):
+ * hashes[0] = leaf hashes, hashes[l] = hash2 calls that produced level-l nodes, l = 1 .. depth -- the number of distinct
+ * nodes the batch touched at every level.  Host memory; waits for that call.  IMT_ERR_ARG if there has been none. */
 int imt_itree_apply_stats(imt_itree *t, uint64_t *hashes /*[depth + 1]*/);
 /* GOING BACK, for the same callers when the last blocks are dropped (a reorg, a failed proof, a batch the L1 did not
  * accept).  The tree as it was when it held new_size leaves (sentinel included; 1 = the empty tree): byte for byte --
@@ -713,6 +714,40 @@ int imt_itree_mixed_filtered(imt_itree *t, const void *vals /*[n][32]*/, const u
                              uint8_t *status /*[n]*/, uint64_t *leaf_index /*[n] or NULL*/,
                              const imt_insert_out *ins /*may be NULL*/, const imt_read_out *rd /*may be NULL*/,
                              uint64_t *n_inserted /*host*/, uint64_t *n_read /*host*/, unsigned flags);
+/* THE SAME TWO BLOCKS WITHOUT WITNESSES, for whoever applies a block now and proves it elsewhere or later (the sequencer
+ * and the chain follower of INTEGRATION.md 4): the ordered walk decides what each READ may see, and nothing is proved.
+ * DEFINED BY THE CALLS ABOVE.  imt_itree_apply_mixed IS
+ *     imt_itree_mixed_batch(t, vals, op, n, NULL, NULL, n_inserted, bad_op, flags)
+ * -- the same result, *n_inserted with IMT_OK only and *bad_op with IMT_ERR_VALUE only, every refusal of that call with
+ * the tree untouched (IMT_ERR_VALUE, IMT_ERR_NONCANONICAL, IMT_ERR_FULL counting INSERTs only, and IMT_ERR_ARG: an op byte
+ * above 1; NULL vals or op with n > 0; a misaligned device buffer; IMT_PIPELINE, IMT_HOST_PREP or IMT_INPUTS_READY; a
+ * placed or partitioned tree; a replica of a sliced world with steps in flight; an open slice; a call between
+ * imt_itree_batch_begin and _end), and afterwards the same tree byte for byte: stored nodes, value rows, index, size.  A
+ * block without an INSERT changes nothing, is not counted as a change (views stay fresh) and imt_itree_root_lagged does not
+ * see it.  imt_itree_apply_mixed_filtered IS
+ *     imt_itree_mixed_filtered(t, vals, op, n, status, leaf_index, NULL, NULL, n_inserted, n_read, flags)
+ * in the same sense: status, leaf_index (the low leaf of an accepted READ as of its place in the block included), both
+ * counts and every error case as that call writes them, and the same tree afterwards.
+ * ON TOP OF THAT both write root_out, as imt_itree_apply_batch does: the root after the block, [32] in the flags' format,
+ * host or device memory per IMT_DEVICE_PTRS, may be NULL; the current root when n == 0 or the block inserts nothing;
+ * not written on any refusal.
+ * THE COST IS imt_itree_apply_batch's, exactly: the call hashes what imt_itree_apply_batch of the carried-out INSERT values,
+ * in their order, hashes -- every touched node once, 3 to 9 hashes per INSERT where the calls above spend 2 + 2*depth per
+ * INSERT and 1 + depth per READ -- and imt_itree_apply_stats reports the same depth + 1 counts afterwards.  A READ adds no
+ * hash: it is judged by the checks and reaches no hash kernel.  A block that inserts nothing hashes nothing, and
+ * imt_itree_apply_stats keeps reporting the earlier apply call.
+ * Ordered as imt_itree_apply_batch: on the context's stream, behind every batch in flight (pipelined ones included),
+ * later calls of any kind behind it; witness, apply, mixed and apply-mixed calls alternate freely on one tree.  status,
+ * leaf_index and the counts are complete at return, as for the calls above.
+ * NOT IN THESE CALLS: placed and partitioned trees, pipelining, and witness rows of any kind -- a view at the size before
+ * the block gives them later: imt_itree_view_mixed_witness below, over the operations that were carried out. */
+int imt_itree_apply_mixed(imt_itree *t, const void *vals /*[n][32]*/, const uint8_t *op /*[n]*/, size_t n,
+                          void *root_out /*[32] or NULL*/, uint64_t *n_inserted /*host, may be NULL*/,
+                          uint64_t *bad_op /*host, may be NULL*/, unsigned flags);
+int imt_itree_apply_mixed_filtered(imt_itree *t, const void *vals /*[n][32]*/, const uint8_t *op /*[n]*/, size_t n,
+                                   uint8_t *status /*[n]*/, uint64_t *leaf_index /*[n] or NULL*/,
+                                   uint64_t *n_inserted /*host*/, uint64_t *n_read /*host*/,
+                                   void *root_out /*[32] or NULL*/, unsigned flags);
 /* APPLY A MIXED BLOCK NOW, PROVE IT LATER (beside imt_itree_view_insert_witness; declared here for imt_read_out): the
  * witnesses of a block of INSERTs and READs whose insertions the tree has already made, witness-free or otherwise, and may
  * since have built upon -- every READ's witness against the tree as it stood at that point of the block.

@@ -725,6 +725,41 @@ class IndexedTree:
                                                      _ffi.HOST_PREP if host_prep else 0))
         return status, leaf, n_ins.value, to_int(root)
 
+    def apply_mixed(self, vals, ops):
+        """mixed_batch() without witnesses (imt_itree_apply_mixed): the same refusals and the same tree afterwards, every
+        touched node hashed once and no hash for a READ.  Returns (n_inserted, root): the number of INSERTs and the root
+        after the block.  A refused value raises ValueError with .bad_op = the first offending position; the tree is
+        unchanged."""
+        v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
+        op = np.ascontiguousarray(ops, dtype=np.uint8)
+        n = v.shape[0]
+        if op.shape != (n,):
+            raise ValueError("apply_mixed: one op per value")
+        root = np.empty(32, dtype=np.uint8)
+        n_ins, bad = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = lib.imt_itree_apply_mixed(self.h, _p(v), _p(op), n, _p(root), ctypes.byref(n_ins), ctypes.byref(bad), 0)
+        if rc == _ffi.ERR["VALUE"]:
+            e = ValueError(lib.imt_last_error(self.ctx.h).decode())
+            e.bad_op = bad.value
+            raise e
+        self.ctx._check(rc)
+        return n_ins.value, to_int(root)
+
+    def apply_mixed_filtered(self, vals, ops):
+        """mixed_filtered() without witnesses (imt_itree_apply_mixed_filtered): (status, leaf_index, n_inserted, n_read,
+        root) -- status and leaf_index per operation passed in, the accepted INSERTs and READs, the root after the
+        block."""
+        v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
+        op = np.ascontiguousarray(ops, dtype=np.uint8)
+        n = v.shape[0]
+        if op.shape != (n,):
+            raise ValueError("apply_mixed_filtered: one op per value")
+        status, leaf, root = np.empty(n, np.uint8), np.empty(n, np.uint64), np.empty(32, dtype=np.uint8)
+        n_ins, n_rd = ctypes.c_uint64(), ctypes.c_uint64()
+        self.ctx._check(lib.imt_itree_apply_mixed_filtered(self.h, _p(v), _p(op), n, _p(status), _p(leaf), ctypes.byref(n_ins),
+                                                           ctypes.byref(n_rd), _p(root), 0))
+        return status, leaf, n_ins.value, n_rd.value, to_int(root)
+
     def apply_stats(self):
         """hashes per level of the last apply call: [0] leaf hashes, [l] the hash2 calls that made level-l nodes."""
         out = np.empty(self.depth + 1, dtype=np.uint64)

@@ -1993,33 +1993,32 @@ struct MixedFiltered {
     size_t n_all;           // its length: the operations passed in
 };
 
-// The body of imt_itree_mixed_batch behind the staging of its inputs: n operations (d_vals canonical, d_op, both device
-// memory that stream t->up_stream may read), on plan set P, acquired for >= 2 * stride events, with the error word clear.
-// stride >= n is the level stride of level-major sibling arrays -- the caller's dimensions, imt_itree_insert_filtered's
-// convention; slot: the first context scratch slot the staged outputs may take.
-static int mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, const uint8_t* d_op, size_t n, size_t stride, size_t slot,
-                      const imt_insert_out* ins, const imt_read_out* rd, uint64_t* n_inserted, uint64_t* bad_op, unsigned flags,
-                      const MixedFiltered* filtered) {
+// The per-operation scratch of a mixed batch on plan set P: the filter's and the slot table's, idle by then.
+static prep::MixedWs mixed_scratch(const PlanSet& P) { return prep::MixedWs{P.fw.flag, P.fw.rank, P.fw.idx, P.fw.aux, P.d_slot}; }
+
+// The front of every mixed batch behind the staging of its inputs: n operations (d_vals canonical, d_op, both device
+// memory that stream t->up_stream may read), on plan set P, acquired for >= 2n events, with the error word clear.  Ranks,
+// room for the n_ins INSERTs, their values into rows [M, M + n_ins) of the value array, every check and the neighbours of
+// every operation (P.ws.low / succ) -- two host waits, after which either the batch is refused with nothing of the tree
+// or the caller's changed, or it is accepted and the side stream is idle.
+static int mixed_checks(imt_itree* t, PlanSet& P, const prep::MixedWs& mx, const uint8_t* d_vals, const uint8_t* d_op, size_t n,
+                        uint64_t* bad_op, const MixedFiltered* filtered, size_t& n_ins) {
     imt_ctx* c = t->ctx;
     int rc;
-    const bool dev = flags & IMT_DEVICE_PTRS;
-    const unsigned fmt = flags & IMT_FMT_MASK;
     const uint64_t M = t->size;
     hipStream_t ps = t->up_stream;
-    // the per-operation scratch is the filter's and the slot table's, idle here
-    const prep::MixedWs mx{P.fw.flag, P.fw.rank, P.fw.idx, P.fw.aux, P.d_slot};
     IMT_HIP(c, prep::mixed_ranks(ps, P.ws, mx, d_op, (uint32_t)n));
     IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, mx.word, sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
     IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, ps));
     IMT_HIP(c, hipStreamSynchronize(ps));
     if (*t->h_err_pin & prep::ERR_OP) return c->fail(IMT_ERR_ARG, "an op byte is neither IMT_OP_INSERT nor IMT_OP_READ");
-    const size_t n_ins = *t->h_cnt_pin, n_rd = n - n_ins;
+    n_ins = *t->h_cnt_pin;
     if ((rc = check_room(t, n_ins))) return rc;
     P.ws.part_mod = t->part_mod;
     P.ws.part_res = t->part_res;
     IMT_HIP(c, prep::mixed_check(ps, P.ws, mx, d_vals, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)M, (uint32_t)n,
                                  (uint32_t)n_ins));
-    if (filtered && filtered->d_leaf && n_rd) {
+    if (filtered && filtered->d_leaf && n_ins < n) {
         IMT_HIP(c, prep::mixed_filter_reads(ps, P.fw, P.ws, mx, (uint32_t)n, (uint32_t)n_ins, t->index_base, filtered->d_leaf));
     }
     if (filtered && filtered->h_leaf)
@@ -2040,6 +2039,49 @@ static int mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, const uin
         }
         return rc;
     }
+    return IMT_OK;
+}
+
+// The end of every mixed batch, its hashing enqueued on stream s: the plan set in flight, and if the batch inserted
+// anything the commit of a batch like any other -- the root into the plan set, the merged index and the size current.
+static int mixed_commit(imt_itree* t, PlanSet& P, hipStream_t s, size_t n_ins, unsigned L0) {
+    imt_ctx* c = t->ctx;
+    P.pipelined = false;
+    if (n_ins) {    // the tree has changed: from here the call is a batch like any other
+        IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
+        P.has_root = true;
+        P.sliced = false;
+        P.l0 = L0;
+    }
+    IMT_HIP(c, hipEventRecord(P.done, s));
+    P.in_flight = true;
+    if (n_ins) {
+        t->cur = (t->cur + 1) % imt_itree::NSETS;
+        t->batch_no++;
+        t->sorted_cur ^= 1;
+        t->size += n_ins;
+        t->mirror_valid = false;
+        t->gen++;
+    }
+    return IMT_OK;
+}
+
+// The body of imt_itree_mixed_batch behind the staging of its inputs (mixed_checks says how they are passed).
+// stride >= n is the level stride of level-major sibling arrays -- the caller's dimensions, imt_itree_insert_filtered's
+// convention; slot: the first context scratch slot the staged outputs may take.
+static int mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, const uint8_t* d_op, size_t n, size_t stride, size_t slot,
+                      const imt_insert_out* ins, const imt_read_out* rd, uint64_t* n_inserted, uint64_t* bad_op, unsigned flags,
+                      const MixedFiltered* filtered) {
+    imt_ctx* c = t->ctx;
+    int rc;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    const uint64_t M = t->size;
+    hipStream_t ps = t->up_stream;
+    const prep::MixedWs mx = mixed_scratch(P);
+    size_t n_ins = 0;
+    if ((rc = mixed_checks(t, P, mx, d_vals, d_op, n, bad_op, filtered, n_ins))) return rc;
+    const size_t n_rd = n - n_ins;
 
     // ---- accepted: events, tables, merged index, hash-free outputs (side stream) ----
     const size_t E = n + n_ins;
@@ -2062,35 +2104,73 @@ static int mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, const uin
     const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->depth} : launch::SibLayout{stride, 1};
     if ((rc = mixed_hashes(t, P, s, E, L0, n_ins, d, launch::MixedRoute{mx.erow, (uint8_t*)r.low_sib}, (uint8_t*)r.root, lay, fmt)))
         return rc;
-    P.pipelined = false;
-    if (n_ins) {    // the tree has changed: from here the call is a batch like any other
-        IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
-        P.has_root = true;
-        P.sliced = false;
-        P.l0 = L0;
-    }
-    IMT_HIP(c, hipEventRecord(P.done, s));
-    P.in_flight = true;
-    if (n_ins) {
-        t->cur = (t->cur + 1) % imt_itree::NSETS;
-        t->batch_no++;
-        t->sorted_cur ^= 1;
-        t->size = M + n_ins;
-        t->mirror_valid = false;
-        t->gen++;
-    }
+    if ((rc = mixed_commit(t, P, s, n_ins, L0))) return rc;
 
     // ---- outputs ----
     if (n_inserted) *n_inserted = n_ins;
     return mixed_deliver_outputs(t, s, ins, rd, d, r, n_ins, n_rd, stride, flags);
 }
 
-extern "C" int imt_itree_mixed_batch(imt_itree* t, const void* vals, const uint8_t* op, size_t n, const imt_insert_out* ins,
-                                     const imt_read_out* rd, uint64_t* n_inserted, uint64_t* bad_op, unsigned flags) {
+// The body of imt_itree_apply_mixed behind the same staging: the same checks, then the events of the
+// INSERTs alone and imt_itree_apply_batch's hashing and commit.  A READ is judged by the checks and is heard of no more;
+// a batch without an INSERT ends behind them -- nothing was enqueued outside the side stream, which has been waited for,
+// so the plan set stays idle, nothing is hashed and the only thing read of the tree is its root.
+static int apply_mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, const uint8_t* d_op, size_t n, size_t slot,
+                            uint64_t* n_inserted, uint64_t* bad_op, unsigned flags, const MixedFiltered* filtered,
+                            const ApplyReq& apply) {
+    imt_ctx* c = t->ctx;
+    int rc;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    const uint64_t M = t->size;
+    hipStream_t ps = t->up_stream;
+    size_t n_ins = 0;
+    if ((rc = mixed_checks(t, P, mixed_scratch(P), d_vals, d_op, n, bad_op, filtered, n_ins))) return rc;
+    if (!n_ins) {
+        if (apply.root_out && (rc = imt_itree_root(t, apply.root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS)))) return rc;
+        if (n_inserted) *n_inserted = 0;
+        return IMT_OK;
+    }
+
+    // ---- accepted: the 2 n_ins events an insertion-only batch of the INSERT values has, tables, merged index ----
+    const size_t E = 2 * n_ins;
+    const unsigned L0 = std::min(ceil_log2(M + n_ins), t->depth);
+    IMT_HIP(c, prep::mixed_insert_events(ps, P.ws, t->d_val, t->d_sorted[t->sorted_cur], t->d_sorted[t->sorted_cur ^ 1], (uint32_t)M,
+                                         (uint32_t)n_ins, t->index_base, P.d_pre, P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][2],
+                                         P.d_tab[0][3]));
+    IMT_HIP(c, hipEventRecord(t->up_done, ps));
+
+    // ---- hashing on the context's stream, behind every batch in flight: every touched node once ----
+    hipStream_t s = c->stream;
+    if ((rc = join_top(t))) return rc;
+    IMT_HIP(c, hipStreamWaitEvent(s, t->up_done, 0));
+    if ((rc = apply_hashes(t, P, s, E, L0, t->d_apply_stats))) return rc;
+    t->apply_seen = true;
+    if ((rc = mixed_commit(t, P, s, n_ins, L0))) return rc;
+
+    // ---- outputs ----
+    if (n_inserted) *n_inserted = n_ins;
+    if (apply.root_out) {
+        uint8_t* r = dev ? (uint8_t*)apply.root_out : (uint8_t*)c->dev_scratch(slot++, 32);
+        if (!r) return IMT_ERR_HIP;
+        launch::convert(s, P.d_root, r, 1, IMT_FMT_DEVICE, fmt, c->d_err);
+        if (!dev) IMT_HIP(c, hipMemcpyAsync(apply.root_out, r, 32, hipMemcpyDeviceToHost, s));
+    }
+    if (!dev) IMT_HIP(c, hipStreamSynchronize(s));
+    return IMT_OK;
+}
+
+// imt_itree_mixed_batch and (apply != NULL) imt_itree_apply_mixed: the refusals, the staging of the inputs, then the body
+static int mixed_call(imt_itree* t, const void* vals, const uint8_t* op, size_t n, const imt_insert_out* ins,
+                      const imt_read_out* rd, uint64_t* n_inserted, uint64_t* bad_op, unsigned flags, const ApplyReq* apply) {
     if (!t) return IMT_ERR_ARG;
     imt_ctx* c = t->ctx;
     IMT_NOT_SLICED(t);
     if (n == 0) {
+        if (apply && apply->root_out) {
+            const int rc0 = imt_itree_root(t, apply->root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS));
+            if (rc0) return rc0;
+        }
         if (n_inserted) *n_inserted = 0;
         return IMT_OK;
     }
@@ -2106,6 +2186,7 @@ extern "C" int imt_itree_mixed_batch(imt_itree* t, const void* vals, const uint8
     if (rd && (rc = check_fe_ptrs(c, dev, {rd->low_leaf, rd->root, rd->low_sib}))) return rc;
     if (dev && ((ins && ((uintptr_t)ins->low_index & 7u)) || (rd && ((uintptr_t)rd->low_index & 7u))))
         return c->fail(IMT_ERR_ARG, "device low_index array is not 8-byte aligned");
+    if (apply && (rc = check_fe_ptrs(c, dev, {apply->root_out}))) return rc;
     if (!dev)
         for (size_t p = 0; p < n; p++)
             if (op[p] > IMT_OP_READ) return c->fail(IMT_ERR_ARG, "op[%zu] = %u is neither IMT_OP_INSERT nor IMT_OP_READ", p, op[p]);
@@ -2130,24 +2211,41 @@ extern "C" int imt_itree_mixed_batch(imt_itree* t, const void* vals, const uint8
         IMT_HIP(c, hipMemcpyAsync(o, op, n, hipMemcpyHostToDevice, ps));
         d_op = o;
     }
+    if (apply) return apply_mixed_core(t, P, d_vals, d_op, n, slot, n_inserted, bad_op, flags, nullptr, *apply);
     return mixed_core(t, P, d_vals, d_op, n, n, slot, ins, rd, n_inserted, bad_op, flags, nullptr);
+}
+
+extern "C" int imt_itree_mixed_batch(imt_itree* t, const void* vals, const uint8_t* op, size_t n, const imt_insert_out* ins,
+                                     const imt_read_out* rd, uint64_t* n_inserted, uint64_t* bad_op, unsigned flags) {
+    return mixed_call(t, vals, op, n, ins, rd, n_inserted, bad_op, flags, nullptr);
+}
+
+extern "C" int imt_itree_apply_mixed(imt_itree* t, const void* vals, const uint8_t* op, size_t n, void* root_out,
+                                     uint64_t* n_inserted, uint64_t* bad_op, unsigned flags) {
+    const ApplyReq req{root_out};
+    return mixed_call(t, vals, op, n, nullptr, nullptr, n_inserted, bad_op, flags, &req);
 }
 
 // The filtered twin: prep::mixed_filter classifies the operations on the side stream, one wait brings back
 // the two counts and the error bits, and the accepted operations -- compacted into the plan set, P.fw.acc / aop -- are a
 // mixed batch of their own with the caller's level stride.  status / leaf_index are classified into the plan set's
 // staging whatever the pointers are: a device-pointer caller's op bytes are checked by the class kernel, and a bad one
-// must leave the caller's arrays as they were.
-extern "C" int imt_itree_mixed_filtered(imt_itree* t, const void* vals, const uint8_t* op, size_t n, uint8_t* status,
-                                        uint64_t* leaf_index, const imt_insert_out* ins, const imt_read_out* rd,
-                                        uint64_t* n_inserted, uint64_t* n_read, unsigned flags) {
+// must leave the caller's arrays as they were.  apply != NULL: imt_itree_apply_mixed_filtered -- the accepted operations
+// are a witness-free mixed batch instead, and a call that changes nothing still reports the root.
+static int mixed_filtered_call(imt_itree* t, const void* vals, const uint8_t* op, size_t n, uint8_t* status, uint64_t* leaf_index,
+                               const imt_insert_out* ins, const imt_read_out* rd, uint64_t* n_inserted, uint64_t* n_read,
+                               unsigned flags, const ApplyReq* apply) {
     if (!t) return IMT_ERR_ARG;
     imt_ctx* c = t->ctx;
     if (n_inserted) *n_inserted = 0;        // the counts are 0 on every error
     if (n_read) *n_read = 0;
     IMT_NOT_SLICED(t);
     if (!status || !n_inserted || !n_read) return c->fail(IMT_ERR_ARG, "null status / n_inserted / n_read");
-    if (n == 0) return IMT_OK;
+    auto unchanged_root = [&]() -> int {      // nothing inserted: an apply call still reports the root
+        if (!apply || !apply->root_out) return IMT_OK;
+        return imt_itree_root(t, apply->root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS));
+    };
+    if (n == 0) return unchanged_root();
     if (!vals || !op) return c->fail(IMT_ERR_ARG, "null vals / op");
     if (flags & (IMT_PIPELINE | IMT_HOST_PREP | IMT_INPUTS_READY))
         return c->fail(IMT_ERR_ARG, "mixed batches take neither IMT_PIPELINE, IMT_HOST_PREP nor IMT_INPUTS_READY");
@@ -2161,6 +2259,7 @@ extern "C" int imt_itree_mixed_filtered(imt_itree* t, const void* vals, const ui
     if (dev && ((ins && ((uintptr_t)ins->low_index & 7u)) || (rd && ((uintptr_t)rd->low_index & 7u))))
         return c->fail(IMT_ERR_ARG, "device low_index array is not 8-byte aligned");
     if (dev && ((uintptr_t)leaf_index & 7u)) return c->fail(IMT_ERR_ARG, "device leaf_index array is not 8-byte aligned");
+    if (apply && (rc = check_fe_ptrs(c, dev, {apply->root_out}))) return rc;
     if (!dev)
         for (size_t p = 0; p < n; p++)
             if (op[p] > IMT_OP_READ) return c->fail(IMT_ERR_ARG, "op[%zu] = %u is neither IMT_OP_INSERT nor IMT_OP_READ", p, op[p]);
@@ -2199,7 +2298,7 @@ extern "C" int imt_itree_mixed_filtered(imt_itree* t, const void* vals, const ui
     if (rc || !n_acc) {       // refused, or nothing to carry out: the classification is the whole answer
         if (leaf_index) IMT_HIP(c, hipMemcpyAsync(leaf_index, d_leaf, n * 8, to_user, ps));
         IMT_HIP(c, hipStreamSynchronize(ps));
-        return rc;
+        return rc ? rc : unchanged_root();
     }
 
     // ---- the accepted operations: a mixed batch with the caller's dimensions ----
@@ -2213,10 +2312,25 @@ extern "C" int imt_itree_mixed_filtered(imt_itree* t, const void* vals, const ui
             fl.h_leaf = leaf_index;
         }
     }
-    if ((rc = mixed_core(t, P, P.fw.acc, P.fw.aop, n_acc, n, slot, ins, rd, nullptr, nullptr, flags, &fl))) return rc;
+    rc = apply ? apply_mixed_core(t, P, P.fw.acc, P.fw.aop, n_acc, slot, nullptr, nullptr, flags, &fl, *apply)
+               : mixed_core(t, P, P.fw.acc, P.fw.aop, n_acc, n, slot, ins, rd, nullptr, nullptr, flags, &fl);
+    if (rc) return rc;
     *n_inserted = n_ins;
     *n_read = n_rd;
     return IMT_OK;
+}
+
+extern "C" int imt_itree_mixed_filtered(imt_itree* t, const void* vals, const uint8_t* op, size_t n, uint8_t* status,
+                                        uint64_t* leaf_index, const imt_insert_out* ins, const imt_read_out* rd,
+                                        uint64_t* n_inserted, uint64_t* n_read, unsigned flags) {
+    return mixed_filtered_call(t, vals, op, n, status, leaf_index, ins, rd, n_inserted, n_read, flags, nullptr);
+}
+
+extern "C" int imt_itree_apply_mixed_filtered(imt_itree* t, const void* vals, const uint8_t* op, size_t n, uint8_t* status,
+                                              uint64_t* leaf_index, uint64_t* n_inserted, uint64_t* n_read, void* root_out,
+                                              unsigned flags) {
+    const ApplyReq req{root_out};
+    return mixed_filtered_call(t, vals, op, n, status, leaf_index, nullptr, nullptr, n_inserted, n_read, flags, &req);
 }
 
 // ------------------------------------------------------------------------------------

@@ -306,6 +306,19 @@ k_mixed_events(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ r
     }
 }
 
+// the events of the INSERTs alone (imt_itree_apply_mixed): what k_events writes for an insertion-only batch of the same
+// values, from the neighbours the mixed checks left by rank.  A READ has no event here.
+__global__ void __launch_bounds__(BLOCK)
+k_insert_events(const uint8_t* __restrict__ d_val, uint32_t M, uint32_t n_ins, uint64_t base, const uint32_t* __restrict__ low,
+                const uint32_t* __restrict__ succ, uint8_t* __restrict__ pre, uint64_t* __restrict__ keys) {
+    const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= n_ins) return;
+    const InsertEvent e = insert_event(r, M, low, succ);
+    insert_event_preimages(e, d_val, base, pre + (uint64_t)(2 * r) * 96);
+    keys[2 * r] = e.key_low;
+    keys[2 * r + 1] = e.key_new;
+}
+
 __global__ void __launch_bounds__(BLOCK) k_find_low(const uint8_t* __restrict__ vals, const uint8_t* __restrict__ d_val,
                                                     const uint32_t* __restrict__ sorted, uint32_t M, uint32_t n,
                                                     uint64_t base, uint32_t part_mod, uint32_t part_res,
@@ -854,16 +867,33 @@ static hipError_t mixed_neighbours(hipStream_t s, Workspace& ws, const MixedWs& 
     return hipGetLastError();
 }
 
+static hipError_t mixed_tables(hipStream_t s, Workspace& ws, const uint8_t* d_val, const uint32_t* sorted_old, uint32_t* sorted_new,
+                               uint32_t M, uint32_t E, uint32_t n_ins, uint32_t* node, uint32_t* time, uint32_t* rs, uint32_t* re);
+
 hipError_t mixed_events(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* d_val, const uint32_t* sorted_old,
                         uint32_t* sorted_new, uint32_t M, uint32_t n, uint32_t n_ins, uint64_t base, uint8_t* pre,
                         uint32_t* node, uint32_t* time, uint32_t* rs, uint32_t* re, uint64_t* o_low_index,
                         uint8_t* o_is_largest, uint8_t* o_low_leaf, uint8_t* o_new_leaf, const ReadOut& rd) {
-    hipError_t e;
     if (n == 0 || n > ws.cap_n || n_ins > n) return hipErrorInvalidValue;
-    const uint32_t E = n + n_ins;
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_mixed_events, dim3(nblk(n)), dim3(BLOCK), 0, s, mx.flag, mx.rank, d_val, M, n, n_ins, base, ws.low,
                        ws.succ, pre, ws.keys, mx.erow, o_low_index, o_is_largest, o_low_leaf, o_new_leaf, rd);
+    return mixed_tables(s, ws, d_val, sorted_old, sorted_new, M, n + n_ins, n_ins, node, time, rs, re);
+}
+
+hipError_t mixed_insert_events(hipStream_t s, Workspace& ws, const uint8_t* d_val, const uint32_t* sorted_old, uint32_t* sorted_new,
+                               uint32_t M, uint32_t n_ins, uint64_t base, uint8_t* pre, uint32_t* node, uint32_t* time,
+                               uint32_t* rs, uint32_t* re) {
+    if (n_ins == 0 || n_ins > ws.cap_n) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_insert_events, dim3(nblk(n_ins)), dim3(BLOCK), 0, s, d_val, M, n_ins, base, ws.low, ws.succ, pre, ws.keys);
+    return mixed_tables(s, ws, d_val, sorted_old, sorted_new, M, 2 * n_ins, n_ins, node, time, rs, re);
+}
+
+// behind the event kernel of either: the keys sorted, the level-0 tables from them, the INSERTs merged into the index
+static hipError_t mixed_tables(hipStream_t s, Workspace& ws, const uint8_t* d_val, const uint32_t* sorted_old, uint32_t* sorted_new,
+                               uint32_t M, uint32_t E, uint32_t n_ins, uint32_t* node, uint32_t* time, uint32_t* rs, uint32_t* re) {
+    hipError_t e;
     size_t tb = ws.tmp_bytes;
     if ((e = rocprim::radix_sort_keys(ws.tmp, tb, ws.keys, ws.keys_sorted, (size_t)E, 0, 64, s)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_runs, dim3(nblk(E)), dim3(BLOCK), 0, s, ws.keys_sorted, E, node, time, rs, re);

@@ -114,6 +114,13 @@ hipError_t mixed_events(hipStream_t s, Workspace& ws, const MixedWs& mx, const u
                         uint32_t* sorted_new, uint32_t M, uint32_t n, uint32_t n_ins, uint64_t base, uint8_t* pre,
                         uint32_t* node, uint32_t* time, uint32_t* rs, uint32_t* re, uint64_t* o_low_index,
                         uint8_t* o_is_largest, uint8_t* o_low_leaf, uint8_t* o_new_leaf, const ReadOut& rd);
+// 3'. instead of 3, for a block that is applied without witnesses (imt_itree_apply_mixed), n_ins > 0: the events of the
+// INSERTs alone -- byte for byte the preimages pre[2 n_ins][96], level-0 tables [2 n_ins] and sorted_new[M + n_ins] that
+// run() leaves for an insertion-only batch of the INSERT values in their order, which is what apply_lists reads.  A READ
+// has no event; no output of either kind is written.
+hipError_t mixed_insert_events(hipStream_t s, Workspace& ws, const uint8_t* d_val, const uint32_t* sorted_old, uint32_t* sorted_new,
+                               uint32_t M, uint32_t n_ins, uint64_t base, uint8_t* pre, uint32_t* node, uint32_t* time,
+                               uint32_t* rs, uint32_t* re);
 
 // ---- witness-free insertion (imt_itree_apply_batch): the touched nodes of every level (imt_apply.hpp) ----
 // From the level-0 tables run() left ([total] each): lists.node rows 0 .. l0-1, lists.src and lists.count[0 .. depth].

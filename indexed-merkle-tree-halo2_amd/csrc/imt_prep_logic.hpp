@@ -141,6 +141,56 @@ IMT_PL_HD ReadAnswer read_neighbours(const uint8_t* x, uint32_t R, const uint8_t
     return a;
 }
 
+// ---- witness-free mixed blocks (imt_itree_apply_mixed): the events of the INSERTs alone ---------------------------------
+// Behind the checks low[r] / succ[r] hold, for the INSERT of rank r, its low leaf and that leaf's successor as of its
+// place in the block (rows of val, OP_NONE: no successor).  A READ changes no leaf, so the block's effect on the tree is
+// that of its INSERTs in order, and the INSERT of rank r has the two events an insertion-only batch of those values
+// gives it: event 2r rewrites the low leaf {low.val, v, base + M + r}, event 2r + 1 writes the new leaf M + r, which
+// inherits the low leaf's old pointers {v, succ.val, base + succ} ({v, 0, 0} above everything).  A key is
+// (leaf << 32) | event: sorted, the events of one leaf are a run in the order of the block.
+struct InsertEvent {
+    uint32_t low, succ;             // rows of val
+    uint32_t leaf;                  // the new leaf's row, M + r
+    uint64_t key_low, key_new;      // of events 2r and 2r + 1
+};
+IMT_PL_HD InsertEvent insert_event(uint32_t r, uint32_t M, const uint32_t* low, const uint32_t* succ) {
+    InsertEvent e;
+    e.low = low[r];
+    e.succ = succ[r];
+    e.leaf = M + r;
+    e.key_low = ((uint64_t)e.low << 32) | (uint64_t)(2 * r);
+    e.key_new = ((uint64_t)e.leaf << 32) | (uint64_t)(2 * r + 1);
+    return e;
+}
+// the two preimages of that INSERT, [2][3][32] canonical at `pre`.  Rows move as two 16-byte words, like every row the
+// preparation moves: val and pre are 16-byte aligned.
+struct alignas(16) Word128 { uint64_t lo, hi; };
+IMT_PL_HD void insert_event_preimages(const InsertEvent& e, const uint8_t* val, uint64_t base, uint8_t* pre) {
+    const Word128* v = reinterpret_cast<const Word128*>(val + (uint64_t)e.leaf * 32);
+    const Word128* lv = reinterpret_cast<const Word128*>(val + (uint64_t)e.low * 32);
+    Word128* o = reinterpret_cast<Word128*>(pre);       // 12 words: {low.val, v, leaf} {v, succ.val, succ}
+    const Word128 v0 = v[0], v1 = v[1], zero = {0, 0};
+    o[0] = lv[0];
+    o[1] = lv[1];
+    o[2] = v0;
+    o[3] = v1;
+    o[4] = Word128{base + e.leaf, 0};
+    o[5] = zero;
+    o[6] = v0;
+    o[7] = v1;
+    if (e.succ != OP_NONE) {
+        const Word128* sv = reinterpret_cast<const Word128*>(val + (uint64_t)e.succ * 32);
+        o[8] = sv[0];
+        o[9] = sv[1];
+        o[10] = Word128{base + e.succ, 0};
+    } else {
+        o[8] = zero;
+        o[9] = zero;
+        o[10] = zero;
+    }
+    o[11] = zero;
+}
+
 // ---- a mixed list replayed against the rows the tree stores (imt_itree_view_mixed_witness) ---------------------------
 // The list is the block as it went in at size S: its INSERT of rank r must be the value the tree holds at leaf S + r.
 // What is wrong with the operation at one position on its own: the op_value_class bits of its value and, for an INSERT,
