@@ -280,6 +280,7 @@ extern "C" {
     pub fn imt_itree_find_low_batch(t: *mut imt_itree, vals: *const c_void, n: usize, low_index: *mut u64, flags: c_uint) -> c_int;
     pub fn imt_itree_insert_filtered(t: *mut imt_itree, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, n_inserted: *mut u64, out: *const imt_insert_out, flags: c_uint) -> c_int;
     pub fn imt_itree_apply_batch(t: *mut imt_itree, vals: *const c_void, n: usize, root_out: *mut c_void, flags: c_uint) -> c_int;
+    pub fn imt_itree_apply_pipelined(t: *mut imt_itree, vals: *const c_void, n: usize, root_out: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_apply_filtered(t: *mut imt_itree, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, n_inserted: *mut u64, root_out: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_apply_stats(t: *mut imt_itree, hashes: *mut u64) -> c_int;
     pub fn imt_itree_rewind(t: *mut imt_itree, new_size: u64, root_out: *mut c_void, hashes: *mut u64, flags: c_uint) -> c_int;

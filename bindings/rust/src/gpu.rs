@@ -160,6 +160,40 @@ impl IndexedTree {
         })?;
         Ok(F::from_bytes_le(&r))
     }
+    /// `apply_batch` block after block with the blocks' hashing overlapped (`imt_itree_apply_pipelined`): what a follower
+    /// does that checks every block's root against its header.  Values and roots cross in one page-locked buffer the
+    /// GPU addresses; every block is enqueued as soon as its values are checked, one wait at the end.  Returns the root
+    /// after each block.  A refused block is the error: the blocks before it are in the tree, it and the ones behind it
+    /// are not.
+    pub fn apply_blocks<F: ScalarField>(&mut self, blocks: &[&[F]]) -> Result<Vec<F>, ImtError> {
+        let g = context().lock().unwrap();
+        let total: usize = blocks.iter().map(|b| b.len()).sum();
+        let bytes = (total + blocks.len()).max(1) * 32;
+        let mut buf: *mut c_void = std::ptr::null_mut();
+        check(&g, unsafe { imt_host_alloc(g.ctx, bytes, &mut buf) })?;
+        let mem = unsafe { std::slice::from_raw_parts_mut(buf as *mut u8, bytes) };
+        let roots_at = total * 32;
+        let (mut at, mut rc) = (0usize, IMT_OK);
+        for (k, b) in blocks.iter().enumerate() {
+            mem[at..at + b.len() * 32].copy_from_slice(&to_bytes(b));
+            rc = unsafe {
+                imt_itree_apply_pipelined(self.handle, mem[at..].as_ptr() as *const c_void, b.len(),
+                                          mem[roots_at + k * 32..].as_mut_ptr() as *mut c_void,
+                                          IMT_FMT_CANONICAL | IMT_DEVICE_PTRS | IMT_INPUTS_READY)
+            };
+            if rc != IMT_OK {
+                break;
+            }
+            at += b.len() * 32;
+        }
+        let first = check(&g, rc);                           // the message of the refusal, before anything replaces it
+        let synced = check(&g, unsafe { imt_ctx_sync(g.ctx) });
+        let roots = from_bytes(&mem[roots_at..roots_at + blocks.len() * 32]);
+        unsafe { imt_host_free(g.ctx, buf) };
+        first?;
+        synced?;
+        Ok(roots)
+    }
     /// hashes per level of the last `apply_batch`: `[0]` leaf hashes, `[l]` the hash2 calls that made level-l nodes
     pub fn apply_stats(&self) -> Result<Vec<u64>, ImtError> {
         let g = context().lock().unwrap();

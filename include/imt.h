@@ -494,11 +494,36 @@ int imt_itree_insert_filtered(imt_itree *t, const void *vals /*[n][32]*/, size_t
  * IMT_DEVICE_PTRS, may be NULL.  n == 0: IMT_OK, root_out = the current root.
  * IMT_FMT_*, IMT_DEVICE_PTRS, IMT_HOST_PREP and IMT_INPUTS_READY mean what they mean to imt_itree_insert_batch.  The call
  * runs on the context's stream behind every batch still in flight on the pipeline streams, later calls are ordered
- * behind it, and witness and apply calls may alternate freely on one tree; apply batches are not pipelined against each
- * other: IMT_PIPELINE -> IMT_ERR_ARG.  On a placed / partitioned tree the residue check and the global next_idx come
+ * behind it, and witness and apply calls may alternate freely on one tree; this call does not overlap with the one before:
+ * IMT_PIPELINE -> IMT_ERR_ARG, imt_itree_apply_pipelined below is the call that does.  On a placed / partitioned tree the residue check and the global next_idx come
  * with the shared preparation; only local nodes are written. */
 int imt_itree_apply_batch(imt_itree *t, const void *vals /*[n][32]*/, size_t n, void *root_out /*[32] or NULL*/,
                           unsigned flags);
+/* WITNESS-FREE BATCHES THAT OVERLAP, for the follower that applies block after block and checks every block's root: the
+ * tree after imt_itree_apply_batch(t, vals, n, ...) and nothing else -- same value checks, same error codes with the tree
+ * untouched, same index, size and stored nodes byte for byte -- but the call returns when the batch's values have been
+ * checked on the GPU, as imt_itree_insert_batch with IMT_PIPELINE does, and the hashing goes on running on one of the
+ * tree's pipeline streams behind the batches before it.  An apply batch is some 34 dependent launches of one hash's
+ * latency each; up to four consecutive batches now run them side by side, two launches apart (imt_apply_pipe.hpp has the
+ * rule and the reason it is two), each chain to the root hashed beside the others and only its store ordered.  A fifth
+ * call waits for the first (back-pressure, as for pipelined witness batches).
+ * IMT_DEVICE_PTRS is required (otherwise IMT_ERR_ARG, nothing changed): vals and root_out are device-addressable memory,
+ * 16-byte aligned -- a row of an imt_host_alloc buffer is fine -- and root_out ([32] in the flags' format, may be NULL)
+ * is complete after imt_ctx_sync(), like the outputs of a pipelined witness batch.  Every batch delivers its own root.
+ * IMT_FMT_*, IMT_INPUTS_READY and IMT_HOST_PREP mean what they mean to imt_itree_apply_batch; IMT_PIPELINE may be set and
+ * means nothing more.  Placement and value partition work as there, and the refusals are that call's: a NULL tree, NULL
+ * vals with n > 0, an unknown format, a misaligned row, sliced steps in flight, an open slice, an open sharded batch,
+ * IMT_ERR_FULL.  n == 0: IMT_OK, root_out = the current root, ordered behind everything in flight.  A refused batch
+ * (IMT_ERR_VALUE, IMT_ERR_NONCANONICAL, IMT_ERR_FULL) leaves alone the tree, the batches in flight and their roots.
+ * Every other call on the tree orders itself behind pipelined apply batches exactly as behind pipelined witness batches
+ * (queries, views, imt_itree_rewind, imt_itree_load*, imt_itree_root_lagged, un-pipelined batches of every kind, imt_sliced_*
+ * entry), and pipelined batches of either kind may follow each other in any order.  imt_itree_apply_stats reports the last
+ * apply call of either kind and waits for that call only.
+ * Which call at which block size: profiles/apply_pipelined.txt, README "Witness-free insertion".
+ * Not offered: pipelined forms of imt_itree_apply_filtered, _apply_mixed and _apply_mixed_filtered -- they read counts back
+ * per call, which is the wait this call exists to avoid. */
+int imt_itree_apply_pipelined(imt_itree *t, const void *vals /*[n][32]*/, size_t n, void *root_out /*[32] or NULL*/,
+                              unsigned flags);
 /* imt_itree_insert_filtered without witnesses: status / leaf_index / *n_inserted exactly as that call writes them, then
  * imt_itree_apply_batch of the accepted values.  Nothing accepted: IMT_OK, *n_inserted = 0, root_out = the current
  * root. */

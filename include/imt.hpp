@@ -388,7 +388,13 @@ public:
         c_->check(imt_itree_apply_batch(t_, vals.data(), vals.size(), &root, IMT_FMT_CANONICAL));
         return root;
     }
-    // hashes per level of the last apply_batch: [0] leaf hashes, [l] the hash2 calls that made level-l nodes
+    // apply_batch that overlaps with the batches before it (imt_itree_apply_pipelined): n values and the root's 32 bytes
+    // (or nullptr) in device-addressable memory, 16-byte aligned.  Returns when the values are checked; the root is
+    // complete after the context's sync().
+    void apply_pipelined(const void* device_vals, size_t n, void* device_root = nullptr) {
+        c_->check(imt_itree_apply_pipelined(t_, device_vals, n, device_root, IMT_FMT_CANONICAL | IMT_DEVICE_PTRS));
+    }
+    // hashes per level of the last apply call: [0] leaf hashes, [l] the hash2 calls that made level-l nodes
     std::vector<uint64_t> apply_stats() {
         std::vector<uint64_t> h(depth_ + 1);
         c_->check(imt_itree_apply_stats(t_, h.data()));

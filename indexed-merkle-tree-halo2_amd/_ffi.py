@@ -165,6 +165,7 @@ SIGNATURES = {
     "imt_itree_find_low_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
     "imt_itree_insert_filtered": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, P(c_u64), P(InsertOut), c_uint]),
     "imt_itree_apply_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
+    "imt_itree_apply_pipelined": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
     "imt_itree_apply_filtered": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, P(c_u64), c_void_p, c_uint]),
     "imt_itree_apply_stats": (c_int, [c_void_p, P(c_u64)]),
     "imt_itree_rewind": (c_int, [c_void_p, c_u64, c_void_p, P(c_u64), c_uint]),

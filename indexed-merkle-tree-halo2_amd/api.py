@@ -715,6 +715,18 @@ class IndexedTree:
         self.ctx._check(rc)
         return to_int(root)
 
+    def apply_pipelined(self, device_ptr, n, root_ptr=None, fmt=0, inputs_ready=False):
+        """apply_batch() of n values already in device-addressable memory (16-byte aligned) that overlaps with the batches
+        before it (imt_itree_apply_pipelined): returns once the values are checked, the hashing runs on behind.  The root
+        after the batch goes to root_ptr (32 device-addressable bytes, or None) and is complete after ctx.sync().  A
+        refused value raises ValueError; the tree and the batches in flight are then as they were."""
+        flags = fmt | _ffi.DEVICE_PTRS | (_ffi.INPUTS_READY if inputs_ready else 0)
+        rc = lib.imt_itree_apply_pipelined(self.h, ctypes.c_void_p(device_ptr), n,
+                                           ctypes.c_void_p(root_ptr) if root_ptr is not None else None, flags)
+        if rc == _ffi.ERR["VALUE"]:
+            raise ValueError(lib.imt_last_error(self.ctx.h).decode())
+        self.ctx._check(rc)
+
     def apply_filtered(self, vals, host_prep=False):
         """insert_filtered() without witnesses (imt_itree_apply_filtered): (status, leaf_index, n_inserted, root)."""
         v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))

@@ -11,6 +11,7 @@
 #include "imt_prep.hpp"
 #include "imt_prep_logic.hpp"
 #include "imt_filter_logic.hpp"
+#include "imt_apply_pipe.hpp"
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -99,9 +100,15 @@ struct PlanSet {
     uint8_t* d_root = nullptr;           // stored root right after this batch (device format)
     bool has_root = false;
     hipEvent_t done = nullptr;           // recorded after the batch's last kernel
-    hipEvent_t wb_done[IMT_MAX_DEPTH + 1] = {nullptr};   // recorded after k_writeback of each level
+    // [l]: stored level l is final and this batch no longer reads it (imt_apply_pipe.hpp) -- after k_writeback of the
+    // level for a witness batch, after the launch that reads the level for a pipelined apply batch
+    hipEvent_t wb_done[IMT_MAX_DEPTH + 1] = {nullptr};
     bool in_flight = false;
-    bool pipelined = false;              // ran on a pipeline stream (IMT_PIPELINE)
+    bool pipelined = false;              // ran on a pipeline stream (IMT_PIPELINE, imt_itree_apply_pipelined)
+    bool applied = false;                // ... as an apply batch: which events it recorded, and when
+    // a tree's plan sets only (imt_itree_new), kept when the set grows: what a pipelined apply batch must not share
+    uint64_t* d_count = nullptr;         // [IMT_MAX_DEPTH + 1] its hashes per level, sizing its launches on the device
+    uint8_t* d_chain = nullptr;          // [IMT_MAX_DEPTH + 1][32] node 0 of the levels from its L0 up, before they are stored
     unsigned l0 = 0;                     // its L0
     uint8_t* d_canon = nullptr;          // [E/2][32] canonical copy of the batch's values when they arrive in another format
     // a time slice of a multi-GPU step (imt_itree_slice_*): prepared here, hashed unit by unit on the caller's streams
@@ -165,6 +172,7 @@ struct imt_itree {
     // IMT_PIPELINE: consecutive batches rotate over NPIPE internal streams and run one level
     // apart (batch k+1 sweeps level l once batch k has written level l back), so up to NPIPE hash
     // kernels share the GPU and the SIMDs see several times the waves of a single 2^16 batch.
+    // imt_itree_apply_pipelined rotates over the same streams, two launches apart (imt_apply_pipe.hpp).
     hipStream_t pipe_stream[NPIPE] = {};
     hipEvent_t user_mark = nullptr;  // position of the context's stream when a pipelined call starts
     bool pipe_pending = false;       // pipelined work the context's stream has not been ordered behind
@@ -193,6 +201,8 @@ struct imt_itree {
     // imt_itree_apply_batch: hashes per level of the last apply call, written by its kernels (imt_itree_apply_stats)
     uint64_t* d_apply_stats = nullptr;       // [IMT_MAX_DEPTH + 1]
     bool apply_seen = false;
+    // imt_itree_apply_pipelined keeps them in its plan set: the set of the last apply call if that was a pipelined one
+    const PlanSet* apply_stats_set = nullptr;
     uint64_t* d_rewind_stats = nullptr;      // [IMT_MAX_DEPTH + 1]: the same of the last imt_itree_rewind
     uint64_t gen = 0;                        // bumped by every call that changes the contents: what a view's side table is for
 };
@@ -251,6 +261,8 @@ static void plan_free(PlanSet& p) {
     keep.done = p.done;
     keep.prep_done = p.prep_done;
     for (int l = 0; l <= IMT_MAX_DEPTH; l++) keep.wb_done[l] = p.wb_done[l];
+    keep.d_count = p.d_count;
+    keep.d_chain = p.d_chain;
     p = keep;
 }
 
@@ -347,6 +359,8 @@ extern "C" void imt_itree_free(imt_itree* t) {
         if (p.prep_done) hipEventDestroy(p.prep_done);
         for (auto& e : p.wb_done)
             if (e) hipEventDestroy(e);
+        if (p.d_count) hipFree(p.d_count);
+        if (p.d_chain) hipFree(p.d_chain);
     }
     if (t->up_done) hipEventDestroy(t->up_done);
     if (t->up_stream) hipStreamDestroy(t->up_stream);
@@ -435,12 +449,18 @@ extern "C" int imt_itree_new(imt_ctx* c, unsigned depth, uint64_t capacity, imt_
                 return c->hip_fail(e, "hipEventCreate");
             }
     }
-    for (auto& pl : t->plan)
+    for (auto& pl : t->plan) {
         for (unsigned l = 0; l <= depth; l++)
             if ((e = hipEventCreateWithFlags(&pl.wb_done[l], hipEventDisableTiming)) != hipSuccess) {
                 imt_itree_free(t);
                 return c->hip_fail(e, "hipEventCreate");
             }
+        if ((e = hipMalloc((void**)&pl.d_count, (IMT_MAX_DEPTH + 1) * 8)) != hipSuccess ||
+            (e = hipMalloc((void**)&pl.d_chain, (IMT_MAX_DEPTH + 1) * 32)) != hipSuccess) {
+            imt_itree_free(t);
+            return c->hip_fail(e, "imt_itree_new allocation");
+        }
+    }
     if ((e = hipMemsetAsync(t->d_val, 0, 32, c->stream)) != hipSuccess ||          // leaf 0: the sentinel value 0
         (e = hipMemsetAsync(t->d_sorted[0], 0, 4, c->stream)) != hipSuccess ||     // sorted index = [leaf 0]
         (e = hipMemcpyAsync(t->d_off, t->h_off.data(), (depth + 1) * 8, hipMemcpyHostToDevice, c->stream)) != hipSuccess ||
@@ -1572,6 +1592,22 @@ struct ApplyReq {
     void* root_out;
 };
 static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, uint64_t* count);
+static int apply_hashes_pipelined(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, const PlanSet* prev);
+
+// The order between consecutive batches on the pipeline streams (imt_apply_pipe.hpp): launch x of a batch of `kind`
+// waits for the event of the batch in front that the rule names, and records the event the rule names.
+static int pipe_wait(imt_itree* t, hipStream_t s, const PlanSet* prev, apipe::Kind kind, unsigned L0, apipe::Launch x) {
+    if (!prev) return IMT_OK;
+    const apipe::Event e = apipe::waits(prev->applied ? apipe::APPLY : apipe::WITNESS, prev->l0, kind, L0, t->depth, x);
+    if (e.type == apipe::EV_NONE) return IMT_OK;
+    IMT_HIP(t->ctx, hipStreamWaitEvent(s, e.type == apipe::EV_LEVEL ? prev->wb_done[e.l] : prev->done, 0));
+    return IMT_OK;
+}
+static int pipe_record(imt_itree* t, hipStream_t s, PlanSet& P, apipe::Kind kind, unsigned L0, apipe::Launch x) {
+    const apipe::Event e = apipe::records(kind, L0, t->depth, x);
+    if (e.type == apipe::EV_LEVEL) IMT_HIP(t->ctx, hipEventRecord(P.wb_done[e.l], s));
+    return IMT_OK;
+}
 
 // The hashing of imt_itree_insert_batch on stream s, behind the preparation: leaf hashes, index phase (no hashing), then
 // the hash sweep level by level with each level's write-back.  prev: the batch before this one if it is still on a
@@ -1583,30 +1619,32 @@ static int witness_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, uns
     int pf = c->prof_begin(IMT_PROF_INDEX, s);
     index_phase(P, s, E, L0, nullptr);
     c->prof_end(pf, s);
+    int rc;
     for (unsigned l = 0; l < L0; l++) {
         // stored level l must hold the previous batch's final versions: its write-back of that level,
         // or (at and above its L0) its top kernel
-        if (prev) IMT_HIP(c, hipStreamWaitEvent(s, l < prev->l0 ? prev->wb_done[l] : prev->done, 0));
+        if ((rc = pipe_wait(t, s, prev, apipe::WITNESS, L0, {apipe::WI_LEVEL, l}))) return rc;
         sweep_one_level(t, P, s, l, E, d, lay, fmt);
         pf = c->prof_begin(IMT_PROF_WRITEBACK, s);
         launch::writeback(s, P.d_val[l & 1], P.level(l).from, P.level(l).nodeb, t->nodes(l), (uint32_t)E);
         c->prof_end(pf, s);
-        if (pipelined) IMT_HIP(c, hipEventRecord(P.wb_done[l], s));
+        if (pipelined && (rc = pipe_record(t, s, P, apipe::WITNESS, L0, {apipe::WI_LEVEL, l}))) return rc;
     }
     auto old_root = [&]() -> int {
-        if (prev) IMT_HIP(c, hipStreamWaitEvent(s, prev->done, 0));
+        const int r = pipe_wait(t, s, prev, apipe::WITNESS, L0, {apipe::WI_OLD_ROOT, 0});
+        if (r) return r;
         read_old_root(t, s, d, fmt);
         return IMT_OK;
     };
-    int rc;
     for (unsigned l = L0; l < t->depth; l++) {
         if (l + 1 == t->depth && (rc = old_root())) return rc;
         // the previous batch stored node l + 1 (and node l, at its own L0) from its launch of this level
-        if (prev) IMT_HIP(c, hipStreamWaitEvent(s, l >= prev->l0 ? prev->wb_done[l] : prev->done, 0));
+        if ((rc = pipe_wait(t, s, prev, apipe::WITNESS, L0, {apipe::WI_UPPER, l}))) return rc;
         sweep_one_upper(t, P, s, l, E, L0, d, lay, fmt);
-        if (pipelined) IMT_HIP(c, hipEventRecord(P.wb_done[l], s));
+        if (pipelined && (rc = pipe_record(t, s, P, apipe::WITNESS, L0, {apipe::WI_UPPER, l}))) return rc;
     }
     if (L0 == t->depth && (rc = old_root())) return rc;
+    if ((rc = pipe_wait(t, s, prev, apipe::WITNESS, L0, {apipe::WI_ROOTS, 0}))) return rc;
     finish_roots(t, P, s, E, L0, d, fmt);
     return IMT_OK;
 }
@@ -1758,13 +1796,19 @@ static int insert_core(imt_itree* t, const void* vals, unsigned val_flags, size_
         return IMT_ERR_HIP;
     // a placed tree writes rows [0, depth) of sibling arrays dimensioned for global_depth levels
     const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->global_depth} : launch::SibLayout{sib_stride, 1};
-    rc = apply ? apply_hashes(t, P, s, E, L0, t->d_apply_stats) : witness_hashes(t, P, s, E, L0, prev, pipelined, d, lay, fmt);
+    rc = !apply      ? witness_hashes(t, P, s, E, L0, prev, pipelined, d, lay, fmt)
+         : pipelined ? apply_hashes_pipelined(t, P, s, E, L0, prev)       // its store of the chain fills P.d_root as well
+                     : apply_hashes(t, P, s, E, L0, t->d_apply_stats);
     if (rc) return rc;
-    if (apply) t->apply_seen = true;
-    IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
+    if (apply) {
+        t->apply_seen = true;
+        t->apply_stats_set = pipelined ? &P : nullptr;
+    }
+    if (!(apply && pipelined)) IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
     P.has_root = true;
     IMT_HIP(c, hipEventRecord(P.done, s));
     P.pipelined = pipelined;
+    P.applied = apply && pipelined;
     P.sliced = false;
     P.l0 = L0;
     P.in_flight = true;
@@ -1845,6 +1889,43 @@ static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsig
     return IMT_OK;
 }
 
+// The same hashing for imt_itree_apply_pipelined, on pipeline stream s with the batch in front (prev, if it is still on a
+// pipeline stream) possibly two launches ahead.  What differs from apply_hashes: every launch that writes a stored level
+// first waits for the event imt_apply_pipe.hpp names -- an apply batch in front reads level l in the launch AFTER the one
+// that wrote it -- and records its own; the counts are the plan set's; and the chain to the root is hashed into the plan
+// set's rows (k_apply_chain), beside the chains of the batches in front, with only the store of those rows into the tree
+// and into P.d_root ordered behind them.
+static int apply_hashes_pipelined(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, const PlanSet* prev) {
+    imt_ctx* c = t->ctx;
+    const apply::Lists lists{P.d_nodeb, P.d_timen, P.d_count, P.cap_events};
+    int rc, pf = c->prof_begin(IMT_PROF_APPLY_LISTS, s);
+    IMT_HIP(c, prep::apply_lists(s, P.ws.tmp, P.ws.tmp_bytes, P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][3], (uint32_t)E, L0,
+                                 t->depth, P.d_from, lists));
+    c->prof_end(pf, s);
+    if ((rc = pipe_wait(t, s, prev, apipe::APPLY, L0, {apipe::AP_LEVEL, 0}))) return rc;
+    pf = c->prof_begin(IMT_PROF_APPLY_LEAVES, s);
+    launch::apply_leaves(s, lists.count, apply::bound((uint32_t)E, L0, 0), lists.node, lists.src, P.d_pre, IMT_FMT_CANONICAL,
+                         c->d_err, t->nodes(0), t->h_len[0], c->coop_max_events);
+    c->prof_end(pf, s);
+    for (unsigned l = 0; l + 1 < L0; l++) {
+        if ((rc = pipe_wait(t, s, prev, apipe::APPLY, L0, {apipe::AP_LEVEL, l + 1}))) return rc;
+        pf = c->prof_begin(IMT_PROF_APPLY_LEVEL, s);
+        launch::apply_level(s, lists.count + l + 1, apply::bound((uint32_t)E, L0, l + 1), P.level(l + 1).nodeb,
+                            t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, t->nodes(l + 1), t->h_len[l + 1],
+                            c->coop_max_events);
+        c->prof_end(pf, s);
+        if ((rc = pipe_record(t, s, P, apipe::APPLY, L0, {apipe::AP_LEVEL, l + 1}))) return rc;
+    }
+    if ((rc = pipe_wait(t, s, prev, apipe::APPLY, L0, {apipe::AP_CHAIN, 0}))) return rc;
+    pf = c->prof_begin(IMT_PROF_APPLY_TOP, s);
+    launch::apply_chain(s, t->d_nodes, t->d_off, t->d_len, c->d_zero, P.d_chain, L0 - 1, t->depth);
+    c->prof_end(pf, s);
+    if ((rc = pipe_record(t, s, P, apipe::APPLY, L0, {apipe::AP_CHAIN, 0}))) return rc;
+    if ((rc = pipe_wait(t, s, prev, apipe::APPLY, L0, {apipe::AP_STORE, 0}))) return rc;
+    launch::apply_chain_store(s, P.d_chain, t->d_nodes, t->d_off, L0, t->depth, P.d_root);
+    return IMT_OK;
+}
+
 extern "C" int imt_itree_insert_batch(imt_itree* t, const void* vals, size_t n, const imt_insert_out* out,
                                       unsigned flags) {
     return insert_call(t, vals, n, out, flags, nullptr);
@@ -1861,6 +1942,19 @@ extern "C" int imt_itree_apply_batch(imt_itree* t, const void* vals, size_t n, v
     return insert_call(t, vals, n, nullptr, flags, &req);
 }
 
+// Witness-free batches that overlap (imt.h): imt_itree_apply_batch's checks, preparation and commit, the hashing on one
+// of the tree's pipeline streams behind the batches in front (apply_hashes_pipelined).
+extern "C" int imt_itree_apply_pipelined(imt_itree* t, const void* vals, size_t n, void* root_out, unsigned flags) {
+    if (!t) return IMT_ERR_ARG;
+    if (!(flags & IMT_DEVICE_PTRS)) return t->ctx->fail(IMT_ERR_ARG, "imt_itree_apply_pipelined needs device pointers (IMT_DEVICE_PTRS)");
+    if (n == 0) {
+        IMT_NOT_SLICED(t);
+        return root_out ? imt_itree_root(t, root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS)) : IMT_OK;
+    }
+    const ApplyReq req{root_out};
+    return insert_call(t, vals, n, nullptr, flags | IMT_PIPELINE, &req);
+}
+
 extern "C" int imt_itree_apply_stats(imt_itree* t, uint64_t* hashes) {
     if (!t || !hashes) return IMT_ERR_ARG;
     imt_ctx* c = t->ctx;
@@ -1868,8 +1962,14 @@ extern "C" int imt_itree_apply_stats(imt_itree* t, uint64_t* hashes) {
     if (!t->apply_seen) return c->fail(IMT_ERR_ARG, "no apply call has inserted anything into this tree");
     int rc = c->set_device();
     if (rc) return rc;
-    // the apply call ran on the context's stream, which is therefore behind its last kernel
-    IMT_HIP(c, hipMemcpyAsync(hashes, t->d_apply_stats, (t->depth + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    // the apply call ran on the context's stream, which is therefore behind its last kernel -- or on a pipeline stream
+    // with its counts in its plan set, and then this waits for that batch and for none of those behind it
+    const uint64_t* src = t->d_apply_stats;
+    if (t->apply_stats_set) {
+        src = t->apply_stats_set->d_count;
+        IMT_HIP(c, hipStreamWaitEvent(c->stream, t->apply_stats_set->done, 0));
+    }
+    IMT_HIP(c, hipMemcpyAsync(hashes, src, (t->depth + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     IMT_HIP(c, hipStreamSynchronize(c->stream));
     return IMT_OK;
 }
@@ -2146,6 +2246,7 @@ static int apply_mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, con
     IMT_HIP(c, hipStreamWaitEvent(s, t->up_done, 0));
     if ((rc = apply_hashes(t, P, s, E, L0, t->d_apply_stats))) return rc;
     t->apply_seen = true;
+    t->apply_stats_set = nullptr;
     if ((rc = mixed_commit(t, P, s, n_ins, L0))) return rc;
 
     // ---- outputs ----
@@ -3581,6 +3682,7 @@ extern "C" int imt_itree_slice_unit(imt_itree* t, int slice, unsigned unit, void
         IMT_HIP(c, hipEventRecord(P.done, s));
         P.in_flight = true;
         P.pipelined = true;         // not on the context's stream: join_top orders that stream behind it
+        P.applied = false;
         P.l0 = 0;                   // no per-level events were recorded: a pipelined batch that follows waits for `done`
         t->pipe_pending = true;
         P.open = false;

@@ -1105,8 +1105,9 @@ struct ViewLevel {
 //           this runs (it was written by the launch before); a child outside the stored prefix is the empty subtree of
 //           height l, by the rule k_sweep and k_gather_proof use.
 // The launch is sized by a host-side bound; the count of the list is a device word (the call does not wait for it).
-// An apply batch runs alone on its stream (imt.h: not pipelined), so like k_tree_level this kernel owns its copy of the
-// hash body without sharing the instruction cache with another one.
+// Like k_tree_level this kernel owns its copy of the hash body.  Under imt_itree_apply_pipelined up to NPIPE batches run
+// it side by side on their own streams, one copy of the code between them; what keeps a batch from overwriting a level
+// the one in front still reads is the order of the launches (imt_apply_pipe.hpp), nothing in here.
 // -----------------------------------------------------------------------------------------------
 __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_apply_level(launch::ApplyArgs a) {
     __shared__ uint32_t stash[NL][BLOCK];
@@ -1142,29 +1143,76 @@ __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_apply_level_coop(launc
 #endif
 }
 
+// The chain of node 0 above the occupied part of a tree, levels [from, to): node 0 of level l + 1 = hash2(node 0 of
+// level l, its right sibling) -- `first_sib` at level `from`, the empty subtree of that height above.  Dependent hashes,
+// so one quad runs them (k_zero_chain is the model); store(l + 1) is where a link goes.  The body of k_apply_top,
+// k_apply_chain and k_view_top, which differ in where the first two nodes come from and where the links go.
+#if defined(__HIP_DEVICE_COMPILE__)
+template <class Store>
+__device__ __forceinline__ void node0_chain_quad(uint32_t* tab, const uint8_t* first, const uint8_t* first_sib,
+                                                 const uint8_t* __restrict__ zero, unsigned from, unsigned to, Store store) {
+    coop::tab_fill(tab, g_pc);                       // before anyone leaves: it ends in a barrier
+    if (blockIdx.x != 0 || threadIdx.x >= 4) return;
+    const unsigned role = threadIdx.x, ri = role == 3u ? 0u : role;
+    Fe cur;
+    load_packed(cur, first);
+#pragma unroll 1
+    for (unsigned l = from; l < to; l++) {
+        Fe z, X, o;
+        load_packed(z, l == from ? first_sib : zero + (size_t)l * 32);
+        coop::sel(X, ri == 2u, z, cur);              // lane 1: node 0, lane 2: its right sibling
+        coop::hash23(tab, o, X, X, false, ri);
+        coop::quad_bcast<1>(cur, o);
+        if (role == 1u) store_packed(store(l + 1), cur);
+    }
+}
+// node 0 and its right sibling at stored level `from`: stored node 1 (the other half of the occupied tree) where the
+// level has one, the empty subtree of that height where it does not
+struct StoredPair {
+    const uint8_t *first, *sib;
+    __device__ __forceinline__ StoredPair(const uint8_t* nodes, const uint64_t* off, const uint64_t* len, const uint8_t* zero,
+                                          unsigned from)
+        : first(nodes + off[from] * 32), sib(len[from] > 1 ? nodes + (off[from] + 1) * 32 : zero + (size_t)from * 32) {}
+};
+#endif
+
 // Levels [from, to), from = l0 - 1: the batch's only node of every level above is node 0.  Its right sibling is stored
-// node 1 at level l0 - 1 (the other half of the occupied tree) and the empty subtree of that height from l0 up.  A chain
-// of dependent hashes, so one quad runs it (k_zero_chain is the model); every link goes to the stored tree, the last one
-// is the root.
+// node 1 at level l0 - 1 and the empty subtree of that height from l0 up.  Every link goes to the stored tree, the last
+// one is the root.
 __global__ IMT_HASH_WAVES void k_apply_top(uint8_t* nodes, const uint64_t* __restrict__ off, const uint64_t* __restrict__ len,
                                            const uint8_t* __restrict__ zero, unsigned from, unsigned to) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ uint32_t tab[coop::TAB_DWORDS];
-    coop::tab_fill(tab, g_pc);
-    if (blockIdx.x != 0 || threadIdx.x >= 4) return;
-    const unsigned role = threadIdx.x, ri = role == 3u ? 0u : role;
-    Fe cur;
-    load_packed(cur, nodes + off[from] * 32);
-#pragma unroll 1
-    for (unsigned l = from; l < to; l++) {
-        Fe z, X, o;
-        load_packed(z, l == from && len[l] > 1 ? nodes + (off[l] + 1) * 32 : zero + (size_t)l * 32);
-        coop::sel(X, ri == 2u, z, cur);              // lane 1: node 0, lane 2: its right sibling
-        coop::hash23(tab, o, X, X, false, ri);
-        coop::quad_bcast<1>(cur, o);
-        if (role == 1u) store_packed(nodes + off[l + 1] * 32, cur);
-    }
+    const StoredPair p(nodes, off, len, zero, from);
+    node0_chain_quad(tab, p.first, p.sib, zero, from, to, [&](unsigned l) { return nodes + off[l] * 32; });
 #endif
+}
+
+// The same chain for a pipelined apply batch (imt_itree_apply_pipelined, imt_apply_pipe.hpp): every link into row l + 1
+// of `chain`, which the batch's plan set owns, and none into the tree -- so the dependent hashes of consecutive batches
+// run side by side, and only k_apply_chain_store below is ordered behind the batch in front.  Reads stored level `from`,
+// nodes 0 and 1, and nothing else of the tree.
+__global__ IMT_HASH_WAVES void k_apply_chain(const uint8_t* __restrict__ nodes, const uint64_t* __restrict__ off,
+                                             const uint64_t* __restrict__ len, const uint8_t* __restrict__ zero,
+                                             uint8_t* __restrict__ chain, unsigned from, unsigned to) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __shared__ uint32_t tab[coop::TAB_DWORDS];
+    const StoredPair p(nodes, off, len, zero, from);
+    node0_chain_quad(tab, p.first, p.sib, zero, from, to, [&](unsigned l) { return chain + (size_t)l * 32; });
+#endif
+}
+
+// Rows [from, to] of such a chain into node 0 of stored levels from .. to, the last one (the root) into `root` as well.
+// One dword per thread: (to - from + 1) * 8 <= 264 of them.
+__global__ void __launch_bounds__(BLOCK) k_apply_chain_store(const uint32_t* __restrict__ chain, uint32_t* __restrict__ nodes,
+                                                             const uint64_t* __restrict__ off, unsigned from, unsigned to,
+                                                             uint32_t* __restrict__ root) {
+    const size_t t = gtid();
+    const unsigned l = from + (unsigned)(t >> 3), w = (unsigned)t & 7u;
+    if (l > to) return;
+    const uint32_t x = chain[(size_t)l * 8 + w];
+    nodes[off[l] * 8 + w] = x;
+    if (l == to) root[w] = x;
 }
 
 // -----------------------------------------------------------------------------------------------
@@ -1212,22 +1260,10 @@ __global__ IMT_HASH_WAVES void __launch_bounds__(BLOCK) k_view_level_coop(launch
 __global__ IMT_HASH_WAVES void k_view_top(view::Side sd, launch::TreeView tv, uint8_t* chain, unsigned from, unsigned to) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ uint32_t tab[coop::TAB_DWORDS];
-    coop::tab_fill(tab, g_pc);
-    if (blockIdx.x != 0 || threadIdx.x >= 4) return;
-    const unsigned role = threadIdx.x, ri = role == 3u ? 0u : role;
     const uint8_t* stored = tv.nodes + tv.off[from] * 32;
-    Fe cur;
-    load_packed(cur, view::node_row(sd, from, 0, stored, tv.len[from], tv.zero + (size_t)from * 32));
-#pragma unroll 1
-    for (unsigned l = from; l < to; l++) {
-        Fe z, X, o;
-        load_packed(z, l == from ? view::node_row(sd, from, 1, stored, tv.len[from], tv.zero + (size_t)from * 32)
-                                 : tv.zero + (size_t)l * 32);
-        coop::sel(X, ri == 2u, z, cur);              // lane 1: node 0, lane 2: its right sibling
-        coop::hash23(tab, o, X, X, false, ri);
-        coop::quad_bcast<1>(cur, o);
-        if (role == 1u) store_packed(chain + (size_t)(l + 1) * 32, cur);
-    }
+    const uint8_t* zf = tv.zero + (size_t)from * 32;
+    node0_chain_quad(tab, view::node_row(sd, from, 0, stored, tv.len[from], zf), view::node_row(sd, from, 1, stored, tv.len[from], zf),
+                     tv.zero, from, to, [&](unsigned l) { return chain + (size_t)l * 32; });
 #endif
 }
 
@@ -1822,6 +1858,17 @@ void apply_top(hipStream_t s, uint8_t* nodes, const uint64_t* off, const uint64_
                unsigned to) {
     if (from >= to) return;
     hipLaunchKernelGGL(k_apply_top, dim3(1), dim3(64), 0, s, nodes, off, len, zero, from, to);
+}
+void apply_chain(hipStream_t s, const uint8_t* nodes, const uint64_t* off, const uint64_t* len, const uint8_t* zero,
+                 uint8_t* chain, unsigned from, unsigned to) {
+    if (from >= to) return;
+    hipLaunchKernelGGL(k_apply_chain, dim3(1), dim3(64), 0, s, nodes, off, len, zero, chain, from, to);
+}
+void apply_chain_store(hipStream_t s, const uint8_t* chain, uint8_t* nodes, const uint64_t* off, unsigned from, unsigned to,
+                       uint8_t* root) {
+    if (from > to) return;
+    hipLaunchKernelGGL(k_apply_chain_store, dim3(nblk((size_t)(to - from + 1) * 8)), dim3(BLOCK), 0, s, (const uint32_t*)chain,
+                       (uint32_t*)nodes, off, from, to, (uint32_t*)root);
 }
 // the two forms of k_view_level, chosen as launch_apply chooses
 static void launch_view(hipStream_t s, const ViewArgs& a, uint32_t coop_max) {

@@ -205,6 +205,13 @@ void apply_level(hipStream_t s, const uint64_t* count, uint32_t bound, const uin
 // stored node 1 at level `from`, zero[l] above.  off / len: the tree's device arrays.  One quad.
 void apply_top(hipStream_t s, uint8_t* nodes, const uint64_t* off, const uint64_t* len, const uint8_t* zero, unsigned from,
                unsigned to);
+// the same chain into rows from + 1 .. to of `chain` ([depth + 1][32], the caller's) with nothing written to the tree,
+// and rows [from, to] of such a chain into node 0 of stored levels from .. to, row `to` also into root[32]
+// (imt_itree_apply_pipelined: the hashes of consecutive batches overlap, only the store is ordered)
+void apply_chain(hipStream_t s, const uint8_t* nodes, const uint64_t* off, const uint64_t* len, const uint8_t* zero,
+                 uint8_t* chain, unsigned from, unsigned to);
+void apply_chain_store(hipStream_t s, const uint8_t* chain, uint8_t* nodes, const uint64_t* off, unsigned from, unsigned to,
+                       uint8_t* root);
 
 // ---- a view of the tree at an earlier size (imt_view.hpp): the same hashes into a side table, the tree only read ----
 // argument block of k_view_level: ApplyArgs with another store address -- listed node j goes to out + j * 32 -- and, for a
