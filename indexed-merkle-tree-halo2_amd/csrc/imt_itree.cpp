@@ -551,12 +551,24 @@ static int ensure_device_index(imt_itree* t) {
 
 // ------------------------------------------------------------------------------------
 // The stages the ways into the tree are built from.  A batch enters through imt_itree_insert_batch / _apply_batch,
-// through _insert_filtered / _apply_filtered, through _batch_begin (sharded) or through _slice_prepare + _slice_unit
-// (sliced); each of those is a sequence of the stages below and of what is its own.  None of the stages asks who calls.
+// through _insert_filtered / _apply_filtered, through _mixed_batch / _apply_mixed and their filtered twins, through
+// _batch_begin (sharded) or through _slice_prepare + _slice_unit (sliced), and a view replays what went in
+// (_view_insert_witness, _view_mixed_witness); each of those is a sequence of the stages below -- of the two schedules
+// witness_sweep and apply_hashes above all -- and of what is its own.  None of the stages asks who calls.
 // ------------------------------------------------------------------------------------
 struct HostTimer {      // host milliseconds since it was made
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// Context scratch slots [first, last] borrowed for one bulk call -- a copy or a workspace as large as the tree: given back
+// when the call returns if they have grown beyond 64 MiB (the callers wait for the stream before they return).
+struct ScratchTrim {
+    imt_ctx* c;
+    size_t first, last;
+    ~ScratchTrim() {
+        for (size_t slot = first; slot <= last; slot++) c->trim_scratch(slot, (size_t)64 << 20);
+    }
 };
 
 // A host wait with a time limit (limit_ms <= 0: wait as long as it takes): the sliced mode's waits stand behind work
@@ -1084,10 +1096,7 @@ extern "C" int imt_itree_load(imt_itree* t, const void* preimages, uint64_t n, u
     IMT_HIP(c, hipStreamSynchronize(t->up_stream));
     hipStream_t s = c->stream;
     // the snapshot copy and the sort workspace are as large as the tree: not something a context keeps after the call
-    struct Trim {
-        imt_ctx* c;
-        ~Trim() { c->trim_scratch(2, (size_t)64 << 20); c->trim_scratch(3, (size_t)64 << 20); }
-    } trim{c};
+    const ScratchTrim trim{c, 2, 3};
     // ---- the canonical preimages on the device (what is hashed; next_idx fields are global indices) ----
     const uint8_t* d_pre = (const uint8_t*)preimages;
     if (!dev || fmt != IMT_FMT_CANONICAL) {
@@ -1187,10 +1196,7 @@ extern "C" int imt_itree_load_values(imt_itree* t, const void* vals, uint64_t n,
         if (pl.in_flight) { IMT_HIP(c, hipEventSynchronize(pl.done)); pl.in_flight = false; pl.pipelined = false; }
     IMT_HIP(c, hipStreamSynchronize(t->up_stream));
     hipStream_t s = c->stream;
-    struct Trim {
-        imt_ctx* c;
-        ~Trim() { c->trim_scratch(2, (size_t)64 << 20); c->trim_scratch(3, (size_t)64 << 20); }
-    } trim{c};
+    const ScratchTrim trim{c, 2, 3};
     const size_t ws_bytes = prep::load_values_ws_bytes((size_t)n);
     uint8_t* ws = (uint8_t*)c->dev_scratch(3, ws_bytes + 256);      // [error word, offending position | 256-byte aligned workspace]
     if (!ws) return IMT_ERR_HIP;
@@ -1543,45 +1549,90 @@ int gpu_prepare(imt_itree* t, PlanSet& P, const void* vals, unsigned val_flags, 
     return insertion_verdict(t, *t->h_err_pin, "batch");
 }
 
+// The pipeline context of a batch's hashing (imt_apply_pipe.hpp); the defaults are "on the context's stream, alone"
+struct PipeCtx {
+    const PlanSet* prev = nullptr;        // the batch in front, if it is still on a pipeline stream: whose events are waited for
+    bool pipelined = false;               // this batch is on a pipeline stream and records its own per-level events
+};
+// What a witness sweep is run for: an insertion batch into the live tree (all defaults), a mixed batch (route), a replay
+// through a view (side, the view's root, nothing stored), or both.  Plain data, read by the steps below.
+struct WitnessSweep {
+    const launch::MixedRoute* route = nullptr;    // NULL: event e fills the rows of insertion e / 2; else erow says whose
+    size_t n_ins = 0;                             // with a route: the INSERTs among the operations,
+    uint8_t* read_root = nullptr;                 // and the READs' roots (NULL: not wanted)
+    const view::Side* side = nullptr;             // NULL: base siblings below L0 are read from the stored tree as it is
+    bool store = true;                            // levels written back, the nodes from L0 up and the root stored
+    const uint8_t* view_root = nullptr;           // NULL: old_root[0] is the stored root; else the root in a view's chain
+    PipeCtx pipe;                                 // imt_itree_insert_batch under IMT_PIPELINE only
+};
+
 // ---- one step each of the witness schedule on stream s, with its profile brackets.  `d` holds the device pointers of
-// the outputs (NULL: not wanted), `lay` the layout of its sibling arrays, `fmt` the format of both. ----
+// the outputs (NULL: not wanted), `lay` the layout of its sibling arrays, `fmt` the format of both; `w` picks the launch. ----
 void sweep_leaf_hashes(imt_itree* t, const PlanSet& P, hipStream_t s, size_t E) {
     imt_ctx* c = t->ctx;
     const int pf = c->prof_begin(IMT_PROF_LEAVES, s);
     launch::sweep_leaves(s, P.d_pre, P.d_tab[0][1], P.d_val[0], 0, (uint32_t)E, IMT_FMT_CANONICAL, c->d_err, c->coop_max_events);
     c->prof_end(pf, s);
 }
-// level l < L0 -> l + 1: reads the stored level l, which the caller has made sure holds what came before this batch
+// level l < L0 -> l + 1: reads the stored level l, which the caller has made sure holds what came before this batch --
+// or, through a view's side table, what it held at the view's size
 void sweep_one_level(imt_itree* t, const PlanSet& P, hipStream_t s, unsigned l, size_t E, const imt_insert_out& d,
-                     launch::SibLayout lay, unsigned fmt) {
+                     launch::SibLayout lay, unsigned fmt, const WitnessSweep& w = {}) {
     imt_ctx* c = t->ctx;
     const PlanSet::Level row = P.level(l);
+    const uint8_t *in = P.d_val[l & 1], *zero = c->d_zero + (size_t)l * 32;
+    uint8_t *out = P.d_val[(l & 1) ^ 1], *low_sib = (uint8_t*)d.low_sib, *new_sib = (uint8_t*)d.new_sib;
+    const uint32_t coop = c->coop_max_events;
     const int pf = c->prof_begin(IMT_PROF_LEVEL, s);
-    launch::sweep_level(s, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], row.from, row.sibsrc, row.nodeb, row.timen, t->nodes(l),
-                        t->h_len[l], c->d_zero + (size_t)l * 32, 0, (uint32_t)E, (uint8_t*)d.low_sib, (uint8_t*)d.new_sib, lay, l,
-                        fmt, c->coop_max_events);
+    if (w.route && w.side)
+        launch::sweep_view_level_mixed(s, *w.side, *w.route, in, out, row.from, row.sibsrc, row.nodeb, row.timen, t->nodes(l),
+                                       t->h_len[l], zero, (uint32_t)E, low_sib, new_sib, lay, l, fmt, coop);
+    else if (w.route)
+        launch::sweep_level_mixed(s, *w.route, in, out, row.from, row.sibsrc, row.nodeb, row.timen, t->nodes(l), t->h_len[l], zero,
+                                  (uint32_t)E, low_sib, new_sib, lay, l, fmt, coop);
+    else if (w.side)
+        launch::sweep_view_level(s, *w.side, in, out, row.from, row.sibsrc, row.nodeb, row.timen, t->nodes(l), t->h_len[l], zero,
+                                 (uint32_t)E, low_sib, new_sib, lay, l, fmt, coop);
+    else
+        launch::sweep_level(s, in, out, row.from, row.sibsrc, row.nodeb, row.timen, t->nodes(l), t->h_len[l], zero, 0, (uint32_t)E,
+                            low_sib, new_sib, lay, l, fmt, coop);
     c->prof_end(pf, s);
 }
-// old_root[0] is the root the batch before left: read right before the launch that overwrites the stored root
-void read_old_root(imt_itree* t, hipStream_t s, const imt_insert_out& d, unsigned fmt) {
-    if (d.old_root) launch::convert(s, t->nodes(t->depth), (uint8_t*)d.old_root, 1, IMT_FMT_DEVICE, fmt, t->ctx->d_err);
+// old_root[0] is the root the batch before left -- read right before the launch that overwrites the stored root -- or the
+// root of the view a replay starts from
+void read_old_root(imt_itree* t, hipStream_t s, const imt_insert_out& d, unsigned fmt, const WitnessSweep& w = {}) {
+    const uint8_t* src = w.view_root ? w.view_root : t->nodes(t->depth);
+    if (d.old_root) launch::convert(s, src, (uint8_t*)d.old_root, 1, IMT_FMT_DEVICE, fmt, t->ctx->d_err);
 }
 // level l >= L0 -> l + 1: every event alone in node 0 against the empty subtree of that height.  Ordinary launches of
-// the same kernel, so consecutive batches overlap here level by level as well; the last event's node of every level goes
-// back to the stored tree.
+// the same kernel, so consecutive batches overlap here level by level as well; unless nothing is stored, the last event's
+// node of every level goes back to the stored tree.
 void sweep_one_upper(imt_itree* t, const PlanSet& P, hipStream_t s, unsigned l, size_t E, unsigned L0, const imt_insert_out& d,
-                     launch::SibLayout lay, unsigned fmt) {
+                     launch::SibLayout lay, unsigned fmt, const WitnessSweep& w = {}) {
     imt_ctx* c = t->ctx;
+    const uint8_t *in = P.d_val[l & 1], *zero = c->d_zero + (size_t)l * 32;
+    uint8_t *out = P.d_val[(l & 1) ^ 1], *low_sib = (uint8_t*)d.low_sib, *new_sib = (uint8_t*)d.new_sib;
+    uint8_t *node_in = w.store && l == L0 ? t->nodes(l) : nullptr, *node_out = w.store ? t->nodes(l + 1) : nullptr;
     const int pf = c->prof_begin(IMT_PROF_TOP, s);
-    launch::sweep_upper(s, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], c->d_zero + (size_t)l * 32, 0, (uint32_t)E, (uint32_t)E - 1,
-                        l == L0 ? t->nodes(l) : nullptr, t->nodes(l + 1), (uint8_t*)d.low_sib, (uint8_t*)d.new_sib, lay, l, fmt,
-                        c->coop_max_events);
+    if (w.route)
+        launch::sweep_upper_mixed(s, *w.route, in, out, zero, (uint32_t)E, node_in, node_out, low_sib, new_sib, lay, l, fmt,
+                                  c->coop_max_events);
+    else
+        launch::sweep_upper(s, in, out, zero, 0, (uint32_t)E, w.store ? (uint32_t)E - 1 : 0xffffffffu, node_in, node_out, low_sib,
+                            new_sib, lay, l, fmt, c->coop_max_events);
     c->prof_end(pf, s);
 }
 // the roots of every event from the top values; a batch that fills the tree to its full depth stores its root here
-void finish_roots(imt_itree* t, const PlanSet& P, hipStream_t s, size_t E, unsigned L0, const imt_insert_out& d, unsigned fmt) {
-    launch::emit_roots(s, P.d_val[t->depth & 1], 0, (uint32_t)E, (uint32_t)E, (uint8_t*)d.old_root, (uint8_t*)d.interim_root,
-                       (uint8_t*)d.new_root, fmt, nullptr, L0 == t->depth ? t->nodes(t->depth) : nullptr);
+void finish_roots(imt_itree* t, const PlanSet& P, hipStream_t s, size_t E, unsigned L0, const imt_insert_out& d, unsigned fmt,
+                  const WitnessSweep& w = {}) {
+    const uint8_t* top = P.d_val[t->depth & 1];
+    uint8_t* node_store = w.store && L0 == t->depth ? t->nodes(t->depth) : nullptr;
+    if (w.route)
+        launch::emit_roots_mixed(s, *w.route, top, (uint32_t)E, (uint32_t)w.n_ins, (uint8_t*)d.old_root, (uint8_t*)d.interim_root,
+                                 (uint8_t*)d.new_root, w.read_root, fmt, node_store);
+    else
+        launch::emit_roots(s, top, 0, (uint32_t)E, (uint32_t)E, (uint8_t*)d.old_root, (uint8_t*)d.interim_root,
+                           (uint8_t*)d.new_root, fmt, nullptr, node_store);
 }
 
 }  // namespace
@@ -1591,29 +1642,30 @@ void finish_roots(imt_itree* t, const PlanSet& P, hipStream_t s, size_t E, unsig
 struct ApplyReq {
     void* root_out;
 };
-static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, uint64_t* count);
-static int apply_hashes_pipelined(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, const PlanSet* prev);
-
 // The order between consecutive batches on the pipeline streams (imt_apply_pipe.hpp): launch x of a batch of `kind`
-// waits for the event of the batch in front that the rule names, and records the event the rule names.
-static int pipe_wait(imt_itree* t, hipStream_t s, const PlanSet* prev, apipe::Kind kind, unsigned L0, apipe::Launch x) {
+// waits for the event of the batch in front that the rule names, and records the event the rule names.  A batch that is
+// not on a pipeline stream has nobody in front and records nothing.
+static int pipe_wait(imt_itree* t, hipStream_t s, const PipeCtx& pipe, apipe::Kind kind, unsigned L0, apipe::Launch x) {
+    const PlanSet* prev = pipe.prev;
     if (!prev) return IMT_OK;
     const apipe::Event e = apipe::waits(prev->applied ? apipe::APPLY : apipe::WITNESS, prev->l0, kind, L0, t->depth, x);
     if (e.type == apipe::EV_NONE) return IMT_OK;
     IMT_HIP(t->ctx, hipStreamWaitEvent(s, e.type == apipe::EV_LEVEL ? prev->wb_done[e.l] : prev->done, 0));
     return IMT_OK;
 }
-static int pipe_record(imt_itree* t, hipStream_t s, PlanSet& P, apipe::Kind kind, unsigned L0, apipe::Launch x) {
+static int pipe_record(imt_itree* t, hipStream_t s, PlanSet& P, const PipeCtx& pipe, apipe::Kind kind, unsigned L0, apipe::Launch x) {
+    if (!pipe.pipelined) return IMT_OK;
     const apipe::Event e = apipe::records(kind, L0, t->depth, x);
     if (e.type == apipe::EV_LEVEL) IMT_HIP(t->ctx, hipEventRecord(P.wb_done[e.l], s));
     return IMT_OK;
 }
 
-// The hashing of imt_itree_insert_batch on stream s, behind the preparation: leaf hashes, index phase (no hashing), then
-// the hash sweep level by level with each level's write-back.  prev: the batch before this one if it is still on a
-// pipeline stream -- this batch then runs one level behind it; pipelined: this one records its own per-level events.
-static int witness_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, const PlanSet* prev, bool pipelined,
-                          const imt_insert_out& d, launch::SibLayout lay, unsigned fmt) {
+// The witness schedule on stream s, behind the preparation: leaf hashes, index phase (no hashing), then the hash sweep
+// level by level -- with each level's write-back unless nothing is stored -- and the roots.  Every witness there is comes
+// through here; `w` says which: imt_itree_insert_batch (w.pipe.prev: the batch before this one if it is still on a
+// pipeline stream -- this batch then runs one level behind it), a mixed batch, or a replay of either through a view.
+static int witness_sweep(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, const imt_insert_out& d,
+                         launch::SibLayout lay, unsigned fmt, const WitnessSweep& w) {
     imt_ctx* c = t->ctx;
     sweep_leaf_hashes(t, P, s, E);
     int pf = c->prof_begin(IMT_PROF_INDEX, s);
@@ -1623,29 +1675,75 @@ static int witness_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, uns
     for (unsigned l = 0; l < L0; l++) {
         // stored level l must hold the previous batch's final versions: its write-back of that level,
         // or (at and above its L0) its top kernel
-        if ((rc = pipe_wait(t, s, prev, apipe::WITNESS, L0, {apipe::WI_LEVEL, l}))) return rc;
-        sweep_one_level(t, P, s, l, E, d, lay, fmt);
+        if ((rc = pipe_wait(t, s, w.pipe, apipe::WITNESS, L0, {apipe::WI_LEVEL, l}))) return rc;
+        sweep_one_level(t, P, s, l, E, d, lay, fmt, w);
+        if (!w.store) continue;
         pf = c->prof_begin(IMT_PROF_WRITEBACK, s);
         launch::writeback(s, P.d_val[l & 1], P.level(l).from, P.level(l).nodeb, t->nodes(l), (uint32_t)E);
         c->prof_end(pf, s);
-        if (pipelined && (rc = pipe_record(t, s, P, apipe::WITNESS, L0, {apipe::WI_LEVEL, l}))) return rc;
+        if ((rc = pipe_record(t, s, P, w.pipe, apipe::WITNESS, L0, {apipe::WI_LEVEL, l}))) return rc;
     }
+    // right before the first launch that writes the stored root; a sweep that stores nothing reads it before the roots
     auto old_root = [&]() -> int {
-        const int r = pipe_wait(t, s, prev, apipe::WITNESS, L0, {apipe::WI_OLD_ROOT, 0});
+        const int r = pipe_wait(t, s, w.pipe, apipe::WITNESS, L0, {apipe::WI_OLD_ROOT, 0});
         if (r) return r;
-        read_old_root(t, s, d, fmt);
+        read_old_root(t, s, d, fmt, w);
         return IMT_OK;
     };
     for (unsigned l = L0; l < t->depth; l++) {
-        if (l + 1 == t->depth && (rc = old_root())) return rc;
+        if (w.store && l + 1 == t->depth && (rc = old_root())) return rc;
         // the previous batch stored node l + 1 (and node l, at its own L0) from its launch of this level
-        if ((rc = pipe_wait(t, s, prev, apipe::WITNESS, L0, {apipe::WI_UPPER, l}))) return rc;
-        sweep_one_upper(t, P, s, l, E, L0, d, lay, fmt);
-        if (pipelined && (rc = pipe_record(t, s, P, apipe::WITNESS, L0, {apipe::WI_UPPER, l}))) return rc;
+        if ((rc = pipe_wait(t, s, w.pipe, apipe::WITNESS, L0, {apipe::WI_UPPER, l}))) return rc;
+        sweep_one_upper(t, P, s, l, E, L0, d, lay, fmt, w);
+        if ((rc = pipe_record(t, s, P, w.pipe, apipe::WITNESS, L0, {apipe::WI_UPPER, l}))) return rc;
     }
-    if (L0 == t->depth && (rc = old_root())) return rc;
-    if ((rc = pipe_wait(t, s, prev, apipe::WITNESS, L0, {apipe::WI_ROOTS, 0}))) return rc;
-    finish_roots(t, P, s, E, L0, d, fmt);
+    if ((!w.store || L0 == t->depth) && (rc = old_root())) return rc;
+    if ((rc = pipe_wait(t, s, w.pipe, apipe::WITNESS, L0, {apipe::WI_ROOTS, 0}))) return rc;
+    finish_roots(t, P, s, E, L0, d, fmt, w);
+    return IMT_OK;
+}
+
+// The witness-free schedule (imt_apply.hpp) on stream s, behind the preparation: the lists of every level (index work),
+// the touched leaves from their final preimages, then level by level every touched parent from the stored level below --
+// which the launch before has just made final -- and from level L0 - 1 up the single chain to the root.  The launches
+// are sized by host-side bounds; the counts stay on the device (`count`, [depth + 1]), so nothing here waits for the GPU.
+// imt_itree_rewind hashes through here too: its table has one event per touched leaf, its L0 is that of the size it finds
+// and its counts are its own.
+// On a pipeline stream (imt_itree_apply_pipelined; `count` is then the plan set's) the batch in front may be two launches
+// ahead: every launch that writes a stored level first waits for the event imt_apply_pipe.hpp names -- an apply batch in
+// front reads level l in the launch AFTER the one that wrote it -- and records its own; and the chain to the root is
+// hashed into the plan set's rows (k_apply_chain), beside the chains of the batches in front, with only the store of those
+// rows into the tree and into P.d_root ordered behind them.
+static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, uint64_t* count, const PipeCtx& pipe = {}) {
+    imt_ctx* c = t->ctx;
+    const apply::Lists lists{P.d_nodeb, P.d_timen, count, P.cap_events};
+    int rc, pf = c->prof_begin(IMT_PROF_APPLY_LISTS, s);
+    IMT_HIP(c, prep::apply_lists(s, P.ws.tmp, P.ws.tmp_bytes, P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][3], (uint32_t)E, L0,
+                                 t->depth, P.d_from, lists));
+    c->prof_end(pf, s);
+    if ((rc = pipe_wait(t, s, pipe, apipe::APPLY, L0, {apipe::AP_LEVEL, 0}))) return rc;
+    pf = c->prof_begin(IMT_PROF_APPLY_LEAVES, s);
+    launch::apply_leaves(s, lists.count, apply::bound((uint32_t)E, L0, 0), lists.node, lists.src, P.d_pre, IMT_FMT_CANONICAL,
+                         c->d_err, t->nodes(0), t->h_len[0], c->coop_max_events);
+    c->prof_end(pf, s);
+    for (unsigned l = 0; l + 1 < L0; l++) {
+        if ((rc = pipe_wait(t, s, pipe, apipe::APPLY, L0, {apipe::AP_LEVEL, l + 1}))) return rc;
+        pf = c->prof_begin(IMT_PROF_APPLY_LEVEL, s);
+        launch::apply_level(s, lists.count + l + 1, apply::bound((uint32_t)E, L0, l + 1), P.level(l + 1).nodeb,
+                            t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, t->nodes(l + 1), t->h_len[l + 1],
+                            c->coop_max_events);
+        c->prof_end(pf, s);
+        if ((rc = pipe_record(t, s, P, pipe, apipe::APPLY, L0, {apipe::AP_LEVEL, l + 1}))) return rc;
+    }
+    if ((rc = pipe_wait(t, s, pipe, apipe::APPLY, L0, {apipe::AP_CHAIN, 0}))) return rc;
+    pf = c->prof_begin(IMT_PROF_APPLY_TOP, s);
+    if (pipe.pipelined) launch::apply_chain(s, t->d_nodes, t->d_off, t->d_len, c->d_zero, P.d_chain, L0 - 1, t->depth);
+    else launch::apply_top(s, t->d_nodes, t->d_off, t->d_len, c->d_zero, L0 - 1, t->depth);
+    c->prof_end(pf, s);
+    if (!pipe.pipelined) return IMT_OK;
+    if ((rc = pipe_record(t, s, P, pipe, apipe::APPLY, L0, {apipe::AP_CHAIN, 0}))) return rc;
+    if ((rc = pipe_wait(t, s, pipe, apipe::APPLY, L0, {apipe::AP_STORE, 0}))) return rc;
+    launch::apply_chain_store(s, P.d_chain, t->d_nodes, t->d_off, L0, t->depth, P.d_root);
     return IMT_OK;
 }
 
@@ -1736,6 +1834,46 @@ static int deliver_witness_outputs(imt_itree* t, hipStream_t s, size_t n, const 
     return IMT_OK;
 }
 
+// Nothing was inserted: a call that reports the root (root_out != NULL) reports the one the tree has
+static int report_unchanged_root(imt_itree* t, void* root_out, unsigned flags) {
+    return root_out ? imt_itree_root(t, root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS)) : IMT_OK;
+}
+
+// The root a batch left (src, device format) to the caller on stream s, in the caller's format: straight into a device
+// pointer, through the context's next scratch slot to a host pointer -- which holds it once the caller has waited for s.
+static int deliver_root(imt_ctx* c, hipStream_t s, const uint8_t* src, void* root_out, unsigned flags, size_t& slot) {
+    if (!root_out) return IMT_OK;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    uint8_t* r = dev ? (uint8_t*)root_out : (uint8_t*)c->dev_scratch(slot++, 32);
+    if (!r) return IMT_ERR_HIP;
+    launch::convert(s, src, r, 1, IMT_FMT_DEVICE, flags & IMT_FMT_MASK, c->d_err);
+    if (!dev) IMT_HIP(c, hipMemcpyAsync(root_out, r, 32, hipMemcpyDeviceToHost, s));
+    return IMT_OK;
+}
+
+// The two halves of a batch's commit.  Its plan set launched: the hashing is enqueued on s and P.d_root filled behind it,
+// so the set holds a root, is in flight until `done`, and the next batch takes the next set.
+static int plan_launched(imt_itree* t, PlanSet& P, hipStream_t s, unsigned L0, bool pipelined, bool applied) {
+    P.has_root = true;
+    IMT_HIP(t->ctx, hipEventRecord(P.done, s));
+    P.pipelined = pipelined;
+    P.applied = applied;
+    P.sliced = false;
+    P.l0 = L0;
+    P.in_flight = true;
+    t->cur = (t->cur + 1) % imt_itree::NSETS;
+    t->batch_no++;
+    return IMT_OK;
+}
+// The device index committed: the merged index the preparation left in the other buffer becomes current together with
+// the size; the host mirror is rebuilt from it when a host-side call needs it.
+static void index_committed(imt_itree* t, uint64_t size) {
+    t->sorted_cur ^= 1;
+    t->size = size;
+    t->mirror_valid = false;
+    t->gen++;
+}
+
 // A batch behind its validation: n values (val_flags: where they are and in which format) into the tree, the outputs as
 // `flags` say.  Level-major sibling arrays have level stride sib_stride (>= n).  The sequence: plan set, side stream
 // behind the caller, hash-free part, compute stream, hashing, record, commit, outputs.
@@ -1772,13 +1910,13 @@ static int insert_core(imt_itree* t, const void* vals, unsigned val_flags, size_
 
     // ---- compute stream: the context's, or one of the NPIPE pipeline streams ----
     hipStream_t s = c->stream;
-    const PlanSet* prev = nullptr;      // the batch before this one, if it is still on a pipeline stream
+    PipeCtx pipe{nullptr, pipelined};   // prev: the batch before this one, if it is still on a pipeline stream
     if (pipelined) {
         s = t->pipe_stream[t->batch_no % imt_itree::NPIPE];
         IMT_HIP(c, hipEventRecord(t->user_mark, c->stream));     // buffers last used on the user's stream
         IMT_HIP(c, hipStreamWaitEvent(s, t->user_mark, 0));
         const PlanSet& o = t->plan[(t->cur + imt_itree::NSETS - 1) % imt_itree::NSETS];
-        if (o.in_flight && o.pipelined) prev = &o;
+        if (o.in_flight && o.pipelined) pipe.prev = &o;
         t->pipe_pending = true;
     } else {
         if ((rc = join_top(t))) return rc;
@@ -1796,43 +1934,32 @@ static int insert_core(imt_itree* t, const void* vals, unsigned val_flags, size_
         return IMT_ERR_HIP;
     // a placed tree writes rows [0, depth) of sibling arrays dimensioned for global_depth levels
     const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->global_depth} : launch::SibLayout{sib_stride, 1};
-    rc = !apply      ? witness_hashes(t, P, s, E, L0, prev, pipelined, d, lay, fmt)
-         : pipelined ? apply_hashes_pipelined(t, P, s, E, L0, prev)       // its store of the chain fills P.d_root as well
-                     : apply_hashes(t, P, s, E, L0, t->d_apply_stats);
+    if (!apply) {
+        WitnessSweep w;
+        w.pipe = pipe;
+        rc = witness_sweep(t, P, s, E, L0, d, lay, fmt, w);
+    } else {    // a pipelined apply batch keeps its counts in its plan set, and its store of the chain fills P.d_root as well
+        rc = apply_hashes(t, P, s, E, L0, pipelined ? P.d_count : t->d_apply_stats, pipe);
+    }
     if (rc) return rc;
     if (apply) {
         t->apply_seen = true;
         t->apply_stats_set = pipelined ? &P : nullptr;
     }
     if (!(apply && pipelined)) IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
-    P.has_root = true;
-    IMT_HIP(c, hipEventRecord(P.done, s));
-    P.pipelined = pipelined;
-    P.applied = apply && pipelined;
-    P.sliced = false;
-    P.l0 = L0;
-    P.in_flight = true;
-    t->cur = (t->cur + 1) % imt_itree::NSETS;
-    t->batch_no++;
+    if ((rc = plan_launched(t, P, s, L0, pipelined, apply && pipelined))) return rc;
 
     // ---- commit the hash-free state ----
     if (gpu_prep) {
-        t->sorted_cur ^= 1;          // the merged index becomes current together with the size
-        t->size = M + n;
-        t->mirror_valid = false;     // rebuilt from the device index when a host-side call needs it
+        index_committed(t, M + n);
     } else {
         host_commit(t, hp, n);
+        t->gen++;
     }
-    t->gen++;
 
     // ---- outputs ----
     if (out && (rc = deliver_hashfree_outputs(t, s, n, out, d, hp, flags, slot))) return rc;
-    if (apply && apply->root_out) {
-        uint8_t* r = dev ? (uint8_t*)apply->root_out : (uint8_t*)c->dev_scratch(slot++, 32);
-        if (!r) return IMT_ERR_HIP;
-        launch::convert(s, P.d_root, r, 1, IMT_FMT_DEVICE, fmt, c->d_err);
-        if (!dev) IMT_HIP(c, hipMemcpyAsync(apply->root_out, r, 32, hipMemcpyDeviceToHost, s));
-    }
+    if (apply && (rc = deliver_root(c, s, P.d_root, apply->root_out, flags, slot))) return rc;
     if (out && !dev && (rc = deliver_witness_outputs(t, s, n, out, d, item_major, sib_stride))) return rc;
     if (c->profiling) {
         c->prof_ms[IMT_PROF_HOST] += host.ms() - host_wait_ms;
@@ -1859,73 +1986,6 @@ static int insert_call(imt_itree* t, const void* vals, size_t n, const imt_inser
     return insert_core(t, vals, flags, n, out, flags, n, apply);
 }
 
-// The hashing of imt_itree_apply_batch on stream s, behind the preparation: the lists of every level (index work), the
-// touched leaves from their final preimages, then level by level every touched parent from the stored level below --
-// which the launch before has just made final -- and from level L0 - 1 up the single chain to the root.  The launches
-// are sized by host-side bounds; the counts stay on the device (`count`, [depth + 1]: t->d_apply_stats for an apply
-// batch), so nothing here waits for the GPU.  imt_itree_rewind hashes through here too: its table has one event per
-// touched leaf, its L0 is that of the size it finds and its counts are its own.
-static int apply_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, uint64_t* count) {
-    imt_ctx* c = t->ctx;
-    const apply::Lists lists{P.d_nodeb, P.d_timen, count, P.cap_events};
-    int pf = c->prof_begin(IMT_PROF_APPLY_LISTS, s);
-    IMT_HIP(c, prep::apply_lists(s, P.ws.tmp, P.ws.tmp_bytes, P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][3], (uint32_t)E, L0,
-                                 t->depth, P.d_from, lists));
-    c->prof_end(pf, s);
-    pf = c->prof_begin(IMT_PROF_APPLY_LEAVES, s);
-    launch::apply_leaves(s, lists.count, apply::bound((uint32_t)E, L0, 0), lists.node, lists.src, P.d_pre, IMT_FMT_CANONICAL,
-                         c->d_err, t->nodes(0), t->h_len[0], c->coop_max_events);
-    c->prof_end(pf, s);
-    for (unsigned l = 0; l + 1 < L0; l++) {
-        pf = c->prof_begin(IMT_PROF_APPLY_LEVEL, s);
-        launch::apply_level(s, lists.count + l + 1, apply::bound((uint32_t)E, L0, l + 1), P.level(l + 1).nodeb,
-                            t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, t->nodes(l + 1), t->h_len[l + 1],
-                            c->coop_max_events);
-        c->prof_end(pf, s);
-    }
-    pf = c->prof_begin(IMT_PROF_APPLY_TOP, s);
-    launch::apply_top(s, t->d_nodes, t->d_off, t->d_len, c->d_zero, L0 - 1, t->depth);
-    c->prof_end(pf, s);
-    return IMT_OK;
-}
-
-// The same hashing for imt_itree_apply_pipelined, on pipeline stream s with the batch in front (prev, if it is still on a
-// pipeline stream) possibly two launches ahead.  What differs from apply_hashes: every launch that writes a stored level
-// first waits for the event imt_apply_pipe.hpp names -- an apply batch in front reads level l in the launch AFTER the one
-// that wrote it -- and records its own; the counts are the plan set's; and the chain to the root is hashed into the plan
-// set's rows (k_apply_chain), beside the chains of the batches in front, with only the store of those rows into the tree
-// and into P.d_root ordered behind them.
-static int apply_hashes_pipelined(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, const PlanSet* prev) {
-    imt_ctx* c = t->ctx;
-    const apply::Lists lists{P.d_nodeb, P.d_timen, P.d_count, P.cap_events};
-    int rc, pf = c->prof_begin(IMT_PROF_APPLY_LISTS, s);
-    IMT_HIP(c, prep::apply_lists(s, P.ws.tmp, P.ws.tmp_bytes, P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][3], (uint32_t)E, L0,
-                                 t->depth, P.d_from, lists));
-    c->prof_end(pf, s);
-    if ((rc = pipe_wait(t, s, prev, apipe::APPLY, L0, {apipe::AP_LEVEL, 0}))) return rc;
-    pf = c->prof_begin(IMT_PROF_APPLY_LEAVES, s);
-    launch::apply_leaves(s, lists.count, apply::bound((uint32_t)E, L0, 0), lists.node, lists.src, P.d_pre, IMT_FMT_CANONICAL,
-                         c->d_err, t->nodes(0), t->h_len[0], c->coop_max_events);
-    c->prof_end(pf, s);
-    for (unsigned l = 0; l + 1 < L0; l++) {
-        if ((rc = pipe_wait(t, s, prev, apipe::APPLY, L0, {apipe::AP_LEVEL, l + 1}))) return rc;
-        pf = c->prof_begin(IMT_PROF_APPLY_LEVEL, s);
-        launch::apply_level(s, lists.count + l + 1, apply::bound((uint32_t)E, L0, l + 1), P.level(l + 1).nodeb,
-                            t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, t->nodes(l + 1), t->h_len[l + 1],
-                            c->coop_max_events);
-        c->prof_end(pf, s);
-        if ((rc = pipe_record(t, s, P, apipe::APPLY, L0, {apipe::AP_LEVEL, l + 1}))) return rc;
-    }
-    if ((rc = pipe_wait(t, s, prev, apipe::APPLY, L0, {apipe::AP_CHAIN, 0}))) return rc;
-    pf = c->prof_begin(IMT_PROF_APPLY_TOP, s);
-    launch::apply_chain(s, t->d_nodes, t->d_off, t->d_len, c->d_zero, P.d_chain, L0 - 1, t->depth);
-    c->prof_end(pf, s);
-    if ((rc = pipe_record(t, s, P, apipe::APPLY, L0, {apipe::AP_CHAIN, 0}))) return rc;
-    if ((rc = pipe_wait(t, s, prev, apipe::APPLY, L0, {apipe::AP_STORE, 0}))) return rc;
-    launch::apply_chain_store(s, P.d_chain, t->d_nodes, t->d_off, L0, t->depth, P.d_root);
-    return IMT_OK;
-}
-
 extern "C" int imt_itree_insert_batch(imt_itree* t, const void* vals, size_t n, const imt_insert_out* out,
                                       unsigned flags) {
     return insert_call(t, vals, n, out, flags, nullptr);
@@ -1936,20 +1996,20 @@ extern "C" int imt_itree_apply_batch(imt_itree* t, const void* vals, size_t n, v
     if (flags & IMT_PIPELINE) return t->ctx->fail(IMT_ERR_ARG, "apply batches are not pipelined (IMT_PIPELINE)");
     if (n == 0) {
         IMT_NOT_SLICED(t);
-        return root_out ? imt_itree_root(t, root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS)) : IMT_OK;
+        return report_unchanged_root(t, root_out, flags);
     }
     const ApplyReq req{root_out};
     return insert_call(t, vals, n, nullptr, flags, &req);
 }
 
 // Witness-free batches that overlap (imt.h): imt_itree_apply_batch's checks, preparation and commit, the hashing on one
-// of the tree's pipeline streams behind the batches in front (apply_hashes_pipelined).
+// of the tree's pipeline streams behind the batches in front (apply_hashes with a pipeline context).
 extern "C" int imt_itree_apply_pipelined(imt_itree* t, const void* vals, size_t n, void* root_out, unsigned flags) {
     if (!t) return IMT_ERR_ARG;
     if (!(flags & IMT_DEVICE_PTRS)) return t->ctx->fail(IMT_ERR_ARG, "imt_itree_apply_pipelined needs device pointers (IMT_DEVICE_PTRS)");
     if (n == 0) {
         IMT_NOT_SLICED(t);
-        return root_out ? imt_itree_root(t, root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS)) : IMT_OK;
+        return report_unchanged_root(t, root_out, flags);
     }
     const ApplyReq req{root_out};
     return insert_call(t, vals, n, nullptr, flags | IMT_PIPELINE, &req);
@@ -1977,42 +2037,6 @@ extern "C" int imt_itree_apply_stats(imt_itree* t, uint64_t* hashes) {
 // ------------------------------------------------------------------------------------
 // mixed batches: non-inclusion READs between the INSERTs of one call
 // ------------------------------------------------------------------------------------
-// The hashing of imt_itree_mixed_batch on stream s, behind the preparation: witness_hashes' sequence for a batch that runs
-// alone on the context's stream, with the LEVEL launches and the roots routed through erow (an event's id no longer says
-// whose rows it fills).  Leaf hashes, index phase and write-back are the stages witness_hashes uses; a READ's versions go
-// back to the stored tree like any other -- they are the bytes already there.
-static int mixed_hashes(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, size_t n_ins, const imt_insert_out& d,
-                        const launch::MixedRoute& route, uint8_t* read_root, launch::SibLayout lay, unsigned fmt) {
-    imt_ctx* c = t->ctx;
-    read_old_root(t, s, d, fmt);        // nothing on this stream has touched the stored root yet
-    sweep_leaf_hashes(t, P, s, E);
-    int pf = c->prof_begin(IMT_PROF_INDEX, s);
-    index_phase(P, s, E, L0, nullptr);
-    c->prof_end(pf, s);
-    for (unsigned l = 0; l < L0; l++) {
-        const PlanSet::Level row = P.level(l);
-        pf = c->prof_begin(IMT_PROF_LEVEL, s);
-        launch::sweep_level_mixed(s, route, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], row.from, row.sibsrc, row.nodeb, row.timen,
-                                  t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, (uint32_t)E, (uint8_t*)d.low_sib,
-                                  (uint8_t*)d.new_sib, lay, l, fmt, c->coop_max_events);
-        c->prof_end(pf, s);
-        pf = c->prof_begin(IMT_PROF_WRITEBACK, s);
-        launch::writeback(s, P.d_val[l & 1], row.from, row.nodeb, t->nodes(l), (uint32_t)E);
-        c->prof_end(pf, s);
-    }
-    for (unsigned l = L0; l < t->depth; l++) {
-        pf = c->prof_begin(IMT_PROF_TOP, s);
-        launch::sweep_upper_mixed(s, route, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], c->d_zero + (size_t)l * 32, (uint32_t)E,
-                                  l == L0 ? t->nodes(l) : nullptr, t->nodes(l + 1), (uint8_t*)d.low_sib, (uint8_t*)d.new_sib,
-                                  lay, l, fmt, c->coop_max_events);
-        c->prof_end(pf, s);
-    }
-    launch::emit_roots_mixed(s, route, P.d_val[t->depth & 1], (uint32_t)E, (uint32_t)n_ins, (uint8_t*)d.old_root,
-                             (uint8_t*)d.interim_root, (uint8_t*)d.new_root, read_root, fmt,
-                             L0 == t->depth ? t->nodes(t->depth) : nullptr);
-    return IMT_OK;
-}
-
 // rows [0, rows) of a staged sibling array to the caller's: item-major they are one block, level-major they are the
 // first `rows` of every level's n
 static int copy_sib_rows(imt_itree* t, hipStream_t s, void* user, const void* dev_buf, size_t rows, size_t n, bool item_major) {
@@ -2025,20 +2049,21 @@ static int copy_sib_rows(imt_itree* t, hipStream_t s, void* user, const void* de
     return IMT_OK;
 }
 
-// Where the kernels of a mixed batch write the outputs the caller asked for (stage_out, row r of `ins` the r-th INSERT, row
-// q of `rd` the q-th READ; sib_bytes: a sibling array of the caller's dimensions).  False: scratch could not be had.
+// Where the kernels write the nine outputs of n insertions the caller asked for (stage_out; sib_bytes: a sibling array of
+// the caller's dimensions), in the one order the scratch slots are handed out in.  False: scratch could not be had.
+static bool stage_insert_outputs(imt_ctx* c, bool dev, size_t& slot, const imt_insert_out* ins, size_t n, size_t sib_bytes,
+                                 imt_insert_out& d) {
+    return stage_out(c, dev, slot, ins->low_index, n * 8, d.low_index) && stage_out(c, dev, slot, ins->is_largest, n, d.is_largest) &&
+           stage_out(c, dev, slot, ins->low_leaf, n * 96, d.low_leaf) && stage_out(c, dev, slot, ins->new_leaf, n * 96, d.new_leaf) &&
+           stage_out(c, dev, slot, ins->old_root, n * 32, d.old_root) &&
+           stage_out(c, dev, slot, ins->interim_root, n * 32, d.interim_root) &&
+           stage_out(c, dev, slot, ins->new_root, n * 32, d.new_root) && stage_out(c, dev, slot, ins->low_sib, sib_bytes, d.low_sib) &&
+           stage_out(c, dev, slot, ins->new_sib, sib_bytes, d.new_sib);
+}
+// The same for a mixed batch: row r of `ins` the r-th INSERT, row q of `rd` the q-th READ.
 static bool mixed_stage_outputs(imt_ctx* c, bool dev, size_t& slot, const imt_insert_out* ins, const imt_read_out* rd, size_t n_ins,
                                 size_t n_rd, size_t sib_bytes, imt_insert_out& d, imt_read_out& r) {
-    if (ins && n_ins &&
-        (!stage_out(c, dev, slot, ins->low_index, n_ins * 8, d.low_index) ||
-         !stage_out(c, dev, slot, ins->is_largest, n_ins, d.is_largest) ||
-         !stage_out(c, dev, slot, ins->low_leaf, n_ins * 96, d.low_leaf) ||
-         !stage_out(c, dev, slot, ins->new_leaf, n_ins * 96, d.new_leaf) ||
-         !stage_out(c, dev, slot, ins->old_root, n_ins * 32, d.old_root) ||
-         !stage_out(c, dev, slot, ins->interim_root, n_ins * 32, d.interim_root) ||
-         !stage_out(c, dev, slot, ins->new_root, n_ins * 32, d.new_root) ||
-         !stage_out(c, dev, slot, ins->low_sib, sib_bytes, d.low_sib) || !stage_out(c, dev, slot, ins->new_sib, sib_bytes, d.new_sib)))
-        return false;
+    if (ins && n_ins && !stage_insert_outputs(c, dev, slot, ins, n_ins, sib_bytes, d)) return false;
     if (rd && n_rd &&
         (!stage_out(c, dev, slot, rd->low_index, n_rd * 8, r.low_index) ||
          !stage_out(c, dev, slot, rd->is_largest, n_rd, r.is_largest) ||
@@ -2096,6 +2121,68 @@ struct MixedFiltered {
 // The per-operation scratch of a mixed batch on plan set P: the filter's and the slot table's, idle by then.
 static prep::MixedWs mixed_scratch(const PlanSet& P) { return prep::MixedWs{P.fw.flag, P.fw.rank, P.fw.idx, P.fw.aux, P.d_slot}; }
 
+// ---- the front the mixed entry points share (batch, filtered, replay): each makes these refusals at its own point of
+// its own order, in its own words where the words differ ----
+struct MixedNoun {
+    const char *takes, *plural;
+};
+static const MixedNoun MIXED_BATCH{"mixed batches take", "mixed batches"}, MIXED_REPLAY{"a mixed replay takes", "mixed replays"};
+static int check_mixed_mode(imt_itree* t, unsigned flags, const MixedNoun& noun) {
+    imt_ctx* c = t->ctx;
+    if (flags & (IMT_PIPELINE | IMT_HOST_PREP | IMT_INPUTS_READY))
+        return c->fail(IMT_ERR_ARG, "%s neither IMT_PIPELINE, IMT_HOST_PREP nor IMT_INPUTS_READY", noun.takes);
+    if (t->index_base || t->global_depth != t->depth || t->part_mod > 1)
+        return c->fail(IMT_ERR_ARG, "%s are not available on a placed or partitioned tree", noun.plural);
+    return IMT_OK;
+}
+static int check_mixed_ptrs(imt_ctx* c, bool dev, const void* vals, const imt_insert_out* ins, const imt_read_out* rd) {
+    int rc;
+    if ((rc = check_fe_ptrs(c, dev, {vals})) || (rc = check_out_ptrs(c, dev, ins))) return rc;
+    if (rd && (rc = check_fe_ptrs(c, dev, {rd->low_leaf, rd->root, rd->low_sib}))) return rc;
+    if (dev && ((ins && ((uintptr_t)ins->low_index & 7u)) || (rd && ((uintptr_t)rd->low_index & 7u))))
+        return c->fail(IMT_ERR_ARG, "device low_index array is not 8-byte aligned");
+    return IMT_OK;
+}
+// a host-pointer caller's op bytes, before anything is enqueued; a device-pointer caller's are checked by the rank kernel
+static int check_host_ops(imt_ctx* c, bool dev, const uint8_t* op, size_t n) {
+    if (!dev)
+        for (size_t p = 0; p < n; p++)
+            if (op[p] > IMT_OP_READ) return c->fail(IMT_ERR_ARG, "op[%zu] = %u is neither IMT_OP_INSERT nor IMT_OP_READ", p, op[p]);
+    return IMT_OK;
+}
+// the op bytes where stream s may read them: a host-pointer caller's through the context's next scratch slot
+static int stage_ops(imt_ctx* c, hipStream_t s, bool dev, const uint8_t* op, size_t n, size_t& slot, const uint8_t** d_op) {
+    *d_op = op;
+    if (dev) return IMT_OK;
+    uint8_t* o = (uint8_t*)c->dev_scratch(slot++, n);
+    if (!o) return IMT_ERR_HIP;
+    IMT_HIP(c, hipMemcpyAsync(o, op, n, hipMemcpyHostToDevice, s));
+    *d_op = o;
+    return IMT_OK;
+}
+// The rank stage on stream s, the error word clear: every operation's rank among its kind, and -- one host wait -- a bad
+// op byte refused and the number of INSERTs.
+static int mixed_rank_stage(imt_itree* t, PlanSet& P, const prep::MixedWs& mx, hipStream_t s, const uint8_t* d_op, size_t n,
+                            size_t& n_ins) {
+    imt_ctx* c = t->ctx;
+    IMT_HIP(c, prep::mixed_ranks(s, P.ws, mx, d_op, (uint32_t)n));
+    IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, mx.word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, s));
+    IMT_HIP(c, hipStreamSynchronize(s));
+    if (*t->h_err_pin & prep::ERR_OP) return c->fail(IMT_ERR_ARG, "an op byte is neither IMT_OP_INSERT nor IMT_OP_READ");
+    n_ins = *t->h_cnt_pin;
+    return IMT_OK;
+}
+// The end of the check stage on stream s -- the second host wait: the checks' error bits in *t->h_err_pin, the first
+// position they refuse in *t->h_cnt_pin.
+static int mixed_check_verdict(imt_itree* t, PlanSet& P, const prep::MixedWs& mx, hipStream_t s) {
+    imt_ctx* c = t->ctx;
+    IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, mx.word + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, s));
+    IMT_HIP(c, hipStreamSynchronize(s));
+    return IMT_OK;
+}
+
 // The front of every mixed batch behind the staging of its inputs: n operations (d_vals canonical, d_op, both device
 // memory that stream t->up_stream may read), on plan set P, acquired for >= 2n events, with the error word clear.  Ranks,
 // room for the n_ins INSERTs, their values into rows [M, M + n_ins) of the value array, every check and the neighbours of
@@ -2107,12 +2194,7 @@ static int mixed_checks(imt_itree* t, PlanSet& P, const prep::MixedWs& mx, const
     int rc;
     const uint64_t M = t->size;
     hipStream_t ps = t->up_stream;
-    IMT_HIP(c, prep::mixed_ranks(ps, P.ws, mx, d_op, (uint32_t)n));
-    IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, mx.word, sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
-    IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, ps));
-    IMT_HIP(c, hipStreamSynchronize(ps));
-    if (*t->h_err_pin & prep::ERR_OP) return c->fail(IMT_ERR_ARG, "an op byte is neither IMT_OP_INSERT nor IMT_OP_READ");
-    n_ins = *t->h_cnt_pin;
+    if ((rc = mixed_rank_stage(t, P, mx, ps, d_op, n, n_ins))) return rc;
     if ((rc = check_room(t, n_ins))) return rc;
     P.ws.part_mod = t->part_mod;
     P.ws.part_res = t->part_res;
@@ -2123,9 +2205,7 @@ static int mixed_checks(imt_itree* t, PlanSet& P, const prep::MixedWs& mx, const
     }
     if (filtered && filtered->h_leaf)
         IMT_HIP(c, hipMemcpyAsync(filtered->h_leaf, filtered->d_leaf, filtered->n_all * 8, hipMemcpyDeviceToHost, ps));
-    IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, mx.word + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
-    IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, ps));
-    IMT_HIP(c, hipStreamSynchronize(ps));
+    if ((rc = mixed_check_verdict(t, P, mx, ps))) return rc;
     if ((rc = insertion_verdict(t, *t->h_err_pin, "batch"))) {
         if (filtered) {
             std::string why = c->last_error;
@@ -2142,27 +2222,20 @@ static int mixed_checks(imt_itree* t, PlanSet& P, const prep::MixedWs& mx, const
     return IMT_OK;
 }
 
-// The end of every mixed batch, its hashing enqueued on stream s: the plan set in flight, and if the batch inserted
-// anything the commit of a batch like any other -- the root into the plan set, the merged index and the size current.
+// The end of every mixed batch, its hashing enqueued on stream s.  Only READs: the plan set is in flight and that is all
+// -- the rotation, the batch count, the size and the generation stay.  Otherwise the commit of a batch like any other.
 static int mixed_commit(imt_itree* t, PlanSet& P, hipStream_t s, size_t n_ins, unsigned L0) {
     imt_ctx* c = t->ctx;
-    P.pipelined = false;
-    if (n_ins) {    // the tree has changed: from here the call is a batch like any other
-        IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
-        P.has_root = true;
-        P.sliced = false;
-        P.l0 = L0;
+    if (!n_ins) {
+        P.pipelined = false;
+        IMT_HIP(c, hipEventRecord(P.done, s));
+        P.in_flight = true;
+        return IMT_OK;
     }
-    IMT_HIP(c, hipEventRecord(P.done, s));
-    P.in_flight = true;
-    if (n_ins) {
-        t->cur = (t->cur + 1) % imt_itree::NSETS;
-        t->batch_no++;
-        t->sorted_cur ^= 1;
-        t->size += n_ins;
-        t->mirror_valid = false;
-        t->gen++;
-    }
+    IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
+    int rc = plan_launched(t, P, s, L0, false, false);
+    if (rc) return rc;
+    index_committed(t, t->size + n_ins);
     return IMT_OK;
 }
 
@@ -2202,8 +2275,12 @@ static int mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, const uin
     if ((rc = join_top(t))) return rc;
     IMT_HIP(c, hipStreamWaitEvent(s, t->up_done, 0));
     const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->depth} : launch::SibLayout{stride, 1};
-    if ((rc = mixed_hashes(t, P, s, E, L0, n_ins, d, launch::MixedRoute{mx.erow, (uint8_t*)r.low_sib}, (uint8_t*)r.root, lay, fmt)))
-        return rc;
+    const launch::MixedRoute route{mx.erow, (uint8_t*)r.low_sib};
+    WitnessSweep w;
+    w.route = &route;
+    w.n_ins = n_ins;
+    w.read_root = (uint8_t*)r.root;
+    if ((rc = witness_sweep(t, P, s, E, L0, d, lay, fmt, w))) return rc;
     if ((rc = mixed_commit(t, P, s, n_ins, L0))) return rc;
 
     // ---- outputs ----
@@ -2221,13 +2298,12 @@ static int apply_mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, con
     imt_ctx* c = t->ctx;
     int rc;
     const bool dev = flags & IMT_DEVICE_PTRS;
-    const unsigned fmt = flags & IMT_FMT_MASK;
     const uint64_t M = t->size;
     hipStream_t ps = t->up_stream;
     size_t n_ins = 0;
     if ((rc = mixed_checks(t, P, mixed_scratch(P), d_vals, d_op, n, bad_op, filtered, n_ins))) return rc;
     if (!n_ins) {
-        if (apply.root_out && (rc = imt_itree_root(t, apply.root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS)))) return rc;
+        if ((rc = report_unchanged_root(t, apply.root_out, flags))) return rc;
         if (n_inserted) *n_inserted = 0;
         return IMT_OK;
     }
@@ -2251,12 +2327,7 @@ static int apply_mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, con
 
     // ---- outputs ----
     if (n_inserted) *n_inserted = n_ins;
-    if (apply.root_out) {
-        uint8_t* r = dev ? (uint8_t*)apply.root_out : (uint8_t*)c->dev_scratch(slot++, 32);
-        if (!r) return IMT_ERR_HIP;
-        launch::convert(s, P.d_root, r, 1, IMT_FMT_DEVICE, fmt, c->d_err);
-        if (!dev) IMT_HIP(c, hipMemcpyAsync(apply.root_out, r, 32, hipMemcpyDeviceToHost, s));
-    }
+    if ((rc = deliver_root(c, s, P.d_root, apply.root_out, flags, slot))) return rc;
     if (!dev) IMT_HIP(c, hipStreamSynchronize(s));
     return IMT_OK;
 }
@@ -2267,30 +2338,18 @@ static int mixed_call(imt_itree* t, const void* vals, const uint8_t* op, size_t 
     if (!t) return IMT_ERR_ARG;
     imt_ctx* c = t->ctx;
     IMT_NOT_SLICED(t);
+    int rc;
     if (n == 0) {
-        if (apply && apply->root_out) {
-            const int rc0 = imt_itree_root(t, apply->root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS));
-            if (rc0) return rc0;
-        }
+        if (apply && (rc = report_unchanged_root(t, apply->root_out, flags))) return rc;
         if (n_inserted) *n_inserted = 0;
         return IMT_OK;
     }
     if (!vals || !op) return c->fail(IMT_ERR_ARG, "null vals / op");
-    if (flags & (IMT_PIPELINE | IMT_HOST_PREP | IMT_INPUTS_READY))
-        return c->fail(IMT_ERR_ARG, "mixed batches take neither IMT_PIPELINE, IMT_HOST_PREP nor IMT_INPUTS_READY");
-    if (t->index_base || t->global_depth != t->depth || t->part_mod > 1)
-        return c->fail(IMT_ERR_ARG, "mixed batches are not available on a placed or partitioned tree");
-    int rc = check_batch_call(t, n, flags);
-    if (rc) return rc;
+    if ((rc = check_mixed_mode(t, flags, MIXED_BATCH)) || (rc = check_batch_call(t, n, flags))) return rc;
     const bool dev = flags & IMT_DEVICE_PTRS;
-    if ((rc = check_fe_ptrs(c, dev, {vals})) || (rc = check_out_ptrs(c, dev, ins))) return rc;
-    if (rd && (rc = check_fe_ptrs(c, dev, {rd->low_leaf, rd->root, rd->low_sib}))) return rc;
-    if (dev && ((ins && ((uintptr_t)ins->low_index & 7u)) || (rd && ((uintptr_t)rd->low_index & 7u))))
-        return c->fail(IMT_ERR_ARG, "device low_index array is not 8-byte aligned");
+    if ((rc = check_mixed_ptrs(c, dev, vals, ins, rd))) return rc;
     if (apply && (rc = check_fe_ptrs(c, dev, {apply->root_out}))) return rc;
-    if (!dev)
-        for (size_t p = 0; p < n; p++)
-            if (op[p] > IMT_OP_READ) return c->fail(IMT_ERR_ARG, "op[%zu] = %u is neither IMT_OP_INSERT nor IMT_OP_READ", p, op[p]);
+    if ((rc = check_host_ops(c, dev, op, n))) return rc;
     if ((rc = ensure_device_index(t))) return rc;
     double waited_ms = 0;
 
@@ -2305,13 +2364,8 @@ static int mixed_call(imt_itree* t, const void* vals, const uint8_t* op, size_t 
     const uint8_t* d_vals = nullptr;
     uint8_t* up = dev ? nullptr : (uint8_t*)c->dev_scratch(slot++, n * 32);
     if ((rc = stage_canonical(c, ps, vals, n, flags, up, P.d_canon, P.ws.err, &d_vals))) return rc;
-    const uint8_t* d_op = op;
-    if (!dev) {
-        uint8_t* o = (uint8_t*)c->dev_scratch(slot++, n);
-        if (!o) return IMT_ERR_HIP;
-        IMT_HIP(c, hipMemcpyAsync(o, op, n, hipMemcpyHostToDevice, ps));
-        d_op = o;
-    }
+    const uint8_t* d_op = nullptr;
+    if ((rc = stage_ops(c, ps, dev, op, n, slot, &d_op))) return rc;
     if (apply) return apply_mixed_core(t, P, d_vals, d_op, n, slot, n_inserted, bad_op, flags, nullptr, *apply);
     return mixed_core(t, P, d_vals, d_op, n, n, slot, ins, rd, n_inserted, bad_op, flags, nullptr);
 }
@@ -2342,28 +2396,15 @@ static int mixed_filtered_call(imt_itree* t, const void* vals, const uint8_t* op
     if (n_read) *n_read = 0;
     IMT_NOT_SLICED(t);
     if (!status || !n_inserted || !n_read) return c->fail(IMT_ERR_ARG, "null status / n_inserted / n_read");
-    auto unchanged_root = [&]() -> int {      // nothing inserted: an apply call still reports the root
-        if (!apply || !apply->root_out) return IMT_OK;
-        return imt_itree_root(t, apply->root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS));
-    };
-    if (n == 0) return unchanged_root();
+    void* const root_out = apply ? apply->root_out : nullptr;     // nothing inserted: an apply call still reports the root
+    if (n == 0) return report_unchanged_root(t, root_out, flags);
     if (!vals || !op) return c->fail(IMT_ERR_ARG, "null vals / op");
-    if (flags & (IMT_PIPELINE | IMT_HOST_PREP | IMT_INPUTS_READY))
-        return c->fail(IMT_ERR_ARG, "mixed batches take neither IMT_PIPELINE, IMT_HOST_PREP nor IMT_INPUTS_READY");
-    if (t->index_base || t->global_depth != t->depth || t->part_mod > 1)
-        return c->fail(IMT_ERR_ARG, "mixed batches are not available on a placed or partitioned tree");
-    int rc = check_batch_call(t, n, flags);
-    if (rc) return rc;
+    int rc;
+    if ((rc = check_mixed_mode(t, flags, MIXED_BATCH)) || (rc = check_batch_call(t, n, flags))) return rc;
     const bool dev = flags & IMT_DEVICE_PTRS;
-    if ((rc = check_fe_ptrs(c, dev, {vals})) || (rc = check_out_ptrs(c, dev, ins))) return rc;
-    if (rd && (rc = check_fe_ptrs(c, dev, {rd->low_leaf, rd->root, rd->low_sib}))) return rc;
-    if (dev && ((ins && ((uintptr_t)ins->low_index & 7u)) || (rd && ((uintptr_t)rd->low_index & 7u))))
-        return c->fail(IMT_ERR_ARG, "device low_index array is not 8-byte aligned");
+    if ((rc = check_mixed_ptrs(c, dev, vals, ins, rd))) return rc;
     if (dev && ((uintptr_t)leaf_index & 7u)) return c->fail(IMT_ERR_ARG, "device leaf_index array is not 8-byte aligned");
-    if (apply && (rc = check_fe_ptrs(c, dev, {apply->root_out}))) return rc;
-    if (!dev)
-        for (size_t p = 0; p < n; p++)
-            if (op[p] > IMT_OP_READ) return c->fail(IMT_ERR_ARG, "op[%zu] = %u is neither IMT_OP_INSERT nor IMT_OP_READ", p, op[p]);
+    if ((rc = check_fe_ptrs(c, dev, {root_out})) || (rc = check_host_ops(c, dev, op, n))) return rc;
     if ((rc = ensure_device_index(t))) return rc;
     double waited_ms = 0;
     PlanSet& P = t->plan[t->cur];
@@ -2376,13 +2417,8 @@ static int mixed_filtered_call(imt_itree* t, const void* vals, const uint8_t* op
     const uint8_t* d_vals = nullptr;
     // the plan's own buffer for the upload as well, as gpu_filter has it
     if ((rc = stage_canonical(c, ps, vals, n, flags, P.d_canon, P.d_canon, P.ws.err, &d_vals))) return rc;
-    const uint8_t* d_op = op;
-    if (!dev) {
-        uint8_t* o = (uint8_t*)c->dev_scratch(slot++, n);
-        if (!o) return IMT_ERR_HIP;
-        IMT_HIP(c, hipMemcpyAsync(o, op, n, hipMemcpyHostToDevice, ps));
-        d_op = o;
-    }
+    const uint8_t* d_op = nullptr;
+    if ((rc = stage_ops(c, ps, dev, op, n, slot, &d_op))) return rc;
     uint64_t* d_leaf = leaf_index ? P.fw.leaf : nullptr;
     IMT_HIP(c, prep::mixed_filter(ps, P.fw, d_vals, d_op, (uint32_t)n, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)t->size,
                                   t->index_base, P.fw.status, d_leaf, P.ws.err));
@@ -2399,7 +2435,7 @@ static int mixed_filtered_call(imt_itree* t, const void* vals, const uint8_t* op
     if (rc || !n_acc) {       // refused, or nothing to carry out: the classification is the whole answer
         if (leaf_index) IMT_HIP(c, hipMemcpyAsync(leaf_index, d_leaf, n * 8, to_user, ps));
         IMT_HIP(c, hipStreamSynchronize(ps));
-        return rc ? rc : unchanged_root();
+        return rc ? rc : report_unchanged_root(t, root_out, flags);
     }
 
     // ---- the accepted operations: a mixed batch with the caller's dimensions ----
@@ -2456,7 +2492,7 @@ extern "C" int imt_itree_rewind(imt_itree* t, uint64_t new_size, void* root_out,
     const uint64_t M = t->size, S = new_size;
     if (S == M) {
         if (hashes) std::memset(hashes, 0, (t->depth + 1) * 8);
-        return root_out ? imt_itree_root(t, root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS)) : IMT_OK;
+        return report_unchanged_root(t, root_out, flags);
     }
     // ---- behind everything in flight, the caller's stream included: from here on the tree is this call's alone ----
     if ((rc = ensure_device_index(t))) return rc;
@@ -2467,10 +2503,7 @@ extern "C" int imt_itree_rewind(imt_itree* t, uint64_t new_size, void* root_out,
     hipStream_t s = c->stream;
     const unsigned L0 = std::min(ceil_log2(M), t->depth);       // of the size the call finds: the nodes in use reach that high
     const size_t max_rows = (size_t)std::min(M - S, S) + 1;
-    struct Trim {           // the scan's places are 8 bytes per leaf of the tree: not something a context keeps
-        imt_ctx* c;
-        ~Trim() { c->trim_scratch(3, (size_t)64 << 20); }
-    } trim{c};
+    const ScratchTrim trim{c, 3, 3};        // the scan's places are 8 bytes per leaf of the tree: not something a context keeps
     const size_t ws_bytes = prep::rewind_ws_bytes((size_t)M, max_rows);
     void* ws = c->dev_scratch(3, ws_bytes);
     uint8_t* d_root = (root_out && !dev) ? (uint8_t*)c->dev_scratch(0, 32) : (uint8_t*)root_out;
@@ -2624,13 +2657,10 @@ static int filtered_core(imt_itree* t, const void* vals, size_t n, uint8_t* stat
     IMT_NOT_SLICED(t);
     if (!status || !n_inserted) return c->fail(IMT_ERR_ARG, "null status / n_inserted");
     if (apply && (flags & IMT_PIPELINE)) return c->fail(IMT_ERR_ARG, "apply batches are not pipelined (IMT_PIPELINE)");
-    auto unchanged_root = [&]() -> int {      // nothing inserted: an apply call still reports the root
-        if (!apply || !apply->root_out) return IMT_OK;
-        return imt_itree_root(t, apply->root_out, flags & (IMT_FMT_MASK | IMT_DEVICE_PTRS));
-    };
+    void* const root_out = apply ? apply->root_out : nullptr;     // nothing inserted: an apply call still reports the root
     if (n == 0) {
         *n_inserted = 0;
-        return unchanged_root();
+        return report_unchanged_root(t, root_out, flags);
     }
     if (!vals) return c->fail(IMT_ERR_ARG, "null vals");
     int rc = check_batch_call(t, n, flags);
@@ -2662,10 +2692,9 @@ static int filtered_core(imt_itree* t, const void* vals, size_t n, uint8_t* stat
     }
     if (rc) return rc;
     if (!n_acc) {
-        if ((rc = unchanged_root())) return rc;
+        if ((rc = report_unchanged_root(t, root_out, flags))) return rc;
     } else {
-        if (apply && (rc = check_fe_ptrs(c, dev, {apply->root_out}))) return rc;
-        if ((rc = check_room(t, n_acc))) return rc;
+        if ((rc = check_fe_ptrs(c, dev, {root_out})) || (rc = check_room(t, n_acc))) return rc;
         // The insertion of the accepted values, on the plan set taken above: insert_core's own acquire_plan finds it idle
         // and reserved for 2 * n >= 2 * n_acc events, so P.fw.acc stays where it is, and its order_behind_caller repeats
         // the one above.  The outputs keep the caller's dimensions: level stride n, not n_acc.
@@ -2823,10 +2852,7 @@ static int view_build(imt_itree_view* v) {
     hipStream_t s = c->stream;
     const unsigned L0 = std::min(ceil_log2(M), t->depth);
     const size_t max_rows = (size_t)std::min(M - S, S) + 1;
-    struct Trim {
-        imt_ctx* c;
-        ~Trim() { c->trim_scratch(3, (size_t)64 << 20); }
-    } trim{c};
+    const ScratchTrim trim{c, 3, 3};
     const size_t ws_bytes = prep::rewind_ws_bytes((size_t)M, max_rows);
     void* ws = c->dev_scratch(3, ws_bytes);
     if (!ws) return IMT_ERR_HIP;
@@ -3002,23 +3028,14 @@ static int view_replay(imt_itree_view* v, size_t n, const imt_insert_out* out, u
     PlanSet& P = v->plan;
     if (P.cap_events < E || P.cap_levels < t->depth) IMT_HIP(c, hipStreamSynchronize(s));   // an earlier replay may still use it
     if ((rc = plan_reserve(c, P, E, t->depth, t->cap))) return rc;
-    struct Trim {           // the merged index is 4 bytes per leaf of the tree as of size + n: borrowed, like a build's scratch
-        imt_ctx* c;
-        ~Trim() { c->trim_scratch(3, (size_t)64 << 20); }
-    } trim{c};
+    const ScratchTrim trim{c, 3, 3};        // the merged index is 4 bytes per leaf of the tree as of size + n: like a build's scratch
     uint32_t* merged = (uint32_t*)c->dev_scratch(3, (size_t)(S + n) * 4);
     if (!merged) return IMT_ERR_HIP;
     // ---- where each requested output is written: the caller's array, or scratch copied back at the end ----
     size_t slot = 4;
     imt_insert_out d = {};
     const size_t sib_bytes = (size_t)t->global_depth * n * 32;
-    if (!stage_out(c, dev, slot, out->low_index, n * 8, d.low_index) || !stage_out(c, dev, slot, out->is_largest, n, d.is_largest) ||
-        !stage_out(c, dev, slot, out->low_leaf, n * 96, d.low_leaf) || !stage_out(c, dev, slot, out->new_leaf, n * 96, d.new_leaf) ||
-        !stage_out(c, dev, slot, out->old_root, n * 32, d.old_root) ||
-        !stage_out(c, dev, slot, out->interim_root, n * 32, d.interim_root) ||
-        !stage_out(c, dev, slot, out->new_root, n * 32, d.new_root) || !stage_out(c, dev, slot, out->low_sib, sib_bytes, d.low_sib) ||
-        !stage_out(c, dev, slot, out->new_sib, sib_bytes, d.new_sib))
-        return IMT_ERR_HIP;
+    if (!stage_insert_outputs(c, dev, slot, out, n, sib_bytes, d)) return IMT_ERR_HIP;
     // ---- hash-free part: the values are rows [S, S + n) of d_val, the index is the view's ----
     IMT_HIP(c, hipMemsetAsync(P.ws.err, 0, sizeof(int), s));
     P.ws.part_mod = t->part_mod;
@@ -3026,31 +3043,15 @@ static int view_replay(imt_itree_view* v, size_t n, const imt_insert_out* out, u
     IMT_HIP(c, prep::run(s, P.ws, nullptr, t->d_val, v->d_sorted, merged, (uint32_t)S, (uint32_t)n, t->index_base, P.d_pre,
                          P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][2], P.d_tab[0][3], d.low_index, d.is_largest,
                          (uint8_t*)d.low_leaf, (uint8_t*)d.new_leaf));
-    // ---- hashing: witness_hashes' stages, the levels below L0 against the view and none of them written back ----
+    // ---- hashing: the levels below L0 against the view, nothing written back or stored; old_root[0] is the view's root,
+    // the other roots are the events' top values ----
     const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->global_depth} : launch::SibLayout{n, 1};
     const view::Side side = v->side();
-    sweep_leaf_hashes(t, P, s, E);
-    int pf = c->prof_begin(IMT_PROF_INDEX, s);
-    index_phase(P, s, E, L0, nullptr);
-    c->prof_end(pf, s);
-    for (unsigned l = 0; l < L0; l++) {
-        const PlanSet::Level row = P.level(l);
-        pf = c->prof_begin(IMT_PROF_LEVEL, s);
-        launch::sweep_view_level(s, side, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], row.from, row.sibsrc, row.nodeb, row.timen,
-                                 t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, (uint32_t)E, (uint8_t*)d.low_sib,
-                                 (uint8_t*)d.new_sib, lay, l, fmt, c->coop_max_events);
-        c->prof_end(pf, s);
-    }
-    for (unsigned l = L0; l < t->depth; l++) {
-        pf = c->prof_begin(IMT_PROF_TOP, s);
-        launch::sweep_upper(s, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], c->d_zero + (size_t)l * 32, 0, (uint32_t)E, 0xffffffffu, nullptr,
-                            nullptr, (uint8_t*)d.low_sib, (uint8_t*)d.new_sib, lay, l, fmt, c->coop_max_events);
-        c->prof_end(pf, s);
-    }
-    // old_root[0] is the view's root; the other roots are the events' top values
-    if (d.old_root) launch::convert(s, v->d_chain + (size_t)t->depth * 32, (uint8_t*)d.old_root, 1, IMT_FMT_DEVICE, fmt, c->d_err);
-    launch::emit_roots(s, P.d_val[t->depth & 1], 0, (uint32_t)E, (uint32_t)E, (uint8_t*)d.old_root, (uint8_t*)d.interim_root,
-                       (uint8_t*)d.new_root, fmt, nullptr, nullptr);
+    WitnessSweep w;
+    w.side = &side;
+    w.store = false;
+    w.view_root = v->d_chain + (size_t)t->depth * 32;
+    if ((rc = witness_sweep(t, P, s, E, L0, d, lay, fmt, w))) return rc;
     // ---- outputs ----
     const HostPlan hp;
     if ((rc = deliver_hashfree_outputs(t, s, n, out, d, hp, flags, slot))) return rc;
@@ -3101,20 +3102,12 @@ static int view_replay_mixed(imt_itree_view* v, const void* vals, const uint8_t*
     const uint8_t* d_vals = nullptr;
     uint8_t* up = dev ? nullptr : (uint8_t*)c->dev_scratch(slot++, n * 32);
     if ((rc = stage_canonical(c, s, vals, n, flags, up, P.d_canon, P.ws.err, &d_vals))) return rc;
-    const uint8_t* d_op = op;
-    if (!dev) {
-        uint8_t* o = (uint8_t*)c->dev_scratch(slot++, n);
-        if (!o) return IMT_ERR_HIP;
-        IMT_HIP(c, hipMemcpyAsync(o, op, n, hipMemcpyHostToDevice, s));
-        d_op = o;
-    }
-    const prep::MixedWs mx{P.fw.flag, P.fw.rank, P.fw.idx, P.fw.aux, P.d_slot};
-    IMT_HIP(c, prep::mixed_ranks(s, P.ws, mx, d_op, (uint32_t)n));
-    IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, mx.word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, s));
-    IMT_HIP(c, hipStreamSynchronize(s));
-    if (*t->h_err_pin & prep::ERR_OP) return c->fail(IMT_ERR_ARG, "an op byte is neither IMT_OP_INSERT nor IMT_OP_READ");
-    const size_t n_ins = *t->h_cnt_pin, n_rd = n - n_ins;
+    const uint8_t* d_op = nullptr;
+    if ((rc = stage_ops(c, s, dev, op, n, slot, &d_op))) return rc;
+    const prep::MixedWs mx = mixed_scratch(P);
+    size_t n_ins = 0;
+    if ((rc = mixed_rank_stage(t, P, mx, s, d_op, n, n_ins))) return rc;
+    const size_t n_rd = n - n_ins;
     if (n_ins > t->size - S)
         return c->fail(IMT_ERR_RANGE, "the tree holds %llu leaves: no %zu insertions follow the view's %llu", (unsigned long long)t->size,
                        n_ins, (unsigned long long)S);
@@ -3122,9 +3115,7 @@ static int view_replay_mixed(imt_itree_view* v, const void* vals, const uint8_t*
     P.ws.part_mod = t->part_mod;
     P.ws.part_res = t->part_res;
     IMT_HIP(c, prep::mixed_check_view(s, P.ws, mx, d_vals, t->d_val, index, (uint32_t)S, (uint32_t)n, (uint32_t)n_ins));
-    IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, mx.word + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, s));
-    IMT_HIP(c, hipStreamSynchronize(s));
+    if ((rc = mixed_check_verdict(t, P, mx, s))) return rc;
     const int perr = *t->h_err_pin;
     if (perr & prep::ERR_NONCANONICAL) return c->fail(IMT_ERR_NONCANONICAL, "a value is not reduced (>= p)");
     if (perr & (prep::ERR_ZERO | prep::ERR_FOREIGN | prep::ERR_DUPLICATE | prep::ERR_MISMATCH)) {
@@ -3152,10 +3143,7 @@ static int view_replay_mixed(imt_itree_view* v, const void* vals, const uint8_t*
     // ---- accepted: events, tables, hash-free outputs ----
     const size_t E = n + n_ins;
     const unsigned L0 = std::min(ceil_log2(S + n_ins), t->depth);       // of the tree the block was applied to
-    struct Trim {           // the merged index is computed and dropped: borrowed, like a build's scratch
-        imt_ctx* c;
-        ~Trim() { c->trim_scratch(3, (size_t)64 << 20); }
-    } trim{c};
+    const ScratchTrim trim{c, 3, 3};        // the merged index is computed and dropped: borrowed, like a build's scratch
     uint32_t* merged = (uint32_t*)c->dev_scratch(3, (size_t)(S + n_ins) * 4);
     if (!merged) return IMT_ERR_HIP;
     imt_insert_out d = {};
@@ -3166,37 +3154,20 @@ static int view_replay_mixed(imt_itree_view* v, const void* vals, const uint8_t*
                                   (uint8_t*)d.low_leaf, (uint8_t*)d.new_leaf,
                                   prep::ReadOut{r.low_index, r.is_largest, (uint8_t*)r.low_leaf}));
 
-    // ---- hashing: mixed_hashes' stages, the levels below L0 against the view and none of them written back ----
+    // ---- hashing: the levels below L0 against the view -- against the stored tree as it is for a view at its size --
+    // and nothing written back or stored.  old_root[0] is the view's root (an INSERT means the view is not at the tree's
+    // size: the chain exists); the other roots, a READ's before the first INSERT included, are the events' top values ----
     const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->depth} : launch::SibLayout{n, 1};
     const launch::MixedRoute route{mx.erow, (uint8_t*)r.low_sib};
-    sweep_leaf_hashes(t, P, s, E);
-    int pf = c->prof_begin(IMT_PROF_INDEX, s);
-    index_phase(P, s, E, L0, nullptr);
-    c->prof_end(pf, s);
-    for (unsigned l = 0; l < L0; l++) {
-        const PlanSet::Level row = P.level(l);
-        pf = c->prof_begin(IMT_PROF_LEVEL, s);
-        if (v->current)
-            launch::sweep_level_mixed(s, route, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], row.from, row.sibsrc, row.nodeb, row.timen,
-                                      t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, (uint32_t)E, (uint8_t*)d.low_sib,
-                                      (uint8_t*)d.new_sib, lay, l, fmt, c->coop_max_events);
-        else
-            launch::sweep_view_level_mixed(s, v->side(), route, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], row.from, row.sibsrc,
-                                           row.nodeb, row.timen, t->nodes(l), t->h_len[l], c->d_zero + (size_t)l * 32, (uint32_t)E,
-                                           (uint8_t*)d.low_sib, (uint8_t*)d.new_sib, lay, l, fmt, c->coop_max_events);
-        c->prof_end(pf, s);
-    }
-    for (unsigned l = L0; l < t->depth; l++) {
-        pf = c->prof_begin(IMT_PROF_TOP, s);
-        launch::sweep_upper_mixed(s, route, P.d_val[l & 1], P.d_val[(l & 1) ^ 1], c->d_zero + (size_t)l * 32, (uint32_t)E, nullptr,
-                                  nullptr, (uint8_t*)d.low_sib, (uint8_t*)d.new_sib, lay, l, fmt, c->coop_max_events);
-        c->prof_end(pf, s);
-    }
-    // old_root[0] is the view's root (an INSERT means the view is not at the tree's size: the chain exists); the other
-    // roots, a READ's before the first INSERT included, are the events' top values
-    if (d.old_root) launch::convert(s, v->d_chain + (size_t)t->depth * 32, (uint8_t*)d.old_root, 1, IMT_FMT_DEVICE, fmt, c->d_err);
-    launch::emit_roots_mixed(s, route, P.d_val[t->depth & 1], (uint32_t)E, (uint32_t)n_ins, (uint8_t*)d.old_root,
-                             (uint8_t*)d.interim_root, (uint8_t*)d.new_root, (uint8_t*)r.root, fmt, nullptr);
+    const view::Side side = v->side();
+    WitnessSweep w;
+    w.route = &route;
+    w.n_ins = n_ins;
+    w.read_root = (uint8_t*)r.root;
+    w.side = v->current ? nullptr : &side;
+    w.store = false;
+    w.view_root = v->d_chain + (size_t)t->depth * 32;
+    if ((rc = witness_sweep(t, P, s, E, L0, d, lay, fmt, w))) return rc;
     if (n_inserted) *n_inserted = n_ins;
     return mixed_deliver_outputs(t, s, ins, rd, d, r, n_ins, n_rd, n, flags);
 }
@@ -3208,20 +3179,11 @@ extern "C" int imt_itree_view_mixed_witness(imt_itree_view* v, const void* vals,
     imt_itree* t = v->t;
     imt_ctx* c = t->ctx;
     if (n && (!vals || !op)) return c->fail(IMT_ERR_ARG, "null vals / op");
-    if (flags & (IMT_PIPELINE | IMT_HOST_PREP | IMT_INPUTS_READY))
-        return c->fail(IMT_ERR_ARG, "a mixed replay takes neither IMT_PIPELINE, IMT_HOST_PREP nor IMT_INPUTS_READY");
-    if (t->index_base || t->global_depth != t->depth || t->part_mod > 1)
-        return c->fail(IMT_ERR_ARG, "mixed replays are not available on a placed or partitioned tree");
+    int rc;
+    if ((rc = check_mixed_mode(t, flags, MIXED_REPLAY))) return rc;
     if (n > ((size_t)1 << 30)) return c->fail(IMT_ERR_RANGE, "list too large");
     const bool dev = flags & IMT_DEVICE_PTRS;
-    int rc;
-    if ((rc = check_fe_ptrs(c, dev, {vals})) || (rc = check_out_ptrs(c, dev, ins))) return rc;
-    if (rd && (rc = check_fe_ptrs(c, dev, {rd->low_leaf, rd->root, rd->low_sib}))) return rc;
-    if (dev && ((ins && ((uintptr_t)ins->low_index & 7u)) || (rd && ((uintptr_t)rd->low_index & 7u))))
-        return c->fail(IMT_ERR_ARG, "device low_index array is not 8-byte aligned");
-    if (!dev)
-        for (size_t p = 0; p < n; p++)
-            if (op[p] > IMT_OP_READ) return c->fail(IMT_ERR_ARG, "op[%zu] = %u is neither IMT_OP_INSERT nor IMT_OP_READ", p, op[p]);
+    if ((rc = check_mixed_ptrs(c, dev, vals, ins, rd)) || (rc = check_host_ops(c, dev, op, n))) return rc;
     if ((rc = view_enter(v, flags))) return rc;
     if (n == 0) {
         if (n_inserted) *n_inserted = 0;

@@ -34,7 +34,7 @@ struct Batch {
     std::vector<Node> launches;     // in stream order
 };
 
-// the model: written from what the kernels touch (imt_itree.cpp: apply_hashes, witness_hashes), not from the header
+// the model: written from what the kernels touch (imt_itree.cpp: apply_hashes, witness_sweep), not from the header
 Batch make_batch(Kind kind, unsigned l0, unsigned depth) {
     Batch b{kind, l0, {}};
     auto bit = [](unsigned l) { return (uint32_t)1 << l; };
