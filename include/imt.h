@@ -520,8 +520,11 @@ int imt_itree_apply_batch(imt_itree *t, const void *vals /*[n][32]*/, size_t n, 
  * entry), and pipelined batches of either kind may follow each other in any order.  imt_itree_apply_stats reports the last
  * apply call of either kind and waits for that call only.
  * Which call at which block size: profiles/apply_pipelined.txt, README "Witness-free insertion".
- * Not offered: pipelined forms of imt_itree_apply_filtered, _apply_mixed and _apply_mixed_filtered -- they read counts back
- * per call, which is the wait this call exists to avoid. */
+ * Blocks with READs overlap through imt_itree_apply_mixed_pipelined / imt_itree_mixed_pipelined below: the INSERT count and
+ * the verdict they read back come with the waits for the value checks that every pipelined call makes anyway.
+ * Not offered: pipelined forms of imt_itree_apply_filtered, imt_itree_mixed_filtered and imt_itree_apply_mixed_filtered --
+ * they return a status per value or operation, complete at return, and (the mixed ones) make a third wait for the
+ * classification: a call that has waited that long on the side stream has little left to overlap. */
 int imt_itree_apply_pipelined(imt_itree *t, const void *vals /*[n][32]*/, size_t n, void *root_out /*[32] or NULL*/,
                               unsigned flags);
 /* imt_itree_insert_filtered without witnesses: status / leaf_index / *n_inserted exactly as that call writes them, then
@@ -678,7 +681,7 @@ int imt_itree_non_membership_witness(imt_itree *t, const void *vals /*[n][32]*/,
  * n > 0; a misaligned device buffer; IMT_PIPELINE, IMT_HOST_PREP or IMT_INPUTS_READY in flags; a placed or partitioned
  * tree (so a value of another subtree's residue cannot occur); a replica of a sliced world with steps in flight; an open
  * slice; a call between imt_itree_batch_begin and _end.  n == 0: IMT_OK.
- * NOT IN THIS CALL: pipelining against other batches and placed / partitioned trees.
+ * NOT IN THIS CALL: placed / partitioned trees, and overlap with the batches around it -- imt_itree_mixed_pipelined below.
  * IMT_FMT_*, IMT_SIB_ITEM_MAJOR and IMT_DEVICE_PTRS mean what they mean to imt_itree_insert_batch; with IMT_DEVICE_PTRS
  * `op` is a device pointer too, n_inserted and bad_op are host memory always.  The call orders itself behind batches in
  * flight (pipelined ones included), later calls are ordered behind it, and like imt_itree_insert_batch it returns once the
@@ -764,8 +767,9 @@ int imt_itree_mixed_filtered(imt_itree *t, const void *vals /*[n][32]*/, const u
  * Ordered as imt_itree_apply_batch: on the context's stream, behind every batch in flight (pipelined ones included),
  * later calls of any kind behind it; witness, apply, mixed and apply-mixed calls alternate freely on one tree.  status,
  * leaf_index and the counts are complete at return, as for the calls above.
- * NOT IN THESE CALLS: placed and partitioned trees, pipelining, and witness rows of any kind -- a view at the size before
- * the block gives them later: imt_itree_view_mixed_witness below, over the operations that were carried out. */
+ * NOT IN THESE CALLS: placed and partitioned trees, overlap between consecutive blocks (imt_itree_apply_mixed_pipelined
+ * below has it; the filtered twin does not, see imt_itree_apply_pipelined), and witness rows of any kind -- a view at the
+ * size before the block gives them later: imt_itree_view_mixed_witness below, over the operations that were carried out. */
 int imt_itree_apply_mixed(imt_itree *t, const void *vals /*[n][32]*/, const uint8_t *op /*[n]*/, size_t n,
                           void *root_out /*[32] or NULL*/, uint64_t *n_inserted /*host, may be NULL*/,
                           uint64_t *bad_op /*host, may be NULL*/, unsigned flags);
@@ -773,6 +777,52 @@ int imt_itree_apply_mixed_filtered(imt_itree *t, const void *vals /*[n][32]*/, c
                                    uint8_t *status /*[n]*/, uint64_t *leaf_index /*[n] or NULL*/,
                                    uint64_t *n_inserted /*host*/, uint64_t *n_read /*host*/,
                                    void *root_out /*[32] or NULL*/, unsigned flags);
+/* CONSECUTIVE MIXED BLOCKS THAT OVERLAP, for the prover and the follower of a chain whose blocks hold
+ * verify_non_inclusion transactions: imt_itree_mixed_batch and imt_itree_apply_mixed on the tree's pipeline streams.
+ * DEFINED BY THE CALLS ABOVE.  Play the same blocks on a twin tree through imt_itree_mixed_batch (imt_itree_apply_mixed for
+ * the apply form), one at a time with imt_ctx_sync() after each.  AT RETURN this call has given the same return code, the
+ * same *n_inserted (with IMT_OK only) and *bad_op (with IMT_ERR_VALUE only) -- host memory, complete at return -- and the
+ * same imt_itree_size.  AFTER imt_ctx_sync() every array of `ins` and `rd` holds the same rows byte for byte (NULL fields
+ * skipped, level stride n, IMT_FMT_* and IMT_SIB_ITEM_MAJOR as there, nothing written at or beyond row n_inserted of `ins`
+ * or row n - n_inserted of `rd`), root_out holds the same root, and the tree is the same tree: index, leaf preimages,
+ * every stored node, root -- so every later call answers the same, imt_itree_root_lagged, imt_itree_apply_stats and whether
+ * a view rebuilds included.
+ * WHAT DIFFERS.  The call returns once the block has passed the mixed checks on the GPU (the two host waits of the calls
+ * above: the INSERT count, then the verdict); its hashing runs on one of the tree's pipeline streams behind the blocks
+ * before it -- a witness block one level behind the block in front, an apply block two launches behind
+ * (imt_apply_pipe.hpp: by the levels it reads and writes a mixed witness block is a witness batch of its events, a READ's
+ * write-back putting back the bytes it read, and a mixed apply block is the apply batch of its INSERTs).  Up to four
+ * consecutive blocks hash at once; a fifth call waits for the first.
+ * IMT_DEVICE_PTRS is required (otherwise IMT_ERR_ARG, nothing changed): vals, op, every output array and root_out are
+ * device-addressable memory -- a row of an imt_host_alloc buffer is fine -- aligned as the device-pointer path of the calls
+ * above demands; n_inserted and bad_op stay host pointers.  IMT_PIPELINE may be set and means nothing more; IMT_HOST_PREP
+ * and IMT_INPUTS_READY are IMT_ERR_ARG, and so is every other refusal of the calls above (placed and partitioned trees, an
+ * open slice, ...).
+ * vals AND op MAY BE REUSED WHEN THE CALL RETURNS, whatever it returns: nothing enqueued after the checks reads them (the
+ * INSERT values are in the tree's value rows by then, the op bytes in the block's own tables).  The output arrays and
+ * root_out belong to the block until imt_ctx_sync() or any later call on the tree has ordered the context's stream
+ * behind it.
+ * A REFUSED BLOCK (IMT_ERR_VALUE with *bad_op, IMT_ERR_NONCANONICAL, IMT_ERR_FULL, a bad op byte as IMT_ERR_ARG) leaves
+ * alone the tree, the blocks in flight and their outputs, and writes nothing of the caller's but *bad_op.
+ * A BLOCK OF READS ONLY goes through imt_itree_mixed_pipelined like any other block: it runs behind the block before it,
+ * so its rows carry that block's effects, and the block behind it waits for it level by level; as in the calls above it
+ * is no change of the tree (views stay fresh, imt_itree_root_lagged does not see it, the size stays).  Through
+ * imt_itree_apply_mixed_pipelined it hashes nothing: root_out = the current root, ordered behind everything in flight, and
+ * imt_itree_apply_stats keeps reporting the earlier apply call.  n == 0: IMT_OK, *n_inserted = 0, root_out likewise.
+ * imt_itree_apply_stats treats imt_itree_apply_mixed_pipelined as it treats imt_itree_apply_pipelined: the counts are
+ * those of imt_itree_apply_batch of the carried-out INSERT values, and it waits for that call only.
+ * Every other call on the tree orders itself behind these blocks exactly as behind pipelined batches (queries, views and
+ * their replays, imt_itree_rewind, imt_itree_load*, un-pipelined batches of every kind, imt_sliced_* entry), and the four
+ * pipelined kinds -- imt_itree_insert_batch with IMT_PIPELINE, imt_itree_apply_pipelined and these two -- may follow each
+ * other in any order with no synchronisation between them.
+ * Measured against the calls above: profiles/mixed_pipelined.txt, README "Mixed blocks that overlap". */
+int imt_itree_mixed_pipelined(imt_itree *t, const void *vals /*[n][32]*/, const uint8_t *op /*[n]*/, size_t n,
+                              const imt_insert_out *ins /*may be NULL*/, const imt_read_out *rd /*may be NULL*/,
+                              uint64_t *n_inserted /*host, may be NULL*/, uint64_t *bad_op /*host, may be NULL*/,
+                              unsigned flags);
+int imt_itree_apply_mixed_pipelined(imt_itree *t, const void *vals /*[n][32]*/, const uint8_t *op /*[n]*/, size_t n,
+                                    void *root_out /*[32] or NULL*/, uint64_t *n_inserted /*host, may be NULL*/,
+                                    uint64_t *bad_op /*host, may be NULL*/, unsigned flags);
 /* APPLY A MIXED BLOCK NOW, PROVE IT LATER (beside imt_itree_view_insert_witness; declared here for imt_read_out): the
  * witnesses of a block of INSERTs and READs whose insertions the tree has already made, witness-free or otherwise, and may
  * since have built upon -- every READ's witness against the tree as it stood at that point of the block.

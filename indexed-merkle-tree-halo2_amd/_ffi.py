@@ -159,6 +159,9 @@ SIGNATURES = {
     "imt_itree_apply_mixed": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, P(c_u64), P(c_u64), c_uint]),
     "imt_itree_apply_mixed_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, P(c_u64), P(c_u64),
                                                c_void_p, c_uint]),
+    "imt_itree_mixed_pipelined": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, P(InsertOut), P(ReadOut), P(c_u64), P(c_u64),
+                                          c_uint]),
+    "imt_itree_apply_mixed_pipelined": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, P(c_u64), P(c_u64), c_uint]),
     "imt_itree_load": (c_int, [c_void_p, c_void_p, c_u64, c_uint]),
     "imt_itree_load_values": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_uint]),
     "imt_itree_get_values": (c_int, [c_void_p, c_u64, c_size_t, c_void_p, c_uint]),

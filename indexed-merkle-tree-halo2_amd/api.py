@@ -757,6 +757,43 @@ class IndexedTree:
         self.ctx._check(rc)
         return n_ins.value, to_int(root)
 
+    def _mixed_verdict(self, rc, bad):
+        if rc == _ffi.ERR["VALUE"]:
+            e = ValueError(lib.imt_last_error(self.ctx.h).decode())
+            e.bad_op = bad.value
+            raise e
+        self.ctx._check(rc)
+
+    def mixed_pipelined(self, vals_ptr, ops_ptr, n, ins=None, rd=None, fmt=0, item_major=False):
+        """mixed_batch() of n operations already in device-addressable memory that overlaps with the blocks before it
+        (imt_itree_mixed_pipelined): vals_ptr -> [n][32] values (16-byte aligned), ops_ptr -> [n] op bytes.  ins / rd:
+        dicts of device-addressable addresses by field name (the fields of imt_insert_out / imt_read_out; a missing
+        field is not written), sibling arrays with level stride n; their rows are complete after ctx.sync().  Returns
+        the number of INSERTs once the block has passed its checks; vals and ops may be reused then.  A refused value
+        raises ValueError with .bad_op; the tree and the blocks in flight are then as they were."""
+        out = _ffi.InsertOut(**(ins or {}))
+        rout = _ffi.ReadOut(**(rd or {}))
+        n_ins, bad = ctypes.c_uint64(), ctypes.c_uint64()
+        flags = fmt | _ffi.DEVICE_PTRS | (_ffi.SIB_ITEM_MAJOR if item_major else 0)
+        rc = lib.imt_itree_mixed_pipelined(self.h, ctypes.c_void_p(vals_ptr), ctypes.c_void_p(ops_ptr), n,
+                                           ctypes.byref(out) if ins is not None else None,
+                                           ctypes.byref(rout) if rd is not None else None, ctypes.byref(n_ins),
+                                           ctypes.byref(bad), flags)
+        self._mixed_verdict(rc, bad)
+        return n_ins.value
+
+    def apply_mixed_pipelined(self, vals_ptr, ops_ptr, n, root_ptr=None, fmt=0):
+        """apply_mixed() of n operations already in device-addressable memory that overlaps with the blocks before it
+        (imt_itree_apply_mixed_pipelined).  The root after the block goes to root_ptr (32 device-addressable bytes, or
+        None) and is complete after ctx.sync().  Returns the number of INSERTs once the block has passed its checks;
+        a refused value raises ValueError with .bad_op, the tree and the blocks in flight as they were."""
+        n_ins, bad = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = lib.imt_itree_apply_mixed_pipelined(self.h, ctypes.c_void_p(vals_ptr), ctypes.c_void_p(ops_ptr), n,
+                                                 ctypes.c_void_p(root_ptr) if root_ptr is not None else None,
+                                                 ctypes.byref(n_ins), ctypes.byref(bad), fmt | _ffi.DEVICE_PTRS)
+        self._mixed_verdict(rc, bad)
+        return n_ins.value
+
     def apply_mixed_filtered(self, vals, ops):
         """mixed_filtered() without witnesses (imt_itree_apply_mixed_filtered): (status, leaf_index, n_inserted, n_read,
         root) -- status and leaf_index per operation passed in, the accepted INSERTs and READs, the root after the

@@ -97,14 +97,18 @@ struct PlanSet {
     prep::FilterWs fw;                   // classification scratch of imt_itree_insert_filtered
     uint32_t* d_slot = nullptr;          // [levels + 1][E] slot of every event per level (sharded mode)
     const uint8_t** d_valptr = nullptr;  // [levels + 1] device array of level value pointers (sharded mode)
-    uint8_t* d_root = nullptr;           // stored root right after this batch (device format)
+    uint8_t* d_root = nullptr;           // [2][32] stored root right after this batch (device format); row 1: see reads_only
     bool has_root = false;
+    // A pipelined mixed block of READs only (imt_itree_mixed_pipelined) takes a turn in the rotation without being a batch:
+    // row 0 of d_root is then the root it found, row 1 (has_root2) the root one batch before that, carried along so that
+    // imt_itree_root_lagged answers as if the block had not rotated.  sliced1 / sliced2: the set the row stands for was a slice's.
+    bool reads_only = false, has_root2 = false, sliced1 = false, sliced2 = false;
     hipEvent_t done = nullptr;           // recorded after the batch's last kernel
     // [l]: stored level l is final and this batch no longer reads it (imt_apply_pipe.hpp) -- after k_writeback of the
     // level for a witness batch, after the launch that reads the level for a pipelined apply batch
     hipEvent_t wb_done[IMT_MAX_DEPTH + 1] = {nullptr};
     bool in_flight = false;
-    bool pipelined = false;              // ran on a pipeline stream (IMT_PIPELINE, imt_itree_apply_pipelined)
+    bool pipelined = false;              // ran on a pipeline stream (IMT_PIPELINE, imt_itree_*_pipelined)
     bool applied = false;                // ... as an apply batch: which events it recorded, and when
     // a tree's plan sets only (imt_itree_new), kept when the set grows: what a pipelined apply batch must not share
     uint64_t* d_count = nullptr;         // [IMT_MAX_DEPTH + 1] its hashes per level, sizing its launches on the device
@@ -175,6 +179,7 @@ struct imt_itree {
     // imt_itree_apply_pipelined rotates over the same streams, two launches apart (imt_apply_pipe.hpp).
     hipStream_t pipe_stream[NPIPE] = {};
     hipEvent_t user_mark = nullptr;  // position of the context's stream when a pipelined call starts
+    uint64_t pipe_turn = 0;          // pipelined blocks so far: whose turn among the pipeline streams it is
     bool pipe_pending = false;       // pipelined work the context's stream has not been ordered behind
     // reusable host work arrays of insert_batch
     std::vector<uint32_t> w_ord, w_rank;
@@ -286,7 +291,7 @@ static int plan_reserve(imt_ctx* c, PlanSet& p, size_t events, unsigned levels, 
     A((void**)&p.d_timen, (size_t)L * E * 4);
     A((void**)&p.d_val[0], E * 32);
     A((void**)&p.d_val[1], E * 32);
-    A((void**)&p.d_root, 32);
+    A((void**)&p.d_root, 64);
     {   // GPU-prepare workspace for E/2 insertions
         const size_t N = E / 2;
         int lv = 1;
@@ -758,19 +763,27 @@ extern "C" int imt_itree_root_lagged(imt_itree* t, unsigned lag, void* root, uns
     if (rc) return rc;
     if (t->batch_no <= lag) return c->fail(IMT_ERR_RANGE, "no batch %u calls ago", lag);
     if ((rc = check_fe_ptrs(c, flags & IMT_DEVICE_PTRS, {root}))) return rc;
-    const PlanSet& P = t->plan[(t->cur + 2 * imt_itree::NSETS - 1 - (int)lag) % imt_itree::NSETS];
-    if (!P.has_root)
-        return c->fail(P.sliced ? IMT_ERR_ARG : IMT_ERR_INTERNAL,
-                       P.sliced ? "imt_itree_root_lagged does not see slices: imt_sliced_flush, then imt_itree_root" : "batch root not recorded");
+    // The newest turn of the rotation is a pipelined block of READs only: not a batch, so it answers for the batches
+    // in front of it from the two roots it carries.  (One further back holds the root it found, which is the root of
+    // the batch before it: the right answer for lag 1 as it stands.)
+    const PlanSet& newest = t->plan[(t->cur + imt_itree::NSETS - 1) % imt_itree::NSETS];
+    const bool carried = newest.reads_only;
+    const PlanSet& P = carried ? newest : t->plan[(t->cur + 2 * imt_itree::NSETS - 1 - (int)lag) % imt_itree::NSETS];
+    const bool row1 = carried && lag == 1;
+    const bool have = row1 ? P.has_root2 : P.has_root, sliced = row1 ? P.sliced2 : P.reads_only ? P.sliced1 : P.sliced;
+    if (!have)
+        return c->fail(sliced ? IMT_ERR_ARG : IMT_ERR_INTERNAL,
+                       sliced ? "imt_itree_root_lagged does not see slices: imt_sliced_flush, then imt_itree_root" : "batch root not recorded");
     IMT_HIP(c, hipStreamWaitEvent(c->stream, P.done, 0));
     const unsigned fmt = flags & IMT_FMT_MASK;
+    const uint8_t* src = P.d_root + (row1 ? 32 : 0);
     if (flags & IMT_DEVICE_PTRS) {
-        launch::convert(c->stream, P.d_root, (uint8_t*)root, 1, IMT_FMT_DEVICE, fmt, c->d_err);
+        launch::convert(c->stream, src, (uint8_t*)root, 1, IMT_FMT_DEVICE, fmt, c->d_err);
         return IMT_OK;
     }
     uint8_t* d = (uint8_t*)c->dev_scratch(0, 32);
     if (!d) return IMT_ERR_HIP;
-    launch::convert(c->stream, P.d_root, d, 1, IMT_FMT_DEVICE, fmt, c->d_err);
+    launch::convert(c->stream, src, d, 1, IMT_FMT_DEVICE, fmt, c->d_err);
     IMT_HIP(c, hipMemcpyAsync(root, d, 32, hipMemcpyDeviceToHost, c->stream));
     IMT_HIP(c, hipStreamSynchronize(c->stream));
     return IMT_OK;
@@ -1169,7 +1182,7 @@ extern "C" int imt_itree_load(imt_itree* t, const void* preimages, uint64_t n, u
     t->dev_index_valid = true;
     t->pending.active = false;
     t->gen++;
-    for (auto& pl : t->plan) pl.has_root = false;
+    for (auto& pl : t->plan) pl.has_root = pl.has_root2 = false;
     return IMT_OK;
 }
 
@@ -1274,7 +1287,7 @@ extern "C" int imt_itree_load_values(imt_itree* t, const void* vals, uint64_t n,
     t->dev_index_valid = true;
     t->pending.active = false;
     t->gen++;
-    for (auto& pl : t->plan) pl.has_root = false;
+    for (auto& pl : t->plan) pl.has_root = pl.has_root2 = false;
     return IMT_OK;
 }
 
@@ -1563,7 +1576,7 @@ struct WitnessSweep {
     const view::Side* side = nullptr;             // NULL: base siblings below L0 are read from the stored tree as it is
     bool store = true;                            // levels written back, the nodes from L0 up and the root stored
     const uint8_t* view_root = nullptr;           // NULL: old_root[0] is the stored root; else the root in a view's chain
-    PipeCtx pipe;                                 // imt_itree_insert_batch under IMT_PIPELINE only
+    PipeCtx pipe;                                 // imt_itree_insert_batch under IMT_PIPELINE, imt_itree_mixed_pipelined
 };
 
 // ---- one step each of the witness schedule on stream s, with its profile brackets.  `d` holds the device pointers of
@@ -1662,8 +1675,8 @@ static int pipe_record(imt_itree* t, hipStream_t s, PlanSet& P, const PipeCtx& p
 
 // The witness schedule on stream s, behind the preparation: leaf hashes, index phase (no hashing), then the hash sweep
 // level by level -- with each level's write-back unless nothing is stored -- and the roots.  Every witness there is comes
-// through here; `w` says which: imt_itree_insert_batch (w.pipe.prev: the batch before this one if it is still on a
-// pipeline stream -- this batch then runs one level behind it), a mixed batch, or a replay of either through a view.
+// through here; `w` says which: imt_itree_insert_batch, a mixed batch (of either: w.pipe.prev is the batch before this one
+// if it is still on a pipeline stream -- this batch then runs one level behind it), or a replay of either through a view.
 static int witness_sweep(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsigned L0, const imt_insert_out& d,
                          launch::SibLayout lay, unsigned fmt, const WitnessSweep& w) {
     imt_ctx* c = t->ctx;
@@ -1709,8 +1722,8 @@ static int witness_sweep(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsi
 // are sized by host-side bounds; the counts stay on the device (`count`, [depth + 1]), so nothing here waits for the GPU.
 // imt_itree_rewind hashes through here too: its table has one event per touched leaf, its L0 is that of the size it finds
 // and its counts are its own.
-// On a pipeline stream (imt_itree_apply_pipelined; `count` is then the plan set's) the batch in front may be two launches
-// ahead: every launch that writes a stored level first waits for the event imt_apply_pipe.hpp names -- an apply batch in
+// On a pipeline stream (imt_itree_apply_pipelined, imt_itree_apply_mixed_pipelined; `count` is then the plan set's) the
+// batch in front may be two launches ahead: every launch that writes a stored level first waits for the event imt_apply_pipe.hpp names -- an apply batch in
 // front reads level l in the launch AFTER the one that wrote it -- and records its own; and the chain to the root is
 // hashed into the plan set's rows (k_apply_chain), beside the chains of the batches in front, with only the store of those
 // rows into the tree and into P.d_root ordered behind them.
@@ -1855,6 +1868,7 @@ static int deliver_root(imt_ctx* c, hipStream_t s, const uint8_t* src, void* roo
 // so the set holds a root, is in flight until `done`, and the next batch takes the next set.
 static int plan_launched(imt_itree* t, PlanSet& P, hipStream_t s, unsigned L0, bool pipelined, bool applied) {
     P.has_root = true;
+    P.reads_only = false;
     IMT_HIP(t->ctx, hipEventRecord(P.done, s));
     P.pipelined = pipelined;
     P.applied = applied;
@@ -1863,6 +1877,23 @@ static int plan_launched(imt_itree* t, PlanSet& P, hipStream_t s, unsigned L0, b
     P.in_flight = true;
     t->cur = (t->cur + 1) % imt_itree::NSETS;
     t->batch_no++;
+    return IMT_OK;
+}
+// The stream a batch hashes on and its pipeline context: the context's stream behind every batch in flight, or -- a
+// pipelined block -- the next of the NPIPE pipeline streams, behind what the caller has enqueued on the context's stream
+// (the buffers were last used there) and with the block in front, if that is still on a pipeline stream, to take its waits
+// from.  Called with t->cur the block's own plan set.
+static int hashing_stream(imt_itree* t, bool pipelined, hipStream_t& s, PipeCtx& pipe) {
+    imt_ctx* c = t->ctx;
+    s = c->stream;
+    pipe = PipeCtx{nullptr, pipelined};
+    if (!pipelined) return join_top(t);
+    s = t->pipe_stream[t->pipe_turn++ % imt_itree::NPIPE];
+    IMT_HIP(c, hipEventRecord(t->user_mark, c->stream));
+    IMT_HIP(c, hipStreamWaitEvent(s, t->user_mark, 0));
+    const PlanSet& o = t->plan[(t->cur + imt_itree::NSETS - 1) % imt_itree::NSETS];
+    if (o.in_flight && o.pipelined) pipe.prev = &o;
+    t->pipe_pending = true;
     return IMT_OK;
 }
 // The device index committed: the merged index the preparation left in the other buffer becomes current together with
@@ -1909,18 +1940,9 @@ static int insert_core(imt_itree* t, const void* vals, unsigned val_flags, size_
     IMT_HIP(c, hipEventRecord(t->up_done, t->up_stream));
 
     // ---- compute stream: the context's, or one of the NPIPE pipeline streams ----
-    hipStream_t s = c->stream;
-    PipeCtx pipe{nullptr, pipelined};   // prev: the batch before this one, if it is still on a pipeline stream
-    if (pipelined) {
-        s = t->pipe_stream[t->batch_no % imt_itree::NPIPE];
-        IMT_HIP(c, hipEventRecord(t->user_mark, c->stream));     // buffers last used on the user's stream
-        IMT_HIP(c, hipStreamWaitEvent(s, t->user_mark, 0));
-        const PlanSet& o = t->plan[(t->cur + imt_itree::NSETS - 1) % imt_itree::NSETS];
-        if (o.in_flight && o.pipelined) pipe.prev = &o;
-        t->pipe_pending = true;
-    } else {
-        if ((rc = join_top(t))) return rc;
-    }
+    hipStream_t s;
+    PipeCtx pipe;
+    if ((rc = hashing_stream(t, pipelined, s, pipe))) return rc;
     IMT_HIP(c, hipStreamWaitEvent(s, t->up_done, 0));
 
     // ---- hashing: one hash per touched node straight into the stored tree (imt_apply.hpp), or the witness sweep ----
@@ -2224,16 +2246,49 @@ static int mixed_checks(imt_itree* t, PlanSet& P, const prep::MixedWs& mx, const
 
 // The end of every mixed batch, its hashing enqueued on stream s.  Only READs: the plan set is in flight and that is all
 // -- the rotation, the batch count, the size and the generation stay.  Otherwise the commit of a batch like any other.
-static int mixed_commit(imt_itree* t, PlanSet& P, hipStream_t s, size_t n_ins, unsigned L0) {
+// On a pipeline stream (pipe.pipelined; `applied`: as an apply batch, whose store of the chain has filled P.d_root) a block
+// of READs only takes its turn in the rotation all the same: the block behind it takes its waits from this set's events,
+// and this set stays the block's own until its `done`.  It is still no batch -- the batch count, the size and the
+// generation stay -- so it carries the roots imt_itree_root_lagged would have found without it (PlanSet::reads_only).
+static int mixed_commit(imt_itree* t, PlanSet& P, hipStream_t s, size_t n_ins, unsigned L0, const PipeCtx& pipe = {},
+                        bool applied = false) {
     imt_ctx* c = t->ctx;
-    if (!n_ins) {
+    if (!n_ins && !pipe.pipelined) {
         P.pipelined = false;
         IMT_HIP(c, hipEventRecord(P.done, s));
         P.in_flight = true;
         return IMT_OK;
     }
-    IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
-    int rc = plan_launched(t, P, s, L0, false, false);
+    if (!n_ins) {
+        // the turn before this one, and the one before that: both behind `s` already -- a pipelined one through the waits
+        // of the sweep (WI_OLD_ROOT waits for DONE, as every pipelined kind does before it ends), any other through the
+        // context's stream -- the explicit wait says so where the copy is
+        const PlanSet& o1 = t->plan[(t->cur + imt_itree::NSETS - 1) % imt_itree::NSETS];
+        const PlanSet& o2 = t->plan[(t->cur + imt_itree::NSETS - 2) % imt_itree::NSETS];
+        const bool chained = o1.reads_only;
+        const PlanSet& from = chained ? o1 : o2;
+        const bool have2 = chained ? o1.has_root2 : o2.has_root;
+        if (have2) {
+            IMT_HIP(c, hipStreamWaitEvent(s, from.done, 0));
+            IMT_HIP(c, hipMemcpyAsync(P.d_root + 32, from.d_root + (chained ? 32 : 0), 32, hipMemcpyDeviceToDevice, s));
+        }
+        IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
+        P.has_root = o1.has_root;        // a turn without a root in front (a slice's, or none since a rewind) stays one
+        P.reads_only = true;
+        P.has_root2 = have2;
+        P.sliced1 = chained ? o1.sliced1 : o1.sliced;
+        P.sliced2 = chained ? o1.sliced2 : o2.sliced;
+        IMT_HIP(c, hipEventRecord(P.done, s));
+        P.pipelined = true;
+        P.applied = false;
+        P.sliced = false;
+        P.l0 = L0;
+        P.in_flight = true;
+        t->cur = (t->cur + 1) % imt_itree::NSETS;
+        return IMT_OK;
+    }
+    if (!applied) IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
+    int rc = plan_launched(t, P, s, L0, pipe.pipelined, applied);
     if (rc) return rc;
     index_committed(t, t->size + n_ins);
     return IMT_OK;
@@ -2244,7 +2299,7 @@ static int mixed_commit(imt_itree* t, PlanSet& P, hipStream_t s, size_t n_ins, u
 // convention; slot: the first context scratch slot the staged outputs may take.
 static int mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, const uint8_t* d_op, size_t n, size_t stride, size_t slot,
                       const imt_insert_out* ins, const imt_read_out* rd, uint64_t* n_inserted, uint64_t* bad_op, unsigned flags,
-                      const MixedFiltered* filtered) {
+                      const MixedFiltered* filtered, bool pipelined = false) {
     imt_ctx* c = t->ctx;
     int rc;
     const bool dev = flags & IMT_DEVICE_PTRS;
@@ -2270,18 +2325,24 @@ static int mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, const uin
                                   (uint8_t*)d.new_leaf, prep::ReadOut{r.low_index, r.is_largest, (uint8_t*)r.low_leaf}));
     IMT_HIP(c, hipEventRecord(t->up_done, ps));
 
-    // ---- hashing on the context's stream, behind every batch in flight ----
-    hipStream_t s = c->stream;
-    if ((rc = join_top(t))) return rc;
+    // ---- hashing on the context's stream, behind every batch in flight -- or on a pipeline stream, one level behind the
+    // block in front: by its footprint on the stored levels a mixed block is a witness batch of its E events, a READ's
+    // write-back putting back the bytes it read (imt_apply_pipe.hpp) ----
+    hipStream_t s;
+    WitnessSweep w;
+    if ((rc = hashing_stream(t, pipelined, s, w.pipe))) return rc;
+    if (w.pipe.prev && L0 == 0) {    // READs of a tree that holds the sentinel alone: below the heights the rule is checked for,
+        IMT_HIP(c, hipStreamWaitEvent(s, w.pipe.prev->done, 0));      // and nothing to overlap -- behind all of the block in front
+        w.pipe.prev = nullptr;
+    }
     IMT_HIP(c, hipStreamWaitEvent(s, t->up_done, 0));
     const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->depth} : launch::SibLayout{stride, 1};
     const launch::MixedRoute route{mx.erow, (uint8_t*)r.low_sib};
-    WitnessSweep w;
     w.route = &route;
     w.n_ins = n_ins;
     w.read_root = (uint8_t*)r.root;
     if ((rc = witness_sweep(t, P, s, E, L0, d, lay, fmt, w))) return rc;
-    if ((rc = mixed_commit(t, P, s, n_ins, L0))) return rc;
+    if ((rc = mixed_commit(t, P, s, n_ins, L0, w.pipe))) return rc;
 
     // ---- outputs ----
     if (n_inserted) *n_inserted = n_ins;
@@ -2294,7 +2355,7 @@ static int mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, const uin
 // so the plan set stays idle, nothing is hashed and the only thing read of the tree is its root.
 static int apply_mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, const uint8_t* d_op, size_t n, size_t slot,
                             uint64_t* n_inserted, uint64_t* bad_op, unsigned flags, const MixedFiltered* filtered,
-                            const ApplyReq& apply) {
+                            const ApplyReq& apply, bool pipelined = false) {
     imt_ctx* c = t->ctx;
     int rc;
     const bool dev = flags & IMT_DEVICE_PTRS;
@@ -2316,14 +2377,17 @@ static int apply_mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, con
                                          P.d_tab[0][3]));
     IMT_HIP(c, hipEventRecord(t->up_done, ps));
 
-    // ---- hashing on the context's stream, behind every batch in flight: every touched node once ----
-    hipStream_t s = c->stream;
-    if ((rc = join_top(t))) return rc;
+    // ---- hashing on the context's stream, behind every batch in flight: every touched node once -- or on a pipeline
+    // stream two launches behind the block in front, as the apply batch of its INSERTs that it is, with its counts in its
+    // plan set and its store of the chain filling P.d_root ----
+    hipStream_t s;
+    PipeCtx pipe;
+    if ((rc = hashing_stream(t, pipelined, s, pipe))) return rc;
     IMT_HIP(c, hipStreamWaitEvent(s, t->up_done, 0));
-    if ((rc = apply_hashes(t, P, s, E, L0, t->d_apply_stats))) return rc;
+    if ((rc = apply_hashes(t, P, s, E, L0, pipelined ? P.d_count : t->d_apply_stats, pipe))) return rc;
     t->apply_seen = true;
-    t->apply_stats_set = nullptr;
-    if ((rc = mixed_commit(t, P, s, n_ins, L0))) return rc;
+    t->apply_stats_set = pipelined ? &P : nullptr;
+    if ((rc = mixed_commit(t, P, s, n_ins, L0, pipe, pipelined))) return rc;
 
     // ---- outputs ----
     if (n_inserted) *n_inserted = n_ins;
@@ -2333,12 +2397,19 @@ static int apply_mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, con
 }
 
 // imt_itree_mixed_batch and (apply != NULL) imt_itree_apply_mixed: the refusals, the staging of the inputs, then the body
+// pipelined: imt_itree_mixed_pipelined / imt_itree_apply_mixed_pipelined -- the same call with its hashing on a pipeline
+// stream; device pointers only, IMT_PIPELINE allowed and without a meaning of its own.
 static int mixed_call(imt_itree* t, const void* vals, const uint8_t* op, size_t n, const imt_insert_out* ins,
-                      const imt_read_out* rd, uint64_t* n_inserted, uint64_t* bad_op, unsigned flags, const ApplyReq* apply) {
+                      const imt_read_out* rd, uint64_t* n_inserted, uint64_t* bad_op, unsigned flags, const ApplyReq* apply,
+                      bool pipelined = false) {
     if (!t) return IMT_ERR_ARG;
     imt_ctx* c = t->ctx;
     IMT_NOT_SLICED(t);
     int rc;
+    if (pipelined) {
+        if (!(flags & IMT_DEVICE_PTRS)) return c->fail(IMT_ERR_ARG, "pipelined mixed blocks need device pointers (IMT_DEVICE_PTRS)");
+        flags &= ~(unsigned)IMT_PIPELINE;
+    }
     if (n == 0) {
         if (apply && (rc = report_unchanged_root(t, apply->root_out, flags))) return rc;
         if (n_inserted) *n_inserted = 0;
@@ -2356,6 +2427,7 @@ static int mixed_call(imt_itree* t, const void* vals, const uint8_t* op, size_t 
     // ---- plan buffers: 2n events hold any mix ----
     PlanSet& P = t->plan[t->cur];
     if ((rc = acquire_plan(t, 2 * n, 0, waited_ms))) return rc;
+    if (pipelined && (rc = reserve_all_plans(t, 2 * n))) return rc;
 
     // ---- ranks, then the checks: nothing of the caller's is written before the batch is accepted ----
     hipStream_t ps = t->up_stream;
@@ -2366,8 +2438,8 @@ static int mixed_call(imt_itree* t, const void* vals, const uint8_t* op, size_t 
     if ((rc = stage_canonical(c, ps, vals, n, flags, up, P.d_canon, P.ws.err, &d_vals))) return rc;
     const uint8_t* d_op = nullptr;
     if ((rc = stage_ops(c, ps, dev, op, n, slot, &d_op))) return rc;
-    if (apply) return apply_mixed_core(t, P, d_vals, d_op, n, slot, n_inserted, bad_op, flags, nullptr, *apply);
-    return mixed_core(t, P, d_vals, d_op, n, n, slot, ins, rd, n_inserted, bad_op, flags, nullptr);
+    if (apply) return apply_mixed_core(t, P, d_vals, d_op, n, slot, n_inserted, bad_op, flags, nullptr, *apply, pipelined);
+    return mixed_core(t, P, d_vals, d_op, n, n, slot, ins, rd, n_inserted, bad_op, flags, nullptr, pipelined);
 }
 
 extern "C" int imt_itree_mixed_batch(imt_itree* t, const void* vals, const uint8_t* op, size_t n, const imt_insert_out* ins,
@@ -2379,6 +2451,18 @@ extern "C" int imt_itree_apply_mixed(imt_itree* t, const void* vals, const uint8
                                      uint64_t* n_inserted, uint64_t* bad_op, unsigned flags) {
     const ApplyReq req{root_out};
     return mixed_call(t, vals, op, n, nullptr, nullptr, n_inserted, bad_op, flags, &req);
+}
+
+// Mixed blocks that overlap (imt.h): the calls above with their hashing on the tree's pipeline streams.
+extern "C" int imt_itree_mixed_pipelined(imt_itree* t, const void* vals, const uint8_t* op, size_t n, const imt_insert_out* ins,
+                                         const imt_read_out* rd, uint64_t* n_inserted, uint64_t* bad_op, unsigned flags) {
+    return mixed_call(t, vals, op, n, ins, rd, n_inserted, bad_op, flags, nullptr, true);
+}
+
+extern "C" int imt_itree_apply_mixed_pipelined(imt_itree* t, const void* vals, const uint8_t* op, size_t n, void* root_out,
+                                               uint64_t* n_inserted, uint64_t* bad_op, unsigned flags) {
+    const ApplyReq req{root_out};
+    return mixed_call(t, vals, op, n, nullptr, nullptr, n_inserted, bad_op, flags, &req, true);
 }
 
 // The filtered twin: prep::mixed_filter classifies the operations on the side stream, one wait brings back
@@ -2540,7 +2624,7 @@ extern "C" int imt_itree_rewind(imt_itree* t, uint64_t new_size, void* root_out,
     t->mirror_valid = false;
     t->dev_index_valid = true;
     t->gen++;
-    for (auto& pl : t->plan) pl.has_root = false;
+    for (auto& pl : t->plan) pl.has_root = pl.has_root2 = false;
     IMT_HIP(c, hipStreamSynchronize(s));
     return IMT_OK;
 }
@@ -3378,6 +3462,7 @@ extern "C" int imt_itree_batch_end(imt_itree* t, const void* const* val_levels, 
     launch::store_top_path(s, (const uint8_t*)top_path, t->d_nodes, t->d_off, L0, t->depth);
     IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
     P.has_root = true;
+    P.reads_only = false;
     IMT_HIP(c, hipEventRecord(P.done, s));
     P.in_flight = true;
     P.pipelined = false;
@@ -3582,6 +3667,7 @@ extern "C" int imt_itree_slice_prepare(imt_itree* t, const void* vals, size_t n_
     P.slice_lay = (flags & IMT_SIB_ITEM_MAJOR) ? launch::SibLayout{1, t->depth} : launch::SibLayout{n_own, 1};
     P.l0 = L0;
     P.has_root = false;
+    P.reads_only = false;
     t->cur = (t->cur + 1) % imt_itree::NSETS;
     t->batch_no++;
     *slice_out = set;
