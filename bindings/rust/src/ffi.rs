@@ -138,6 +138,7 @@ pub const IMT_ROOT_PER_ITEM: c_uint = 0x40;
 pub const IMT_PIPELINE: c_uint = 0x80;
 pub const IMT_HOST_PREP: c_uint = 0x100;
 pub const IMT_INPUTS_READY: c_uint = 0x200;
+pub const IMT_MEMBER_OPS: c_uint = 0x400;
 
 pub const IMT_F_RANGE_PRED: u8 = 0x01;
 pub const IMT_F_LOW_IN_ROOT: u8 = 0x02;
@@ -151,6 +152,7 @@ pub const IMT_F_BAD_BIT: u8 = 0x80;
 // kind of an operation (imt_itree_mixed_batch)
 pub const IMT_OP_INSERT: u8 = 0;
 pub const IMT_OP_READ: u8 = 1;
+pub const IMT_OP_MEMBER: u8 = 2; // a presence read; legal under IMT_MEMBER_OPS only
 
 // status of a value (imt_itree_insert_filtered / imt_itree_lookup_batch)
 pub const IMT_VAL_NEW: u8 = 0;

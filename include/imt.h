@@ -85,6 +85,8 @@ extern "C" {
                                      imt_itree_root / get_proof / non-pipelined call on the tree), not by
                                      the context's stream. */
 
+#define IMT_MEMBER_OPS 0x400u     /* the mixed-block calls: op byte IMT_OP_MEMBER is legal -- see "PRESENCE READS" at
+                                     imt_itree_mixed_batch.  Without it the calls take op bytes 0 and 1 only, as ever. */
 #define IMT_INPUTS_READY 0x200u   /* imt_itree_insert_batch with IMT_DEVICE_PTRS: `vals` and the hash-free output buffers
                                      (low_index, is_largest, low_leaf, new_leaf) are idle -- nothing enqueued on the
                                      context's stream still writes `vals` or reads those outputs.  Without it the
@@ -677,7 +679,8 @@ int imt_itree_non_membership_witness(imt_itree *t, const void *vals /*[n][32]*/,
  * imt_itree_insert_batch would refuse at that point of the walk (0, stored, inserted earlier in the batch), or a READ of
  * 0, of a stored value or of a value an EARLIER operation of the batch inserts; *bad_op is then the smallest offending
  * position (written in this case only; *n_inserted with IMT_OK only).  IMT_ERR_NONCANONICAL and IMT_ERR_FULL as for
- * imt_itree_insert_batch, the latter counting INSERTs only.  IMT_ERR_ARG: an op byte above 1; NULL vals or op with
+ * imt_itree_insert_batch, the latter counting INSERTs only.  IMT_ERR_ARG: an op byte above 1 (above 2 under
+ * IMT_MEMBER_OPS, which adds IMT_OP_MEMBER: "PRESENCE READS" below); NULL vals or op with
  * n > 0; a misaligned device buffer; IMT_PIPELINE, IMT_HOST_PREP or IMT_INPUTS_READY in flags; a placed or partitioned
  * tree (so a value of another subtree's residue cannot occur); a replica of a sliced world with steps in flight; an open
  * slice; a call between imt_itree_batch_begin and _end.  n == 0: IMT_OK.
@@ -688,7 +691,37 @@ int imt_itree_non_membership_witness(imt_itree *t, const void *vals /*[n][32]*/,
  * values have been checked on the GPU: n_inserted and bad_op are complete at return. */
 #define IMT_OP_INSERT 0
 #define IMT_OP_READ 1
-typedef struct imt_read_out {   /* rows of the q-th READ; every pointer may be NULL; host or device per flags */
+/* PRESENCE READS (IMT_MEMBER_OPS in flags; the third kind of operation, for a transaction that asserts a value IS in the
+ * tree as of its place in the block: "this nullifier has been emitted").  Accepted by the seven mixed-block calls --
+ * imt_itree_mixed_batch, _mixed_filtered, _apply_mixed, _apply_mixed_filtered, _mixed_pipelined, _apply_mixed_pipelined and
+ * imt_itree_view_mixed_witness.  WITHOUT THE FLAG every one of them is what its comment says and nothing more: op byte 2
+ * is "an op byte above 1".  WITH IT op bytes 0, 1 and 2 are legal and anything above is IMT_ERR_ARG.
+ * DEFINED BY THE WALK, like the other two kinds: op[p] == IMT_OP_MEMBER with value v asks imt_itree_lookup_batch of v on
+ * the tree at that moment; the answer must be IMT_VAL_PRESENT at some leaf L, and the row the call writes holds
+ *     low_index = L,  low_leaf = imt_itree_get_leaves(L) then = {v, next_val, next_idx},  is_largest = (next_val == 0),
+ *     root = imt_itree_root then,  low_sib = imt_itree_get_proof_batch(L) then.
+ * A consumer checks low_leaf.val == v and imt_verify_proof_batch(hash3(low_leaf), low_index, root, low_sib).
+ * THE ROWS go to the `rd` arrays: row q of `rd` belongs to the q-th operation that is NOT AN INSERT, so READs and MEMBERs
+ * share one numbering in block order and the caller tells them apart by `op`; without MEMBERs that is the numbering of
+ * the READs.  Level stride, IMT_FMT_*, IMT_SIB_ITEM_MAJOR and IMT_DEVICE_PTRS as for a READ.
+ * REFUSED (IMT_ERR_VALUE, tree and outputs untouched, *bad_op the smallest offending position over all kinds): a MEMBER
+ * of 0, or of a value that is neither stored before the call nor put in by an INSERT at a SMALLER position -- a later
+ * INSERT does not help.  The rules of INSERT and READ do not change; IMT_ERR_FULL counts INSERTs only.
+ * COST: 1 + depth hashes in the witness forms, as a READ.  In the apply forms no hash and no event: imt_itree_apply_stats
+ * is that of the INSERTs alone.  A block with no INSERT is no change of the tree (views stay fresh, imt_itree_root_lagged
+ * does not see it).
+ * THE FILTERED TWINS: status[p] keeps its meaning for every kind -- it says what the VALUE is at that place.  What is
+ * carried out depends on the kind: an INSERT or a READ iff IMT_VAL_NEW, a MEMBER iff IMT_VAL_PRESENT or IMT_VAL_REPEATED.
+ * With A the carried-out positions the call IS the strict call on vals[A], op[A] with the same flags; *n_read counts the
+ * carried-out READs plus MEMBERs.  leaf_index[p] of a MEMBER: PRESENT -> the stored leaf; REPEATED -> the leaf the INSERT
+ * at f(v) wrote; ZERO -> the sentinel; NEW (skipped: the value is not there) -> UINT64_MAX.
+ * THE REPLAY (imt_itree_view_mixed_witness) judges a MEMBER on the fresh tree of the view's size plus the list's INSERTs
+ * before it: values the tree received after size + n_ins do not count.
+ * Placed and partitioned trees stay refused either way. */
+#define IMT_OP_MEMBER 2
+typedef struct imt_read_out {   /* rows of the q-th READ (under IMT_MEMBER_OPS: of the q-th operation that is no INSERT; for a
+                                   MEMBER read "the leaf that holds the value" for "the low leaf"); every pointer may be NULL;
+                                   host or device per flags */
     uint64_t *low_index;     /* [n]        the low leaf of the value as of the READ */
     void *low_leaf;          /* [n][3][32] its preimage then */
     uint8_t *is_largest;     /* [n]        low_leaf.next_val == 0 */
@@ -728,7 +761,8 @@ int imt_itree_mixed_batch(imt_itree *t, const void *vals /*[n][32]*/, const uint
  *  - a block in which nothing is accepted, or only READs are, returns IMT_OK and changes nothing: it is not counted as a
  *    change of the tree (views stay fresh) and imt_itree_root_lagged does not see it.
  * ERRORS, the tree and every ins / rd buffer untouched, both counts 0.  IMT_ERR_ARG, nothing else written at all: NULL
- * status, n_inserted or n_read; NULL vals or op with n > 0; an op byte above 1; a misaligned device buffer;
+ * status, n_inserted or n_read; NULL vals or op with n > 0; an op byte above 1 (above 2 under IMT_MEMBER_OPS, which also
+ * says what is carried out of a MEMBER and what its leaf_index is: "PRESENCE READS" above); a misaligned device buffer;
  * IMT_PIPELINE, IMT_HOST_PREP or IMT_INPUTS_READY; a placed or partitioned tree; a replica of a sliced world with steps
  * in flight; an open slice; a call between imt_itree_batch_begin and _end.  IMT_ERR_NONCANONICAL for a value >= p
  * (malformed input, not a rejection); IMT_ERR_FULL if size + the accepted INSERTs exceeds the capacity (skipped INSERTs
@@ -748,7 +782,8 @@ int imt_itree_mixed_filtered(imt_itree *t, const void *vals /*[n][32]*/, const u
  *     imt_itree_mixed_batch(t, vals, op, n, NULL, NULL, n_inserted, bad_op, flags)
  * -- the same result, *n_inserted with IMT_OK only and *bad_op with IMT_ERR_VALUE only, every refusal of that call with
  * the tree untouched (IMT_ERR_VALUE, IMT_ERR_NONCANONICAL, IMT_ERR_FULL counting INSERTs only, and IMT_ERR_ARG: an op byte
- * above 1; NULL vals or op with n > 0; a misaligned device buffer; IMT_PIPELINE, IMT_HOST_PREP or IMT_INPUTS_READY; a
+ * above 1, above 2 under IMT_MEMBER_OPS -- a MEMBER is judged like a READ and like a READ costs no hash and no event,
+ * "PRESENCE READS" above; NULL vals or op with n > 0; a misaligned device buffer; IMT_PIPELINE, IMT_HOST_PREP or IMT_INPUTS_READY; a
  * placed or partitioned tree; a replica of a sliced world with steps in flight; an open slice; a call between
  * imt_itree_batch_begin and _end), and afterwards the same tree byte for byte: stored nodes, value rows, index, size.  A
  * block without an INSERT changes nothing, is not counted as a change (views stay fresh) and imt_itree_root_lagged does not
@@ -797,7 +832,8 @@ int imt_itree_apply_mixed_filtered(imt_itree *t, const void *vals /*[n][32]*/, c
  * device-addressable memory -- a row of an imt_host_alloc buffer is fine -- aligned as the device-pointer path of the calls
  * above demands; n_inserted and bad_op stay host pointers.  IMT_PIPELINE may be set and means nothing more; IMT_HOST_PREP
  * and IMT_INPUTS_READY are IMT_ERR_ARG, and so is every other refusal of the calls above (placed and partitioned trees, an
- * open slice, ...).
+ * open slice, ...).  IMT_MEMBER_OPS means what it means to the calls above ("PRESENCE READS"): the rows of MEMBERs are rows
+ * of `rd`, and a block of READs and MEMBERs only is "a block of READs only" below.
  * vals AND op MAY BE REUSED WHEN THE CALL RETURNS, whatever it returns: nothing enqueued after the checks reads them (the
  * INSERT values are in the tree's value rows by then, the op bytes in the block's own tables).  The output arrays and
  * root_out belong to the block until imt_ctx_sync() or any later call on the tree has ordered the context's stream
@@ -850,7 +886,9 @@ int imt_itree_apply_mixed_pipelined(imt_itree *t, const void *vals /*[n][32]*/, 
  * size, or of a value an earlier INSERT of the list put in) or the operation is an INSERT of rank r whose value is not the
  * one the tree holds at leaf size + r.  IMT_ERR_RANGE: more INSERTs in the list than imt_itree_size(t) - size, or a tree
  * smaller than the view.  IMT_ERR_NONCANONICAL for a value >= p.  IMT_ERR_ARG: a handle that is not a live view; NULL
- * vals or op with n > 0; an op byte above 1; a misaligned device buffer; IMT_PIPELINE, IMT_HOST_PREP or
+ * vals or op with n > 0; an op byte above 1 (above 2 under IMT_MEMBER_OPS: a MEMBER is judged on that fresh tree plus
+ * the list's INSERTs before it, "PRESENCE READS" above -- a value the tree received after size + n_ins is not there);
+ * a misaligned device buffer; IMT_PIPELINE, IMT_HOST_PREP or
  * IMT_INPUTS_READY in flags; a placed or partitioned tree; a replica of a sliced world with steps in flight; an open
  * slice; a call between imt_itree_batch_begin and _end.  n == 0: IMT_OK, *n_inserted = 0.  Never IMT_ERR_FULL.
  * NOT IN THIS CALL: a filtered form (the caller kept the statuses from when the block went in and passes the accepted

@@ -457,12 +457,15 @@ public:
     // answered against the tree as it stands at that point.  inserted: the witnesses of the INSERTs in their order, as
     // insert_batch returns them; reads[q] / read_root[q]: the witness of the q-th READ and the root it verifies against.
     // A refused value: Error(IMT_ERR_VALUE), the tree unchanged, *bad_op (if given) = the first offending position.
+    // members = true (IMT_MEMBER_OPS) makes IMT_OP_MEMBER legal: a presence read, whose value must be in the tree as of its
+    // place.  reads[q] / read_root[q] then belong to the q-th operation that is no INSERT, and the row of a MEMBER is a
+    // membership witness: low_leaf.val is the value, low_leaf_proof proves hash3(low_leaf) at low_index in read_root[q].
     struct Mixed {
         Insertions inserted;
         std::vector<NonMembership> reads;
         std::vector<Fr> read_root;
     };
-    Mixed mixed_batch(const std::vector<Fr>& vals, const std::vector<uint8_t>& op, uint64_t* bad_op = nullptr) {
+    Mixed mixed_batch(const std::vector<Fr>& vals, const std::vector<uint8_t>& op, uint64_t* bad_op = nullptr, bool members = false) {
         const size_t n = vals.size(), d = depth_;
         Mixed m;
         if (!n) return m;
@@ -485,7 +488,8 @@ public:
                            r.interim_root.data(), r.new_root.data(), r.new_leaf.data(), ls.data(), ns.data()};
         imt_read_out rd{q_low.data(), q_leaf.data(), q_largest.data(), m.read_root.data(), rs.data()};
         uint64_t k = 0;
-        c_->check(imt_itree_mixed_batch(t_, vals.data(), op.data(), n, &out, &rd, &k, bad_op, IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR));
+        c_->check(imt_itree_mixed_batch(t_, vals.data(), op.data(), n, &out, &rd, &k, bad_op,
+                                        IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR | (members ? IMT_MEMBER_OPS : 0u)));
         for (auto* v : {&r.low_leaf, &r.new_leaf}) v->resize(k);
         for (auto* v : {&r.old_root, &r.interim_root, &r.new_root}) v->resize(k);
         r.low_index.resize(k);
@@ -511,12 +515,13 @@ public:
     // The same block when it may hold invalid transactions (imt_itree_mixed_filtered): an operation whose value is 0,
     // stored, or put in by an earlier INSERT of the block is skipped with a status, whichever kind it is.  rows: what
     // mixed_batch returns for the accepted operations; status[p] (IMT_VAL_*) and leaf_index[p] per operation passed in.
+    // members = true: IMT_OP_MEMBER is legal, and a MEMBER is carried out iff its value IS there (PRESENT or REPEATED).
     struct MixedFiltered {
         Mixed rows;
         std::vector<uint8_t> status;
         std::vector<uint64_t> leaf_index;
     };
-    MixedFiltered mixed_filtered(const std::vector<Fr>& vals, const std::vector<uint8_t>& op) {
+    MixedFiltered mixed_filtered(const std::vector<Fr>& vals, const std::vector<uint8_t>& op, bool members = false) {
         const size_t n = vals.size(), d = depth_;
         MixedFiltered f;
         if (!n) return f;
@@ -543,7 +548,7 @@ public:
         imt_read_out rd{q_low.data(), q_leaf.data(), q_largest.data(), m.read_root.data(), rs.data()};
         uint64_t k = 0, nr = 0;
         c_->check(imt_itree_mixed_filtered(t_, vals.data(), op.data(), n, f.status.data(), f.leaf_index.data(), &out, &rd, &k, &nr,
-                                           IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR));
+                                           IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR | (members ? IMT_MEMBER_OPS : 0u)));
         for (auto* v : {&r.low_leaf, &r.new_leaf}) v->resize(k);
         for (auto* v : {&r.old_root, &r.interim_root, &r.new_root}) v->resize(k);
         r.low_index.resize(k);
@@ -620,7 +625,8 @@ public:
     // IndexedTree::mixed_batch returns on a fresh tree fed the first size - 1 values.  The INSERTs of the list must be the
     // values the tree holds from the view's size on.  A refused operation or an INSERT that is not the stored value:
     // Error(IMT_ERR_VALUE), *bad_op (if given) = the first offending position.  Nothing of the tree changes.
-    IndexedTree::Mixed mixed_witness(const std::vector<Fr>& vals, const std::vector<uint8_t>& op, uint64_t* bad_op = nullptr) {
+    IndexedTree::Mixed mixed_witness(const std::vector<Fr>& vals, const std::vector<uint8_t>& op, uint64_t* bad_op = nullptr,
+                                     bool members = false) {
         const size_t n = vals.size(), d = depth_;
         IndexedTree::Mixed m;
         if (!n) return m;
@@ -644,7 +650,7 @@ public:
         imt_read_out rd{q_low.data(), q_leaf.data(), q_largest.data(), m.read_root.data(), rs.data()};
         uint64_t k = 0;
         c_->check(imt_itree_view_mixed_witness(v_, vals.data(), op.data(), n, &out, &rd, &k, bad_op,
-                                               IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR));
+                                               IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR | (members ? IMT_MEMBER_OPS : 0u)));
         for (auto* v : {&r.low_leaf, &r.new_leaf}) v->resize(k);
         for (auto* v : {&r.old_root, &r.interim_root, &r.new_root}) v->resize(k);
         r.low_index.resize(k);

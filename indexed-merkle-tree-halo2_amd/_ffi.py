@@ -247,6 +247,7 @@ ERR = dict(NO_LEAVES=-1, ODD_LEAVES=-2, NOT_POW2=-3, RANGE=-4, NONCANONICAL=-5, 
 FMT_CANONICAL, FMT_MONT256, FMT_DEVICE = 0, 1, 2
 DEVICE_PTRS, SIB_ITEM_MAJOR, ROOT_PER_ITEM, PIPELINE, HOST_PREP, INPUTS_READY = 0x10, 0x20, 0x40, 0x80, 0x100, 0x200
 OP_INSERT, OP_READ = 0, 1     # imt_itree_mixed_batch
+OP_MEMBER, MEMBER_OPS = 2, 0x400     # the presence read and the flag that makes it legal (IMT_MEMBER_OPS)
 VAL_NEW, VAL_ZERO, VAL_PRESENT, VAL_REPEATED, VAL_FOREIGN = 0, 1, 2, 3, 4     # imt_itree_insert_filtered / lookup_batch
 F_RANGE_PRED, F_LOW_IN_ROOT, F_LOW_LT_NEW, F_ZERO_SLOT, F_NEXT_VAL, F_NEXT_IDX, F_NEW_ROOT, F_BAD_BIT = (
     0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80)

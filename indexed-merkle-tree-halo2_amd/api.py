@@ -634,13 +634,16 @@ class IndexedTree:
         res.update(status=status, leaf_index=leaf, n_inserted=m)
         return res
 
-    def mixed_batch(self, vals, ops, proofs=True, item_major=False):
+    def mixed_batch(self, vals, ops, proofs=True, item_major=False, members=False):
         """A block of interleaved operations (imt_itree_mixed_batch): ops[p] = OP_INSERT / OP_READ for vals[p], each
         answered against the tree as it stands at that point of the list.  Returns (ins, rd): ins is the insert_batch()
         dict of the INSERTs in their order, rd the rows of the READs -- low_index, low_leaf, is_largest, root and (proofs)
         low_sib, what non_membership_witness() and root() would answer there.  Sibling arrays keep stride len(vals) in
         memory and are cut to their rows.  A refused value raises ValueError with .bad_op = the first offending
-        position; the tree is unchanged."""
+        position; the tree is unchanged.
+        members=True (IMT_MEMBER_OPS) makes OP_MEMBER legal: a presence read, whose value must be in the tree as of its
+        place.  Its row goes to rd -- row q of rd is then the q-th operation that is no INSERT -- and holds the leaf that
+        stores the value: low_leaf[0] is the value itself, and low_sib proves hash3(low_leaf) at low_index in root."""
         v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
         op = np.ascontiguousarray(ops, dtype=np.uint8)
         n, d = v.shape[0], self.depth
@@ -659,7 +662,7 @@ class IndexedTree:
         rout = _ffi.ReadOut(**{k: a.ctypes.data for k, a in rd.items()})
         n_ins, bad = ctypes.c_uint64(), ctypes.c_uint64()
         rc = lib.imt_itree_mixed_batch(self.h, _p(v), _p(op), n, ctypes.byref(out), ctypes.byref(rout), ctypes.byref(n_ins),
-                                       ctypes.byref(bad), _ffi.SIB_ITEM_MAJOR if item_major else 0)
+                                       ctypes.byref(bad), (_ffi.SIB_ITEM_MAJOR if item_major else 0) | (_ffi.MEMBER_OPS if members else 0))
         if rc == _ffi.ERR["VALUE"]:
             e = ValueError(lib.imt_last_error(self.ctx.h).decode())
             e.bad_op = bad.value
@@ -671,12 +674,14 @@ class IndexedTree:
         ins["new_index"] = np.arange(self.size - n_ins.value, self.size, dtype=np.uint64)
         return ins, rd
 
-    def mixed_filtered(self, vals, ops, proofs=True, item_major=False):
+    def mixed_filtered(self, vals, ops, proofs=True, item_major=False, members=False):
         """mixed_batch() of the operations that block would not be refused for (imt_itree_mixed_filtered): an operation
         whose value is 0 (VAL_ZERO), stored (VAL_PRESENT) or put in by an earlier INSERT of the block (VAL_REPEATED) is
         skipped, whichever kind it is.  Returns (ins, rd, status, leaf_index): ins / rd as mixed_batch() returns them
         for the accepted operations, cut to their rows (sibling arrays keep stride len(vals) in memory); status and
-        leaf_index per operation passed in."""
+        leaf_index per operation passed in.
+        members=True: OP_MEMBER is legal, and a MEMBER is carried out iff its value IS there (VAL_PRESENT or VAL_REPEATED);
+        the rows of rd are those of the carried-out READs and MEMBERs in block order."""
         v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
         op = np.ascontiguousarray(ops, dtype=np.uint8)
         n, d = v.shape[0], self.depth
@@ -697,7 +702,7 @@ class IndexedTree:
         n_ins, n_rd = ctypes.c_uint64(), ctypes.c_uint64()
         self.ctx._check(lib.imt_itree_mixed_filtered(self.h, _p(v), _p(op), n, _p(status), _p(leaf), ctypes.byref(out),
                                                      ctypes.byref(rout), ctypes.byref(n_ins), ctypes.byref(n_rd),
-                                                     _ffi.SIB_ITEM_MAJOR if item_major else 0))
+                                                     (_ffi.SIB_ITEM_MAJOR if item_major else 0) | (_ffi.MEMBER_OPS if members else 0)))
         for res, m in ((ins, n_ins.value), (rd, n_rd.value)):
             for k in list(res):
                 res[k] = res[k][:, :m] if k.endswith("_sib") and not item_major else res[k][:m]
@@ -737,11 +742,11 @@ class IndexedTree:
                                                      _ffi.HOST_PREP if host_prep else 0))
         return status, leaf, n_ins.value, to_int(root)
 
-    def apply_mixed(self, vals, ops):
+    def apply_mixed(self, vals, ops, members=False):
         """mixed_batch() without witnesses (imt_itree_apply_mixed): the same refusals and the same tree afterwards, every
         touched node hashed once and no hash for a READ.  Returns (n_inserted, root): the number of INSERTs and the root
         after the block.  A refused value raises ValueError with .bad_op = the first offending position; the tree is
-        unchanged."""
+        unchanged.  members=True: OP_MEMBER is legal and, like a READ, is judged and costs no hash."""
         v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
         op = np.ascontiguousarray(ops, dtype=np.uint8)
         n = v.shape[0]
@@ -749,7 +754,8 @@ class IndexedTree:
             raise ValueError("apply_mixed: one op per value")
         root = np.empty(32, dtype=np.uint8)
         n_ins, bad = ctypes.c_uint64(), ctypes.c_uint64()
-        rc = lib.imt_itree_apply_mixed(self.h, _p(v), _p(op), n, _p(root), ctypes.byref(n_ins), ctypes.byref(bad), 0)
+        rc = lib.imt_itree_apply_mixed(self.h, _p(v), _p(op), n, _p(root), ctypes.byref(n_ins), ctypes.byref(bad),
+                                       _ffi.MEMBER_OPS if members else 0)
         if rc == _ffi.ERR["VALUE"]:
             e = ValueError(lib.imt_last_error(self.ctx.h).decode())
             e.bad_op = bad.value
@@ -764,17 +770,17 @@ class IndexedTree:
             raise e
         self.ctx._check(rc)
 
-    def mixed_pipelined(self, vals_ptr, ops_ptr, n, ins=None, rd=None, fmt=0, item_major=False):
+    def mixed_pipelined(self, vals_ptr, ops_ptr, n, ins=None, rd=None, fmt=0, item_major=False, members=False):
         """mixed_batch() of n operations already in device-addressable memory that overlaps with the blocks before it
         (imt_itree_mixed_pipelined): vals_ptr -> [n][32] values (16-byte aligned), ops_ptr -> [n] op bytes.  ins / rd:
         dicts of device-addressable addresses by field name (the fields of imt_insert_out / imt_read_out; a missing
         field is not written), sibling arrays with level stride n; their rows are complete after ctx.sync().  Returns
         the number of INSERTs once the block has passed its checks; vals and ops may be reused then.  A refused value
-        raises ValueError with .bad_op; the tree and the blocks in flight are then as they were."""
+        raises ValueError with .bad_op; the tree and the blocks in flight are then as they were.  members: as mixed_batch()."""
         out = _ffi.InsertOut(**(ins or {}))
         rout = _ffi.ReadOut(**(rd or {}))
         n_ins, bad = ctypes.c_uint64(), ctypes.c_uint64()
-        flags = fmt | _ffi.DEVICE_PTRS | (_ffi.SIB_ITEM_MAJOR if item_major else 0)
+        flags = fmt | _ffi.DEVICE_PTRS | (_ffi.SIB_ITEM_MAJOR if item_major else 0) | (_ffi.MEMBER_OPS if members else 0)
         rc = lib.imt_itree_mixed_pipelined(self.h, ctypes.c_void_p(vals_ptr), ctypes.c_void_p(ops_ptr), n,
                                            ctypes.byref(out) if ins is not None else None,
                                            ctypes.byref(rout) if rd is not None else None, ctypes.byref(n_ins),
@@ -782,22 +788,24 @@ class IndexedTree:
         self._mixed_verdict(rc, bad)
         return n_ins.value
 
-    def apply_mixed_pipelined(self, vals_ptr, ops_ptr, n, root_ptr=None, fmt=0):
+    def apply_mixed_pipelined(self, vals_ptr, ops_ptr, n, root_ptr=None, fmt=0, members=False):
         """apply_mixed() of n operations already in device-addressable memory that overlaps with the blocks before it
         (imt_itree_apply_mixed_pipelined).  The root after the block goes to root_ptr (32 device-addressable bytes, or
         None) and is complete after ctx.sync().  Returns the number of INSERTs once the block has passed its checks;
-        a refused value raises ValueError with .bad_op, the tree and the blocks in flight as they were."""
+        a refused value raises ValueError with .bad_op, the tree and the blocks in flight as they were.  members: as
+        apply_mixed()."""
         n_ins, bad = ctypes.c_uint64(), ctypes.c_uint64()
         rc = lib.imt_itree_apply_mixed_pipelined(self.h, ctypes.c_void_p(vals_ptr), ctypes.c_void_p(ops_ptr), n,
                                                  ctypes.c_void_p(root_ptr) if root_ptr is not None else None,
-                                                 ctypes.byref(n_ins), ctypes.byref(bad), fmt | _ffi.DEVICE_PTRS)
+                                                 ctypes.byref(n_ins), ctypes.byref(bad),
+                                                 fmt | _ffi.DEVICE_PTRS | (_ffi.MEMBER_OPS if members else 0))
         self._mixed_verdict(rc, bad)
         return n_ins.value
 
-    def apply_mixed_filtered(self, vals, ops):
+    def apply_mixed_filtered(self, vals, ops, members=False):
         """mixed_filtered() without witnesses (imt_itree_apply_mixed_filtered): (status, leaf_index, n_inserted, n_read,
         root) -- status and leaf_index per operation passed in, the accepted INSERTs and READs, the root after the
-        block."""
+        block.  members: as mixed_filtered(); n_read counts the carried-out READs and MEMBERs."""
         v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
         op = np.ascontiguousarray(ops, dtype=np.uint8)
         n = v.shape[0]
@@ -806,7 +814,7 @@ class IndexedTree:
         status, leaf, root = np.empty(n, np.uint8), np.empty(n, np.uint64), np.empty(32, dtype=np.uint8)
         n_ins, n_rd = ctypes.c_uint64(), ctypes.c_uint64()
         self.ctx._check(lib.imt_itree_apply_mixed_filtered(self.h, _p(v), _p(op), n, _p(status), _p(leaf), ctypes.byref(n_ins),
-                                                           ctypes.byref(n_rd), _p(root), 0))
+                                                           ctypes.byref(n_rd), _p(root), _ffi.MEMBER_OPS if members else 0))
         return status, leaf, n_ins.value, n_rd.value, to_int(root)
 
     def apply_stats(self):
@@ -1058,12 +1066,13 @@ class IndexedTreeView:
         res["new_index"] = np.arange(size, size + n, dtype=np.uint64) + np.uint64(tree.index_base)
         return res
 
-    def mixed_witness(self, vals, ops, proofs=True, item_major=False):
+    def mixed_witness(self, vals, ops, proofs=True, item_major=False, members=False):
         """The witnesses of a mixed block the tree applied at this view's size (imt_itree_view_mixed_witness): the
         (ins, rd) dicts IndexedTree.mixed_batch returns on a fresh tree fed the first size - 1 values.  The INSERTs of
         the list must be the values the tree holds from the view's size on, in that order.  A refused operation, or an
         INSERT that is not the stored value, raises ValueError with .bad_op = the first offending position.  Nothing of
-        the tree changes."""
+        the tree changes.  members: as IndexedTree.mixed_batch(); a MEMBER is judged on that fresh tree plus the list's
+        INSERTs before it, so a value the tree received later does not count."""
         v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
         op = np.ascontiguousarray(ops, dtype=np.uint8)
         n, d = v.shape[0], self.depth
@@ -1082,7 +1091,8 @@ class IndexedTreeView:
         rout = _ffi.ReadOut(**{k: a.ctypes.data for k, a in rd.items()})
         n_ins, bad = ctypes.c_uint64(), ctypes.c_uint64()
         rc = lib.imt_itree_view_mixed_witness(self.h, _p(v), _p(op), n, ctypes.byref(out), ctypes.byref(rout),
-                                              ctypes.byref(n_ins), ctypes.byref(bad), _ffi.SIB_ITEM_MAJOR if item_major else 0)
+                                              ctypes.byref(n_ins), ctypes.byref(bad),
+                                              (_ffi.SIB_ITEM_MAJOR if item_major else 0) | (_ffi.MEMBER_OPS if members else 0))
         if rc == _ffi.ERR["VALUE"]:
             e = ValueError(lib.imt_last_error(self.ctx.h).decode())
             e.bad_op = bad.value

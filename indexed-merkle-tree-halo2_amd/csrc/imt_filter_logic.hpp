@@ -139,6 +139,22 @@ IMT_PL_HD uint64_t mixed_filter_leaf(uint8_t st, uint32_t aux, const uint32_t* r
     }
 }
 
+// ---- MEMBERs in a filtered block (IMT_MEMBER_OPS) ----
+// The status says what the VALUE is at that place, whichever kind the operation is, so mixed_pos_less and
+// mixed_filter_rank take a MEMBER as they take a READ (any byte but 0).  What is carried out depends on the kind: an
+// INSERT or a READ iff the value is not there (NEW), a MEMBER iff it is -- stored before the call (PRESENT) or put in by
+// the INSERT at f(v) < p (REPEATED), which is then NEW and carried out itself.
+IMT_PL_HD bool mixed_carried(uint8_t op, uint8_t st) {
+    return op == OP_MEMBER ? (st == VAL_PRESENT || st == VAL_REPEATED) : st == VAL_NEW;
+}
+// mixed_filter_leaf for an operation of any kind: a MEMBER of a value that is not there (NEW, skipped) names no leaf; a
+// carried-out one gets the leaf that holds its value, which is what its status reports already.
+IMT_PL_HD uint64_t mixed_filter_op_leaf(uint8_t op, uint8_t st, uint32_t aux, const uint32_t* rank_ins, uint32_t p, uint64_t base,
+                                        uint64_t M) {
+    if (op == OP_MEMBER && st == VAL_NEW) return LEAF_NONE;
+    return mixed_filter_leaf(st, aux, rank_ins, p, base, M);
+}
+
 // imt_itree_lookup_batch: status of one candidate against the stored index; *leaf = the stored leaf (PRESENT), the low
 // leaf (NEW: greatest stored value below x), the sentinel (ZERO) or LEAF_NONE (FOREIGN)
 IMT_PL_HD uint8_t lookup_one(const uint8_t* x, const uint8_t* val, const uint32_t* sorted, uint32_t M, uint64_t base,

@@ -2057,7 +2057,8 @@ extern "C" int imt_itree_apply_stats(imt_itree* t, uint64_t* hashes) {
 }
 
 // ------------------------------------------------------------------------------------
-// mixed batches: non-inclusion READs between the INSERTs of one call
+// mixed batches: non-inclusion READs between the INSERTs of one call and, under IMT_MEMBER_OPS, presence
+// reads (IMT_OP_MEMBER) -- to everything below the checks a MEMBER is a READ: one event, one row of `rd`
 // ------------------------------------------------------------------------------------
 // rows [0, rows) of a staged sibling array to the caller's: item-major they are one block, level-major they are the
 // first `rows` of every level's n
@@ -2165,11 +2166,18 @@ static int check_mixed_ptrs(imt_ctx* c, bool dev, const void* vals, const imt_in
         return c->fail(IMT_ERR_ARG, "device low_index array is not 8-byte aligned");
     return IMT_OK;
 }
+// The op bytes a call takes: IMT_OP_MEMBER only under IMT_MEMBER_OPS, so that a caller who never asked for presence reads
+// has byte 2 refused as it always was, in the words it always was.
+static uint8_t mixed_max_op(unsigned flags) { return (flags & IMT_MEMBER_OPS) ? IMT_OP_MEMBER : IMT_OP_READ; }
+static const char* mixed_op_kinds(unsigned flags) {
+    return (flags & IMT_MEMBER_OPS) ? "neither IMT_OP_INSERT, IMT_OP_READ nor IMT_OP_MEMBER"
+                                    : "neither IMT_OP_INSERT nor IMT_OP_READ";
+}
 // a host-pointer caller's op bytes, before anything is enqueued; a device-pointer caller's are checked by the rank kernel
-static int check_host_ops(imt_ctx* c, bool dev, const uint8_t* op, size_t n) {
+static int check_host_ops(imt_ctx* c, bool dev, const uint8_t* op, size_t n, unsigned flags) {
     if (!dev)
         for (size_t p = 0; p < n; p++)
-            if (op[p] > IMT_OP_READ) return c->fail(IMT_ERR_ARG, "op[%zu] = %u is neither IMT_OP_INSERT nor IMT_OP_READ", p, op[p]);
+            if (op[p] > mixed_max_op(flags)) return c->fail(IMT_ERR_ARG, "op[%zu] = %u is %s", p, op[p], mixed_op_kinds(flags));
     return IMT_OK;
 }
 // the op bytes where stream s may read them: a host-pointer caller's through the context's next scratch slot
@@ -2185,13 +2193,13 @@ static int stage_ops(imt_ctx* c, hipStream_t s, bool dev, const uint8_t* op, siz
 // The rank stage on stream s, the error word clear: every operation's rank among its kind, and -- one host wait -- a bad
 // op byte refused and the number of INSERTs.
 static int mixed_rank_stage(imt_itree* t, PlanSet& P, const prep::MixedWs& mx, hipStream_t s, const uint8_t* d_op, size_t n,
-                            size_t& n_ins) {
+                            unsigned flags, size_t& n_ins) {
     imt_ctx* c = t->ctx;
-    IMT_HIP(c, prep::mixed_ranks(s, P.ws, mx, d_op, (uint32_t)n));
+    IMT_HIP(c, prep::mixed_ranks(s, P.ws, mx, d_op, (uint32_t)n, mixed_max_op(flags)));
     IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, mx.word, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, s));
     IMT_HIP(c, hipStreamSynchronize(s));
-    if (*t->h_err_pin & prep::ERR_OP) return c->fail(IMT_ERR_ARG, "an op byte is neither IMT_OP_INSERT nor IMT_OP_READ");
+    if (*t->h_err_pin & prep::ERR_OP) return c->fail(IMT_ERR_ARG, "an op byte is %s", mixed_op_kinds(flags));
     n_ins = *t->h_cnt_pin;
     return IMT_OK;
 }
@@ -2211,16 +2219,16 @@ static int mixed_check_verdict(imt_itree* t, PlanSet& P, const prep::MixedWs& mx
 // every operation (P.ws.low / succ) -- two host waits, after which either the batch is refused with nothing of the tree
 // or the caller's changed, or it is accepted and the side stream is idle.
 static int mixed_checks(imt_itree* t, PlanSet& P, const prep::MixedWs& mx, const uint8_t* d_vals, const uint8_t* d_op, size_t n,
-                        uint64_t* bad_op, const MixedFiltered* filtered, size_t& n_ins) {
+                        unsigned flags, uint64_t* bad_op, const MixedFiltered* filtered, size_t& n_ins) {
     imt_ctx* c = t->ctx;
     int rc;
     const uint64_t M = t->size;
     hipStream_t ps = t->up_stream;
-    if ((rc = mixed_rank_stage(t, P, mx, ps, d_op, n, n_ins))) return rc;
+    if ((rc = mixed_rank_stage(t, P, mx, ps, d_op, n, flags, n_ins))) return rc;
     if ((rc = check_room(t, n_ins))) return rc;
     P.ws.part_mod = t->part_mod;
     P.ws.part_res = t->part_res;
-    IMT_HIP(c, prep::mixed_check(ps, P.ws, mx, d_vals, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)M, (uint32_t)n,
+    IMT_HIP(c, prep::mixed_check(ps, P.ws, mx, d_vals, d_op, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)M, (uint32_t)n,
                                  (uint32_t)n_ins));
     if (filtered && filtered->d_leaf && n_ins < n) {
         IMT_HIP(c, prep::mixed_filter_reads(ps, P.fw, P.ws, mx, (uint32_t)n, (uint32_t)n_ins, t->index_base, filtered->d_leaf));
@@ -2228,7 +2236,10 @@ static int mixed_checks(imt_itree* t, PlanSet& P, const prep::MixedWs& mx, const
     if (filtered && filtered->h_leaf)
         IMT_HIP(c, hipMemcpyAsync(filtered->h_leaf, filtered->d_leaf, filtered->n_all * 8, hipMemcpyDeviceToHost, ps));
     if ((rc = mixed_check_verdict(t, P, mx, ps))) return rc;
-    if ((rc = insertion_verdict(t, *t->h_err_pin, "batch"))) {
+    rc = insertion_verdict(t, *t->h_err_pin, "batch");
+    // a MEMBER of a value that is not there; among several refusals of one block the others keep their words
+    if (!rc && (*t->h_err_pin & prep::ERR_ABSENT)) rc = c->fail(IMT_ERR_VALUE, "the value of a MEMBER is not in the tree");
+    if (rc) {
         if (filtered) {
             std::string why = c->last_error;
             return c->fail(IMT_ERR_INTERNAL, "the mixed checks refuse operation %u of those the filter accepted: %s", *t->h_cnt_pin,
@@ -2237,6 +2248,9 @@ static int mixed_checks(imt_itree* t, PlanSet& P, const prep::MixedWs& mx, const
         if (rc == IMT_ERR_VALUE) {
             if (bad_op) *bad_op = *t->h_cnt_pin;
             std::string why = c->last_error;
+            if (flags & IMT_MEMBER_OPS)
+                return c->fail(rc, "operation %u: %s (a READ: 0, stored, or inserted earlier in the batch; a MEMBER: 0, or neither "
+                               "stored nor inserted earlier in the batch)", *t->h_cnt_pin, why.c_str());
             return c->fail(rc, "operation %u: %s (a READ: 0, stored, or inserted earlier in the batch)", *t->h_cnt_pin, why.c_str());
         }
         return rc;
@@ -2308,7 +2322,7 @@ static int mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, const uin
     hipStream_t ps = t->up_stream;
     const prep::MixedWs mx = mixed_scratch(P);
     size_t n_ins = 0;
-    if ((rc = mixed_checks(t, P, mx, d_vals, d_op, n, bad_op, filtered, n_ins))) return rc;
+    if ((rc = mixed_checks(t, P, mx, d_vals, d_op, n, flags, bad_op, filtered, n_ins))) return rc;
     const size_t n_rd = n - n_ins;
 
     // ---- accepted: events, tables, merged index, hash-free outputs (side stream) ----
@@ -2362,7 +2376,7 @@ static int apply_mixed_core(imt_itree* t, PlanSet& P, const uint8_t* d_vals, con
     const uint64_t M = t->size;
     hipStream_t ps = t->up_stream;
     size_t n_ins = 0;
-    if ((rc = mixed_checks(t, P, mixed_scratch(P), d_vals, d_op, n, bad_op, filtered, n_ins))) return rc;
+    if ((rc = mixed_checks(t, P, mixed_scratch(P), d_vals, d_op, n, flags, bad_op, filtered, n_ins))) return rc;
     if (!n_ins) {
         if ((rc = report_unchanged_root(t, apply.root_out, flags))) return rc;
         if (n_inserted) *n_inserted = 0;
@@ -2420,7 +2434,7 @@ static int mixed_call(imt_itree* t, const void* vals, const uint8_t* op, size_t 
     const bool dev = flags & IMT_DEVICE_PTRS;
     if ((rc = check_mixed_ptrs(c, dev, vals, ins, rd))) return rc;
     if (apply && (rc = check_fe_ptrs(c, dev, {apply->root_out}))) return rc;
-    if ((rc = check_host_ops(c, dev, op, n))) return rc;
+    if ((rc = check_host_ops(c, dev, op, n, flags))) return rc;
     if ((rc = ensure_device_index(t))) return rc;
     double waited_ms = 0;
 
@@ -2488,7 +2502,7 @@ static int mixed_filtered_call(imt_itree* t, const void* vals, const uint8_t* op
     const bool dev = flags & IMT_DEVICE_PTRS;
     if ((rc = check_mixed_ptrs(c, dev, vals, ins, rd))) return rc;
     if (dev && ((uintptr_t)leaf_index & 7u)) return c->fail(IMT_ERR_ARG, "device leaf_index array is not 8-byte aligned");
-    if ((rc = check_fe_ptrs(c, dev, {root_out})) || (rc = check_host_ops(c, dev, op, n))) return rc;
+    if ((rc = check_fe_ptrs(c, dev, {root_out})) || (rc = check_host_ops(c, dev, op, n, flags))) return rc;
     if ((rc = ensure_device_index(t))) return rc;
     double waited_ms = 0;
     PlanSet& P = t->plan[t->cur];
@@ -2504,13 +2518,13 @@ static int mixed_filtered_call(imt_itree* t, const void* vals, const uint8_t* op
     const uint8_t* d_op = nullptr;
     if ((rc = stage_ops(c, ps, dev, op, n, slot, &d_op))) return rc;
     uint64_t* d_leaf = leaf_index ? P.fw.leaf : nullptr;
-    IMT_HIP(c, prep::mixed_filter(ps, P.fw, d_vals, d_op, (uint32_t)n, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)t->size,
-                                  t->index_base, P.fw.status, d_leaf, P.ws.err));
+    IMT_HIP(c, prep::mixed_filter(ps, P.fw, d_vals, d_op, (uint32_t)n, mixed_max_op(flags), t->d_val, t->d_sorted[t->sorted_cur],
+                                  (uint32_t)t->size, t->index_base, P.fw.status, d_leaf, P.ws.err));
     IMT_HIP(c, hipMemcpyAsync(t->h_cnt_pin, P.fw.count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
     IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, ps));
     if (!dev) IMT_HIP(c, hipMemcpyAsync(status, P.fw.status, n, hipMemcpyDeviceToHost, ps));     // its op bytes were checked above
     IMT_HIP(c, hipStreamSynchronize(ps));
-    if (*t->h_err_pin & prep::ERR_OP) return c->fail(IMT_ERR_ARG, "an op byte is neither IMT_OP_INSERT nor IMT_OP_READ");
+    if (*t->h_err_pin & prep::ERR_OP) return c->fail(IMT_ERR_ARG, "an op byte is %s", mixed_op_kinds(flags));
     if (dev) IMT_HIP(c, hipMemcpyAsync(status, P.fw.status, n, hipMemcpyDeviceToDevice, ps));
     const size_t n_ins = t->h_cnt_pin[0], n_rd = t->h_cnt_pin[1], n_acc = n_ins + n_rd;
     if (*t->h_err_pin & prep::ERR_NONCANONICAL) rc = c->fail(IMT_ERR_NONCANONICAL, "a value is not reduced (>= p)");
@@ -3190,7 +3204,7 @@ static int view_replay_mixed(imt_itree_view* v, const void* vals, const uint8_t*
     if ((rc = stage_ops(c, s, dev, op, n, slot, &d_op))) return rc;
     const prep::MixedWs mx = mixed_scratch(P);
     size_t n_ins = 0;
-    if ((rc = mixed_rank_stage(t, P, mx, s, d_op, n, n_ins))) return rc;
+    if ((rc = mixed_rank_stage(t, P, mx, s, d_op, n, flags, n_ins))) return rc;
     const size_t n_rd = n - n_ins;
     if (n_ins > t->size - S)
         return c->fail(IMT_ERR_RANGE, "the tree holds %llu leaves: no %zu insertions follow the view's %llu", (unsigned long long)t->size,
@@ -3198,11 +3212,11 @@ static int view_replay_mixed(imt_itree_view* v, const void* vals, const uint8_t*
     const uint32_t* index = v->current ? t->d_sorted[t->sorted_cur] : v->d_sorted;
     P.ws.part_mod = t->part_mod;
     P.ws.part_res = t->part_res;
-    IMT_HIP(c, prep::mixed_check_view(s, P.ws, mx, d_vals, t->d_val, index, (uint32_t)S, (uint32_t)n, (uint32_t)n_ins));
+    IMT_HIP(c, prep::mixed_check_view(s, P.ws, mx, d_vals, d_op, t->d_val, index, (uint32_t)S, (uint32_t)n, (uint32_t)n_ins));
     if ((rc = mixed_check_verdict(t, P, mx, s))) return rc;
     const int perr = *t->h_err_pin;
     if (perr & prep::ERR_NONCANONICAL) return c->fail(IMT_ERR_NONCANONICAL, "a value is not reduced (>= p)");
-    if (perr & (prep::ERR_ZERO | prep::ERR_FOREIGN | prep::ERR_DUPLICATE | prep::ERR_MISMATCH)) {
+    if (perr & (prep::ERR_ZERO | prep::ERR_FOREIGN | prep::ERR_DUPLICATE | prep::ERR_MISMATCH | prep::ERR_ABSENT)) {
         const uint32_t bad = *t->h_cnt_pin;
         if (bad_op && bad < n) *bad_op = bad;
         // which of the two it is at that position: an INSERT that matches its row has nothing else wrong with it
@@ -3220,6 +3234,9 @@ static int view_replay_mixed(imt_itree_view* v, const void* vals, const uint8_t*
                 return c->fail(IMT_ERR_VALUE, "operation %u: INSERT %u of the list is not the value stored at leaf %llu", bad, rank,
                                (unsigned long long)(S + rank));
         }
+        if (flags & IMT_MEMBER_OPS)
+            return c->fail(IMT_ERR_VALUE, "operation %u: refused as of its place in the list (0, stored at the view's size, or "
+                           "inserted earlier in the list; a MEMBER: 0, or neither of the two)", bad);
         return c->fail(IMT_ERR_VALUE, "operation %u: refused as of its place in the list (0, stored at the view's size, or inserted "
                        "earlier in the list)", bad);
     }
@@ -3267,7 +3284,7 @@ extern "C" int imt_itree_view_mixed_witness(imt_itree_view* v, const void* vals,
     if ((rc = check_mixed_mode(t, flags, MIXED_REPLAY))) return rc;
     if (n > ((size_t)1 << 30)) return c->fail(IMT_ERR_RANGE, "list too large");
     const bool dev = flags & IMT_DEVICE_PTRS;
-    if ((rc = check_mixed_ptrs(c, dev, vals, ins, rd)) || (rc = check_host_ops(c, dev, op, n))) return rc;
+    if ((rc = check_mixed_ptrs(c, dev, vals, ins, rd)) || (rc = check_host_ops(c, dev, op, n, flags))) return rc;
     if ((rc = view_enter(v, flags))) return rc;
     if (n == 0) {
         if (n_inserted) *n_inserted = 0;

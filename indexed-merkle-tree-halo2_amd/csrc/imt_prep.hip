@@ -167,7 +167,8 @@ __global__ void __launch_bounds__(BLOCK) k_runs(const uint64_t* __restrict__ key
 }
 
 // ---- mixed batches (imt_itree_mixed_batch; the rules are in imt_prep_logic.hpp) ----
-static_assert(OP_ZERO == ERR_ZERO && OP_DUPLICATE == ERR_DUPLICATE && OP_FOREIGN == ERR_FOREIGN, "one set of error bits");
+static_assert(OP_ZERO == ERR_ZERO && OP_DUPLICATE == ERR_DUPLICATE && OP_FOREIGN == ERR_FOREIGN && OP_ABSENT == ERR_ABSENT,
+              "one set of error bits");
 struct ValRankLess {                   // ValLess with equal values ordered by leaf index, i.e. by rank
     const uint8_t* val;
     __device__ bool operator()(uint32_t a, uint32_t b) const {
@@ -176,12 +177,13 @@ struct ValRankLess {                   // ValLess with equal values ordered by l
     }
 };
 
-__global__ void __launch_bounds__(BLOCK) k_mixed_flag(const uint8_t* __restrict__ op, uint32_t n, uint32_t* __restrict__ flag,
-                                                      int* err) {
+// max_op: the greatest op byte the call takes -- OP_READ, OP_MEMBER under IMT_MEMBER_OPS
+__global__ void __launch_bounds__(BLOCK) k_mixed_flag(const uint8_t* __restrict__ op, uint32_t n, uint8_t max_op,
+                                                      uint32_t* __restrict__ flag, int* err) {
     const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= n) return;
     const uint8_t o = op[p];
-    if (o > 1) atomicOr(err, ERR_OP);
+    if (o > max_op) atomicOr(err, ERR_OP);
     flag[p] = o == 0 ? 1u : 0u;
 }
 __global__ void k_mixed_count(const uint32_t* __restrict__ flag, const uint32_t* __restrict__ rank, uint32_t n,
@@ -236,18 +238,21 @@ k_mixed_gap(const uint8_t* __restrict__ d_val, const uint32_t* __restrict__ sort
     st0[j] = bsorted[j] - M;
     if (insert_is_duplicate(d_val, sorted_old, M, bsorted, j, g)) { atomicOr(err, ERR_DUPLICATE); atomicMin(bad, ipos[bsorted[j] - M]); }
 }
-// low leaf and successor of every READ, as of its place in the batch: behind the INSERTs' in low / succ
+// low leaf and successor of every READ, as of its place in the batch: behind the INSERTs' in low / succ.  A MEMBER's are
+// the leaf that holds its value and that leaf's successor (member_neighbours): the same two words, the verdict inverted.
 __global__ void __launch_bounds__(BLOCK)
-k_mixed_reads(const uint8_t* __restrict__ vals, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ rank,
-              const uint8_t* __restrict__ d_val, const uint32_t* __restrict__ sorted_old, uint32_t M,
+k_mixed_reads(const uint8_t* __restrict__ vals, const uint8_t* __restrict__ op, const uint32_t* __restrict__ flag,
+              const uint32_t* __restrict__ rank, const uint8_t* __restrict__ d_val, const uint32_t* __restrict__ sorted_old, uint32_t M,
               const uint32_t* __restrict__ bsorted, const uint32_t* __restrict__ gap, const uint32_t* __restrict__ st,
               uint32_t n, uint32_t n_ins, int levels, uint32_t part_mod, uint32_t part_res, uint32_t* __restrict__ low,
               uint32_t* __restrict__ succ, int* err, uint32_t* bad) {
     const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= n || flag[p]) return;
     const uint32_t R = rank[p], q = p - R;
-    const ReadAnswer a = read_neighbours(vals + (uint64_t)p * 32, R, d_val, sorted_old, M, bsorted, gap, st, n_ins, levels,
-                                         part_mod, part_res);
+    const uint8_t* x = vals + (uint64_t)p * 32;
+    const ReadAnswer a = op[p] == OP_MEMBER
+                             ? member_neighbours(x, R, d_val, sorted_old, M, bsorted, gap, st, n_ins, levels, part_mod, part_res)
+                             : read_neighbours(x, R, d_val, sorted_old, M, bsorted, gap, st, n_ins, levels, part_mod, part_res);
     if (a.err) { atomicOr(err, a.err); atomicMin(bad, p); }
     low[n_ins + q] = a.low;
     succ[n_ins + q] = a.succ;
@@ -414,18 +419,19 @@ struct MixedPosLess {                  // order positions by value, INSERT befor
 };
 
 __global__ void __launch_bounds__(BLOCK) k_mixed_filter_class(const uint8_t* __restrict__ vals, const uint8_t* __restrict__ op,
-                                                              uint32_t n, uint32_t* __restrict__ idx, uint8_t* __restrict__ st,
-                                                              int* err) {
+                                                              uint32_t n, uint8_t max_op, uint32_t* __restrict__ idx,
+                                                              uint8_t* __restrict__ st, int* err) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     const uint8_t* v = vals + (uint64_t)i * 32;
     if (geq_p(v)) atomicOr(err, ERR_NONCANONICAL);
-    if (op[i] > 1) atomicOr(err, ERR_OP);
+    if (op[i] > max_op) atomicOr(err, ERR_OP);
     st[i] = filter_class(v, 0, 0);
     idx[i] = i;
 }
 
 // over the batch order: PRESENT against the stored index, REPEATED against the head of the run; the accepted flags by kind
+// (flag_rd: the READs and the MEMBERs, which share the rows of rd)
 __global__ void __launch_bounds__(BLOCK)
 k_mixed_filter_rank(const uint8_t* __restrict__ vals, const uint8_t* __restrict__ op, const uint32_t* __restrict__ ord, uint32_t n,
                     const uint8_t* __restrict__ d_val, const uint32_t* __restrict__ sorted, uint32_t M, uint8_t* __restrict__ st,
@@ -435,14 +441,15 @@ k_mixed_filter_rank(const uint8_t* __restrict__ vals, const uint8_t* __restrict_
     const uint32_t i = ord[j];
     uint32_t a = 0;
     const uint8_t s = mixed_filter_rank(vals, op, ord, j, st[i], d_val, sorted, M, &a);
-    const bool ins = op[i] == 0;
+    const uint8_t o = op[i];
     st[i] = s;
     aux[i] = a;
-    flag_ins[i] = (s == VAL_NEW && ins) ? 1u : 0u;
-    flag_rd[i] = (s == VAL_NEW && !ins) ? 1u : 0u;
+    flag_ins[i] = (o == OP_INSERT && mixed_carried(o, s)) ? 1u : 0u;
+    flag_rd[i] = (o != OP_INSERT && mixed_carried(o, s)) ? 1u : 0u;
 }
 
-// input order: status, the leaf of everything but an accepted READ, the accepted operations side by side, the counts
+// input order: status, the leaf of everything but an accepted READ (a MEMBER's is known here: the leaf that holds its
+// value), the accepted operations side by side, the counts
 __global__ void __launch_bounds__(BLOCK)
 k_mixed_filter_compact(const uint8_t* __restrict__ vals, const uint8_t* __restrict__ op, uint32_t n, const uint8_t* __restrict__ st,
                        const uint32_t* __restrict__ aux, const uint32_t* __restrict__ flag_ins,
@@ -453,14 +460,15 @@ k_mixed_filter_compact(const uint8_t* __restrict__ vals, const uint8_t* __restri
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     const uint8_t s = st[i], o = op[i];
-    if (s == VAL_NEW) {
+    const bool carried = mixed_carried(o, s);
+    if (carried) {
         const uint32_t k = rank_ins[i] + rank_rd[i];
         copy32(acc + (uint64_t)k * 32, vals + (uint64_t)i * 32);
         aop[k] = o;
         apos[k] = i;
     }
     status[i] = s;
-    if (leaf && !(s == VAL_NEW && o != 0)) leaf[i] = mixed_filter_leaf(s, aux[i], rank_ins, i, base, M);
+    if (leaf && !(carried && o == OP_READ)) leaf[i] = mixed_filter_op_leaf(o, s, aux[i], rank_ins, i, base, M);
     if (i + 1 == n) {
         count[0] = rank_ins[i] + flag_ins[i];
         count[1] = rank_rd[i] + flag_rd[i];
@@ -472,7 +480,7 @@ __global__ void __launch_bounds__(BLOCK)
 k_mixed_filter_reads(const uint8_t* __restrict__ aop, const uint32_t* __restrict__ apos, const uint32_t* __restrict__ rank,
                      const uint32_t* __restrict__ low, uint32_t n_acc, uint32_t n_ins, uint64_t base, uint64_t* __restrict__ leaf) {
     const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
-    if (k >= n_acc || aop[k] == 0) return;
+    if (k >= n_acc || aop[k] != OP_READ) return;
     leaf[apos[k]] = base + low[n_ins + (k - rank[k])];
 }
 
@@ -807,14 +815,14 @@ hipError_t index_only(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t
     return hipGetLastError();
 }
 
-hipError_t mixed_ranks(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* op, uint32_t n) {
+hipError_t mixed_ranks(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* op, uint32_t n, uint8_t max_op) {
     hipError_t e;
     size_t need = 0;
     (void)rocprim::exclusive_scan(nullptr, need, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n, rocprim::plus<uint32_t>(),
                                   nullptr);
     if (n == 0 || n > ws.cap_n || need > ws.tmp_bytes) return hipErrorInvalidValue;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_mixed_flag, dim3(nblk(n)), dim3(BLOCK), 0, s, op, n, mx.flag, ws.err);
+    hipLaunchKernelGGL(k_mixed_flag, dim3(nblk(n)), dim3(BLOCK), 0, s, op, n, max_op, mx.flag, ws.err);
     size_t tb = ws.tmp_bytes;
     if ((e = rocprim::exclusive_scan(ws.tmp, tb, mx.flag, mx.rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), s)) != hipSuccess)
         return e;
@@ -823,30 +831,30 @@ hipError_t mixed_ranks(hipStream_t s, Workspace& ws, const MixedWs& mx, const ui
 }
 
 // the checks behind the first kernel of mixed_check / mixed_check_view: the INSERT values are rows [M, M + n_ins) of d_val
-static hipError_t mixed_neighbours(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, const uint8_t* d_val,
-                                   const uint32_t* sorted_old, uint32_t M, uint32_t n, uint32_t n_ins);
+static hipError_t mixed_neighbours(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, const uint8_t* op,
+                                   const uint8_t* d_val, const uint32_t* sorted_old, uint32_t M, uint32_t n, uint32_t n_ins);
 
-hipError_t mixed_check(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, uint8_t* d_val,
+hipError_t mixed_check(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, const uint8_t* op, uint8_t* d_val,
                        const uint32_t* sorted_old, uint32_t M, uint32_t n, uint32_t n_ins) {
     if (n == 0 || n > ws.cap_n || n_ins > n || temp_bytes_needed(n_ins, (size_t)M) > ws.tmp_bytes) return hipErrorInvalidValue;
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_mixed_scatter, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, mx.flag, mx.rank, d_val, M, n, ws.part_mod,
                        ws.part_res, ws.iota, mx.ipos, ws.err, mx.word + 1);
-    return mixed_neighbours(s, ws, mx, vals, d_val, sorted_old, M, n, n_ins);
+    return mixed_neighbours(s, ws, mx, vals, op, d_val, sorted_old, M, n, n_ins);
 }
 
-hipError_t mixed_check_view(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, const uint8_t* d_val,
-                            const uint32_t* sorted_view, uint32_t S, uint32_t n, uint32_t n_ins) {
+hipError_t mixed_check_view(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, const uint8_t* op,
+                            const uint8_t* d_val, const uint32_t* sorted_view, uint32_t S, uint32_t n, uint32_t n_ins) {
     static_assert(OP_MISMATCH == ERR_MISMATCH, "one set of error bits");
     if (n == 0 || n > ws.cap_n || n_ins > n || temp_bytes_needed(n_ins, (size_t)S) > ws.tmp_bytes) return hipErrorInvalidValue;
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_mixed_match, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, mx.flag, mx.rank, d_val, S, n, ws.part_mod,
                        ws.part_res, ws.iota, mx.ipos, ws.err, mx.word + 1);
-    return mixed_neighbours(s, ws, mx, vals, d_val, sorted_view, S, n, n_ins);
+    return mixed_neighbours(s, ws, mx, vals, op, d_val, sorted_view, S, n, n_ins);
 }
 
-static hipError_t mixed_neighbours(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, const uint8_t* d_val,
-                                   const uint32_t* sorted_old, uint32_t M, uint32_t n, uint32_t n_ins) {
+static hipError_t mixed_neighbours(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, const uint8_t* op,
+                                   const uint8_t* d_val, const uint32_t* sorted_old, uint32_t M, uint32_t n, uint32_t n_ins) {
     const int levels = levels_for(n_ins);
     hipError_t e;
     if (n_ins) {
@@ -861,7 +869,7 @@ static hipError_t mixed_neighbours(hipStream_t s, Workspace& ws, const MixedWs& 
                            n_ins, ws.low, ws.succ);
     }
     if (n_ins < n)
-        hipLaunchKernelGGL(k_mixed_reads, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, mx.flag, mx.rank, d_val, sorted_old, M,
+        hipLaunchKernelGGL(k_mixed_reads, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, op, mx.flag, mx.rank, d_val, sorted_old, M,
                            ws.bsorted, ws.gap, ws.st, n, n_ins, levels, ws.part_mod, ws.part_res, ws.low, ws.succ, ws.err,
                            mx.word + 1);
     return hipGetLastError();
@@ -941,13 +949,14 @@ static size_t mixed_filter_temp_bytes(size_t n) {
     return a + 256;
 }
 
-hipError_t mixed_filter(hipStream_t s, FilterWs& ws, const uint8_t* vals, const uint8_t* op, uint32_t n, const uint8_t* d_val,
-                        const uint32_t* sorted, uint32_t M, uint64_t base, uint8_t* status, uint64_t* leaf, int* err) {
+hipError_t mixed_filter(hipStream_t s, FilterWs& ws, const uint8_t* vals, const uint8_t* op, uint32_t n, uint8_t max_op,
+                        const uint8_t* d_val, const uint32_t* sorted, uint32_t M, uint64_t base, uint8_t* status, uint64_t* leaf,
+                        int* err) {
     hipError_t e;
     if (n == 0 || n > ws.cap_n || filter_temp_bytes(n) > ws.tmp_bytes || mixed_filter_temp_bytes(n) > ws.tmp_bytes)
         return hipErrorInvalidValue;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_mixed_filter_class, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, op, n, ws.idx, ws.st, err);
+    hipLaunchKernelGGL(k_mixed_filter_class, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, op, n, max_op, ws.idx, ws.st, err);
     size_t tb = ws.tmp_bytes;
     if ((e = rocprim::merge_sort(ws.tmp, tb, ws.idx, ws.ord, (size_t)n, MixedPosLess{vals, op}, s)) != hipSuccess) return e;
     // ws.idx has been sorted from and is free: it holds the accepted-READ flags, and ws.ord, read for the last time by the

@@ -80,7 +80,8 @@ hipError_t index_only(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t
 // An operation at position p that R INSERTs precede has the events p + R (the low leaf: rewritten by an INSERT, rewritten
 // with the bytes it holds by a READ) and, an INSERT, p + R + 1 (the new leaf): E = 2 n_ins + n_reads events whose ids keep
 // the order of the operations.  erow[e] says whose rows event e's proof elements and root are.
-constexpr int ERR_OP = 512;                  // an op byte that is neither INSERT (0) nor READ (1)
+constexpr int ERR_OP = 512;                  // an op byte above the greatest the call takes (max_op below)
+constexpr int ERR_ABSENT = 2048;             // a MEMBER whose value is not there as of its place (OP_ABSENT, imt_prep_logic.hpp)
 constexpr uint32_t ROW_LOW = 0, ROW_NEW = 1, ROW_READ = 2;      // erow[e] = (row << 2) | one of these
 struct MixedWs {              // scratch of one mixed batch of n operations, beside the Workspace
     uint32_t* flag = nullptr;      // [n]   1 = INSERT
@@ -89,25 +90,28 @@ struct MixedWs {              // scratch of one mixed batch of n operations, bes
     uint32_t* word = nullptr;      // [2]   number of INSERTs, smallest offending position (0xffffffff: none)
     uint32_t* erow = nullptr;      // [2n]  indexed by event
 };
-struct ReadOut {              // device pointers, any may be NULL: row q belongs to the q-th READ
+struct ReadOut {              // device pointers, any may be NULL: row q belongs to the q-th operation that is no INSERT
     uint64_t* low_index;
     uint8_t* is_largest;
     uint8_t* low_leaf;             // [..][3][32] canonical
 };
-// 1. ranks and the number of INSERTs (mx.word[0]); ERR_OP into ws.err.  op: [n] device.
-hipError_t mixed_ranks(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* op, uint32_t n);
+// 1. ranks and the number of INSERTs (mx.word[0]); ERR_OP into ws.err for a byte above max_op -- 1 (READ), or 2 (MEMBER)
+// for a call that takes presence reads (IMT_MEMBER_OPS).  op: [n] device.
+hipError_t mixed_ranks(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* op, uint32_t n, uint8_t max_op);
 // 2. behind it, n_ins read back and M + n_ins within the capacity: the INSERT values into rows [M, M + n_ins) of d_val,
 // every check of the values (ERR_* into ws.err, the smallest offending position into mx.word[1]) and the neighbours of
-// every operation (ws.low / ws.succ: INSERTs by rank, then READs by rank).  Writes nothing else of the tree, no output.
-hipError_t mixed_check(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, uint8_t* d_val,
+// every operation (ws.low / ws.succ: INSERTs by rank, then READs and MEMBERs by rank among the two -- a MEMBER's `low` is the
+// leaf that holds its value, ERR_ABSENT if none does).  op: the bytes mixed_ranks read.  Writes nothing else of the tree,
+// no output.
+hipError_t mixed_check(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, const uint8_t* op, uint8_t* d_val,
                        const uint32_t* sorted_old, uint32_t M, uint32_t n, uint32_t n_ins);
 // 2'. the same for a list replayed against a view (imt_itree_view_mixed_witness): sorted_view[S] is the view's index, and
 // the INSERT of rank r must be the value row S + r of d_val holds (S + n_ins <= the tree's size: the caller has checked).
 // Writes NO row of d_val: the value is compared instead, ERR_MISMATCH into ws.err and the position into mx.word[1] like
 // every other offender (replay_op_class, imt_prep_logic.hpp); the remaining checks run over the stored rows.
 constexpr int ERR_MISMATCH = 1024;
-hipError_t mixed_check_view(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, const uint8_t* d_val,
-                            const uint32_t* sorted_view, uint32_t S, uint32_t n, uint32_t n_ins);
+hipError_t mixed_check_view(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* vals, const uint8_t* op,
+                            const uint8_t* d_val, const uint32_t* sorted_view, uint32_t S, uint32_t n, uint32_t n_ins);
 // 3. behind it, the batch accepted: what run() leaves -- preimages pre[E][96] by event, the level-0 tables [E],
 // sorted_new[M + n_ins] (untouched if n_ins == 0), the hash-free outputs of both kinds -- and mx.erow.
 hipError_t mixed_events(hipStream_t s, Workspace& ws, const MixedWs& mx, const uint8_t* d_val, const uint32_t* sorted_old,
@@ -181,11 +185,13 @@ hipError_t filter(hipStream_t s, FilterWs& ws, const uint8_t* vals, uint32_t n, 
 // Classifies the operations (vals [n][32] canonical, op [n], both device) against the stored index of a tree that is
 // neither placed nor partitioned (mixed_filter_rank, imt_filter_logic.hpp): status[i]; leaf[i] (may be NULL) for every
 // operation but an accepted READ; the accepted operations compacted in input order -- values into ws.acc, op bytes into
-// ws.aop, positions into ws.apos -- and their numbers into ws.count[0] (INSERTs) and ws.count[1] (READs).
+// ws.aop, positions into ws.apos -- and their numbers into ws.count[0] (INSERTs) and ws.count[1] (READs and MEMBERs).
+// max_op as in mixed_ranks; which operations are accepted: mixed_carried, imt_filter_logic.hpp.
 // ERR_NONCANONICAL / ERR_OP are OR-ed into *err.  Writes nothing but ws, status, leaf and err.  ws.flag / rank / idx / ord /
 // aux are scratch: MixedWs may be laid over them afterwards, ws.acc / aop / apos stay.
-hipError_t mixed_filter(hipStream_t s, FilterWs& ws, const uint8_t* vals, const uint8_t* op, uint32_t n, const uint8_t* d_val,
-                        const uint32_t* sorted, uint32_t M, uint64_t base, uint8_t* status, uint64_t* leaf, int* err);
+hipError_t mixed_filter(hipStream_t s, FilterWs& ws, const uint8_t* vals, const uint8_t* op, uint32_t n, uint8_t max_op,
+                        const uint8_t* d_val, const uint32_t* sorted, uint32_t M, uint64_t base, uint8_t* status, uint64_t* leaf,
+                        int* err);
 // Behind mixed_ranks + mixed_check of (ws.acc, ws.aop, n_acc): leaf[ws.apos[k]] = base + the low leaf of the k-th accepted
 // operation, for the READs among them.
 hipError_t mixed_filter_reads(hipStream_t s, const FilterWs& ws, const Workspace& prep_ws, const MixedWs& mx, uint32_t n_acc,

@@ -71,6 +71,7 @@ IMT_PL_HD uint32_t nearest_smaller_right(const uint32_t* st, uint32_t n, int lev
 // n_ins).  An operation's rank R is the number of INSERTs before it, so "an INSERT with a smaller position" is "an INSERT
 // of rank < R" for an INSERT and a READ alike.  A READ is a query point of that table and nothing else: it is in none of
 // these arrays, so it is nobody's neighbour.
+constexpr uint8_t OP_INSERT = 0, OP_READ = 1, OP_MEMBER = 2;      // include/imt.h IMT_OP_*
 // Nearest position left of j0 (right: at or right of j0) whose rank is < thr; n if there is none.
 IMT_PL_HD uint32_t nearest_below_left(const uint32_t* st, uint32_t n, int levels, uint32_t j0, uint32_t thr) {
     uint32_t p = j0;                      // invariant: every entry in [p, j0) is >= thr
@@ -138,6 +139,46 @@ IMT_PL_HD ReadAnswer read_neighbours(const uint8_t* x, uint32_t R, const uint8_t
     const uint32_t jr = nearest_below_right(st, n_ins, levels, j0, R);
     a.low = (jl < n_ins && gap[jl] == g) ? bsorted[jl] : sorted_old[g > 0 ? g - 1 : 0];
     a.succ = (jr < n_ins && gap[jr] == g) ? bsorted[jr] : (g < M ? sorted_old[g] : OP_NONE);
+    return a;
+}
+// number of the batch's INSERT values at or below x
+IMT_PL_HD uint32_t batch_not_above(const uint8_t* val, const uint32_t* bsorted, uint32_t n_ins, const uint8_t* x) {
+    uint32_t lo = 0, hi = n_ins;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (lt256(x, val + (uint64_t)bsorted[mid] * 32)) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+// A MEMBER of x behind R INSERTs (IMT_OP_MEMBER, IMT_MEMBER_OPS): the presence read.  Its leaf is the one that holds x as
+// of its place -- the stored hit, or the first INSERT of an equal run if that one has rank < R (an accepted block has at
+// most one of the two: an INSERT of a value that is there is a duplicate) -- and OP_ABSENT says there is none: x is not
+// stored and no INSERT of rank < R put it in; an equal INSERT of rank >= R comes later and does not help.  Its successor
+// is what that leaf points at as of R: the nearest INSERT of rank < R strictly above x if no stored value lies between
+// (the gap right of x: g + 1 behind a stored hit, which count_below counts for everything above it), else the stored
+// successor, OP_NONE if x is above everything.  Always in bounds, also for the refused value 0 and for an absent x, whose
+// `low` is the READ's low leaf.  `low` and `succ` go where a READ's go: to the sweep a MEMBER is a READ of another leaf.
+constexpr int OP_ABSENT = 2048;
+IMT_PL_HD ReadAnswer member_neighbours(const uint8_t* x, uint32_t R, const uint8_t* val, const uint32_t* sorted_old, uint32_t M,
+                                       const uint32_t* bsorted, const uint32_t* gap, const uint32_t* st, uint32_t n_ins,
+                                       int levels, uint32_t part_mod, uint32_t part_res) {
+    ReadAnswer a;
+    a.err = op_value_class(x, part_mod, part_res);
+    const uint32_t g = count_below(val, sorted_old, M, x);
+    const bool stored = g < M && eq256(val + (uint64_t)sorted_old[g] * 32, x);
+    const uint32_t j0 = batch_below(val, bsorted, n_ins, x);
+    const bool put_in = j0 < n_ins && st[j0] < R && eq256(val + (uint64_t)bsorted[j0] * 32, x);
+    if (stored) a.low = sorted_old[g];
+    else if (put_in) a.low = bsorted[j0];
+    else {
+        a.err |= OP_ABSENT;
+        const uint32_t jl = nearest_below_left(st, n_ins, levels, j0, R);
+        a.low = (jl < n_ins && gap[jl] == g) ? bsorted[jl] : sorted_old[g > 0 ? g - 1 : 0];
+    }
+    const uint32_t gs = stored ? g + 1 : g;
+    const uint32_t j1 = batch_not_above(val, bsorted, n_ins, x);
+    const uint32_t jr = nearest_below_right(st, n_ins, levels, j1, R);
+    a.succ = (jr < n_ins && gap[jr] == gs) ? bsorted[jr] : (gs < M ? sorted_old[gs] : OP_NONE);
     return a;
 }
 
