@@ -286,6 +286,9 @@ extern "C" {
     pub fn imt_itree_apply_filtered(t: *mut imt_itree, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, n_inserted: *mut u64, root_out: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_apply_stats(t: *mut imt_itree, hashes: *mut u64) -> c_int;
     pub fn imt_itree_rewind(t: *mut imt_itree, new_size: u64, root_out: *mut c_void, hashes: *mut u64, flags: c_uint) -> c_int;
+    pub fn imt_itree_capacity(t: *const imt_itree) -> u64;
+    pub fn imt_itree_reserve(t: *mut imt_itree, new_capacity: u64, flags: c_uint) -> c_int;
+    pub fn imt_itree_reserve_stats(t: *const imt_itree, ms: *mut c_double) -> c_int;
     pub fn imt_itree_view_create(t: *mut imt_itree, size: u64, out: *mut *mut imt_itree_view) -> c_int;
     pub fn imt_itree_view_free(v: *mut imt_itree_view);
     pub fn imt_itree_view_size(v: *const imt_itree_view) -> u64;

@@ -212,6 +212,16 @@ impl IndexedTree {
         })?;
         Ok((F::from_bytes_le(&r), h))
     }
+    /// leaves the tree can hold, sentinel included
+    pub fn capacity(&self) -> u64 {
+        unsafe { imt_itree_capacity(self.handle) }
+    }
+    /// Another capacity for the tree as it stands: a power of two that holds `size()`, larger (a batch answered
+    /// `IMT_ERR_FULL`) or smaller (memory back after a `rewind`).  A copy, no hash; nothing else a call can see changes.
+    pub fn reserve(&mut self, new_capacity: u64) -> Result<(), ImtError> {
+        let g = context().lock().unwrap();
+        check(&g, unsafe { imt_itree_reserve(self.handle, new_capacity, 0) })
+    }
     /// n sequential insertions; one [`InsertWitness`] each (66 hashes per insertion at depth 32, all on the GPU)
     pub fn insert_batch<F: ScalarField>(&mut self, vals: &[F]) -> Result<Vec<InsertWitness<F>>, ImtError> {
         let g = context().lock().unwrap();

@@ -568,6 +568,35 @@ int imt_itree_apply_stats(imt_itree *t, uint64_t *hashes /*[depth + 1]*/);
  * no root to give until the next batch. */
 int imt_itree_rewind(imt_itree *t, uint64_t new_size, void *root_out /*[32] or NULL*/,
                      uint64_t *hashes /*[depth + 1] host, or NULL*/, unsigned flags);
+/* ANOTHER CAPACITY, for the same callers once the tree has outgrown the first guess (a batch answered IMT_ERR_FULL) or
+ * should give memory back (after a deep imt_itree_rewind, after an over-generous guess).  After IMT_OK no call can tell
+ * the tree from one made by imt_itree_new(ctx, depth, new_capacity, ..) with the same placement and value partition that
+ * received the same values in the same order: size, root, every leaf preimage and proof at every index below
+ * new_capacity (the empty slots included), get_values, lookup_batch, find_low_batch, non_membership_witness, and every
+ * later batch of every kind byte for byte, prepared on the device or with IMT_HOST_PREP.
+ * It costs a copy and hashes nothing: level l stores max(1, capacity >> l) nodes as a filled prefix and every node outside
+ * the prefix reads as the empty subtree Z[l], so node i of level l of the new layout is the old node i where the old
+ * layout has one and Z[l] where it has not (imt_resize.hpp; one launch for all levels), and of the values and the index
+ * only the imt_itree_size(t) rows in use move.  A growing tree migrates one array at a time -- the nodes, the values,
+ * each index buffer -- and allocates the new array before it frees the old one, so the extra memory at the peak is the
+ * largest new array (the nodes, 64 bytes per leaf of new_capacity), not a second tree; a shrinking tree, whose new arrays
+ * together are at most half the old ones, allocates all of them first.  IMT_ERR_ALLOC leaves the capacity as it was and
+ * the tree usable (an array that has grown already stays grown).
+ * new_capacity > capacity grows, imt_itree_size(t) <= new_capacity < capacity shrinks, == capacity: IMT_OK, nothing runs.
+ * IMT_ERR_RANGE, the tree untouched: new_capacity not a power of two in [2, 2^31], above 2^depth, or below the size.
+ * flags must be 0 (IMT_PIPELINE or any other bit: IMT_ERR_ARG).  Synchronous and ordered like imt_itree_rewind: behind
+ * everything in flight on the tree, pipelined batches of every kind and the caller's stream included, and refused where
+ * a rewind is refused (steps of a sliced world in flight -- after imt_sliced_flush every replica may be reserved alike --
+ * an open slice, a sharded batch between _batch_begin and _end: IMT_ERR_ARG), the tree and its capacity untouched.
+ * The contents do not change: a view made before the call answers afterwards without rebuilding its side table
+ * (imt_itree_view_stats), and imt_itree_root_lagged keeps answering.  The batch calls do not grow the tree themselves:
+ * the caller knows the size, n and the capacity, and reserves between calls. */
+uint64_t imt_itree_capacity(const imt_itree *t);   /* leaves the tree can hold, sentinel included; 0 for NULL */
+int imt_itree_reserve(imt_itree *t, uint64_t new_capacity, unsigned flags);
+/* Where the last imt_itree_reserve that changed the capacity spent its time, in milliseconds: ms[0] the whole call (host
+ * clock), ms[1] the kernel that moved the nodes (device time), ms[2] hipMalloc + hipFree (host clock).  All zero before
+ * the first such call.  Host memory.  IMT_ERR_ARG for NULL. */
+int imt_itree_reserve_stats(const imt_itree *t, double *ms /*[3]*/);
 /* READING AT AN EARLIER SIZE, for whoever answers against a root that lags the head: the non-membership service bound to
  * the finalized root, a prover catching up on a block that has since been built upon, a node asking whether a value would
  * have been a double spend at block B.  A view is the tree as it was when it held `size` leaves (sentinel included),

@@ -408,9 +408,13 @@ public:
         c_->check(imt_itree_rewind(t_, new_size, &root, hashes ? hashes->data() : nullptr, IMT_FMT_CANONICAL));
         return root;
     }
+    // leaves the tree can hold, sentinel included; reserve() gives it another capacity as it stands (imt_itree_reserve):
+    // a power of two that holds size(), larger or smaller -- a copy, no hash, nothing else a call can see changes
+    uint64_t capacity() const { return imt_itree_capacity(t_); }
+    void reserve(uint64_t new_capacity) { c_->check(imt_itree_reserve(t_, new_capacity, 0)); }
     std::vector<IndexedMerkleTreeLeaf> get_leaves(const std::vector<uint64_t>& index) {
         std::vector<IndexedMerkleTreeLeaf> out(index.size());
-        if (!index.empty()) c_->check(imt_itree_get_leaves(t_, index.data(), index.size(), out.data(), IMT_FMT_CANONICAL));
+        if (!index.empty()) c_->check(imt_itree_get_leaves(t_,index.data(), index.size(), out.data(), IMT_FMT_CANONICAL));
         return out;
     }
     // checkpoint / resume (the reference's serde leaf, src/utils.rs:12-17): every leaf in index order; load() checks the

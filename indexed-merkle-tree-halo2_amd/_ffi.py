@@ -172,6 +172,9 @@ SIGNATURES = {
     "imt_itree_apply_filtered": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, P(c_u64), c_void_p, c_uint]),
     "imt_itree_apply_stats": (c_int, [c_void_p, P(c_u64)]),
     "imt_itree_rewind": (c_int, [c_void_p, c_u64, c_void_p, P(c_u64), c_uint]),
+    "imt_itree_capacity": (c_u64, [c_void_p]),
+    "imt_itree_reserve": (c_int, [c_void_p, c_u64, c_uint]),
+    "imt_itree_reserve_stats": (c_int, [c_void_p, P(ctypes.c_double)]),
     "imt_itree_view_create": (c_int, [c_void_p, c_u64, P(c_void_p)]),
     "imt_itree_view_free": (None, [c_void_p]),
     "imt_itree_view_size": (c_u64, [c_void_p]),

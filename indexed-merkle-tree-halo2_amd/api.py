@@ -536,7 +536,7 @@ class IndexedTree:
     lands on leaf `size + i`, empty slots hash to H(0,0,0) (src/indexed_merkle_tree.rs:373-376)."""
 
     def __init__(self, ctx, depth, capacity):
-        self.ctx, self.depth, self.capacity = ctx, depth, capacity
+        self.ctx, self.depth = ctx, depth
         self.global_depth, self.index_base = depth, 0
         self.rewind_stats = None         # hashes per level of the last rewind() (numpy uint64 [depth + 1])
         self._views = weakref.WeakSet()  # views of this tree: imt.h wants them freed before it
@@ -580,6 +580,11 @@ class IndexedTree:
     @property
     def size(self):
         return lib.imt_itree_size(self.h)
+
+    @property
+    def capacity(self):
+        """leaves the tree can hold, sentinel included (imt_itree_capacity); reserve() changes it"""
+        return lib.imt_itree_capacity(self.h)
 
     def root(self):
         out = np.empty(32, dtype=np.uint8)
@@ -831,6 +836,18 @@ class IndexedTree:
         self.ctx._check(lib.imt_itree_rewind(self.h, size, _p(root), stats.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), 0))
         self.rewind_stats = stats
         return to_int(root)
+
+    def reserve(self, capacity):
+        """Another capacity for the tree as it stands (imt_itree_reserve): a power of two that holds `size`, larger or
+        smaller than the present one.  Nothing is hashed and nothing a call can see changes but the room; ordered behind
+        everything in flight.  A batch that raised IMT_ERR_FULL goes in after reserve(2 * capacity)."""
+        self.ctx._check(lib.imt_itree_reserve(self.h, capacity, 0))
+
+    def reserve_stats(self):
+        """milliseconds of the last reserve() that changed the capacity: (the call, its node kernel, hipMalloc + hipFree)"""
+        ms = (ctypes.c_double * 3)()
+        self.ctx._check(lib.imt_itree_reserve_stats(self.h, ms))
+        return tuple(ms)
 
     def view(self, size):
         """A read-only IndexedTreeView of this tree as it was when it held `size` leaves (imt_itree_view_create); the tree

@@ -12,6 +12,7 @@
 #include "imt_prep_logic.hpp"
 #include "imt_filter_logic.hpp"
 #include "imt_apply_pipe.hpp"
+#include "imt_resize.hpp"
 #include <algorithm>
 #include <array>
 #include <chrono>
@@ -209,6 +210,7 @@ struct imt_itree {
     // imt_itree_apply_pipelined keeps them in its plan set: the set of the last apply call if that was a pipelined one
     const PlanSet* apply_stats_set = nullptr;
     uint64_t* d_rewind_stats = nullptr;      // [IMT_MAX_DEPTH + 1]: the same of the last imt_itree_rewind
+    double reserve_ms[3] = {0, 0, 0};        // the last imt_itree_reserve: the call, its node kernel, its hipMalloc + hipFree
     uint64_t gen = 0;                        // bumped by every call that changes the contents: what a view's side table is for
 };
 
@@ -411,8 +413,7 @@ extern "C" int imt_itree_new(imt_ctx* c, unsigned depth, uint64_t capacity, imt_
     t->cap = capacity;
     uint64_t off = 0;
     for (unsigned l = 0; l <= depth; l++) {
-        uint64_t n = l < 63 ? capacity >> l : 0;
-        if (n == 0) n = 1;
+        const uint64_t n = resize::level_len(capacity, l);
         t->h_off.push_back(off);
         t->h_len.push_back(n);
         off += n;
@@ -607,7 +608,7 @@ static int check_batch_call(imt_itree* t, size_t n, unsigned flags) {
     return c->set_device();
 }
 static int check_room(imt_itree* t, size_t n) {
-    if (t->size + n > t->cap) return t->ctx->fail(IMT_ERR_FULL, "tree capacity %llu exceeded", (unsigned long long)t->cap);
+    if (t->size + n > t->cap) return t->ctx->fail(IMT_ERR_FULL, "tree capacity %llu exceeded (imt_itree_reserve)", (unsigned long long)t->cap);
     return IMT_OK;
 }
 
@@ -3054,6 +3055,194 @@ extern "C" void imt_itree_view_free(imt_itree_view* v) {
 }
 
 extern "C" uint64_t imt_itree_view_size(const imt_itree_view* v) { return view_alive(v) ? v->size : 0; }
+
+// ------------------------------------------------------------------------------------
+// another capacity for the tree that exists (imt_resize.hpp)
+// ------------------------------------------------------------------------------------
+extern "C" uint64_t imt_itree_capacity(const imt_itree* t) { return t ? t->cap : 0; }
+
+static int reserve_alloc(imt_ctx* c, void** q, size_t bytes, const char* what);
+static void reserve_free(void* q);
+// A workspace's temporary storage was sized for (cap_n values, the capacity of the day): large enough for new_cap, the
+// rest of the workspace -- and of the plan set around it, d_root above all -- left where it is.  Nothing is in flight.
+static int ws_fit(imt_ctx* c, prep::Workspace& w, size_t new_cap) {
+    if (!w.cap_n) return IMT_OK;
+    const size_t need = prep::temp_bytes_needed(w.cap_n, new_cap);
+    if (need <= w.tmp_bytes) return IMT_OK;
+    void* q = nullptr;
+    int rc = reserve_alloc(c, &q, need, "a batch workspace");
+    if (rc) return rc;
+    if (w.tmp) reserve_free(w.tmp);
+    w.tmp = q;
+    w.tmp_bytes = need;
+    return IMT_OK;
+}
+
+// host milliseconds the running imt_itree_reserve has spent in hipMalloc and hipFree (imt_itree_reserve_stats)
+static thread_local double g_reserve_mem_ms = 0;
+static void reserve_free(void* q) {
+    const HostTimer w;
+    hipFree(q);
+    g_reserve_mem_ms += w.ms();
+}
+static int reserve_alloc(imt_ctx* c, void** q, size_t bytes, const char* what) {
+    const HostTimer w;
+    const hipError_t e = hipMalloc(q, bytes);
+    g_reserve_mem_ms += w.ms();
+    if (e == hipSuccess) return IMT_OK;
+    (void)hipGetLastError();
+    *q = nullptr;
+    return c->fail(IMT_ERR_ALLOC, "imt_itree_reserve: no %zu bytes for %s", bytes, what);
+}
+// `rows` rows of `row_bytes` into a new array of new_cap rows -- q if the caller has it already -- and the old array
+// freed once the copy has left the stream: the new one exists before the old one goes, so the peak is one array more,
+// and a failure leaves *arr as it was.
+template <class T>
+static int reserve_rows(imt_ctx* c, T** arr, void* have, size_t new_cap, size_t rows, size_t row_bytes, const char* what) {
+    T* q = (T*)have;
+    int rc;
+    if (!q && (rc = reserve_alloc(c, (void**)&q, new_cap * row_bytes, what))) return rc;
+    hipError_t e = hipSuccess;
+    if (rows) e = hipMemcpyAsync(q, *arr, rows * row_bytes, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        hipFree(q);
+        return c->hip_fail(e, "imt_itree_reserve copy");
+    }
+    reserve_free(*arr);
+    *arr = q;
+    return IMT_OK;
+}
+
+extern "C" int imt_itree_reserve(imt_itree* t, uint64_t new_capacity, unsigned flags) {
+    if (!t) return IMT_ERR_ARG;
+    imt_ctx* c = t->ctx;
+    IMT_NOT_SLICED(t);
+    if (flags & IMT_PIPELINE) return c->fail(IMT_ERR_ARG, "a reserve is not pipelined (IMT_PIPELINE)");
+    if (flags) return c->fail(IMT_ERR_ARG, "imt_itree_reserve takes no flags");
+    const uint64_t C = new_capacity;
+    if (C < 2 || (C & (C - 1)) || C > ((uint64_t)1 << 31))
+        return c->fail(IMT_ERR_RANGE, "capacity must be a power of two in [2, 2^31]");
+    if (t->depth < 63 && C > ((uint64_t)1 << t->depth)) return c->fail(IMT_ERR_RANGE, "capacity exceeds 2^depth");
+    if (C < t->size)
+        return c->fail(IMT_ERR_RANGE, "a tree of %llu leaves does not fit a capacity of %llu", (unsigned long long)t->size,
+                       (unsigned long long)C);
+    if (slice_open(t)) return c->fail(IMT_ERR_ARG, "a slice is open (issue its remaining units first)");
+    if (t->pending.active) return c->fail(IMT_ERR_ARG, "a sharded batch is open (imt_itree_batch_end first)");
+    int rc = c->set_device();
+    if (rc) return rc;
+    if (C == t->cap) return IMT_OK;
+    const HostTimer whole;
+    g_reserve_mem_ms = 0;
+    float kernel_ms = 0;
+    // ---- behind everything in flight, the caller's stream included (imt_itree_rewind's sequence) ----
+    if ((rc = join_top(t))) return rc;
+    for (auto& pl : t->plan)
+        if (pl.in_flight) { IMT_HIP(c, hipEventSynchronize(pl.done)); pl.in_flight = false; pl.pipelined = false; }
+    IMT_HIP(c, hipStreamSynchronize(t->up_stream));
+    hipStream_t s = c->stream;
+    IMT_HIP(c, hipStreamSynchronize(s));
+    const unsigned D = t->depth;
+    const uint64_t total = resize::total_nodes(C, D);
+    // A shrinking tree must not be left with its capacity over an array of the smaller one, so every new array exists
+    // before the first old one goes (together they are at most half the old tree).  A growing tree takes one at a time.
+    void *q_val = nullptr, *q_sorted[2] = {nullptr, nullptr}, *q_extra = nullptr;
+    if (C < t->cap) {
+        if ((rc = reserve_alloc(c, &q_val, C * 32, "the values")) || (rc = reserve_alloc(c, &q_sorted[0], C * 4, "the index")) ||
+            (rc = reserve_alloc(c, &q_sorted[1], C * 4, "the index")) ||
+            (t->d_sorted_extra && (rc = reserve_alloc(c, &q_extra, C * 4, "the index")))) {
+            for (void* q : {q_val, q_sorted[0], q_sorted[1], q_extra})
+                if (q) hipFree(q);
+            return rc;
+        }
+    }
+    // ---- the nodes: every level of the new layout in one launch, Z[l] where the old layout has no node ----
+    {
+        std::vector<uint64_t> off(D + 1), len(D + 1);
+        for (unsigned l = 0; l <= D; l++) {
+            off[l] = resize::level_off(C, l);
+            len[l] = resize::level_len(C, l);
+        }
+        uint8_t* nodes = nullptr;
+        uint64_t *d_off = nullptr, *d_len = nullptr;
+        hipError_t e;
+        if ((rc = reserve_alloc(c, (void**)&nodes, total * 32, "the nodes")) || (rc = reserve_alloc(c, (void**)&d_off, (D + 1) * 8, "the offsets")) ||
+            (rc = reserve_alloc(c, (void**)&d_len, (D + 1) * 8, "the lengths"))) {
+            for (void* q : {(void*)nodes, (void*)d_off, (void*)d_len, q_val, q_sorted[0], q_sorted[1], q_extra})
+                if (q) hipFree(q);
+            return rc;
+        }
+        hipEvent_t k0 = nullptr, k1 = nullptr;          // the kernel's own time, for imt_itree_reserve_stats; optional
+        if (hipEventCreate(&k0) != hipSuccess || hipEventCreate(&k1) != hipSuccess) {
+            (void)hipGetLastError();
+            if (k0) hipEventDestroy(k0);
+            k0 = k1 = nullptr;
+        }
+        if ((e = hipMemcpyAsync(d_off, off.data(), (D + 1) * 8, hipMemcpyHostToDevice, s)) == hipSuccess &&
+            (e = hipMemcpyAsync(d_len, len.data(), (D + 1) * 8, hipMemcpyHostToDevice, s)) == hipSuccess) {
+            if (k0) hipEventRecord(k0, s);
+            launch::restride_levels(s, t->d_nodes, t->d_off, t->d_len, nodes, d_off, total, c->d_zero, D);
+            e = hipGetLastError();
+            if (k1) hipEventRecord(k1, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e == hipSuccess && k1 && hipEventElapsedTime(&kernel_ms, k0, k1) != hipSuccess) kernel_ms = 0;
+        }
+        if (k0) hipEventDestroy(k0);
+        if (k1) hipEventDestroy(k1);
+        if (e != hipSuccess) {
+            for (void* q : {(void*)nodes, (void*)d_off, (void*)d_len, q_val, q_sorted[0], q_sorted[1], q_extra})
+                if (q) hipFree(q);
+            return c->hip_fail(e, "imt_itree_reserve nodes");
+        }
+        // The nodes are in the new layout from here on.  Should a later array of a growing tree fail, the tree keeps its
+        // capacity over a node array of the larger one: every reader and writer goes through h_len / d_len, and between
+        // the two layouts the nodes differ only where both read Z[l].
+        for (void* q : {(void*)t->d_nodes, (void*)t->d_off, (void*)t->d_len}) reserve_free(q);
+        t->d_nodes = nodes;
+        t->d_off = d_off;
+        t->d_len = d_len;
+        t->h_off = off;
+        t->h_len = len;
+    }
+    // ---- one array at a time: the values, the index buffers (only the current one holds anything), the third one ----
+    rc = reserve_rows(c, &t->d_val, q_val, C, t->size, 32, "the values");
+    q_val = nullptr;                // the tree's now, or freed
+    for (int b = 0; b < 2 && !rc; b++) {
+        rc = reserve_rows(c, &t->d_sorted[b], q_sorted[b], C, b == t->sorted_cur ? t->size : 0, 4, "the index");
+        q_sorted[b] = nullptr;
+    }
+    if (t->d_sorted_extra && !rc) {
+        rc = reserve_rows(c, &t->d_sorted_extra, q_extra, C, 0, 4, "the index");
+        q_extra = nullptr;
+    }
+    if (rc) {
+        for (void* q : {q_val, q_sorted[0], q_sorted[1], q_extra})
+            if (q) hipFree(q);
+        return rc;
+    }
+    // ---- workspaces sized from the capacity: the tree's plan sets, each view's own, the slices' ----
+    if (C > t->cap) {
+        for (auto& pl : t->plan)
+            if ((rc = ws_fit(c, pl.ws, C))) return rc;
+        if ((rc = ws_fit(c, t->fws, C))) return rc;
+        std::lock_guard<std::mutex> lock(g_views_mu);
+        for (const imt_itree_view* cv : g_views) {
+            imt_itree_view* v = const_cast<imt_itree_view*>(cv);
+            if (v->t == t && (rc = ws_fit(c, v->plan.ws, C))) return rc;
+        }
+    }
+    t->cap = C;
+    t->reserve_ms[0] = whole.ms();
+    t->reserve_ms[1] = kernel_ms;
+    t->reserve_ms[2] = g_reserve_mem_ms;
+    return IMT_OK;
+}
+
+extern "C" int imt_itree_reserve_stats(const imt_itree* t, double* ms) {
+    if (!t || !ms) return IMT_ERR_ARG;
+    for (int i = 0; i < 3; i++) ms[i] = t->reserve_ms[i];
+    return IMT_OK;
+}
 
 extern "C" int imt_itree_view_root(imt_itree_view* v, void* root, unsigned flags) {
     if (!view_alive(v) || !root) return IMT_ERR_ARG;

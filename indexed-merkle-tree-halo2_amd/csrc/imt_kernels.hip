@@ -18,6 +18,7 @@
 #include "imt_trace_device.hpp"
 #include "imt_launch.hpp"
 #include "imt_sweep.hpp"
+#include "imt_resize.hpp"
 #if defined(__HIP_DEVICE_COMPILE__)
 #include "imt_coop_device.hpp"
 #endif
@@ -809,6 +810,24 @@ __global__ void __launch_bounds__(BLOCK) k_fill_level(uint8_t* __restrict__ node
     Word4* o = reinterpret_cast<Word4*>(nodes + i * 32);
     o[0] = z[0];
     o[1] = z[1];
+}
+
+// imt_itree_reserve: the stored nodes of all levels into the layout of another capacity (imt_resize.hpp), one launch.
+// A lane moves one 16-byte half of a node and consecutive lanes consecutive halves of the new array, so a wave writes
+// 1 KiB contiguous and -- within a level -- reads 1 KiB contiguous; nothing is shared between lanes.
+__global__ void __launch_bounds__(BLOCK) k_restride_levels(const uint8_t* __restrict__ old_nodes,
+                                                           const uint64_t* __restrict__ old_off,
+                                                           const uint64_t* __restrict__ old_len,
+                                                           uint8_t* __restrict__ new_nodes,
+                                                           const uint64_t* __restrict__ new_off, uint64_t new_total,
+                                                           const uint8_t* __restrict__ zero, unsigned depth) {
+    const size_t pieces = (size_t)new_total * 2, step = (size_t)gridDim.x * blockDim.x;
+    for (size_t p = gtid(); p < pieces; p += step) {
+        unsigned l;
+        const uint64_t src = resize::source_of(new_off, old_off, old_len, depth, p >> 1, &l);
+        const uint8_t* row = src != ~(uint64_t)0 ? old_nodes + src * 32 : zero + (size_t)l * 32;
+        reinterpret_cast<Word4*>(new_nodes)[p] = reinterpret_cast<const Word4*>(row)[p & 1];
+    }
 }
 
 __global__ void __launch_bounds__(BLOCK) k_merge_level(sweep::LevelTable in, sweep::LevelOut out, uint32_t total) {
@@ -1740,6 +1759,14 @@ void mad_peak(hipStream_t s, uint32_t* out, unsigned blocks, int iters) {
 void fill_level(hipStream_t s, uint8_t* nodes, size_t n, const uint8_t* zero_l) {
     if (!n) return;
     hipLaunchKernelGGL(k_fill_level, dim3(nblk(n)), dim3(BLOCK), 0, s, nodes, n, zero_l);
+}
+void restride_levels(hipStream_t s, const uint8_t* old_nodes, const uint64_t* old_off, const uint64_t* old_len,
+                     uint8_t* new_nodes, const uint64_t* new_off, uint64_t new_total, const uint8_t* zero, unsigned depth) {
+    if (!new_total) return;
+    // a grid-stride loop: enough blocks to fill the chip several times over, not one per 4 KiB of a 64 GiB array
+    const unsigned blocks = std::min(nblk((size_t)new_total * 2), 256u * 16u);
+    hipLaunchKernelGGL(k_restride_levels, dim3(blocks), dim3(BLOCK), 0, s, old_nodes, old_off, old_len, new_nodes, new_off,
+                       new_total, zero, depth);
 }
 // one thread per event, or -- while the launch is small enough to leave most SIMDs idle -- one quad per event
 static void launch_sweep(hipStream_t s, const SweepArgs& a, uint32_t coop_max) {

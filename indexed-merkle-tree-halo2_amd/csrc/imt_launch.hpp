@@ -155,6 +155,11 @@ struct SweepArgs {
     unsigned fmt_out;
 };
 void fill_level(hipStream_t s, uint8_t* nodes, size_t n, const uint8_t* zero_l);
+// imt_itree_reserve (imt_resize.hpp): every node of the new layout -- new_total nodes, levels at new_off [depth+1] --
+// from the node at the same level and position of the old layout (old_off / old_len [depth+1]) or, where that has none,
+// from zero [depth+1][32].  All offset arrays are device arrays; the two node arrays do not overlap.
+void restride_levels(hipStream_t s, const uint8_t* old_nodes, const uint64_t* old_off, const uint64_t* old_len,
+                     uint8_t* new_nodes, const uint64_t* new_off, uint64_t new_total, const uint8_t* zero, unsigned depth);
 // coop_max: launches of at most this many events use the latency form of the kernel (a quad of lanes per event,
 // imt_coop_device.hpp); 0 = never
 void sweep_leaves(hipStream_t s, const uint8_t* pre, const uint32_t* time0, uint8_t* val0, uint32_t k_begin,
