@@ -4,14 +4,15 @@
 //! `hasher.hash_fix_len_array(ctx, gate, &inp)` at `src/indexed_merkle_tree.rs:92` (inside the path loop `:90-93`),
 //! `:194`, `:271-275`, `:299-303` -- 3 + 4 d hashes per `insert_leaf`.  [`TracedPoseidonHasher`] has the same method
 //! and lays down the SAME cells (same gates, same copy constraints, same constants), but takes every new value
-//! from a witness trace the GPU produced (`imt_path_trace_batch` / `imt_hash_trace_batch`) instead of computing it.
+//! from a witness trace the GPU produced (`imt_path_trace_batch` / `imt_hash_trace_batch`, or `imt_hash_n_trace_batch`
+//! for the 1- to 16-input hashes a circuit computes besides tree nodes) instead of computing it.
 //! To use it, the reference's private helpers only change the TYPE of their `hasher` parameter (or become generic
 //! over [`FixLenHasher`], which both hashers implement) -- see INTEGRATION.md.
 //!
 //! [`IndexedMerkleTreeChip`] is the optional sugar `north_star` names: the reference has no chip struct, only the
 //! free functions `insert_leaf` (`:231`) and `verify_non_inclusion` (`:127`).
 
-use crate::ffi::{imt_trace_cell, IMT_CELL_CONST, IMT_CELL_COPY, IMT_CELL_INIT, IMT_CELL_INPUT, IMT_CELL_WITNESS};
+use crate::ffi::{imt_trace_cell, IMT_CELL_CONST, IMT_CELL_COPY, IMT_CELL_INIT, IMT_CELL_INPUT, IMT_CELL_WITNESS, IMT_HASH_MAX_INPUTS};
 use crate::gpu::{self, InsertWitness};
 use halo2_base::gates::GateInstructions;
 use halo2_base::poseidon::hasher::PoseidonHasher;
@@ -20,6 +21,7 @@ use halo2_base::QuantumCell::{Constant, Existing, Witness};
 use halo2_base::{AssignedValue, Context};
 use std::cell::RefCell;
 use std::collections::VecDeque;
+use std::rc::Rc;
 
 /// What `compute_merkle_root` & co. need from a hasher (`PoseidonHasher::hash_fix_len_array`'s signature).
 pub trait FixLenHasher<F: BigPrimeField> {
@@ -37,7 +39,7 @@ impl<F: BigPrimeField, const T: usize, const RATE: usize> FixLenHasher<F> for Po
     }
 }
 
-/// One arity's static cell map.
+/// One input length's static cell map.
 pub struct TraceLayout<F> {
     pub cells: Vec<imt_trace_cell>,
     pub constants: Vec<F>,
@@ -45,39 +47,52 @@ pub struct TraceLayout<F> {
     pub rows: usize,
 }
 
-/// Assigns precomputed traces.  Traces are queued in the order the circuit will ask for them (one `Vec<F>` of 1208 /
-/// 1209 rows per hash); `init_state` are the hasher's three initial-state cells ([2^64, 0, 0], loaded once with
-/// `ctx.load_constant`, exactly what `PoseidonHasher::initialize_consts` does at `:442`).
+/// Assigns precomputed traces.  Traces are queued in the order the circuit will ask for them (one `Vec<F>` of
+/// `imt_hash_n_trace_rows(len)` rows per hash: 1208 / 1209 for the tree's own 2- and 3-input hashes); `init_state` are
+/// the hasher's three initial-state cells ([2^64, 0, 0], loaded once with `ctx.load_constant`, exactly what
+/// `PoseidonHasher::initialize_consts` does at `:442`).  One hasher serves the whole circuit: the cell map of an input
+/// length is fetched the first time a hash of that length is pushed or assigned, for any length from 1 to
+/// `IMT_HASH_MAX_INPUTS`.
 pub struct TracedPoseidonHasher<F: BigPrimeField> {
-    layout2: TraceLayout<F>,
-    layout3: TraceLayout<F>,
+    layouts: RefCell<Vec<Option<Rc<TraceLayout<F>>>>>, // by input length; None until first used
     init_state: [AssignedValue<F>; 3],
     queue: RefCell<VecDeque<Vec<F>>>,
 }
 
 impl<F: BigPrimeField> TracedPoseidonHasher<F> {
     pub fn new(ctx: &mut Context<F>) -> Self {
-        let mk = |arity: usize| {
-            let (cells, constants, out_row) = gpu::trace_layout::<F>(arity).expect("imt_hash_trace_layout");
-            let rows = cells.iter().filter(|c| c.kind == IMT_CELL_WITNESS).count();
-            TraceLayout { cells, constants, out_row, rows }
-        };
         let init_state = [
             ctx.load_constant(F::from_u128(1u128 << 64)),
             ctx.load_constant(F::ZERO),
             ctx.load_constant(F::ZERO),
         ];
-        TracedPoseidonHasher { layout2: mk(2), layout3: mk(3), init_state, queue: RefCell::new(VecDeque::new()) }
+        let layouts = RefCell::new((0..=IMT_HASH_MAX_INPUTS).map(|_| None).collect());
+        TracedPoseidonHasher { layouts, init_state, queue: RefCell::new(VecDeque::new()) }
+    }
+
+    /// The cell map of a hash of `len` inputs, built on first use.  Panics for 0 inputs or more than
+    /// `IMT_HASH_MAX_INPUTS`: the library has neither.
+    pub fn layout(&self, len: usize) -> Rc<TraceLayout<F>> {
+        assert!(
+            (1..=IMT_HASH_MAX_INPUTS).contains(&len),
+            "no trace layout for {len} inputs: hash_fix_len_array is traced for 1 to {IMT_HASH_MAX_INPUTS} inputs"
+        );
+        let mut layouts = self.layouts.borrow_mut();
+        if layouts[len].is_none() {
+            let (cells, constants, out_row) = gpu::trace_layout::<F>(len).expect("imt_hash_n_trace_layout");
+            let rows = cells.iter().filter(|c| c.kind == IMT_CELL_WITNESS).count();
+            layouts[len] = Some(Rc::new(TraceLayout { cells, constants, out_row, rows }));
+        }
+        Rc::clone(layouts[len].as_ref().unwrap())
     }
 
     /// Queue traces in call order.  `rows` may hold several hashes back to back (what `gpu::path_traces` returns
-    /// per item): it is split by the row counts of `arities`.
+    /// per item): it is split by the row counts of `arities`, the input lengths of those hashes.
     pub fn push_traces(&self, rows: &[F], arities: &[usize]) {
         let mut off = 0;
-        let mut q = self.queue.borrow_mut();
         for &a in arities {
-            let n = if a == 3 { self.layout3.rows } else { self.layout2.rows };
-            q.push_back(rows[off..off + n].to_vec());
+            let n = self.layout(a).rows;
+            self.queue.borrow_mut().push_back(rows[off..off + n].to_vec());
             off += n;
         }
         assert_eq!(off, rows.len(), "trace length does not match the hash sequence");
@@ -90,13 +105,10 @@ impl<F: BigPrimeField> TracedPoseidonHasher<F> {
 
 impl<F: BigPrimeField> FixLenHasher<F> for TracedPoseidonHasher<F> {
     /// Cell for cell what `PoseidonHasher::hash_fix_len_array` assigns, region by region (a region = one
-    /// `ctx.assign_region` call of the original gadget: a `gate.add` / `sum` / `mul` / `mul_add` / `inner_product`).
+    /// `ctx.assign_region` call of the original gadget: a `gate.add` / `sum` / `mul` / `mul_add` / `inner_product`),
+    /// for 1 to `IMT_HASH_MAX_INPUTS` inputs.
     fn hash_fix_len_array(&self, ctx: &mut Context<F>, _gate: &impl GateInstructions<F>, inputs: &[AssignedValue<F>]) -> AssignedValue<F> {
-        let layout = match inputs.len() {
-            2 => &self.layout2,
-            3 => &self.layout3,
-            n => panic!("no trace layout for {n} inputs"),
-        };
+        let layout = self.layout(inputs.len());
         let rows = self.queue.borrow_mut().pop_front().expect("no precomputed trace queued for this hash");
         assert_eq!(rows.len(), layout.rows);
         let assigned = assign_layout(ctx, &layout.cells, &layout.constants, inputs, &self.init_state, &rows);

@@ -202,6 +202,8 @@ pub const IMT_CELL_INPUT: u8 = 1;
 pub const IMT_CELL_INIT: u8 = 2;
 pub const IMT_CELL_WITNESS: u8 = 3;
 pub const IMT_CELL_COPY: u8 = 4;
+/// the longest input `imt_hash_n_*` takes
+pub const IMT_HASH_MAX_INPUTS: usize = 16;
 
 extern "C" {
     // ---- context
@@ -231,6 +233,12 @@ extern "C" {
     pub fn imt_insert_trace_rows(depth: c_uint) -> usize;
     pub fn imt_insert_trace_batch(ctx: *mut imt_ctx, low_leaf: *const c_void, low_index: *const u64, low_sib: *const c_void, new_leaf: *const c_void, new_index: *const u64, new_path_index: *const u64, new_sib: *const c_void, depth: c_uint, n: usize, trace: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_hash_trace_layout(ctx: *mut imt_ctx, arity: c_int, cells: *mut imt_trace_cell, cells_cap: usize, n_cells: *mut usize, constants: *mut c_void, const_cap: usize, n_constants: *mut usize, out_row: *mut u32, flags: c_uint) -> c_int;
+
+    // ---- a1 / f1 for 1 to IMT_HASH_MAX_INPUTS inputs
+    pub fn imt_hash_n_batch(ctx: *mut imt_ctx, input: *const c_void, len: c_uint, out: *mut c_void, n: usize, flags: c_uint) -> c_int;
+    pub fn imt_hash_n_trace_rows(len: c_uint) -> usize;
+    pub fn imt_hash_n_trace_batch(ctx: *mut imt_ctx, input: *const c_void, len: c_uint, n: usize, trace: *mut c_void, flags: c_uint) -> c_int;
+    pub fn imt_hash_n_trace_layout(ctx: *mut imt_ctx, len: c_uint, cells: *mut imt_trace_cell, cells_cap: usize, n_cells: *mut usize, constants: *mut c_void, const_cap: usize, n_constants: *mut usize, out_row: *mut u32, flags: c_uint) -> c_int;
 
     // ---- a2 / a3 / a4: dense native tree
     // ---- f3: the rest of insert_leaf's advice column

@@ -81,6 +81,21 @@ pub fn hash3_batch<F: ScalarField>(triples: &[[F; 3]]) -> Result<Vec<F>, ImtErro
     Ok(from_bytes(&out))
 }
 
+/// `hasher.hash_fix_len_array(.., &inp)` for n input vectors of one length, 1 to 16 (`imt_hash_n_batch`): what a circuit
+/// that embeds the chip hashes besides tree nodes -- a note commitment, a nullifier -- computed where the tree lives.
+/// Lengths 2 and 3 equal `hash2_batch` / `hash3_batch`.
+pub fn hash_n_batch<F: ScalarField>(inputs: &[Vec<F>]) -> Result<Vec<F>, ImtError> {
+    let len = inputs.first().map_or(1, |v| v.len());
+    assert!(inputs.iter().all(|v| v.len() == len), "one call hashes vectors of one length");
+    let g = context().lock().unwrap();
+    let input: Vec<u8> = inputs.iter().flat_map(|p| to_bytes(p)).collect();
+    let mut out = vec![0u8; inputs.len() * 32];
+    check(&g, unsafe {
+        imt_hash_n_batch(g.ctx, input.as_ptr() as *const c_void, len as u32, out.as_mut_ptr() as *mut c_void, inputs.len(), IMT_FMT_CANONICAL)
+    })?;
+    Ok(from_bytes(&out))
+}
+
 /// all levels of the dense tree, bottom-up, concatenated (2n - 1 elements)
 pub fn tree_build<F: ScalarField>(leaves: &[F]) -> Result<Vec<F>, ImtError> {
     let g = context().lock().unwrap();
@@ -518,17 +533,36 @@ pub fn insert_traces<F: ScalarField>(w: &[InsertWitness<F>], depth: usize) -> Re
     Ok(trace.chunks_exact(rows * 32).map(from_bytes).collect())
 }
 
-/// The static cell map of one hash (`imt_hash_trace_layout`): cells, constants, output row.
+/// Every new advice value of `hash_fix_len_array` for n input vectors of one length, 1 to 16, item-major: `rows[i]` =
+/// `imt_hash_n_trace_rows(len)` elements in assignment order (`imt_hash_n_trace_batch`), ready for
+/// `TracedPoseidonHasher::push_traces(&rows[i], &[len])`.
+pub fn hash_n_traces<F: ScalarField>(inputs: &[Vec<F>]) -> Result<Vec<Vec<F>>, ImtError> {
+    let len = inputs.first().map_or(1, |v| v.len());
+    assert!(inputs.iter().all(|v| v.len() == len), "one call traces vectors of one length");
+    let g = context().lock().unwrap();
+    let n = inputs.len();
+    let rows = unsafe { imt_hash_n_trace_rows(len as u32) };
+    let input: Vec<u8> = inputs.iter().flat_map(|p| to_bytes(p)).collect();
+    let mut trace = vec![0u8; n * rows * 32];
+    check(&g, unsafe {
+        imt_hash_n_trace_batch(g.ctx, input.as_ptr() as *const c_void, len as u32, n, trace.as_mut_ptr() as *mut c_void,
+                               IMT_FMT_CANONICAL | IMT_TRACE_ITEM_MAJOR)
+    })?;
+    Ok((0..n).map(|i| from_bytes(&trace[i * rows * 32..][..rows * 32])).collect())
+}
+
+/// The static cell map of one hash of `arity` = 1 to 16 inputs (`imt_hash_n_trace_layout`; for 2 and 3 inputs it is
+/// `imt_hash_trace_layout`'s, cell for cell): cells, constants, output row.
 pub fn trace_layout<F: ScalarField>(arity: usize) -> Result<(Vec<imt_trace_cell>, Vec<F>, usize), ImtError> {
     let g = context().lock().unwrap();
     let (mut nc, mut nk, mut row) = (0usize, 0usize, 0u32);
     check(&g, unsafe {
-        imt_hash_trace_layout(g.ctx, arity as i32, std::ptr::null_mut(), 0, &mut nc, std::ptr::null_mut(), 0, &mut nk, &mut row, IMT_FMT_CANONICAL)
+        imt_hash_n_trace_layout(g.ctx, arity as u32, std::ptr::null_mut(), 0, &mut nc, std::ptr::null_mut(), 0, &mut nk, &mut row, IMT_FMT_CANONICAL)
     })?;
     let mut cells = vec![imt_trace_cell::default(); nc];
     let mut consts = vec![0u8; nk * 32];
     check(&g, unsafe {
-        imt_hash_trace_layout(g.ctx, arity as i32, cells.as_mut_ptr(), nc, &mut nc, consts.as_mut_ptr() as *mut c_void, nk, &mut nk, &mut row, IMT_FMT_CANONICAL)
+        imt_hash_n_trace_layout(g.ctx, arity as u32, cells.as_mut_ptr(), nc, &mut nc, consts.as_mut_ptr() as *mut c_void, nk, &mut nk, &mut row, IMT_FMT_CANONICAL)
     })?;
     Ok((cells, from_bytes(&consts), row as usize))
 }

@@ -232,6 +232,37 @@ typedef struct imt_trace_cell {
 int imt_hash_trace_layout(imt_ctx *ctx, int arity, imt_trace_cell *cells, size_t cells_cap, size_t *n_cells,
                           void *constants, size_t const_cap, size_t *n_constants, uint32_t *out_row, unsigned flags);
 
+/* ---- a1 / f1 for any input length: hash_fix_len_array over 1 to 16 inputs ------------------------
+ * The reference hands the CALLER's PoseidonHasher to hasher.hash_fix_len_array(ctx, gate, &inp), halo2-base's sponge over
+ * a slice of any length; the tree itself calls it with 2 and 3 inputs (the calls above), a circuit that embeds the chip
+ * hashes other things with the same hasher (a note commitment of 4-6 fields, a nullifier derived from a commitment and
+ * a key).  These calls are the same hash -- T = 3, rate 2, the same permutation -- for `len` inputs, 1 <= len <=
+ * IMT_HASH_MAX_INPUTS, with the same three faces: values, witness traces, the static cell map.
+ *   The state starts as [2^64, 0, 0]; every full pair of inputs is added to lanes 1, 2 and permuted; then the leftover
+ *   input (len odd) and the padding 1 are added to the next free lane(s) and the state is permuted once more; the
+ *   result is lane 1: floor(len / 2) + 1 permutations.  len = 2 and 3 return what imt_hash2_batch / imt_hash3_batch and
+ *   imt_hash_trace_batch / imt_hash_trace_layout return, bit for bit (those calls stay as they are and stay the ones to
+ *   use for 2 and 3 inputs).
+ *   rows: the NEW advice values in assignment order as in f1; a permutation that absorbs k inputs has 3 + k + 600 of
+ *   them: imt_hash_n_trace_rows(len) = 605 floor(len / 2) + 603 + (len odd) = 604, 1208, 1209, 1813, ... 5443 at 16;
+ *   the hash itself is row rows - 4.  The cell map has 2256 floor(len / 2) + 2250 + 3 (len odd) cells; IMT_CELL_INPUT
+ *   indices run to len - 1.  Order and cell structure follow the published halo2-lib v0.4.x gadget
+ *   (poseidon/hasher/state.rs over GateChip's vertical gate); halo2-base is not vendored in the reference, so this
+ *   order is UNPINNED BY THE REFERENCE.  What pins it: the output row is the hash (reference KAT), every gate of the
+ *   reconstructed column holds, and the CPU oracle restates it independently (oracle/trace.c).
+ *   Formats, IMT_DEVICE_PTRS, errors reported at imt_ctx_sync, n == 0 and IMT_ERR_NONCANONICAL for an input >= p: as
+ *   imt_hash2_batch / imt_hash_trace_batch.  len outside 1..16 -> IMT_ERR_ARG (imt_hash_n_trace_rows: 0).
+ *   trace layout: [rows][n][32] or, with IMT_TRACE_ITEM_MAJOR, [n][rows][32]: 32 rows(len) bytes per hash. */
+#define IMT_HASH_MAX_INPUTS 16
+int imt_hash_n_batch(imt_ctx *ctx, const void *in /*[n][len][32]*/, unsigned len, void *out /*[n][32]*/, size_t n,
+                     unsigned flags);
+size_t imt_hash_n_trace_rows(unsigned len);
+int imt_hash_n_trace_batch(imt_ctx *ctx, const void *in /*[n][len][32]*/, unsigned len, size_t n,
+                           void *trace /*[rows][n][32]*/, unsigned flags);
+/* cells / constants may be NULL (sizes only), as imt_hash_trace_layout; host pointers only */
+int imt_hash_n_trace_layout(imt_ctx *ctx, unsigned len, imt_trace_cell *cells, size_t cells_cap, size_t *n_cells,
+                            void *constants, size_t const_cap, size_t *n_constants, uint32_t *out_row, unsigned flags);
+
 /* ---- f3: the rest of insert_leaf's advice column --------------------------------------------------
  * After f1 the only advice values of insert_leaf (src/indexed_merkle_tree.rs:231-314) a chip would still compute on the
  * CPU are those outside hash_fix_len_array: the two is_less_than calls of verify_non_inclusion (:180, :226 -> :98-125:

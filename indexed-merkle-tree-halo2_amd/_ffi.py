@@ -109,6 +109,11 @@ SIGNATURES = {
                                        c_size_t, c_void_p, c_uint]),
     "imt_hash_trace_layout": (c_int, [c_void_p, c_int, P(TraceCell), c_size_t, P(c_size_t), c_void_p, c_size_t,
                                       P(c_size_t), P(ctypes.c_uint32), c_uint]),
+    "imt_hash_n_batch": (c_int, [c_void_p, c_void_p, c_uint, c_void_p, c_size_t, c_uint]),
+    "imt_hash_n_trace_rows": (c_size_t, [c_uint]),
+    "imt_hash_n_trace_batch": (c_int, [c_void_p, c_void_p, c_uint, c_size_t, c_void_p, c_uint]),
+    "imt_hash_n_trace_layout": (c_int, [c_void_p, c_uint, P(TraceCell), c_size_t, P(c_size_t), c_void_p, c_size_t,
+                                        P(c_size_t), P(ctypes.c_uint32), c_uint]),
     "imt_less_than_trace_rows": (c_size_t, [c_uint]),
     "imt_less_than_trace_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_uint, c_void_p, c_void_p, c_uint]),
     "imt_less_than_trace_layout": (c_int, [c_void_p, c_uint, P(TraceCell), c_size_t, P(c_size_t), c_void_p, c_size_t,
@@ -256,6 +261,7 @@ F_RANGE_PRED, F_LOW_IN_ROOT, F_LOW_LT_NEW, F_ZERO_SLOT, F_NEXT_VAL, F_NEXT_IDX, 
     0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x80)
 CELL_CONST, CELL_INPUT, CELL_INIT, CELL_WITNESS, CELL_COPY = 0, 1, 2, 3, 4
 TRACE_ITEM_MAJOR = SIB_ITEM_MAJOR
+HASH_MAX_INPUTS = 16
 OPT_COOP_MAX_EVENTS = 1
 PROF_NAMES = ("leaves", "index", "level", "top", "writeback", "host", "apply_lists", "apply_leaves", "apply_level", "apply_top")
 SEG_GLUE, SEG_HASH = 0, 1

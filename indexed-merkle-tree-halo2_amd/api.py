@@ -134,6 +134,15 @@ class Context:
         self._check(lib.imt_hash3_batch(self.h, _p(a), _p(out), n, fmt))
         return out
 
+    def hash_n(self, inputs, fmt=0):
+        """inputs uint8 [n, len, 32], 1 <= len <= 16 -> uint8 [n, 32]: hash_fix_len_array over `len` inputs
+        (imt_hash_n_batch); len = 2, 3 equal hash2 / hash3."""
+        a = _inputs_n(inputs)
+        n = a.shape[0]
+        out = np.empty((n, 32), dtype=np.uint8)
+        self._check(lib.imt_hash_n_batch(self.h, _p(a), a.shape[1], _p(out), n, fmt))
+        return out
+
     def permute(self, states, fmt=0):
         a = _arr(states, (3, 32))
         out = np.empty_like(a)
@@ -152,6 +161,17 @@ class Context:
         out = np.empty((n, rows, 32) if item_major else (rows, n, 32), dtype=np.uint8)
         self._check(lib.imt_hash_trace_batch(self.h, _p(a), arity, n, _p(out),
                                              fmt | (_ffi.TRACE_ITEM_MAJOR if item_major else 0)))
+        return out
+
+    def hash_n_trace(self, inputs, fmt=0, item_major=False):
+        """inputs uint8 [n, len, 32], 1 <= len <= 16 -> the trace rows of hash_n, as hash_trace returns them:
+        uint8 [rows, n, 32] (item_major: [n, rows, 32]); rows = imt_hash_n_trace_rows(len)."""
+        a = _inputs_n(inputs)
+        n, length = a.shape[0], a.shape[1]
+        rows = lib.imt_hash_n_trace_rows(length)
+        out = np.empty((n, rows, 32) if item_major else (rows, n, 32), dtype=np.uint8)
+        self._check(lib.imt_hash_n_trace_batch(self.h, _p(a), length, n, _p(out),
+                                               fmt | (_ffi.TRACE_ITEM_MAJOR if item_major else 0)))
         return out
 
     def path_trace(self, index, sib, depth, leaf=None, leaf3=None, fmt=0, item_major=False):
@@ -263,6 +283,10 @@ class Context:
         cells: structured array with fields kind (_ffi.CELL_*), gate, index; constants: uint8 [k, 32]."""
         return trace_layout(lambda *a: lib.imt_hash_trace_layout(self.h, *a), arity, fmt, self._check)
 
+    def hash_n_trace_layout(self, length, fmt=0):
+        """the same for a hash of `length` = 1..16 inputs (imt_hash_n_trace_layout)"""
+        return trace_layout(lambda *a: lib.imt_hash_n_trace_layout(self.h, *a), length, fmt, self._check)
+
     # ---- a5 / a8 / a9 ----
     def path_root(self, leaf, index, sib, depth, item_major=False, fmt=0):
         leaf = _arr(leaf, (32,))
@@ -350,6 +374,13 @@ class Context:
         out = np.empty(32, dtype=np.uint8)
         self._check(lib.imt_combine_subtree_roots(self.h, _p(r), r.shape[0], sub_height, depth, _p(out), fmt))
         return out
+
+
+def _inputs_n(inputs):
+    a = np.ascontiguousarray(inputs, dtype=np.uint8)
+    if a.ndim != 3 or not 1 <= a.shape[1] <= _ffi.HASH_MAX_INPUTS or a.shape[2] != 32:
+        raise ValueError(f"expected [n, 1..{_ffi.HASH_MAX_INPUTS}, 32], got {a.shape}")
+    return a
 
 
 CELL_DTYPE = np.dtype([("kind", "u1"), ("gate", "u1"), ("region", "<u2"), ("index", "<u4")])

@@ -189,7 +189,8 @@ extern "C" int imt_ctx_create(int device, imt_ctx** out) {
     c->hp.fill_trace_consts(tc);
     hipError_t e;
     if ((e = hipSetDevice(device)) != hipSuccess || (e = hipStreamCreate(&c->own_stream)) != hipSuccess ||
-        (e = launch::upload_consts(pc)) != hipSuccess || (e = launch::upload_trace_consts(tc)) != hipSuccess || (e = hipMalloc((void**)&c->d_err, sizeof(int))) != hipSuccess ||
+        (e = launch::upload_consts(pc)) != hipSuccess || (e = launch::upload_trace_consts(tc)) != hipSuccess || (e = launch::upload_hash_n_consts(pc, tc)) != hipSuccess ||
+        (e = hipMalloc((void**)&c->d_err, sizeof(int))) != hipSuccess ||
         (e = hipMalloc((void**)&c->d_zero, (IMT_MAX_DEPTH + 1) * 32)) != hipSuccess) {
         if (c->own_stream) hipStreamDestroy(c->own_stream);
         if (c->d_err) hipFree(c->d_err);
@@ -338,6 +339,21 @@ extern "C" int imt_hash2_batch(imt_ctx* c, const void* in, void* out, size_t n, 
 extern "C" int imt_hash3_batch(imt_ctx* c, const void* in, void* out, size_t n, unsigned flags) {
     return hash_n(c, in, out, n, 3, flags);
 }
+// hash_fix_len_array over 1..16 inputs (imt_hash_n.hip)
+extern "C" int imt_hash_n_batch(imt_ctx* c, const void* in, unsigned len, void* out, size_t n, unsigned flags) {
+    int rc = begin(c, flags);
+    if (rc) return rc;
+    if (len < 1 || len > IMT_HASH_MAX_INPUTS) return c->fail(IMT_ERR_ARG, "len must be 1..%d", IMT_HASH_MAX_INPUTS);
+    if (n == 0) return IMT_OK;
+    if (!in || !out) return c->fail(IMT_ERR_ARG, "null buffer");
+    Io io(c, flags);
+    const uint8_t* d_in = io.in_fe(in, n * 32 * (size_t)len);
+    uint8_t* d_out = io.out_fe(out, n * 32);
+    if (io.rc) return io.rc;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    launch::hash_n_batch(c->stream, d_in, len, d_out, n, fmt, fmt, c->d_err, c->coop_max_events);
+    return io.finish();
+}
 extern "C" int imt_permute_batch(imt_ctx* c, const void* in, void* out, size_t n, unsigned flags) {
     int rc = begin(c, flags);
     if (rc) return rc;
@@ -369,6 +385,23 @@ extern "C" int imt_hash_trace_batch(imt_ctx* c, const void* in, int arity, size_
     const unsigned fmt = flags & IMT_FMT_MASK;
     const bool item_major = flags & IMT_TRACE_ITEM_MAJOR;
     launch::hash_trace(c->stream, d_in, n, arity, d_tr, n, 0, rows, item_major, fmt, fmt, c->d_err);
+    return io.finish();
+}
+
+extern "C" int imt_hash_n_trace_batch(imt_ctx* c, const void* in, unsigned len, size_t n, void* trace, unsigned flags) {
+    int rc = begin(c, flags);
+    if (rc) return rc;
+    const size_t rows = imt_hash_n_trace_rows(len);
+    if (!rows) return c->fail(IMT_ERR_ARG, "len must be 1..%d", IMT_HASH_MAX_INPUTS);
+    if (n == 0) return IMT_OK;
+    if (!in || !trace) return c->fail(IMT_ERR_ARG, "null buffer");
+    Io io(c, flags);
+    const uint8_t* d_in = io.in_fe(in, n * 32 * (size_t)len);
+    uint8_t* d_tr = io.out_fe(trace, n * rows * 32);
+    if (io.rc) return io.rc;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    const bool item_major = flags & IMT_TRACE_ITEM_MAJOR;
+    launch::hash_n_trace(c->stream, d_in, len, n, d_tr, rows, item_major, fmt, fmt, c->d_err);
     return io.finish();
 }
 

@@ -133,6 +133,39 @@ __device__ __forceinline__ void hash23(const uint32_t* tab, Fe& out, const Fe& X
     canonicalize(out);
 }
 
+// The sponge for any len >= 1 (imt_device.hpp::hash_sponge has the absorb rule), one loop around ONE permute().
+// `load(j, x)` fetches input j of this quad's hash; every lane calls it with the index its role absorbs (lane 2 the odd
+// input of a full pair, the others the even one), so each input is read -- and validated -- by the lane that uses it.
+// Absorbing is hash23's `three` branch: the lane's state plus an input below p, normalised.  Returns the hash on lane 1
+// (canonical); other lanes return their own state lane.  len = 2, 3 give hash23's values limb for limb.
+template <class LoadInput>
+__device__ __forceinline__ void hash_sponge(const uint32_t* tab, Fe& out, unsigned len, unsigned ri, LoadInput load) {
+    Fe S;
+    tab_fe(S, tab, IMT_COOP_E(cap0));
+#pragma unroll
+    for (int i = 0; i < NL; i++) S.v[i] = ri == 0 ? S.v[i] : 0u;     // PoseidonState::default: [2^64, 0, 0]
+    const unsigned full = len >> 1;
+#pragma unroll 1
+    for (unsigned ch = 0; ch <= full; ch++) {
+        unsigned first_rc = IMT_COOP_E(rc_full);
+        if (ch < full || (len & 1u)) {
+            const bool pair = ch < full;
+            Fe x, one;
+            load(2 * ch + (pair && ri == 2 ? 1u : 0u), x);
+            tab_fe(one, tab, IMT_COOP_E(one));
+#pragma unroll
+            for (int i = 0; i < NL; i++) x.v[i] = ri == 0 ? 0u : (ri == 2 && !pair ? one.v[i] : x.v[i]);
+            add_lazy(S, S, x);
+            normalize(S);
+        } else {                                                 // the padding 1 alone rides on the constants
+            first_rc = IMT_COOP_E(rc_h2p2);
+        }
+        permute(tab, S, ri, first_rc);
+    }
+    out = S;
+    canonicalize(out);
+}
+
 }  // namespace coop
 }  // namespace dev
 }  // namespace imt

@@ -475,6 +475,41 @@ IMT_HD void hash23_stashed(const PoseidonConsts& pc, Fe& out, const Fe& a, const
     out = s[1];
     canonicalize(out);
 }
+// Poseidon::update(&in[0 .. len]) followed by squeeze_and_reset() for any len >= 1 -- halo2-base's hash_fix_len_array over
+// a slice of the caller's choosing: floor(len / 2) + 1 permutations.  Every full pair of inputs goes into lanes 1, 2; the
+// last permutation takes the leftover input (len odd) and the padding 1 in the next free lane(s).  One loop around ONE
+// permute(), the inputs of a chunk fetched inside it by `load(j, x)` (input j of this hash, canonical device form), so
+// that no more than one input is ever held beside the state.  Absorbing is hash23's `three` branch: lanes 1, 2 leave
+// permute() below 9p, an input is below p, so they enter the next one below 10p (entry bound 16p); lane 0 is untouched
+// (< 30p, bound 32p).  For len even the padding rides on the round-0 constants (rc_h2p2).  `len` must be wave-uniform.
+// len = 2, 3 give hash23's values limb for limb.
+template <class LoadInput>
+IMT_HD void hash_sponge(const PoseidonConsts& pc, Fe& out, unsigned len, LoadInput load) {
+    Fe s[3];
+    s[0] = pc.cap0;
+#pragma unroll
+    for (int i = 0; i < NL; i++) s[1].v[i] = s[2].v[i] = 0;     // PoseidonState::default: [2^64, 0, 0]
+    const unsigned full = len >> 1;
+#pragma unroll 1
+    for (unsigned ch = 0; ch <= full; ch++) {
+        const Fe* rc0 = pc.rc_full[0];
+        if (ch < full || (len & 1u)) {
+            Fe x;
+            load(2 * ch, x);
+            add_lazy(s[1], s[1], x);
+            normalize(s[1]);
+            if (ch < full) load(2 * ch + 1, x);
+            else x = pc.one;                                    // the padding behind the leftover input
+            add_lazy(s[2], s[2], x);
+            normalize(s[2]);
+        } else {                       // nothing left but the padding 1 in lane 1 (folded into rc)
+            rc0 = pc.rc_h2p2;
+        }
+        permute(pc, s, rc0);
+    }
+    out = s[1];
+    canonicalize(out);
+}
 IMT_HD void hash2(const PoseidonConsts& pc, Fe& out, const Fe& a, const Fe& b) { hash23(pc, out, a, b, a, false); }
 IMT_HD void hash3(const PoseidonConsts& pc, Fe& out, const Fe& a, const Fe& b, const Fe& c) { hash23(pc, out, a, b, c, true); }
 

@@ -79,6 +79,14 @@ void path_pairs(hipStream_t s, const PathChains& a, uint32_t coop_max);
 
 void hash_batch(hipStream_t s, const uint8_t* in, uint8_t* out, size_t n, int arity, unsigned fmt_in,
                 unsigned fmt_out, int* err, uint32_t coop_max = 0);
+// imt_hash_n.hip: the hash of `len` = 1..16 inputs per item, in[n][len][32].  That translation unit keeps its own copies
+// of the two tables (upload_hash_n_consts, once per context).  coop_max as for hash_batch.
+hipError_t upload_hash_n_consts(const dev::PoseidonConsts& pc, const dev::TraceConsts& tc);
+void hash_n_batch(hipStream_t s, const uint8_t* in, unsigned len, uint8_t* out, size_t n, unsigned fmt_in, unsigned fmt_out,
+                  int* err, uint32_t coop_max);
+// ... and its witness trace: `rows` = imt_hash_n_trace_rows(len) rows per hash, [rows][n] or item-major [n][rows]
+void hash_n_trace(hipStream_t s, const uint8_t* in, unsigned len, size_t n, uint8_t* trace, size_t rows, bool item_major,
+                  unsigned fmt_in, unsigned fmt_out, int* err);
 void permute_batch(hipStream_t s, const uint8_t* in, uint8_t* out, size_t n, unsigned fmt_in,
                    unsigned fmt_out, int* err);
 void convert(hipStream_t s, const uint8_t* in, uint8_t* out, size_t n, unsigned fmt_in,

@@ -18,6 +18,8 @@
 //     4 x      as the first four
 //   hash2 = permutation([a, b]), permutation([])      : 5 + 600 + 3 + 600 = 1208 rows
 //   hash3 = permutation([a, b]), permutation([c])     : 5 + 600 + 4 + 600 = 1209 rows
+//   hash of len inputs (hash_sponge_trace) = floor(len / 2) x permutation([a, b]), then permutation([c]) or permutation([])
+//                                                     : 605 floor(len / 2) + 603 + (len odd) rows
 //   result = lane 1 of the last apply_mds = row (rows - 4).
 //
 // Parity status: UNPINNED BY THE REFERENCE (no trace vector exists in it, halo2-base cannot be built here).
@@ -246,6 +248,27 @@ IMT_HD void hash_trace(const PoseidonConsts& pc, const TraceConsts& tc, TraceSin
     for (int blk = 0; blk < 2; blk++) {
         const int n_in = blk == 0 ? 2 : (three ? 1 : 0);
         permute_trace<FMT>(pc, tc, o, s, n_in, blk == 0 ? a : c, b);
+    }
+}
+
+// The same for any len >= 1 (imt_device.hpp::hash_sponge has the absorb rule): floor(len / 2) permutations of two inputs
+// (605 rows each), then one of the leftover input or none (604 / 603 rows).  `load(j, x)` fetches input j of this hash
+// (canonical device form) inside the loop.  Lanes leave permute_trace below 3.12p, its entry bound is 4p.  `len` must
+// be wave-uniform.  len = 2, 3 give hash_trace's rows.
+template <unsigned FMT, class LoadInput>
+IMT_HD void hash_sponge_trace(const PoseidonConsts& pc, const TraceConsts& tc, TraceSink& o, unsigned len, LoadInput load) {
+    Fe s[3];
+    s[0] = pc.cap0;
+#pragma unroll
+    for (int i = 0; i < NL; i++) s[1].v[i] = s[2].v[i] = 0;     // PoseidonState::default: [2^64, 0, 0]
+    const unsigned full = len >> 1;
+#pragma unroll 1
+    for (unsigned ch = 0; ch <= full; ch++) {
+        const int n_in = ch < full ? 2 : (int)(len & 1u);
+        Fe in0 = pc.one, in1 = pc.one;                          // read only for n_in >= 1 / 2
+        if (n_in >= 1) load(2 * ch, in0);
+        if (n_in >= 2) load(2 * ch + 1, in1);
+        permute_trace<FMT>(pc, tc, o, s, n_in, in0, in1);
     }
 }
 

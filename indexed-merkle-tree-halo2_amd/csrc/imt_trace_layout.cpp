@@ -97,32 +97,25 @@ struct Walker {
             apply_mds(s, hp.mds);
         }
     }
-    uint32_t hash(int arity) {                       // fix_len_array_squeeze; returns the output's trace row
-        Ref in[3] = {{IMT_CELL_INPUT, 0}, {IMT_CELL_INPUT, 1}, {IMT_CELL_INPUT, 2}};
+    uint32_t hash(unsigned len) {                    // fix_len_array_squeeze; returns the output's trace row
+        Ref in[IMT_HASH_MAX_INPUTS];
+        for (uint32_t i = 0; i < IMT_HASH_MAX_INPUTS; i++) in[i] = Ref{IMT_CELL_INPUT, i};
         Ref s[3] = {{IMT_CELL_INIT, 0}, {IMT_CELL_INIT, 1}, {IMT_CELL_INIT, 2}};
-        permutation(s, in, 2);
-        permutation(s, in + 2, arity == 3 ? 1 : 0);
+        for (unsigned ch = 0; ch < len / 2; ch++) permutation(s, in + 2 * ch, 2);      // every full pair
+        permutation(s, in + (len & ~1u), (int)(len & 1u));                              // the leftover input, the padding
         return s[1].index;
     }
 };
 
-}  // namespace
-
-extern "C" size_t imt_hash_trace_rows(int arity) {
-    return arity == 2 ? (size_t)dev::TRACE_ROWS_H2 : arity == 3 ? (size_t)dev::TRACE_ROWS_H3 : 0;
-}
-
-extern "C" int imt_hash_trace_layout(imt_ctx* c, int arity, imt_trace_cell* cells, size_t cells_cap, size_t* n_cells,
-                                     void* constants, size_t const_cap, size_t* n_constants, uint32_t* out_row,
-                                     unsigned flags) {
-    if (!c) return IMT_ERR_ARG;
-    if (arity != 2 && arity != 3) return c->fail(IMT_ERR_ARG, "arity must be 2 or 3");
-    if (flags & IMT_DEVICE_PTRS) return c->fail(IMT_ERR_ARG, "imt_hash_trace_layout takes host pointers");
+// the body of both layout calls: `rows` is what the kernels of that call write per hash
+int layout(imt_ctx* c, unsigned len, size_t rows, imt_trace_cell* cells, size_t cells_cap, size_t* n_cells, void* constants,
+           size_t const_cap, size_t* n_constants, uint32_t* out_row, unsigned flags, const char* who) {
+    if (flags & IMT_DEVICE_PTRS) return c->fail(IMT_ERR_ARG, "%s takes host pointers", who);
     const unsigned fmt = flags & IMT_FMT_MASK;
     if (fmt == 3) return c->fail(IMT_ERR_ARG, "unknown field-element format");
     Walker w(c->hp);
-    const uint32_t row = w.hash(arity);
-    if (w.n_witness != imt_hash_trace_rows(arity)) return c->fail(IMT_ERR_INTERNAL, "trace layout and kernel disagree");
+    const uint32_t row = w.hash(len);
+    if (w.n_witness != rows) return c->fail(IMT_ERR_INTERNAL, "trace layout and kernel disagree");
     if (n_cells) *n_cells = w.cells.size();
     if (n_constants) *n_constants = w.consts.size();
     if (out_row) *out_row = row;
@@ -146,4 +139,33 @@ extern "C" int imt_hash_trace_layout(imt_ctx* c, int arity, imt_trace_cell* cell
         }
     }
     return IMT_OK;
+}
+
+}  // namespace
+
+extern "C" size_t imt_hash_trace_rows(int arity) {
+    return arity == 2 ? (size_t)dev::TRACE_ROWS_H2 : arity == 3 ? (size_t)dev::TRACE_ROWS_H3 : 0;
+}
+
+extern "C" int imt_hash_trace_layout(imt_ctx* c, int arity, imt_trace_cell* cells, size_t cells_cap, size_t* n_cells,
+                                     void* constants, size_t const_cap, size_t* n_constants, uint32_t* out_row,
+                                     unsigned flags) {
+    if (!c) return IMT_ERR_ARG;
+    if (arity != 2 && arity != 3) return c->fail(IMT_ERR_ARG, "arity must be 2 or 3");
+    return layout(c, (unsigned)arity, imt_hash_trace_rows(arity), cells, cells_cap, n_cells, constants, const_cap, n_constants,
+                  out_row, flags, "imt_hash_trace_layout");
+}
+
+// a permutation that absorbs k inputs assigns 3 + k + 600 new values (imt_trace_device.hpp)
+extern "C" size_t imt_hash_n_trace_rows(unsigned len) {
+    return len >= 1 && len <= IMT_HASH_MAX_INPUTS ? (size_t)605 * (len / 2) + 603 + (len & 1u) : 0;
+}
+
+extern "C" int imt_hash_n_trace_layout(imt_ctx* c, unsigned len, imt_trace_cell* cells, size_t cells_cap, size_t* n_cells,
+                                       void* constants, size_t const_cap, size_t* n_constants, uint32_t* out_row,
+                                       unsigned flags) {
+    if (!c) return IMT_ERR_ARG;
+    if (len < 1 || len > IMT_HASH_MAX_INPUTS) return c->fail(IMT_ERR_ARG, "len must be 1..%d", IMT_HASH_MAX_INPUTS);
+    return layout(c, len, imt_hash_n_trace_rows(len), cells, cells_cap, n_cells, constants, const_cap, n_constants, out_row, flags,
+                  "imt_hash_n_trace_layout");
 }

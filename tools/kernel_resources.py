@@ -8,7 +8,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "indexed-merkle-tree-halo2_amd", "csrc")
-files = [os.path.abspath(f) for f in sys.argv[1:]] or [os.path.join(CSRC, "imt_kernels.hip"), os.path.join(CSRC, "imt_prep.hip")]
+files = [os.path.abspath(f) for f in sys.argv[1:]] or [os.path.join(CSRC, "imt_kernels.hip"), os.path.join(CSRC, "imt_hash_n.hip"), os.path.join(CSRC, "imt_prep.hip")]
 print(f"{'kernel':44s} {'VGPR':>5s} {'spill':>6s} {'scratch B':>9s} {'LDS B':>6s} {'waves/SIMD':>10s}")
 for f in files:
     r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-c", f, "-o", "/dev/null",
