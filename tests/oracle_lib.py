@@ -100,11 +100,17 @@ class Oracle:
 
     def less_than_trace(self, a, b, lookup_bits=18):
         """the column of ONE is_less_than(a_q, a_r, b_q, b_r) (src/indexed_merkle_tree.rs:98-125): same dict as hash_trace"""
-        cap, wcap = 1200, 400
+        # sizes from the oracle itself: a count-only call (no buffers) and the row formula; 543 rows at lookup_bits = 1
+        nc, nw, row = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_uint32()
+        rc = self.lib.orc_less_than_trace(b32(a), b32(b), ctypes.c_uint(lookup_bits), None, None, ctypes.c_size_t(0),
+                                          ctypes.byref(nc), None, ctypes.c_size_t(0), ctypes.byref(nw), None)
+        assert rc == 0, rc
+        self.lib.orc_less_than_trace_rows.restype = ctypes.c_size_t
+        cap, wcap = nc.value, self.lib.orc_less_than_trace_rows(ctypes.c_uint(lookup_bits))
+        assert nw.value == wcap, (nw.value, wcap)
         cells = np.empty((cap, 32), np.uint8)
         desc = (TraceCell * cap)()
         wit = np.empty((wcap, 32), np.uint8)
-        nc, nw, row = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_uint32()
         rc = self.lib.orc_less_than_trace(b32(a), b32(b), ctypes.c_uint(lookup_bits), cells.ctypes.data_as(ctypes.c_void_p), desc,
                                           ctypes.c_size_t(cap), ctypes.byref(nc), wit.ctypes.data_as(ctypes.c_void_p),
                                           ctypes.c_size_t(wcap), ctypes.byref(nw), ctypes.byref(row))

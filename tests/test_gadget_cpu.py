@@ -31,7 +31,7 @@ def column_of(tr):
     return [int.from_bytes(c.tobytes(), "little") for c in tr["cells"]]
 
 
-@pytest.mark.parametrize("lookup_bits", [18, 8, 17, 28])
+@pytest.mark.parametrize("lookup_bits", [18, 8, 17, 28, 1, 2, 27])
 def test_less_than_column_gates_model_and_result(lookup_bits):
     orc = oracle_lib.load()
     rng = random.Random(1800 + lookup_bits)
@@ -143,7 +143,7 @@ def test_less_than_rejects_bad_arguments():
                                        ctypes.c_size_t(0), ctypes.byref(nc), None, ctypes.c_size_t(0), None, None) != 0
 
 
-@pytest.mark.parametrize("lookup_bits", [18, 17, 8, 4, 28])
+@pytest.mark.parametrize("lookup_bits", [18, 17, 8, 4, 28, 1, 2, 27])
 def test_lookup_rows_are_the_limbs_of_both_range_checks(imt, lookup_bits):
     """imt_less_than_lookup_rows (closed form, no GPU) = the cells oracle/gadget.c's RangeChip restatement adds to the
     lookup; on real columns those rows hold values below 2^lookup_bits that recompose both shifted differences --
@@ -166,7 +166,7 @@ def test_lookup_rows_are_the_limbs_of_both_range_checks(imt, lookup_bits):
     assert imt.lib.imt_less_than_trace_rows(lookup_bits) == 4 * L + 27
 
 
-@pytest.mark.parametrize("lookup_bits", [18, 8, 28])
+@pytest.mark.parametrize("lookup_bits", [18, 8, 28, 1, 2, 27])
 def test_product_less_than_layout_equals_oracle_and_rebuilds_a_satisfied_column(emul, imt, lookup_bits):
     """csrc/imt_gadget_layout.cpp (host code, no GPU needed) against oracle/gadget.c: same cells, kinds, gates, regions
     and indices; the column a chip would assign from the layout + its constants + the four limb inputs + the rows equals
