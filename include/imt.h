@@ -334,21 +334,32 @@ int imt_non_inclusion_column_segments(unsigned depth, unsigned lookup_bits, imt_
 /* ---- a2 / a3 / a4: dense native tree ------------------------------------------- */
 /* IndexedMerkleTree::new (src/utils.rs:20-57): level-by-level build on the device.
  * n_leaves == 0 -> IMT_ERR_NO_LEAVES; 1 -> root = leaf; odd -> IMT_ERR_ODD_LEAVES;
- * even but not a power of two -> IMT_ERR_NOT_POW2. */
+ * even but not a power of two -> IMT_ERR_NOT_POW2.  A leaf >= p -> IMT_ERR_NONCANONICAL and *out = NULL.
+ * The call is synchronous with IMT_DEVICE_PTRS as well (the flag only says where `leaves` lies), so every
+ * error is reported here and not by imt_ctx_sync().  The nodes are stored in the library's own format
+ * whatever the flags' format: a tree built from one format reads back the same in any other. */
 int imt_tree_new(imt_ctx *ctx, const void *leaves /*[n][32]*/, size_t n_leaves, unsigned flags,
                  imt_tree **out);
 void imt_tree_free(imt_tree *t);
 size_t imt_tree_num_levels(const imt_tree *t);           /* tree.len() */
 int imt_tree_get_root(imt_tree *t, void *root /*[32]*/, unsigned flags);          /* utils.rs:59-61 */
 /* get_proof (src/utils.rs:63-85): siblings and helpers (helper = 1 iff the node is a left
- * child, :79) for one index; helper elements are written as field elements like the reference. */
+ * child, :79) for one index; helper elements are written as field elements like the reference
+ * (1 and 0 in the flags' format).  Host pointers only: IMT_DEVICE_PTRS -> IMT_ERR_ARG.
+ * index >= n_leaves -> IMT_ERR_RANGE, nothing written. */
 int imt_tree_get_proof(imt_tree *t, size_t index, void *proof /*[levels-1][32]*/,
                        void *helper /*[levels-1][32] or NULL*/, unsigned flags);
+/* The siblings of n indices (repeats allowed; n == 0 or a one-leaf tree: nothing written).  With host pointers
+ * an index >= n_leaves anywhere in the batch -> IMT_ERR_RANGE before anything is enqueued or written.  With
+ * IMT_DEVICE_PTRS the host cannot see the indices: such an item gets, at every level, the hash of the empty
+ * subtree of that height (imt_zero_hashes) as its sibling, no error is reported and nothing outside the tree
+ * is read -- range-check device-resident indices before relying on the proofs. */
 int imt_tree_get_proof_batch(imt_tree *t, const uint64_t *index /*[n]*/, size_t n,
                              void *proof /*sib layout per flags*/, unsigned flags);
 /* copy one level out (tree[level]); n_out receives its length */
 int imt_tree_get_level(imt_tree *t, size_t level, void *out, size_t *n_out, unsigned flags);
-/* one-shot: build and return root (+ all levels concatenated bottom-up if levels != NULL) */
+/* one-shot: build and return root (+ all levels concatenated bottom-up if levels != NULL); root may be NULL
+ * too.  Synchronous in both pointer modes, like imt_tree_new. */
 int imt_tree_build(imt_ctx *ctx, const void *leaves, size_t n_leaves, void *levels /*[2n-1][32] or NULL*/,
                    void *root /*[32]*/, unsigned flags);
 

@@ -15,13 +15,13 @@ import numpy as np
 import pytest
 
 import witness_corpus as wc
+from mirror_corpus import R_OF, from_fmt, to_fmt     # the three boundary formats, shared with test_gpu_mirror_edges.py
 from oracle_lib import P, arr_ints, ints_to_arr
 
 pytestmark = pytest.mark.gpu
 
 SIZES = (1, 63, 64, 65, 257, 1024, 1025, 4096, 4097)
 FORMS = ("default", "thread", "quad")
-R_OF = {0: 1, 1: pow(2, 256, P), 2: pow(2, 261, P)}          # canonical, MONT256 (halo2curves), DEVICE (the library's)
 
 
 @pytest.fixture(scope="module")
@@ -34,19 +34,6 @@ def forms(imt, ctx):
     yield dict(default=ctx, thread=thread, quad=quad)
     thread.close()
     quad.close()
-
-
-def to_fmt(a, fmt):
-    if fmt == 0:
-        return a
-    return ints_to_arr([x * R_OF[fmt] % P for x in arr_ints(a)]).reshape(a.shape)
-
-
-def from_fmt(a, fmt):
-    if fmt == 0:
-        return a
-    inv = pow(R_OF[fmt], -1, P)
-    return ints_to_arr([x * inv % P for x in arr_ints(a)]).reshape(a.shape)
 
 
 def _fe(xs, shape):
