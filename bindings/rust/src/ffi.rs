@@ -38,6 +38,23 @@ pub struct imt_insert_out {
     pub new_sib: *mut c_void,
 }
 
+/// `imt_bulk_out`: outputs of `imt_itree_insert_bulk`; every pointer may be null.  Rows k are in processing order
+/// (descending values), `new_leaf` in the caller's order.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct imt_bulk_out {
+    pub order: *mut u64,
+    pub low_index: *mut u64,
+    pub low_leaf: *mut c_void,
+    pub is_largest: *mut u8,
+    pub root_before: *mut c_void,
+    pub root_after: *mut c_void,
+    pub low_sib: *mut c_void,
+    pub new_leaf: *mut c_void,
+    pub append_sib: *mut c_void,
+    pub root: *mut c_void,
+}
+
 /// `imt_read_out`: rows of the READs of `imt_itree_mixed_batch`; every pointer may be null.
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -265,6 +282,7 @@ extern "C" {
 
     // ---- a5 / a7 / a8 / a9: batched path recompute
     pub fn imt_path_root_batch(ctx: *mut imt_ctx, leaf: *const c_void, index: *const u64, sib: *const c_void, depth: c_uint, n: usize, root_out: *mut c_void, flags: c_uint) -> c_int;
+    pub fn imt_frontier_append_root(ctx: *mut imt_ctx, sib: *const c_void, start: u64, leaf_hash: *const c_void, leaf3: *const c_void, n: usize, depth: c_uint, root_before: *mut c_void, root_after: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_compute_merkle_root_batch(ctx: *mut imt_ctx, leaf: *const c_void, helper_mask: *const u64, sib: *const c_void, depth: c_uint, n: usize, root_out: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_verify_proof_batch(ctx: *mut imt_ctx, leaf: *const c_void, index: *const u64, root: *const c_void, sib: *const c_void, depth: c_uint, n: usize, ok_out: *mut u8, flags: c_uint) -> c_int;
 
@@ -293,6 +311,7 @@ extern "C" {
     pub fn imt_itree_apply_pipelined(t: *mut imt_itree, vals: *const c_void, n: usize, root_out: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_apply_filtered(t: *mut imt_itree, vals: *const c_void, n: usize, status: *mut u8, leaf_index: *mut u64, n_inserted: *mut u64, root_out: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_apply_stats(t: *mut imt_itree, hashes: *mut u64) -> c_int;
+    pub fn imt_itree_insert_bulk(t: *mut imt_itree, vals: *const c_void, n: usize, out: *const imt_bulk_out, flags: c_uint) -> c_int;
     pub fn imt_itree_rewind(t: *mut imt_itree, new_size: u64, root_out: *mut c_void, hashes: *mut u64, flags: c_uint) -> c_int;
     pub fn imt_itree_capacity(t: *const imt_itree) -> u64;
     pub fn imt_itree_reserve(t: *mut imt_itree, new_capacity: u64, flags: c_uint) -> c_int;

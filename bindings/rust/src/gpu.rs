@@ -124,6 +124,30 @@ pub fn verify_proofs<F: ScalarField>(leaves: &[F], index: &[u64], root: &F, proo
     ok.into_iter().map(|b| b != 0).collect()
 }
 
+/// One row of a bulk insertion (`IndexedTree::insert_bulk`): the rewrite of a stored low leaf for the value at the
+/// caller's `position`.  `low_leaf` is the preimage before the rewrite, proven by `low_leaf_proof` against `root_before`;
+/// afterwards the leaf holds `{low_leaf[0], value, first_new_index + position}` under `root_after`.
+#[derive(Clone, Debug)]
+pub struct BulkRow<F> {
+    pub position: usize,
+    pub low_index: u64,
+    pub low_leaf: [F; 3],
+    pub low_leaf_proof: Vec<F>,
+    pub is_largest: bool,
+    pub root_before: F,
+    pub root_after: F,
+}
+/// The witness of a bulk insertion: the rows in descending value order, then the append of `new_leaves` (caller's order,
+/// final preimages) at `first_new_index` against `append_proof`, the frontier of that slot under the last `root_after`.
+#[derive(Clone, Debug)]
+pub struct BulkWitness<F> {
+    pub rows: Vec<BulkRow<F>>,
+    pub first_new_index: u64,
+    pub new_leaves: Vec<[F; 3]>,
+    pub append_proof: Vec<F>,
+    pub root: F,
+}
+
 /// Everything `insert_leaf` takes for one insertion (`src/indexed_merkle_tree.rs:231-245`), as field values.
 #[derive(Clone, Debug)]
 pub struct InsertWitness<F> {
@@ -236,6 +260,53 @@ impl IndexedTree {
     pub fn reserve(&mut self, new_capacity: u64) -> Result<(), ImtError> {
         let g = context().lock().unwrap();
         check(&g, unsafe { imt_itree_reserve(self.handle, new_capacity, 0) })
+    }
+    /// The tree `insert_batch(vals)` leaves, with the bulk witness rollup circuits use (`imt_itree_insert_bulk`): the
+    /// values in descending order, one rewrite of a stored low leaf each (one path per insertion), then all new leaves
+    /// appended at once against the frontier of the first free slot.  Half the hashes and half the sibling bytes of
+    /// `insert_batch`; not the reference's witness form (INTEGRATION.md says what a circuit over it must constrain).
+    pub fn insert_bulk<F: ScalarField>(&mut self, vals: &[F]) -> Result<BulkWitness<F>, ImtError> {
+        let g = context().lock().unwrap();
+        let (n, d) = (vals.len(), self.depth);
+        let first = self.size();
+        let v = to_bytes(vals);
+        let (mut order, mut low_index, mut is_largest) = (vec![0u64; n], vec![0u64; n], vec![0u8; n]);
+        let (mut low_leaf, mut new_leaf) = (vec![0u8; n * 96], vec![0u8; n * 96]);
+        let (mut root_before, mut root_after) = (vec![0u8; n * 32], vec![0u8; n * 32]);
+        let (mut low_sib, mut append_sib, mut root) = (vec![0u8; n * d * 32], vec![0u8; d * 32], [0u8; 32]);
+        let out = imt_bulk_out {
+            order: order.as_mut_ptr(),
+            low_index: low_index.as_mut_ptr(),
+            low_leaf: low_leaf.as_mut_ptr() as *mut c_void,
+            is_largest: is_largest.as_mut_ptr(),
+            root_before: root_before.as_mut_ptr() as *mut c_void,
+            root_after: root_after.as_mut_ptr() as *mut c_void,
+            low_sib: low_sib.as_mut_ptr() as *mut c_void,
+            new_leaf: new_leaf.as_mut_ptr() as *mut c_void,
+            append_sib: append_sib.as_mut_ptr() as *mut c_void,
+            root: root.as_mut_ptr() as *mut c_void,
+        };
+        check(&g, unsafe {
+            imt_itree_insert_bulk(self.handle, v.as_ptr() as *const c_void, n, &out, IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR)
+        })?;
+        let three = |b: &[u8]| -> [F; 3] { [F::from_bytes_le(&b[0..32]), F::from_bytes_le(&b[32..64]), F::from_bytes_le(&b[64..96])] };
+        Ok(BulkWitness {
+            rows: (0..n)
+                .map(|k| BulkRow {
+                    position: order[k] as usize,
+                    low_index: low_index[k],
+                    low_leaf: three(&low_leaf[k * 96..][..96]),
+                    low_leaf_proof: from_bytes(&low_sib[k * d * 32..][..d * 32]),
+                    is_largest: is_largest[k] != 0,
+                    root_before: F::from_bytes_le(&root_before[k * 32..][..32]),
+                    root_after: F::from_bytes_le(&root_after[k * 32..][..32]),
+                })
+                .collect(),
+            first_new_index: first,
+            new_leaves: (0..n).map(|i| three(&new_leaf[i * 96..][..96])).collect(),
+            append_proof: from_bytes(&append_sib),
+            root: F::from_bytes_le(&root),
+        })
     }
     /// n sequential insertions; one [`InsertWitness`] each (66 hashes per insertion at depth 32, all on the GPU)
     pub fn insert_batch<F: ScalarField>(&mut self, vals: &[F]) -> Result<Vec<InsertWitness<F>>, ImtError> {
@@ -631,4 +702,21 @@ pub fn non_inclusion_gadget_traces<F: ScalarField>(w: &[NonInclusionWitness<F>],
                                              trace.as_mut_ptr() as *mut c_void, IMT_FMT_CANONICAL | IMT_TRACE_ITEM_MAJOR)
     })?;
     Ok((0..n).map(|i| from_bytes(&trace[i * rows * 32..][..rows * 32])).collect())
+}
+
+
+/// `(root_before, root_after)` of a depth-`proof.len()` tree around the append of `leaves` (preimages) at `start`, from the
+/// frontier `proof` of that slot (`imt_frontier_append_root`): right-hand rows of `proof` are not read, Z[l] is used.
+pub fn frontier_append_root<F: ScalarField>(proof: &[F], start: u64, leaves: &[[F; 3]]) -> Result<(F, F), ImtError> {
+    let g = context().lock().unwrap();
+    let sib = to_bytes(proof);
+    let flat: Vec<F> = leaves.iter().flat_map(|l| l.iter().cloned()).collect();
+    let l3 = to_bytes(&flat);
+    let (mut before, mut after) = ([0u8; 32], [0u8; 32]);
+    check(&g, unsafe {
+        imt_frontier_append_root(g.ctx, sib.as_ptr() as *const c_void, start, std::ptr::null(), l3.as_ptr() as *const c_void,
+                                 leaves.len(), proof.len() as u32, before.as_mut_ptr() as *mut c_void,
+                                 after.as_mut_ptr() as *mut c_void, IMT_FMT_CANONICAL)
+    })?;
+    Ok((F::from_bytes_le(&before), F::from_bytes_le(&after)))
 }

@@ -385,6 +385,18 @@ int imt_compute_merkle_root_batch(imt_ctx *ctx, const void *leaf, const uint64_t
 int imt_verify_proof_batch(imt_ctx *ctx, const void *leaf, const uint64_t *index, const void *root,
                            const void *sib, unsigned depth, size_t n, uint8_t *ok_out /*[n]*/,
                            unsigned flags);
+/* Root of a depth-`depth` tree before and after n leaves are written at slots start .. start+n-1, given the proof of
+ * slot `start` while it and everything right of it is empty.  Right-hand siblings (bit l of start == 0) are NOT read:
+ * Z[l] is used, so a forged one cannot pass.  leaf_hash [n][32], or leaf3 [n][3][32] hashed first (exactly one non-NULL).
+ * root_before = path of Z[0] at `start`.  start + n > 2^depth -> IMT_ERR_RANGE.
+ * This is what a circuit computes for an append: every node of the range (start >> l) .. ((start+n-1) >> l) hashed once,
+ * level by level, until one node is left, then that node's path -- n + depth hashes or so instead of n * depth.  It
+ * checks the append of imt_itree_insert_bulk (sib = append_sib, start = the size before, leaf3 = new_leaf) and serves any
+ * append-only tree, a note-commitment tree for one.  n == 0: IMT_OK, nothing written.  sib / the leaves / the roots are
+ * host or device memory per IMT_DEVICE_PTRS, in the flags' format. */
+int imt_frontier_append_root(imt_ctx *ctx, const void *sib /*[depth][32]*/, uint64_t start, const void *leaf_hash,
+                             const void *leaf3, size_t n, unsigned depth, void *root_before /*[32] or NULL*/,
+                             void *root_after /*[32]*/, unsigned flags);
 
 /* ---- a11 / a12 / a13: batched non-membership ----------------------------------- */
 /* verify_non_inclusion (indexed_merkle_tree.rs:127-229) on n items: fail_out[i] is a mask of
@@ -582,6 +594,41 @@ int imt_itree_apply_filtered(imt_itree *t, const void *vals /*[n][32]*/, size_t 
  * hashes[0] = leaf hashes, hashes[l] = hash2 calls that produced level-l nodes, l = 1 .. depth -- the number of distinct
  * nodes the batch touched at every level.  Host memory; waits for that call.  IMT_ERR_ARG if there has been none. */
 int imt_itree_apply_stats(imt_itree *t, uint64_t *hashes /*[depth + 1]*/);
+/* BULK INSERTION: THE BATCH WITNESS ROLLUP CIRCUITS USE, one path per insertion plus one shared append.  The tree, the
+ * value log and the index after this call are byte for byte those after imt_itree_insert_batch(t, vals, n, ...): value
+ * v[i] becomes leaf M + i (M = imt_itree_size before the call), and no later call can tell the two apart.  The witness
+ * is another one.  The values are taken in DESCENDING canonical-integer order, row k = the k-th largest, at the caller's
+ * position order[k].  In that order the low leaf of every value is a leaf stored before the call (index < M), never one
+ * of the batch, so row k rewrites one stored leaf -- low_leaf[k] is its preimage as of step k, which already points at
+ * v[order[k-1]] when that larger value shares the low leaf; low_sib[k] proves it against root_before[k]; root_after[k]
+ * is the root once it holds {low.val, v[order[k]], M + order[k]}; root_before[0] is the root before the call and
+ * root_before[k+1] == root_after[k].  Between the rows the tree is deliberately no closed list: a low leaf points at a
+ * slot that is still empty.  Then all new leaves are appended at once: new_leaf[i] (caller's order) is the FINAL preimage
+ * of leaf M + i, what imt_itree_get_leaves returns afterwards; append_sib is the proof of the empty slot M against
+ * root_after[n-1], with Z[l] (imt_zero_hashes) at every level where bit l of M is 0; root is the root after the call.
+ * imt_frontier_append_root recomputes the append.  The sweep hashes n * (1 + depth) times and the append once per distinct
+ * node of the range M .. M+n-1 at every level (imt_itree_apply_stats reports the latter), against n * (2 + 2 * depth).
+ * This form is not in the reference: what pins it is the reference's verify_non_inclusion relation for every row and the
+ * final tree being the reference's.  The witness-free twin is imt_itree_apply_batch.
+ * Formats, IMT_DEVICE_PTRS, IMT_SIB_ITEM_MAJOR, alignment and refusals are those of imt_itree_insert_batch: 0, a value
+ * >= p (IMT_ERR_NONCANONICAL), a stored value or a repeat -> IMT_ERR_VALUE with the tree and every output untouched;
+ * IMT_ERR_FULL; n == 0 is a no-op.  IMT_PIPELINE, IMT_HOST_PREP, IMT_INPUTS_READY, a placed tree and a partitioned tree
+ * -> IMT_ERR_ARG, as for imt_itree_mixed_batch.  The call runs on the context's stream behind every pipelined batch
+ * still in flight, and afterwards it is a batch like any other (lagged roots, views, rewind into its middle). */
+typedef struct imt_bulk_out {          /* every pointer may be NULL; host or device per flags */
+    uint64_t *order;        /* [n]        caller's position of the k-th row's value (descending values) */
+    uint64_t *low_index;    /* [n]        */
+    void *low_leaf;         /* [n][3][32] preimage before row k's rewrite */
+    uint8_t *is_largest;    /* [n]        */
+    void *root_before;      /* [n][32]    */
+    void *root_after;       /* [n][32]    */
+    void *low_sib;          /* [depth][n][32], layout per flags as for imt_insert_out */
+    void *new_leaf;         /* [n][3][32] caller's order: leaf M + i */
+    void *append_sib;       /* [depth][32] */
+    void *root;             /* [32]       */
+} imt_bulk_out;
+int imt_itree_insert_bulk(imt_itree *t, const void *vals /*[n][32]*/, size_t n,
+                          const imt_bulk_out *out /*may be NULL*/, unsigned flags);
 /* GOING BACK, for the same callers when the last blocks are dropped (a reorg, a failed proof, a batch the L1 did not
  * accept).  The tree as it was when it held new_size leaves (sentinel included; 1 = the empty tree): byte for byte --
  * index, leaf preimages, every stored node, root -- the tree a fresh imt_itree would be after inserting the first

@@ -295,6 +295,17 @@ inline unsigned verify_non_inclusion(Context& c, const Fr& root, const IndexedMe
     return fail;
 }
 
+// {root before, root after} of a tree of depth proof.size() around `leaves` written at slots start .. start + n - 1, from
+// the proof of slot `start` while it and everything right of it is empty (imt_frontier_append_root): the append of
+// IndexedTree::insert_bulk, or of any append-only tree.  Right-hand rows of `proof` are not read: Z[l] is used.
+inline std::pair<Fr, Fr> frontier_append_root(Context& c, const std::vector<Fr>& proof, uint64_t start,
+                                              const std::vector<IndexedMerkleTreeLeaf>& leaves) {
+    Fr before, after;
+    c.check(imt_frontier_append_root(c.get(), proof.data(), start, nullptr, leaves.data(), leaves.size(), (unsigned)proof.size(),
+                                     &before, &after, IMT_FMT_CANONICAL));
+    return {before, after};
+}
+
 // insert_leaf (src/indexed_merkle_tree.rs:231-314) on its witness values; as in the reference, new_leaf_index (hashed
 // into the rewritten low leaf, :265-269) is not tied to new_leaf_proof_helper (which positions the new slot's path).
 inline unsigned insert_leaf(Context& c, const Fr& old_root, const IndexedMerkleTreeLeaf& low_leaf,
@@ -379,6 +390,43 @@ public:
             r.new_leaf_proof[i].assign(ns.begin() + i * d, ns.begin() + (i + 1) * d);
             r.new_index[i] = first + i;
         }
+        return r;
+    }
+    // The witness of a bulk insertion (imt_itree_insert_bulk): rows in descending value order -- row k rewrites the stored
+    // low leaf low_index[k] for the value at the caller's position order[k] --, then new_leaf (caller's order, final
+    // preimages) appended at first_new_index against append_proof, the frontier of that slot under root_after.back().
+    struct BulkInsertion {
+        std::vector<uint64_t> order, low_index;
+        std::vector<IndexedMerkleTreeLeaf> low_leaf, new_leaf;
+        std::vector<uint8_t> is_largest;
+        std::vector<Fr> root_before, root_after;
+        std::vector<std::vector<Fr>> low_leaf_proof;
+        uint64_t first_new_index = 0;
+        std::vector<Fr> append_proof;
+        Fr root;
+    };
+    // The tree insert_batch(vals) leaves, with one path per insertion and one shared append instead of two paths each;
+    // not the reference's witness form.  The same errors, the tree unchanged.
+    BulkInsertion insert_bulk(const std::vector<Fr>& vals) {
+        const size_t n = vals.size(), d = depth_;
+        BulkInsertion r;
+        r.first_new_index = size();
+        r.root = root();
+        if (!n) return r;
+        r.order.resize(n);
+        r.low_index.resize(n);
+        r.low_leaf.resize(n);
+        r.new_leaf.resize(n);
+        r.is_largest.resize(n);
+        r.root_before.resize(n);
+        r.root_after.resize(n);
+        r.append_proof.resize(d);
+        std::vector<Fr> ls(n * d);
+        imt_bulk_out out{r.order.data(), r.low_index.data(), r.low_leaf.data(), r.is_largest.data(), r.root_before.data(),
+                         r.root_after.data(), ls.data(), r.new_leaf.data(), r.append_proof.data(), &r.root};
+        c_->check(imt_itree_insert_bulk(t_, vals.data(), n, &out, IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR));
+        r.low_leaf_proof.resize(n);
+        for (size_t k = 0; k < n; k++) r.low_leaf_proof[k].assign(ls.begin() + k * d, ls.begin() + (k + 1) * d);
         return r;
     }
     // insert_batch without the witnesses (imt_itree_apply_batch): the same tree afterwards, every touched node hashed

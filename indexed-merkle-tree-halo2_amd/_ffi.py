@@ -78,6 +78,11 @@ class InsertOut(ctypes.Structure):
                                         "new_root", "new_leaf", "low_sib", "new_sib")]
 
 
+class BulkOut(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("order", "low_index", "low_leaf", "is_largest", "root_before", "root_after",
+                                        "low_sib", "new_leaf", "append_sib", "root")]
+
+
 class ReadOut(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("low_index", "low_leaf", "is_largest", "root", "low_sib")]
 
@@ -153,6 +158,9 @@ SIGNATURES = {
     "imt_itree_root": (c_int, [c_void_p, c_void_p, c_uint]),
     "imt_itree_root_lagged": (c_int, [c_void_p, c_uint, c_void_p, c_uint]),
     "imt_itree_insert_batch": (c_int, [c_void_p, c_void_p, c_size_t, P(InsertOut), c_uint]),
+    "imt_itree_insert_bulk": (c_int, [c_void_p, c_void_p, c_size_t, P(BulkOut), c_uint]),
+    "imt_frontier_append_root": (c_int, [c_void_p, c_void_p, c_u64, c_void_p, c_void_p, c_size_t, c_uint, c_void_p, c_void_p,
+                                         c_uint]),
     "imt_itree_get_proof_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
     "imt_itree_get_leaves": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint]),
     "imt_itree_non_membership_witness": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -299,6 +299,18 @@ class Context:
         self._check(lib.imt_path_root_batch(self.h, _p(leaf), _p(idx), _p(sib), depth, n, _p(out), flags))
         return out
 
+    def frontier_append_root(self, sib, start, depth, leaf_hash=None, leaf3=None, fmt=0):
+        """(root_before, root_after) of a depth-`depth` tree around n leaves written at start .. start+n-1, from the proof
+        `sib` [depth, 32] of slot `start` while it and everything right of it is empty (imt_frontier_append_root).  Exactly
+        one of leaf_hash [n, 32] / leaf3 [n, 3, 32]."""
+        sib = _arr(sib, (32,)) if depth else np.zeros((0, 32), np.uint8)
+        lh = None if leaf_hash is None else _arr(leaf_hash, (32,))
+        l3 = None if leaf3 is None else _arr(leaf3, (3, 32))
+        n = max(a.shape[0] for a in (lh, l3) if a is not None) if (lh is not None or l3 is not None) else 0
+        before, after = np.empty(32, np.uint8), np.empty(32, np.uint8)
+        self._check(lib.imt_frontier_append_root(self.h, _p(sib), int(start), _p(lh), _p(l3), n, depth, _p(before), _p(after), fmt))
+        return before, after
+
     def compute_merkle_root(self, leaf, helper_mask, sib, depth, item_major=False, fmt=0):
         leaf = _arr(leaf, (32,))
         n = leaf.shape[0]
@@ -641,6 +653,25 @@ class IndexedTree:
             raise ValueError(lib.imt_last_error(self.ctx.h).decode())
         self.ctx._check(rc)
         res["new_index"] = np.arange(self.size - n, self.size, dtype=np.uint64) + np.uint64(self.index_base)
+        return res
+
+    def insert_bulk(self, vals, proofs=True, item_major=False):
+        """The same tree as insert_batch(vals) leaves, with the bulk witness (imt_itree_insert_bulk): rows in descending
+        value order -- order, low_index, low_leaf, is_largest, root_before, root_after, low_sib: one rewrite of a stored
+        low leaf each -- then new_leaf (caller's order), append_sib (the proof of the first free slot) and root."""
+        v = to_bytes(vals) if not isinstance(vals, np.ndarray) else _arr(vals, (32,))
+        n, d = v.shape[0], self.depth
+        res = dict(order=np.empty(n, np.uint64), low_index=np.empty(n, np.uint64), low_leaf=np.empty((n, 3, 32), np.uint8),
+                   is_largest=np.empty(n, np.uint8), root_before=np.empty((n, 32), np.uint8),
+                   root_after=np.empty((n, 32), np.uint8), new_leaf=np.empty((n, 3, 32), np.uint8),
+                   append_sib=np.empty((d, 32), np.uint8), root=np.empty(32, np.uint8))
+        if proofs:
+            res["low_sib"] = np.empty((n, d, 32) if item_major else (d, n, 32), np.uint8)
+        out = _ffi.BulkOut(**{k: a.ctypes.data for k, a in res.items()})
+        rc = lib.imt_itree_insert_bulk(self.h, _p(v), n, ctypes.byref(out), _ffi.SIB_ITEM_MAJOR if item_major else 0)
+        if rc == _ffi.ERR["VALUE"]:
+            raise ValueError(lib.imt_last_error(self.ctx.h).decode())
+        self.ctx._check(rc)
         return res
 
     def insert_filtered(self, vals, proofs=True, item_major=False, host_prep=False):

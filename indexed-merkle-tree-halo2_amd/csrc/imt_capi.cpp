@@ -867,6 +867,57 @@ extern "C" int imt_verify_proof_batch(imt_ctx* c, const void* leaf, const uint64
     return path_common(c, leaf, index, false, root, sib, depth, n, nullptr, ok_out, flags);
 }
 
+// The append of n leaves at `start` from the frontier (imt.h): the leaves into row 0 of the level builder, the boundary
+// slots (k_frontier_bounds), every node of the range once -- pairs of a row are siblings, so a level is one tree_level
+// launch, imt_itree_load_values' builder -- until one node is left, then that node's path; root_before is the path of Z[0].
+// Both paths read the frontier with Z[l] forced at every right-hand level, never the caller's rows there.
+extern "C" int imt_frontier_append_root(imt_ctx* c, const void* sib, uint64_t start, const void* leaf_hash, const void* leaf3,
+                                        size_t n, unsigned depth, void* root_before, void* root_after, unsigned flags) {
+    int rc = begin(c, flags);
+    if (rc) return rc;
+    if (depth > IMT_MAX_DEPTH) return c->fail(IMT_ERR_RANGE, "depth %u > %d", depth, IMT_MAX_DEPTH);
+    if ((leaf_hash == nullptr) == (leaf3 == nullptr)) return c->fail(IMT_ERR_ARG, "exactly one of leaf_hash / leaf3 must be given");
+    const uint64_t room = depth >= 64 ? ~(uint64_t)0 : (uint64_t)1 << depth;
+    if (start > room || n > room - start) return c->fail(IMT_ERR_RANGE, "start + n exceeds 2^depth");
+    if (n == 0) return IMT_OK;
+    if ((depth && !sib) || !root_after) return c->fail(IMT_ERR_ARG, "null buffer");
+    Io io(c, flags);
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    launch::FrontierArgs a{};
+    a.sib = io.in_fe(sib, (size_t)depth * 32);
+    const uint8_t* d_leaf = leaf3 ? io.in_fe(leaf3, n * 96) : io.in_fe(leaf_hash, n * 32);
+    uint8_t* d_before = io.out_fe(root_before, 32);
+    uint8_t* d_after = io.out_fe(root_after, 32);
+    a.fmt_in = fmt;
+    a.err = c->d_err;
+    a.start = start;
+    a.n = n;
+    a.depth = depth;
+    a.zero = c->d_zero;
+    const uint64_t nodes = launch::frontier_rows(a);
+    a.rows = io.temp(nodes * 32);
+    a.fsib = io.temp((size_t)depth * 32 + 32);
+    a.idx = (uint64_t*)io.temp(16);
+    if (io.rc) return io.rc;
+    hipStream_t s = c->stream;
+    const uint32_t coop = c->coop_max_events;
+    auto row = [&](unsigned l) { return a.rows + (a.off[l] + ((start >> l) & 1)) * 32; };     // the first node of the range at level l
+    if (leaf3) launch::hash_batch(s, d_leaf, row(0), n, 3, fmt, IMT_FMT_DEVICE, c->d_err, coop);
+    else launch::convert(s, d_leaf, row(0), n, fmt, IMT_FMT_DEVICE, c->d_err);
+    launch::frontier_bounds(s, a);
+    for (unsigned l = 0; l < a.top; l++) {
+        const uint64_t parents = ((start + n - 1) >> (l + 1)) - (start >> (l + 1)) + 1;
+        launch::tree_level(s, a.rows + a.off[l] * 32, row(l + 1), parents, coop);
+    }
+    const launch::SibLayout one{1, 1};
+    if (d_before)
+        launch::path_root(s, c->d_zero, nullptr, a.idx, false, a.fsib, one, depth, 1, d_before, nullptr, 0, nullptr, IMT_FMT_DEVICE,
+                          fmt, c->d_err, coop);
+    launch::path_root(s, row(a.top), nullptr, a.idx + 1, false, a.fsib + (size_t)a.top * 32, one, depth - a.top, 1, d_after, nullptr, 0,
+                      nullptr, IMT_FMT_DEVICE, fmt, c->d_err, coop);
+    return io.finish();
+}
+
 // ------------------------------------------------------------------------------------
 // a13
 // ------------------------------------------------------------------------------------

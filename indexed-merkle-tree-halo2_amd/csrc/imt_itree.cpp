@@ -1574,6 +1574,8 @@ struct WitnessSweep {
     const launch::MixedRoute* route = nullptr;    // NULL: event e fills the rows of insertion e / 2; else erow says whose
     size_t n_ins = 0;                             // with a route: the INSERTs among the operations,
     uint8_t* read_root = nullptr;                 // and the READs' roots (NULL: not wanted)
+    bool bulk = false;                            // every event is a row's ROW_LOW (imt_itree_insert_bulk): d.old_root / d.interim_root
+                                                  // are its root_before / root_after, chained by the roots kernel
     const view::Side* side = nullptr;             // NULL: base siblings below L0 are read from the stored tree as it is
     bool store = true;                            // levels written back, the nodes from L0 up and the root stored
     const uint8_t* view_root = nullptr;           // NULL: old_root[0] is the stored root; else the root in a view's chain
@@ -1641,7 +1643,9 @@ void finish_roots(imt_itree* t, const PlanSet& P, hipStream_t s, size_t E, unsig
                   const WitnessSweep& w = {}) {
     const uint8_t* top = P.d_val[t->depth & 1];
     uint8_t* node_store = w.store && L0 == t->depth ? t->nodes(t->depth) : nullptr;
-    if (w.route)
+    if (w.bulk)
+        launch::emit_roots_bulk(s, top, (uint32_t)E, (uint8_t*)d.old_root, (uint8_t*)d.interim_root, fmt, node_store);
+    else if (w.route)
         launch::emit_roots_mixed(s, *w.route, top, (uint32_t)E, (uint32_t)w.n_ins, (uint8_t*)d.old_root, (uint8_t*)d.interim_root,
                                  (uint8_t*)d.new_root, w.read_root, fmt, node_store);
     else
@@ -2478,6 +2482,164 @@ extern "C" int imt_itree_apply_mixed_pipelined(imt_itree* t, const void* vals, c
                                                uint64_t* n_inserted, uint64_t* bad_op, unsigned flags) {
     const ApplyReq req{root_out};
     return mixed_call(t, vals, op, n, nullptr, nullptr, n_inserted, bad_op, flags, &req, true);
+}
+
+// ------------------------------------------------------------------------------------
+// bulk insertion: the batch in descending value order -- one rewrite of a stored low leaf per value, swept
+// with witnesses as a mixed batch of ROW_LOW events -- then the frontier of the first free slot and all new leaves at once
+// through the witness-free schedule.  The entry is the stages above plus the three below.
+// ------------------------------------------------------------------------------------
+static const MixedNoun BULK_BATCH{"bulk batches take", "bulk batches"};
+// The device pointers of a bulk call's outputs (the caller's, or staging for a host-pointer caller)
+struct BulkDev {
+    prep::BulkOut hashfree = {};
+    imt_insert_out sweep = {};       // low_sib; old_root = root_before, interim_root = root_after
+    uint8_t *append_sib = nullptr, *root = nullptr;
+};
+static bool bulk_stage_outputs(imt_ctx* c, bool dev, size_t& slot, const imt_bulk_out* o, size_t n, unsigned depth, BulkDev& d) {
+    uint8_t *low_leaf = nullptr, *new_leaf = nullptr;
+    const bool ok = stage_out(c, dev, slot, o->order, n * 8, d.hashfree.order) &&
+                    stage_out(c, dev, slot, o->low_index, n * 8, d.hashfree.low_index) &&
+                    stage_out(c, dev, slot, o->is_largest, n, d.hashfree.is_largest) &&
+                    stage_out(c, dev, slot, (uint8_t*)o->low_leaf, n * 96, low_leaf) &&
+                    stage_out(c, dev, slot, (uint8_t*)o->new_leaf, n * 96, new_leaf) &&
+                    stage_out(c, dev, slot, o->root_before, n * 32, d.sweep.old_root) &&
+                    stage_out(c, dev, slot, o->root_after, n * 32, d.sweep.interim_root) &&
+                    stage_out(c, dev, slot, o->low_sib, (size_t)depth * n * 32, d.sweep.low_sib) &&
+                    stage_out(c, dev, slot, (uint8_t*)o->append_sib, (size_t)depth * 32, d.append_sib) &&
+                    stage_out(c, dev, slot, (uint8_t*)o->root, 32, d.root);
+    d.hashfree.low_leaf = low_leaf;
+    d.hashfree.new_leaf = new_leaf;
+    return ok;
+}
+// The check stage on the side stream, the error word clear and the values staged: the values into rows [M, M + n) of the
+// value array, the batch sorted, its gaps and every check -- one host wait, after which the batch is refused with nothing
+// of the tree or the caller's changed, or accepted.
+static int bulk_checks(imt_itree* t, PlanSet& P, const uint8_t* d_vals, size_t n, double& wait_ms) {
+    imt_ctx* c = t->ctx;
+    hipStream_t ps = t->up_stream;
+    P.ws.part_mod = t->part_mod;
+    P.ws.part_res = t->part_res;
+    IMT_HIP(c, prep::bulk_check(ps, P.ws, d_vals, t->d_val, t->d_sorted[t->sorted_cur], (uint32_t)t->size, (uint32_t)n));
+    IMT_HIP(c, hipMemcpyAsync(t->h_err_pin, P.ws.err, sizeof(int), hipMemcpyDeviceToHost, ps));
+    const HostTimer w;
+    IMT_HIP(c, hipStreamSynchronize(ps));
+    wait_ms += w.ms();
+    return insertion_verdict(t, *t->h_err_pin, "batch");
+}
+// Behind the sweep's last write-back on stream s the stored tree holds every rewritten low leaf and nothing of the batch's
+// own leaves: the proof of the first free slot M, Z[l] wherever the sibling lies to the right.
+static void bulk_frontier(imt_itree* t, hipStream_t s, uint64_t M, uint8_t* append_sib, unsigned fmt) {
+    if (!append_sib) return;
+    imt_ctx* c = t->ctx;
+    launch::gather_frontier(s, launch::TreeView{t->d_nodes, t->d_off, t->d_len, c->d_zero}, M, t->depth, append_sib, fmt);
+}
+// The append: leaves M .. M + n - 1 from their final preimages (rows [n, 2n) of P.d_pre) and every node above them once --
+// apply_hashes over the dense table of the new leaves, in the plan set's tables, which the sweep on s has done with.
+static int bulk_append(imt_itree* t, PlanSet& P, hipStream_t s, uint64_t M, size_t n, unsigned L0) {
+    imt_ctx* c = t->ctx;
+    IMT_HIP(c, prep::append_table(s, (uint32_t)M, (uint32_t)n, P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][2], P.d_tab[0][3]));
+    const int rc = apply_hashes(t, P, s, n, L0, t->d_apply_stats);
+    if (rc) return rc;
+    t->apply_seen = true;
+    t->apply_stats_set = nullptr;
+    return IMT_OK;
+}
+static int bulk_deliver_outputs(imt_itree* t, hipStream_t s, const imt_bulk_out* o, const BulkDev& d, size_t n, unsigned flags) {
+    imt_ctx* c = t->ctx;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    if (fmt != IMT_FMT_CANONICAL) {
+        if (d.hashfree.low_leaf) launch::convert(s, d.hashfree.low_leaf, d.hashfree.low_leaf, n * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
+        if (d.hashfree.new_leaf) launch::convert(s, d.hashfree.new_leaf, d.hashfree.new_leaf, n * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
+    }
+    if (d.root) launch::convert(s, t->nodes(t->depth), d.root, 1, IMT_FMT_DEVICE, fmt, c->d_err);
+    if (flags & IMT_DEVICE_PTRS) return IMT_OK;
+    auto back = [&](void* user, const void* from, size_t bytes) -> int {
+        if (user && from) IMT_HIP(c, hipMemcpyAsync(user, from, bytes, hipMemcpyDeviceToHost, s));
+        return IMT_OK;
+    };
+    int rc;
+    if ((rc = back(o->order, d.hashfree.order, n * 8)) || (rc = back(o->low_index, d.hashfree.low_index, n * 8)) ||
+        (rc = back(o->is_largest, d.hashfree.is_largest, n)) || (rc = back(o->low_leaf, d.hashfree.low_leaf, n * 96)) ||
+        (rc = back(o->new_leaf, d.hashfree.new_leaf, n * 96)) || (rc = back(o->root_before, d.sweep.old_root, n * 32)) ||
+        (rc = back(o->root_after, d.sweep.interim_root, n * 32)) ||
+        (rc = back(o->low_sib, d.sweep.low_sib, (size_t)t->depth * n * 32)) ||
+        (rc = back(o->append_sib, d.append_sib, (size_t)t->depth * 32)) || (rc = back(o->root, d.root, 32)))
+        return rc;
+    IMT_HIP(c, hipStreamSynchronize(s));
+    return IMT_OK;
+}
+
+extern "C" int imt_itree_insert_bulk(imt_itree* t, const void* vals, size_t n, const imt_bulk_out* out, unsigned flags) {
+    if (!t) return IMT_ERR_ARG;
+    imt_ctx* c = t->ctx;
+    IMT_NOT_SLICED(t);
+    if (n == 0) return IMT_OK;
+    if (!vals) return c->fail(IMT_ERR_ARG, "null vals");
+    int rc;
+    if ((rc = check_mixed_mode(t, flags, BULK_BATCH)) || (rc = check_batch_call(t, n, flags))) return rc;
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    if ((rc = check_fe_ptrs(c, dev, {vals}))) return rc;
+    if (out && (rc = check_fe_ptrs(c, dev, {out->low_leaf, out->root_before, out->root_after, out->low_sib, out->new_leaf,
+                                            out->append_sib, out->root})))
+        return rc;
+    if (dev && out && (((uintptr_t)out->order | (uintptr_t)out->low_index) & 7u))
+        return c->fail(IMT_ERR_ARG, "device order / low_index array is not 8-byte aligned");
+    if ((rc = check_room(t, n)) || (rc = ensure_device_index(t))) return rc;
+    const uint64_t M = t->size;
+    const HostTimer host;
+    double waited_ms = 0;
+
+    // ---- plan buffers: n events, and the new leaves' preimages behind theirs ----
+    PlanSet& P = t->plan[t->cur];
+    if ((rc = acquire_plan(t, 2 * n, 0, waited_ms))) return rc;
+
+    // ---- the checks (side stream): nothing of the caller's is written before the batch is accepted ----
+    hipStream_t ps = t->up_stream;
+    if ((rc = order_behind_caller(t, ps, flags))) return rc;
+    size_t slot = 2;
+    const uint8_t* d_vals = nullptr;
+    uint8_t* up = dev ? nullptr : (uint8_t*)c->dev_scratch(slot++, n * 32);
+    if ((rc = stage_canonical(c, ps, vals, n, flags, up, P.d_canon, P.ws.err, &d_vals))) return rc;
+    if ((rc = bulk_checks(t, P, d_vals, n, waited_ms))) return rc;
+
+    // ---- accepted: rows, events, tables, merged index, hash-free outputs ----
+    BulkDev d;
+    if (out && !bulk_stage_outputs(c, dev, slot, out, n, t->depth, d)) return IMT_ERR_HIP;
+    uint32_t* erow = P.d_slot;
+    IMT_HIP(c, prep::bulk_events(ps, P.ws, t->d_val, t->d_sorted[t->sorted_cur], t->d_sorted[t->sorted_cur ^ 1], (uint32_t)M,
+                                 (uint32_t)n, P.d_pre, P.d_tab[0][0], P.d_tab[0][1], P.d_tab[0][2], P.d_tab[0][3], erow,
+                                 d.hashfree));
+    IMT_HIP(c, hipEventRecord(t->up_done, ps));
+
+    // ---- hashing on the context's stream, behind every batch in flight: the rows' sweep over the levels the stored M
+    // leaves occupy (above them every event climbs alone against Z[l]), the frontier, the append ----
+    hipStream_t s;
+    WitnessSweep w;
+    if ((rc = hashing_stream(t, false, s, w.pipe))) return rc;
+    IMT_HIP(c, hipStreamWaitEvent(s, t->up_done, 0));
+    const bool item_major = flags & IMT_SIB_ITEM_MAJOR;
+    const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->depth} : launch::SibLayout{n, 1};
+    const launch::MixedRoute route{erow, nullptr};
+    w.route = &route;
+    w.bulk = true;
+    const unsigned L0_stored = std::min(ceil_log2(M), t->depth), L0 = std::min(ceil_log2(M + n), t->depth);
+    if ((rc = witness_sweep(t, P, s, n, L0_stored, d.sweep, lay, fmt, w))) return rc;
+    bulk_frontier(t, s, M, d.append_sib, fmt);
+    if ((rc = bulk_append(t, P, s, M, n, L0))) return rc;
+
+    // ---- record, commit, outputs: a batch like any other ----
+    IMT_HIP(c, hipMemcpyAsync(P.d_root, t->nodes(t->depth), 32, hipMemcpyDeviceToDevice, s));
+    if ((rc = plan_launched(t, P, s, L0, false, false))) return rc;
+    index_committed(t, M + n);
+    if (c->profiling) {
+        c->prof_ms[IMT_PROF_HOST] += host.ms() - waited_ms;
+        c->prof_n[IMT_PROF_HOST] += 1;
+    }
+    if (out) return bulk_deliver_outputs(t, s, out, d, n, flags);
+    if (!dev) IMT_HIP(c, hipStreamSynchronize(s));
+    return IMT_OK;
 }
 
 // The filtered twin: prep::mixed_filter classifies the operations on the side stream, one wait brings back

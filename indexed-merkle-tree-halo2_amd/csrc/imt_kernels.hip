@@ -1069,6 +1069,63 @@ k_emit_roots(const uint8_t* __restrict__ val, uint32_t e_begin, uint32_t e_count
     }
 }
 
+// k_emit_roots for a bulk insertion (imt_itree_insert_bulk): every event is one row's rewrite of its low leaf, so the top
+// value of event k is root_after[k] and root_before[k + 1]; root_before[0] is the stored root, read before the sweep
+// overwrites it (read_old_root).  No hashing.
+__global__ void __launch_bounds__(BLOCK)
+k_emit_roots_bulk(const uint8_t* __restrict__ val, uint32_t total, uint8_t* __restrict__ root_before,
+                  uint8_t* __restrict__ root_after, unsigned fmt_out, uint8_t* __restrict__ node_store) {
+    const size_t t = gtid();
+    if (t >= total) return;
+    Fe cur;
+    load_packed(cur, val + t * 32);
+    if (t == total - 1 && node_store) store_packed(node_store, cur);
+    if (root_after) store_fe(g_pc, root_after + t * 32, cur, fmt_out);
+    if (root_before && t + 1 < total) store_fe(g_pc, root_before + (t + 1) * 32, cur, fmt_out);
+}
+
+// The frontier of a stored tree: the proof of the first free slot `index` (everything at and right of it is empty).  A
+// left-hand sibling (bit l of index set) is the stored node; a right-hand one lies right of everything stored and is
+// written as the constant zero[l] whatever the array holds there.  One thread per level.
+__global__ void k_gather_frontier(launch::TreeView tv, uint64_t index, unsigned depth, uint8_t* __restrict__ out,
+                                  unsigned fmt_out) {
+    const unsigned l = threadIdx.x + blockIdx.x * blockDim.x;
+    if (l >= depth) return;
+    const uint64_t p = index >> l, s = p ^ 1;
+    const uint8_t* src = ((p & 1) && s < tv.len[l]) ? tv.nodes + (tv.off[l] + s) * 32 : tv.zero + (size_t)l * 32;
+    Fe x;
+    load_packed(x, src);
+    store_fe(g_pc, out + (size_t)l * 32, x, fmt_out);
+}
+
+// The boundary of an append at `start` (imt_frontier_append_root), before its levels are hashed.  Row l of the level
+// builder holds nodes base_l = (start >> l) & ~1 .. ((start + n - 1) >> l) | 1 of level l at rows + off[l] * 32, so that
+// pairs of a row are siblings; this kernel fills what no hash will: slot 0 of row l with the caller's left-hand sibling
+// when bit l of start is set, the slot behind the last node with zero[l] when that node is a left child.  fsib[l] (device
+// format) is the frontier with zero[l] at every right-hand level -- the caller's row there is not read.  idx[0] = start,
+// idx[1] = start >> top: the path indices of the two chains that follow.  One thread per level.
+__global__ void k_frontier_bounds(launch::FrontierArgs a) {
+    const unsigned l = threadIdx.x + blockIdx.x * blockDim.x;
+    if (l == 0) {
+        a.idx[0] = a.start;
+        a.idx[1] = a.start >> a.top;
+    }
+    if (l > a.depth) return;
+    const uint64_t first = a.start >> l, last = (a.start + a.n - 1) >> l;
+    const bool left = first & 1;
+    Fe x, z;
+    load_packed(z, a.zero + (size_t)l * 32);
+    x = z;
+    if (l < a.depth) {
+        if (left) flag_err(a.err, load_fe(g_pc, x, a.sib + (size_t)l * 32, a.fmt_in));
+        store_packed(a.fsib + (size_t)l * 32, x);
+    }
+    if (l > a.top) return;
+    uint8_t* row = a.rows + a.off[l] * 32;
+    if (left) store_packed(row, x);
+    if (!(last & 1)) store_packed(row + (last - (first & ~(uint64_t)1) + 1) * 32, z);
+}
+
 // -----------------------------------------------------------------------------------------------
 // One hash per LISTED node, a quad of lanes each: the body of k_apply_level_coop and k_view_level_coop.  The two differ
 // in `Rule` alone: child(c) is the row of child c of the level below, out(j, p) where the hash of place j of the list,
@@ -1856,6 +1913,30 @@ void emit_roots_mixed(hipStream_t s, const MixedRoute& r, const uint8_t* val, ui
     if (!total) return;
     hipLaunchKernelGGL(k_emit_roots_mixed, dim3(nblk(total)), dim3(BLOCK), 0, s, val, total, r.erow, n_ins, old_root,
                        interim_root, new_root, read_root, fmt_out, node_store);
+}
+void emit_roots_bulk(hipStream_t s, const uint8_t* val, uint32_t total, uint8_t* root_before, uint8_t* root_after,
+                     unsigned fmt_out, uint8_t* node_store) {
+    if (!total) return;
+    hipLaunchKernelGGL(k_emit_roots_bulk, dim3(nblk(total)), dim3(BLOCK), 0, s, val, total, root_before, root_after, fmt_out,
+                       node_store);
+}
+void gather_frontier(hipStream_t s, TreeView tv, uint64_t index, unsigned depth, uint8_t* out, unsigned fmt_out) {
+    if (!depth) return;
+    hipLaunchKernelGGL(k_gather_frontier, dim3((depth + 63) / 64), dim3(64), 0, s, tv, index, depth, out, fmt_out);
+}
+uint64_t frontier_rows(FrontierArgs& a) {
+    uint64_t total = 0;
+    a.top = a.depth;
+    for (unsigned l = 0; l <= a.depth; l++) {
+        const uint64_t count = ((a.start + a.n - 1) >> l) - (a.start >> l) + 1;
+        a.off[l] = total;
+        total += count + 2;             // the left-hand sibling in front, zero[l] behind
+        if (count == 1) { a.top = l; break; }
+    }
+    return total;
+}
+void frontier_bounds(hipStream_t s, const FrontierArgs& a) {
+    hipLaunchKernelGGL(k_frontier_bounds, dim3((a.depth + 64) / 64), dim3(64), 0, s, a);
 }
 // one thread per listed node, or -- while the launch is small enough to leave most SIMDs idle -- one quad per node
 static void launch_apply(hipStream_t s, const ApplyArgs& a, uint32_t coop_max) {

@@ -297,6 +297,35 @@ void sweep_upper_mixed(hipStream_t s, const MixedRoute& r, const uint8_t* val_in
 void emit_roots_mixed(hipStream_t s, const MixedRoute& r, const uint8_t* val, uint32_t total, uint32_t n_ins, uint8_t* old_root,
                       uint8_t* interim_root, uint8_t* new_root, uint8_t* read_root, unsigned fmt_out, uint8_t* node_store);
 
+// ---- bulk insertion (imt_itree_insert_bulk): one low-leaf rewrite per value, then all new leaves at once ----
+// The sweep of a bulk batch is a mixed one whose events are all prep::ROW_LOW (rows of low_sib); these are its roots --
+// root_after[k] = the top value of event k = root_before[k + 1] -- and, behind its last write-back, the proof of the first
+// free slot with zero[l] at every right-hand level.  The append itself is the witness-free schedule (apply_leaves /
+// apply_level / apply_top) over the dense list of the new leaves.
+void emit_roots_bulk(hipStream_t s, const uint8_t* val, uint32_t total, uint8_t* root_before, uint8_t* root_after,
+                     unsigned fmt_out, uint8_t* node_store);
+void gather_frontier(hipStream_t s, TreeView tv, uint64_t index, unsigned depth, uint8_t* out, unsigned fmt_out);
+// The stateless form (imt_frontier_append_root): n nodes of level 0 at start .. start + n - 1 hashed upwards on scratch rows
+// until one node is left at level `top`, then two paths.  frontier_rows says where row l lies (in nodes) and how many
+// nodes it has; frontier_bounds writes the boundary slots, the frontier with its right-hand rows forced to zero[l], and
+// the two path indices (k_frontier_bounds).
+constexpr unsigned FRONTIER_MAX_DEPTH = 64;       // IMT_MAX_DEPTH (imt_ctx.hpp)
+struct FrontierArgs {
+    const uint8_t* sib;                  // [depth][32] the caller's, fmt_in
+    unsigned fmt_in;
+    int* err;
+    uint64_t start, n;
+    unsigned depth, top;                  // top: the first level at which the range is one node
+    const uint8_t* zero;                  // [depth + 1][32] device format
+    uint8_t* rows;                        // scratch of frontier_rows(...) nodes
+    uint64_t off[FRONTIER_MAX_DEPTH + 1];     // row l starts at rows + off[l] * 32
+    uint8_t* fsib;                        // [depth][32] device format
+    uint64_t* idx;                        // [2]
+};
+// fills a.top and a.off from a.start / a.n / a.depth; returns the nodes `rows` must hold
+uint64_t frontier_rows(FrontierArgs& a);
+void frontier_bounds(hipStream_t s, const FrontierArgs& a);
+
 // ---- witnesses of a mixed block already applied (imt_itree_view_mixed_witness): both of the above at once ----
 // argument block of k_sweep_view_mixed: k_sweep_view's (a LEVEL launch below l0 and the view the base siblings are read as
 // of) with k_sweep_mixed's route.  The levels from l0 up are sweep_upper_mixed with both node stores NULL, the roots

@@ -166,6 +166,56 @@ __global__ void __launch_bounds__(BLOCK) k_runs(const uint64_t* __restrict__ key
     re[k] = lo;
 }
 
+// ---- bulk insertion (imt_itree_insert_bulk; the rule is bulk_row, imt_prep_logic.hpp) ----
+// One event per value: row k rewrites its low leaf.  The new leaves' final preimages go to rows [n, 2n) of `pre` by the
+// caller's position, where the append stage hashes them from.
+__global__ void __launch_bounds__(BLOCK)
+k_bulk_events(const uint8_t* __restrict__ d_val, const uint32_t* __restrict__ sorted_old, uint32_t M,
+              const uint32_t* __restrict__ bsorted, const uint32_t* __restrict__ gap, uint32_t n, uint8_t* __restrict__ pre,
+              uint64_t* __restrict__ keys, uint32_t* __restrict__ erow, BulkOut o) {
+    const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n) return;
+    const BulkRow r = bulk_row(sorted_old, M, bsorted, gap, n, j);
+    const uint8_t* v = d_val + (uint64_t)bsorted[j] * 32;
+    const uint8_t* lv = d_val + (uint64_t)r.low * 32;
+    uint8_t* e0 = pre + (uint64_t)r.k * 96;                    // low leaf rewritten: {low.val, v, M + pos}
+    copy32(e0, lv);
+    copy32(e0 + 32, v);
+    put_u64(e0 + 64, (uint64_t)M + r.pos);
+    uint8_t* e1 = pre + ((uint64_t)n + r.pos) * 96;            // the new leaf as the batch leaves it: {v, succ.val, succ.idx}
+    copy32(e1, v);
+    if (r.succ != OP_NONE) { copy32(e1 + 32, d_val + (uint64_t)r.succ * 32); put_u64(e1 + 64, r.succ); }
+    else { zero32(e1 + 32); zero32(e1 + 64); }
+    keys[r.k] = ((uint64_t)r.low << 32) | (uint64_t)r.k;
+    erow[r.k] = (r.k << 2) | ROW_LOW;
+    if (o.order) o.order[r.k] = r.pos;
+    if (o.low_index) o.low_index[r.k] = r.low;
+    if (o.is_largest) o.is_largest[r.k] = r.succ == OP_NONE ? 1 : 0;
+    if (o.low_leaf) {                                          // before the rewrite: {low.val, succ.val, succ.idx}
+        uint8_t* q = o.low_leaf + (uint64_t)r.k * 96;
+        copy32(q, lv);
+        copy32(q + 32, e1 + 32);
+        copy32(q + 64, e1 + 64);
+    }
+    if (o.new_leaf) {
+        uint8_t* q = o.new_leaf + (uint64_t)r.pos * 96;
+        copy32(q, e1);
+        copy32(q + 32, e1 + 32);
+        copy32(q + 64, e1 + 64);
+    }
+}
+// the level-0 table of the append: leaf M + i alone in its run, its preimage row n + i of `pre`
+__global__ void __launch_bounds__(BLOCK) k_append_table(uint32_t M, uint32_t n, uint32_t* __restrict__ node,
+                                                        uint32_t* __restrict__ time, uint32_t* __restrict__ rs,
+                                                        uint32_t* __restrict__ re) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    node[i] = M + i;
+    time[i] = n + i;
+    rs[i] = i;
+    re[i] = i + 1;
+}
+
 // ---- mixed batches (imt_itree_mixed_batch; the rules are in imt_prep_logic.hpp) ----
 static_assert(OP_ZERO == ERR_ZERO && OP_DUPLICATE == ERR_DUPLICATE && OP_FOREIGN == ERR_FOREIGN && OP_ABSENT == ERR_ABSENT,
               "one set of error bits");
@@ -812,6 +862,42 @@ hipError_t index_only(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t
     if ((e = rocprim::merge(ws.tmp, tb, sorted_old, ws.bsorted, sorted_new, (size_t)M, (size_t)n, ValLess{d_val}, s)) !=
         hipSuccess)
         return e;
+    return hipGetLastError();
+}
+
+hipError_t bulk_check(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t* d_val, const uint32_t* sorted_old, uint32_t M,
+                      uint32_t n) {
+    hipError_t e;
+    if (n > ws.cap_n || temp_bytes_needed(n, (size_t)M) > ws.tmp_bytes) return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_scatter, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, d_val, M, n, ws.part_mod, ws.part_res, ws.iota,
+                       ws.err);
+    size_t tb = ws.tmp_bytes;
+    if ((e = rocprim::merge_sort(ws.tmp, tb, ws.iota, ws.bsorted, (size_t)n, ValLess{d_val}, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_gap, dim3(nblk(n)), dim3(BLOCK), 0, s, d_val, sorted_old, M, ws.bsorted, n, ws.gap, ws.st,
+                       ws.err);
+    return hipGetLastError();
+}
+
+hipError_t bulk_events(hipStream_t s, Workspace& ws, const uint8_t* d_val, const uint32_t* sorted_old, uint32_t* sorted_new,
+                       uint32_t M, uint32_t n, uint8_t* pre, uint32_t* node, uint32_t* time, uint32_t* rs, uint32_t* re,
+                       uint32_t* erow, const BulkOut& o) {
+    hipError_t e;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_bulk_events, dim3(nblk(n)), dim3(BLOCK), 0, s, d_val, sorted_old, M, ws.bsorted, ws.gap, n, pre,
+                       ws.keys, erow, o);
+    size_t tb = ws.tmp_bytes;
+    if ((e = rocprim::radix_sort_keys(ws.tmp, tb, ws.keys, ws.keys_sorted, (size_t)n, 0, 64, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_runs, dim3(nblk(n)), dim3(BLOCK), 0, s, ws.keys_sorted, n, node, time, rs, re);
+    tb = ws.tmp_bytes;
+    if ((e = rocprim::merge(ws.tmp, tb, sorted_old, ws.bsorted, sorted_new, (size_t)M, (size_t)n, ValLess{d_val}, s)) !=
+        hipSuccess)
+        return e;
+    return hipGetLastError();
+}
+
+hipError_t append_table(hipStream_t s, uint32_t M, uint32_t n, uint32_t* node, uint32_t* time, uint32_t* rs, uint32_t* re) {
+    hipLaunchKernelGGL(k_append_table, dim3(nblk(n)), dim3(BLOCK), 0, s, M, n, node, time, rs, re);
     return hipGetLastError();
 }
 

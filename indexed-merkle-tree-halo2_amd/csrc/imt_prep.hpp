@@ -126,6 +126,27 @@ hipError_t mixed_insert_events(hipStream_t s, Workspace& ws, const uint8_t* d_va
                                uint32_t M, uint32_t n_ins, uint64_t base, uint8_t* pre, uint32_t* node, uint32_t* time,
                                uint32_t* rs, uint32_t* re);
 
+// ---- bulk insertion (imt_itree_insert_bulk): the batch in descending value order, one event per value ----
+struct BulkOut {              // device pointers, any may be NULL; rows k in processing order except new_leaf (caller's order)
+    uint64_t* order;
+    uint64_t* low_index;
+    uint8_t* is_largest;
+    uint8_t* low_leaf;             // [n][3][32] canonical
+    uint8_t* new_leaf;             // [n][3][32] canonical
+};
+// 1. the values into rows [M, M + n) of d_val, the batch sorted (ws.bsorted), its gaps (ws.gap) and every check of the
+// values into ws.err, by the kernels run() checks an insertion batch with.  Writes nothing else of the tree, no output.
+hipError_t bulk_check(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t* d_val, const uint32_t* sorted_old, uint32_t M,
+                      uint32_t n);
+// 2. behind it, the batch accepted (bulk_row, imt_prep_logic.hpp): event k = row k's rewrite of its low leaf -- preimages
+// pre[0 .. n), the level-0 tables [n], erow[k] = (k << 2) | ROW_LOW --, the new leaves' final preimages pre[n + i] in the
+// caller's order, sorted_new[M + n] and the hash-free outputs.  pre: [2n][96].
+hipError_t bulk_events(hipStream_t s, Workspace& ws, const uint8_t* d_val, const uint32_t* sorted_old, uint32_t* sorted_new,
+                       uint32_t M, uint32_t n, uint8_t* pre, uint32_t* node, uint32_t* time, uint32_t* rs, uint32_t* re,
+                       uint32_t* erow, const BulkOut& o);
+// 3. the level-0 table apply_lists reads for the append of leaves M .. M + n - 1 (runs of one, preimage row n + i)
+hipError_t append_table(hipStream_t s, uint32_t M, uint32_t n, uint32_t* node, uint32_t* time, uint32_t* rs, uint32_t* re);
+
 // ---- witness-free insertion (imt_itree_apply_batch): the touched nodes of every level (imt_apply.hpp) ----
 // From the level-0 tables run() left ([total] each): lists.node rows 0 .. l0-1, lists.src and lists.count[0 .. depth].
 // pos = [l0][lists.stride] scratch for the scans; tmp as in the workspace (temp_bytes_needed covers it).

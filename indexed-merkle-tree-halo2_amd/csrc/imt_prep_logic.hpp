@@ -324,5 +324,39 @@ IMT_PL_HD int load_values_rank(const uint8_t* vals, const uint32_t* ord, uint32_
     return e;
 }
 
+// ---- bulk insertion (imt_itree_insert_bulk): the batch in DESCENDING value order, one low-leaf rewrite per value ----
+// The batch in ascending value order is bsorted[0 .. n) (rows of val, row M + i = the caller's value i) with gap[j] = the
+// stored values below the j-th smallest.  Row k of the witness is the k-th LARGEST value, place j = n - 1 - k.  Every
+// value of gap g has the stored leaf sorted_old[g - 1] as its low leaf -- never a leaf of the batch -- and what that leaf
+// points at as of step k is the neighbour above in the sorted batch if it shares the gap (it was row k - 1), else the
+// stored successor sorted_old[g], else nothing.  That neighbour is also the value's successor in the final tree, so the
+// low leaf's pointer before row k and the new leaf's final pointer are the same pair.  Always in bounds, also for the
+// refused value 0 (g == 0).
+struct BulkRow {
+    uint32_t k;             // the row: n - 1 - j
+    uint32_t pos;           // the caller's position of the value: bsorted[j] - M
+    uint32_t low;           // row of val of the low leaf (a stored leaf)
+    uint32_t succ;          // row of val the low leaf points at before the rewrite = the new leaf's successor; OP_NONE: none
+};
+IMT_PL_HD BulkRow bulk_row(const uint32_t* sorted_old, uint32_t M, const uint32_t* bsorted, const uint32_t* gap, uint32_t n,
+                           uint32_t j) {
+    const uint32_t g = gap[j];
+    BulkRow r;
+    r.k = n - 1 - j;
+    r.pos = bsorted[j] - M;
+    r.low = sorted_old[g > 0 ? g - 1 : 0];
+    r.succ = (j + 1 < n && gap[j + 1] == g) ? bsorted[j + 1] : (g < M ? sorted_old[g] : OP_NONE);
+    return r;
+}
+// place j of the sorted batch is refused as a duplicate: its value is stored, or the place above holds the same value.
+// On the device k_gap makes these two comparisons for every batch (imt_prep.hip); this is their statement for a host
+// driver (tests/native/bulk_rows.cpp).
+IMT_PL_HD bool bulk_is_duplicate(const uint8_t* val, const uint32_t* sorted_old, uint32_t M, const uint32_t* bsorted, uint32_t n,
+                                 uint32_t j, uint32_t g) {
+    const uint8_t* x = val + (uint64_t)bsorted[j] * 32;
+    if (g < M && eq256(val + (uint64_t)sorted_old[g] * 32, x)) return true;
+    return j + 1 < n && eq256(val + (uint64_t)bsorted[j + 1] * 32, x);
+}
+
 }  // namespace prep
 }  // namespace imt
