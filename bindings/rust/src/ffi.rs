@@ -327,6 +327,7 @@ extern "C" {
     pub fn imt_itree_view_non_membership_witness(v: *mut imt_itree_view, vals: *const c_void, n: usize, low_index: *mut u64, low_leaf: *mut c_void, is_largest: *mut u8, low_sib: *mut c_void, flags: c_uint) -> c_int;
     pub fn imt_itree_view_stats(v: *mut imt_itree_view, hashes: *mut u64, builds: *mut u64) -> c_int;
     pub fn imt_itree_view_insert_witness(v: *mut imt_itree_view, n: usize, out: *const imt_insert_out, flags: c_uint) -> c_int;
+    pub fn imt_itree_view_bulk_witness(v: *mut imt_itree_view, n: usize, out: *const imt_bulk_out, flags: c_uint) -> c_int;
     pub fn imt_itree_mixed_batch(t: *mut imt_itree, vals: *const c_void, op: *const u8, n: usize, ins: *const imt_insert_out, rd: *const imt_read_out, n_inserted: *mut u64, bad_op: *mut u64, flags: c_uint) -> c_int;
     pub fn imt_itree_mixed_filtered(t: *mut imt_itree, vals: *const c_void, op: *const u8, n: usize, status: *mut u8, leaf_index: *mut u64, ins: *const imt_insert_out, rd: *const imt_read_out, n_inserted: *mut u64, n_read: *mut u64, flags: c_uint) -> c_int;
     pub fn imt_itree_apply_mixed(t: *mut imt_itree, vals: *const c_void, op: *const u8, n: usize, root_out: *mut c_void, n_inserted: *mut u64, bad_op: *mut u64, flags: c_uint) -> c_int;

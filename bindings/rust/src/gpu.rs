@@ -518,6 +518,50 @@ impl IndexedTreeView {
             })
             .collect())
     }
+    /// The bulk witness of the n insertions that followed this view's size (`imt_itree_view_bulk_witness`): what
+    /// [`IndexedTree::insert_bulk`] returns on a fresh tree fed the first `size - 1` values, for the next n values the tree
+    /// holds -- `position` is a position in that block, `new_leaves` and `root` are as of `size + n`.  Nothing of the tree
+    /// changes; `Err(code -4)` if fewer than n insertions followed the view's size.
+    pub fn bulk_witness<F: ScalarField>(&self, n: usize) -> Result<BulkWitness<F>, ImtError> {
+        let g = context().lock().unwrap();
+        let d = self.depth;
+        let first = self.size();
+        let (mut order, mut low_index, mut is_largest) = (vec![0u64; n], vec![0u64; n], vec![0u8; n]);
+        let (mut low_leaf, mut new_leaf) = (vec![0u8; n * 96], vec![0u8; n * 96]);
+        let (mut root_before, mut root_after) = (vec![0u8; n * 32], vec![0u8; n * 32]);
+        let (mut low_sib, mut append_sib, mut root) = (vec![0u8; n * d * 32], vec![0u8; d * 32], [0u8; 32]);
+        let out = imt_bulk_out {
+            order: order.as_mut_ptr(),
+            low_index: low_index.as_mut_ptr(),
+            low_leaf: low_leaf.as_mut_ptr() as *mut c_void,
+            is_largest: is_largest.as_mut_ptr(),
+            root_before: root_before.as_mut_ptr() as *mut c_void,
+            root_after: root_after.as_mut_ptr() as *mut c_void,
+            low_sib: low_sib.as_mut_ptr() as *mut c_void,
+            new_leaf: new_leaf.as_mut_ptr() as *mut c_void,
+            append_sib: append_sib.as_mut_ptr() as *mut c_void,
+            root: root.as_mut_ptr() as *mut c_void,
+        };
+        check(&g, unsafe { imt_itree_view_bulk_witness(self.handle, n, &out, IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR) })?;
+        let three = |b: &[u8]| -> [F; 3] { [F::from_bytes_le(&b[0..32]), F::from_bytes_le(&b[32..64]), F::from_bytes_le(&b[64..96])] };
+        Ok(BulkWitness {
+            rows: (0..n)
+                .map(|k| BulkRow {
+                    position: order[k] as usize,
+                    low_index: low_index[k],
+                    low_leaf: three(&low_leaf[k * 96..][..96]),
+                    low_leaf_proof: from_bytes(&low_sib[k * d * 32..][..d * 32]),
+                    is_largest: is_largest[k] != 0,
+                    root_before: F::from_bytes_le(&root_before[k * 32..][..32]),
+                    root_after: F::from_bytes_le(&root_after[k * 32..][..32]),
+                })
+                .collect(),
+            first_new_index: first,
+            new_leaves: (0..n).map(|i| three(&new_leaf[i * 96..][..96])).collect(),
+            append_proof: from_bytes(&append_sib),
+            root: F::from_bytes_le(&root),
+        })
+    }
 }
 
 impl Drop for IndexedTreeView {

@@ -756,6 +756,26 @@ int imt_itree_view_stats(imt_itree_view *v, uint64_t *hashes /*[depth + 1] or NU
 int imt_itree_view_insert_witness(imt_itree_view *v, size_t n, const imt_insert_out *out, unsigned flags);
 /* Its twin for a block that also held READs, imt_itree_view_mixed_witness, takes an imt_read_out and is declared with
  * the mixed batches below, behind imt_itree_mixed_filtered. */
+/* ... AND IN THE BULK FORM: the imt_bulk_out of the n insertions that followed the view's size (imt_itree_insert_bulk
+ * above: one low-leaf path per value in descending value order, one shared append).
+ * DEFINED BY THE SIZES ALONE.  Let S = imt_itree_view_size(v).  Take a fresh tree fed the first S - 1 values and call
+ * imt_itree_insert_bulk on it with the values of leaves [S, S + n), in leaf order, and the same flags: this call writes
+ * into `out` what that call would write, byte for byte, in all ten fields; NULL fields are skipped.  order[k] is a position
+ * 0 .. n - 1 of the block (leaf S + order[k]); new_leaf[i] is the preimage of leaf S + i AS OF SIZE S + n, not as the tree
+ * holds it now; root is the root as of S + n.  IMT_FMT_*, IMT_SIB_ITEM_MAJOR, IMT_DEVICE_PTRS and the alignment rules mean
+ * what they mean to imt_itree_insert_bulk.  There is no `vals`: the tree has the values, however they went in (apply,
+ * pipelined, witness, bulk, filtered, load_values).  IMT_HOST_PREP and IMT_INPUTS_READY change nothing.
+ * A view query otherwise, like imt_itree_view_insert_witness: on the context's stream behind everything in flight, a stale
+ * side table rebuilt first, the tree never changed (stored nodes, index buffers, plan sets, apply stats, size, rows of
+ * the value array), nothing rotated or committed; synchronous for host pointers, only enqueued with IMT_DEVICE_PTRS, and
+ * with no host wait of its own -- stored values were accepted when they went in, there is no verdict to read back.
+ * out == NULL: IMT_ERR_ARG.  n == 0: IMT_OK.  S + n above the tree's size (any n > 0 on a view at the current size, any n
+ * while the tree is smaller than the view): IMT_ERR_RANGE.  A placed or value-partitioned tree, IMT_PIPELINE, a misaligned
+ * device buffer: IMT_ERR_ARG, as for imt_itree_insert_bulk.  A dead handle: IMT_ERR_ARG.  Nothing is written in any of
+ * these cases.  Never IMT_ERR_VALUE.
+ * Memory: the view's plan set grows to 2n events; the merged index of S + n entries and the append's rows (about 2n nodes
+ * of 32 bytes) are borrowed from the context for the time of the call. */
+int imt_itree_view_bulk_witness(imt_itree_view *v, size_t n, const imt_bulk_out *out, unsigned flags);
 /* Read-only query of the device-resident index for any mix of values (one kernel, k_lookup): status ZERO / FOREIGN /
  * PRESENT / NEW and leaf_index = the sentinel / UINT64_MAX / the stored leaf / the low leaf (what find_low returns).
  * Fails only for its arguments, a value >= p (IMT_ERR_NONCANONICAL) or a HIP error, never for a value's class.  With

@@ -725,6 +725,31 @@ public:
         }
         return m;
     }
+    // The bulk witness of the n insertions that followed this view's size (imt_itree_view_bulk_witness): what
+    // IndexedTree::insert_bulk returns on a fresh tree fed the first size - 1 values, for the next n values the tree holds --
+    // order[k] a position in that block, new_leaf and root as of size + n.  Nothing of the tree changes.
+    IndexedTree::BulkInsertion bulk_witness(size_t n) {
+        const size_t d = depth_;
+        IndexedTree::BulkInsertion r;
+        r.first_new_index = size();
+        r.root = root();
+        if (!n) return r;
+        r.order.resize(n);
+        r.low_index.resize(n);
+        r.low_leaf.resize(n);
+        r.new_leaf.resize(n);
+        r.is_largest.resize(n);
+        r.root_before.resize(n);
+        r.root_after.resize(n);
+        r.append_proof.resize(d);
+        std::vector<Fr> ls(n * d);
+        imt_bulk_out out{r.order.data(), r.low_index.data(), r.low_leaf.data(), r.is_largest.data(), r.root_before.data(),
+                         r.root_after.data(), ls.data(), r.new_leaf.data(), r.append_proof.data(), &r.root};
+        c_->check(imt_itree_view_bulk_witness(v_, n, &out, IMT_FMT_CANONICAL | IMT_SIB_ITEM_MAJOR));
+        r.low_leaf_proof.resize(n);
+        for (size_t k = 0; k < n; k++) r.low_leaf_proof[k].assign(ls.begin() + k * d, ls.begin() + (k + 1) * d);
+        return r;
+    }
     // hashes per level of the last rebuild ([depth + 1]); builds, if given: rebuilds so far
     std::vector<uint64_t> stats(uint64_t* builds = nullptr) {
         std::vector<uint64_t> h(depth_ + 1);

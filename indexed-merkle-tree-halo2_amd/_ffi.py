@@ -202,6 +202,7 @@ SIGNATURES = {
     "imt_itree_view_insert_witness": (c_int, [c_void_p, c_size_t, P(InsertOut), c_uint]),
     "imt_itree_view_mixed_witness": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, P(InsertOut), P(ReadOut), P(c_u64),
                                              P(c_u64), c_uint]),
+    "imt_itree_view_bulk_witness": (c_int, [c_void_p, c_size_t, P(BulkOut), c_uint]),
     "imt_itree_lookup_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_uint]),
     "imt_itree_batch_begin": (c_int, [c_void_p, c_void_p, c_size_t, c_uint, P(ctypes.c_uint32), P(ctypes.c_uint32)]),
     "imt_itree_batch_leaves": (c_int, [c_void_p, c_void_p, ctypes.c_uint32, ctypes.c_uint32]),

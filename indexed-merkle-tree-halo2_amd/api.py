@@ -1145,6 +1145,22 @@ class IndexedTreeView:
         res["new_index"] = np.arange(size, size + n, dtype=np.uint64) + np.uint64(tree.index_base)
         return res
 
+    def bulk_witness(self, n, proofs=True, item_major=False):
+        """The bulk witness of the n insertions that followed this view's size (imt_itree_view_bulk_witness): the dict
+        IndexedTree.insert_bulk returns on a fresh tree fed the first size - 1 values, for the next n values the tree
+        holds -- order[k] a position in that block, new_leaf and root as of size + n.  Nothing of the tree changes."""
+        d = self.depth
+        res = dict(order=np.empty(n, np.uint64), low_index=np.empty(n, np.uint64), low_leaf=np.empty((n, 3, 32), np.uint8),
+                   is_largest=np.empty(n, np.uint8), root_before=np.empty((n, 32), np.uint8),
+                   root_after=np.empty((n, 32), np.uint8), new_leaf=np.empty((n, 3, 32), np.uint8),
+                   append_sib=np.empty((d, 32), np.uint8), root=np.empty(32, np.uint8))
+        if proofs:
+            res["low_sib"] = np.empty((n, d, 32) if item_major else (d, n, 32), np.uint8)
+        out = _ffi.BulkOut(**{k: a.ctypes.data for k, a in res.items()})
+        self.ctx._check(lib.imt_itree_view_bulk_witness(self.h, n, ctypes.byref(out),
+                                                        _ffi.SIB_ITEM_MAJOR if item_major else 0))
+        return res
+
     def mixed_witness(self, vals, ops, proofs=True, item_major=False, members=False):
         """The witnesses of a mixed block the tree applied at this view's size (imt_itree_view_mixed_witness): the
         (ins, rd) dicts IndexedTree.mixed_batch returns on a fresh tree fed the first size - 1 values.  The INSERTs of

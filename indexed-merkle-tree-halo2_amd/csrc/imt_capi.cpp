@@ -899,22 +899,7 @@ extern "C" int imt_frontier_append_root(imt_ctx* c, const void* sib, uint64_t st
     a.fsib = io.temp((size_t)depth * 32 + 32);
     a.idx = (uint64_t*)io.temp(16);
     if (io.rc) return io.rc;
-    hipStream_t s = c->stream;
-    const uint32_t coop = c->coop_max_events;
-    auto row = [&](unsigned l) { return a.rows + (a.off[l] + ((start >> l) & 1)) * 32; };     // the first node of the range at level l
-    if (leaf3) launch::hash_batch(s, d_leaf, row(0), n, 3, fmt, IMT_FMT_DEVICE, c->d_err, coop);
-    else launch::convert(s, d_leaf, row(0), n, fmt, IMT_FMT_DEVICE, c->d_err);
-    launch::frontier_bounds(s, a);
-    for (unsigned l = 0; l < a.top; l++) {
-        const uint64_t parents = ((start + n - 1) >> (l + 1)) - (start >> (l + 1)) + 1;
-        launch::tree_level(s, a.rows + a.off[l] * 32, row(l + 1), parents, coop);
-    }
-    const launch::SibLayout one{1, 1};
-    if (d_before)
-        launch::path_root(s, c->d_zero, nullptr, a.idx, false, a.fsib, one, depth, 1, d_before, nullptr, 0, nullptr, IMT_FMT_DEVICE,
-                          fmt, c->d_err, coop);
-    launch::path_root(s, row(a.top), nullptr, a.idx + 1, false, a.fsib + (size_t)a.top * 32, one, depth - a.top, 1, d_after, nullptr, 0,
-                      nullptr, IMT_FMT_DEVICE, fmt, c->d_err, coop);
+    launch::frontier_append(c->stream, a, d_leaf, leaf3 != nullptr, fmt, d_before, d_after, fmt, c->coop_max_events);
     return io.finish();
 }
 

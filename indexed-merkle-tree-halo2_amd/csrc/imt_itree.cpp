@@ -1579,6 +1579,8 @@ struct WitnessSweep {
     const view::Side* side = nullptr;             // NULL: base siblings below L0 are read from the stored tree as it is
     bool store = true;                            // levels written back, the nodes from L0 up and the root stored
     const uint8_t* view_root = nullptr;           // NULL: old_root[0] is the stored root; else the root in a view's chain
+    uint8_t* frontier = nullptr;                  // a bulk replay (imt_itree_view_bulk_witness): [depth][32] device format, where
+    uint64_t frontier_size = 0;                   // the final versions of the frontier of slot frontier_size are picked up
     PipeCtx pipe;                                 // imt_itree_insert_batch under IMT_PIPELINE, imt_itree_mixed_pipelined
 };
 
@@ -1695,6 +1697,10 @@ static int witness_sweep(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsi
         // or (at and above its L0) its top kernel
         if ((rc = pipe_wait(t, s, w.pipe, apipe::WITNESS, L0, {apipe::WI_LEVEL, l}))) return rc;
         sweep_one_level(t, P, s, l, E, d, lay, fmt, w);
+        // the versions of level l live until the launch after next: what the write-back would store of the frontier's node
+        if (w.frontier)
+            launch::bulk_frontier_level(s, w.frontier_size, l, P.d_val[l & 1], P.level(l).from, P.level(l).nodeb, (uint32_t)E,
+                                        w.frontier + (size_t)l * 32);
         if (!w.store) continue;
         pf = c->prof_begin(IMT_PROF_WRITEBACK, s);
         launch::writeback(s, P.d_val[l & 1], P.level(l).from, P.level(l).nodeb, t->nodes(l), (uint32_t)E);
@@ -1712,6 +1718,9 @@ static int witness_sweep(imt_itree* t, PlanSet& P, hipStream_t s, size_t E, unsi
         if (w.store && l + 1 == t->depth && (rc = old_root())) return rc;
         // the previous batch stored node l + 1 (and node l, at its own L0) from its launch of this level
         if ((rc = pipe_wait(t, s, w.pipe, apipe::WITNESS, L0, {apipe::WI_UPPER, l}))) return rc;
+        uint32_t last;      // node 0 of level L0 after the last event: what the live sweep stores through node_in
+        if (w.frontier && l == L0 && replay::frontier_top_version(w.frontier_size, L0, (uint32_t)E, last))
+            IMT_HIP(c, hipMemcpyAsync(w.frontier + (size_t)l * 32, P.d_val[l & 1] + (size_t)last * 32, 32, hipMemcpyDeviceToDevice, s));
         sweep_one_upper(t, P, s, l, E, L0, d, lay, fmt, w);
         if ((rc = pipe_record(t, s, P, w.pipe, apipe::WITNESS, L0, {apipe::WI_UPPER, l}))) return rc;
     }
@@ -2545,14 +2554,16 @@ static int bulk_append(imt_itree* t, PlanSet& P, hipStream_t s, uint64_t M, size
     t->apply_stats_set = nullptr;
     return IMT_OK;
 }
-static int bulk_deliver_outputs(imt_itree* t, hipStream_t s, const imt_bulk_out* o, const BulkDev& d, size_t n, unsigned flags) {
+// stored_root: d.root is the stored root, converted here; false: a replay's builder has written it there already
+static int bulk_deliver_outputs(imt_itree* t, hipStream_t s, const imt_bulk_out* o, const BulkDev& d, size_t n, unsigned flags,
+                                bool stored_root = true) {
     imt_ctx* c = t->ctx;
     const unsigned fmt = flags & IMT_FMT_MASK;
     if (fmt != IMT_FMT_CANONICAL) {
         if (d.hashfree.low_leaf) launch::convert(s, d.hashfree.low_leaf, d.hashfree.low_leaf, n * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
         if (d.hashfree.new_leaf) launch::convert(s, d.hashfree.new_leaf, d.hashfree.new_leaf, n * 3, IMT_FMT_CANONICAL, fmt, c->d_err);
     }
-    if (d.root) launch::convert(s, t->nodes(t->depth), d.root, 1, IMT_FMT_DEVICE, fmt, c->d_err);
+    if (d.root && stored_root) launch::convert(s, t->nodes(t->depth), d.root, 1, IMT_FMT_DEVICE, fmt, c->d_err);
     if (flags & IMT_DEVICE_PTRS) return IMT_OK;
     auto back = [&](void* user, const void* from, size_t bytes) -> int {
         if (user && from) IMT_HIP(c, hipMemcpyAsync(user, from, bytes, hipMemcpyDeviceToHost, s));
@@ -3642,6 +3653,104 @@ extern "C" int imt_itree_view_mixed_witness(imt_itree_view* v, const void* vals,
         return IMT_OK;
     }
     return view_replay_mixed(v, vals, op, n, ins, rd, n_inserted, bad_op, flags);
+}
+
+// The bulk witness of the n insertions that followed the view's size, behind view_enter and the argument
+// checks: imt_itree_insert_bulk's sequence with view_replay's differences.  The rows come from the view's index over the
+// values where they are, with no verdict to wait for; the sweep reads its base siblings as of the view's size and writes
+// nothing back, so the frontier of slot S is picked up between the level launches (imt_replay.hpp) instead of gathered from
+// the stored tree; and the append runs on borrowed scratch through imt_frontier_append_root's builder, whose root is the
+// root as of S + n.  No write-back, no stored root, no rotation of plan sets, no commit.
+static int view_replay_bulk(imt_itree_view* v, size_t n, const imt_bulk_out* out, unsigned flags) {
+    imt_itree* t = v->t;
+    imt_ctx* c = t->ctx;
+    const bool dev = flags & IMT_DEVICE_PTRS, item_major = flags & IMT_SIB_ITEM_MAJOR;
+    const unsigned fmt = flags & IMT_FMT_MASK;
+    const uint64_t S = v->size;
+    int rc;
+    if ((rc = view_behind_tree(t))) return rc;
+    hipStream_t s = c->stream;
+    PlanSet& P = v->plan;
+    if (P.cap_events < 2 * n || P.cap_levels < t->depth) IMT_HIP(c, hipStreamSynchronize(s));   // an earlier replay may still use it
+    if ((rc = plan_reserve(c, P, 2 * n, t->depth, t->cap))) return rc;
+    const ScratchTrim trim{c, 3, 4};        // the merged index and the append's rows: borrowed, like a build's scratch
+    uint32_t* merged = (uint32_t*)c->dev_scratch(3, (size_t)(S + n) * 4);
+    if (!merged) return IMT_ERR_HIP;
+
+    // ---- the append's scratch: the level builder's rows, its frontier and path indices, and the frontier as picked up ----
+    launch::FrontierArgs a{};
+    a.fmt_in = IMT_FMT_DEVICE;
+    a.err = c->d_err;
+    a.start = S;
+    a.n = n;
+    a.depth = t->depth;
+    a.zero = c->d_zero;
+    const size_t rows_bytes = (size_t)launch::frontier_rows(a) * 32, fsib_bytes = ((size_t)t->depth + 1) * 32;
+    uint8_t* scr = (uint8_t*)c->dev_scratch(4, rows_bytes + 2 * fsib_bytes + 16);
+    if (!scr) return IMT_ERR_HIP;
+    uint8_t* frontier = scr;
+    a.sib = frontier;
+    a.fsib = scr + fsib_bytes;
+    a.idx = (uint64_t*)(scr + 2 * fsib_bytes);
+    a.rows = scr + 2 * fsib_bytes + 16;
+
+    // ---- rows, events, tables, hash-free outputs: the batch sorted and its gaps against the view's index, then bulk_row ----
+    size_t slot = 5;
+    BulkDev d;
+    if (!bulk_stage_outputs(c, dev, slot, out, n, t->depth, d)) return IMT_ERR_HIP;
+    P.ws.part_mod = t->part_mod;
+    P.ws.part_res = t->part_res;
+    uint32_t* erow = P.d_slot;
+    IMT_HIP(c, prep::bulk_check(s, P.ws, nullptr, t->d_val, v->d_sorted, (uint32_t)S, (uint32_t)n));
+    IMT_HIP(c, prep::bulk_events(s, P.ws, t->d_val, v->d_sorted, merged, (uint32_t)S, (uint32_t)n, P.d_pre, P.d_tab[0][0],
+                                 P.d_tab[0][1], P.d_tab[0][2], P.d_tab[0][3], erow, d.hashfree));
+
+    // ---- the sweep over the levels the S leaves occupy, against the view, nothing written back or stored; the frontier
+    // starts as the view's and takes the final version of every node an event rewrote ----
+    const bool want_frontier = d.append_sib || d.root;
+    const launch::SibLayout lay = item_major ? launch::SibLayout{1, t->depth} : launch::SibLayout{n, 1};
+    const launch::MixedRoute route{erow, nullptr};
+    const view::Side side = v->side();
+    WitnessSweep w;
+    w.route = &route;
+    w.bulk = true;
+    w.side = &side;
+    w.store = false;
+    w.view_root = v->d_chain + (size_t)t->depth * 32;
+    if (want_frontier) {
+        launch::bulk_frontier_base(s, side, launch::TreeView{t->d_nodes, t->d_off, t->d_len, c->d_zero}, t->depth, frontier);
+        w.frontier = frontier;
+        w.frontier_size = S;
+    }
+    const unsigned L0_stored = std::min(ceil_log2(S), t->depth);
+    if ((rc = witness_sweep(t, P, s, n, L0_stored, d.sweep, lay, fmt, w))) return rc;
+
+    // ---- frontier and append ----
+    if (d.append_sib) launch::convert(s, frontier, d.append_sib, t->depth, IMT_FMT_DEVICE, fmt, c->d_err);
+    if (d.root)
+        launch::frontier_append(s, a, P.d_pre + n * 96, true, IMT_FMT_CANONICAL, nullptr, d.root, fmt, c->coop_max_events);
+    return bulk_deliver_outputs(t, s, out, d, n, flags, false);
+}
+
+extern "C" int imt_itree_view_bulk_witness(imt_itree_view* v, size_t n, const imt_bulk_out* out, unsigned flags) {
+    if (!view_alive(v)) return IMT_ERR_ARG;
+    imt_itree* t = v->t;
+    imt_ctx* c = t->ctx;
+    if (!out) return c->fail(IMT_ERR_ARG, "null outputs");
+    int rc;
+    if ((rc = check_mixed_mode(t, flags & ~(unsigned)(IMT_HOST_PREP | IMT_INPUTS_READY), BULK_BATCH))) return rc;
+    if ((rc = view_enter(v, flags))) return rc;
+    if (n == 0) return IMT_OK;
+    if (n > t->size - v->size)
+        return c->fail(IMT_ERR_RANGE, "the tree holds %llu leaves: no %zu insertions follow the view's %llu", (unsigned long long)t->size,
+                       n, (unsigned long long)v->size);
+    const bool dev = flags & IMT_DEVICE_PTRS;
+    if ((rc = check_fe_ptrs(c, dev, {out->low_leaf, out->root_before, out->root_after, out->low_sib, out->new_leaf, out->append_sib,
+                                     out->root})))
+        return rc;
+    if (dev && (((uintptr_t)out->order | (uintptr_t)out->low_index) & 7u))
+        return c->fail(IMT_ERR_ARG, "device order / low_index array is not 8-byte aligned");
+    return view_replay_bulk(v, n, out, flags & ~(unsigned)(IMT_HOST_PREP | IMT_INPUTS_READY));
 }
 
 extern "C" int imt_itree_view_stats(imt_itree_view* v, uint64_t* hashes, uint64_t* builds) {

@@ -1098,6 +1098,36 @@ __global__ void k_gather_frontier(launch::TreeView tv, uint64_t index, unsigned 
     store_fe(g_pc, out + (size_t)l * 32, x, fmt_out);
 }
 
+// The frontier behind a bulk replay (imt_itree_view_bulk_witness; the rule is in imt_replay.hpp), rows in device format.
+// Before the sweep: every row as no event had touched it -- the node as of the view's size where the sibling lies to the
+// left, zero[l] elsewhere.  One thread per level.
+__global__ void k_bulk_frontier_base(view::Side sd, launch::TreeView tv, unsigned depth, uint8_t* __restrict__ out) {
+    const unsigned l = threadIdx.x + blockIdx.x * blockDim.x;
+    if (l >= depth) return;
+    const uint8_t* zero_l = tv.zero + (size_t)l * 32;
+    const uint8_t* src = replay::frontier_base(sd.size, l) == replay::FRONTIER_VIEW
+                             ? view::node_row(sd, l, replay::frontier_node(sd.size, l), tv.nodes + tv.off[l] * 32, tv.len[l], zero_l)
+                             : zero_l;
+    const Word4* s = reinterpret_cast<const Word4*>(src);
+    Word4* d = reinterpret_cast<Word4*>(out + (size_t)l * 32);
+    d[0] = s[0];
+    d[1] = s[1];
+}
+// Between the level launches: k_writeback's pass over the tables of level l, keeping the one node the frontier has there
+// instead of storing them all.  val_l: the versions of level l, which the launch after next overwrites.  No hashing.
+__global__ void __launch_bounds__(BLOCK)
+k_bulk_frontier_level(uint64_t size, unsigned l, const uint8_t* __restrict__ val_l, const uint32_t* __restrict__ from,
+                      const uint32_t* __restrict__ node_below, uint32_t total, uint8_t* __restrict__ out_l) {
+    const size_t kp = gtid();
+    if (kp >= total) return;
+    uint32_t slot;
+    if (!replay::frontier_version(size, l, from[kp], node_below[kp], slot) || slot >= total) return;
+    const Word4* s = reinterpret_cast<const Word4*>(val_l + (size_t)slot * 32);
+    Word4* d = reinterpret_cast<Word4*>(out_l);
+    d[0] = s[0];
+    d[1] = s[1];
+}
+
 // The boundary of an append at `start` (imt_frontier_append_root), before its levels are hashed.  Row l of the level
 // builder holds nodes base_l = (start >> l) & ~1 .. ((start + n - 1) >> l) | 1 of level l at rows + off[l] * 32, so that
 // pairs of a row are siblings; this kernel fills what no hash will: slot 0 of row l with the caller's left-hand sibling
@@ -1923,6 +1953,16 @@ void emit_roots_bulk(hipStream_t s, const uint8_t* val, uint32_t total, uint8_t*
 void gather_frontier(hipStream_t s, TreeView tv, uint64_t index, unsigned depth, uint8_t* out, unsigned fmt_out) {
     if (!depth) return;
     hipLaunchKernelGGL(k_gather_frontier, dim3((depth + 63) / 64), dim3(64), 0, s, tv, index, depth, out, fmt_out);
+}
+void bulk_frontier_base(hipStream_t s, const view::Side& side, TreeView tv, unsigned depth, uint8_t* out) {
+    if (!depth) return;
+    hipLaunchKernelGGL(k_bulk_frontier_base, dim3((depth + 63) / 64), dim3(64), 0, s, side, tv, depth, out);
+}
+void bulk_frontier_level(hipStream_t s, uint64_t size, unsigned level, const uint8_t* val_l, const uint32_t* from,
+                         const uint32_t* node_below, uint32_t total, uint8_t* out_l) {
+    if (!total || !replay::frontier_left(size, level)) return;
+    hipLaunchKernelGGL(k_bulk_frontier_level, dim3(nblk(total)), dim3(BLOCK), 0, s, size, level, val_l, from, node_below, total,
+                       out_l);
 }
 uint64_t frontier_rows(FrontierArgs& a) {
     uint64_t total = 0;

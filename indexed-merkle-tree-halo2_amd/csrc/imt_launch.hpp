@@ -325,6 +325,36 @@ struct FrontierArgs {
 // fills a.top and a.off from a.start / a.n / a.depth; returns the nodes `rows` must hold
 uint64_t frontier_rows(FrontierArgs& a);
 void frontier_bounds(hipStream_t s, const FrontierArgs& a);
+// The builder both callers share (imt_frontier_append_root, imt_itree_view_bulk_witness), with a.rows / a.fsib / a.idx the
+// caller's scratch: the leaves into row 0 -- hash3 of leaf[n][3][32] if leaf3, else leaf[n][32] as they are, fmt_leaf --,
+// the boundary slots, one tree_level per level until one node is left, then that node's path into root_after and (unless
+// NULL) the path of Z[0] from `start` into root_before, both fmt_out.  Host code over the launchers above, nothing else.
+inline void frontier_append(hipStream_t s, const FrontierArgs& a, const uint8_t* leaf, bool leaf3, unsigned fmt_leaf,
+                            uint8_t* root_before, uint8_t* root_after, unsigned fmt_out, uint32_t coop_max) {
+    constexpr unsigned dev = 2u;      // the resident format of stored nodes (FMT_DEVICE, imt_device.hpp)
+    auto row = [&](unsigned l) { return a.rows + (a.off[l] + ((a.start >> l) & 1)) * 32; };   // the first node of the range at level l
+    if (leaf3) hash_batch(s, leaf, row(0), a.n, 3, fmt_leaf, dev, a.err, coop_max);
+    else convert(s, leaf, row(0), a.n, fmt_leaf, dev, a.err);
+    frontier_bounds(s, a);
+    for (unsigned l = 0; l < a.top; l++) {
+        const uint64_t parents = ((a.start + a.n - 1) >> (l + 1)) - (a.start >> (l + 1)) + 1;
+        tree_level(s, a.rows + a.off[l] * 32, row(l + 1), parents, coop_max);
+    }
+    const SibLayout one{1, 1};
+    if (root_before)
+        path_root(s, a.zero, nullptr, a.idx, false, a.fsib, one, a.depth, 1, root_before, nullptr, 0, nullptr, dev,
+                  fmt_out, a.err, coop_max);
+    path_root(s, row(a.top), nullptr, a.idx + 1, false, a.fsib + (size_t)a.top * 32, one, a.depth - a.top, 1, root_after, nullptr, 0,
+              nullptr, dev, fmt_out, a.err, coop_max);
+}
+// ---- the frontier behind a bulk replay (imt_itree_view_bulk_witness; the rule is in imt_replay.hpp) ----
+// out: [depth][32] device format.  bulk_frontier_base before the sweep: row l = the node as of the view's size where bit l
+// of side.size is set, zero[l] elsewhere.  bulk_frontier_level behind the launch that made the versions val_l of level l
+// (from / node_below: row l of the per-level tables, `total` slots) and before the launch after next overwrites them: the
+// final version of the frontier's node of level l into out_l, if an event made one; nothing where bit l of size is clear.
+void bulk_frontier_base(hipStream_t s, const view::Side& side, TreeView tv, unsigned depth, uint8_t* out);
+void bulk_frontier_level(hipStream_t s, uint64_t size, unsigned level, const uint8_t* val_l, const uint32_t* from,
+                         const uint32_t* node_below, uint32_t total, uint8_t* out_l);
 
 // ---- witnesses of a mixed block already applied (imt_itree_view_mixed_witness): both of the above at once ----
 // argument block of k_sweep_view_mixed: k_sweep_view's (a LEVEL launch below l0 and the view the base siblings are read as

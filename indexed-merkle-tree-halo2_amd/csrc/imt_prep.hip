@@ -870,8 +870,11 @@ hipError_t bulk_check(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t
     hipError_t e;
     if (n > ws.cap_n || temp_bytes_needed(n, (size_t)M) > ws.tmp_bytes) return hipErrorInvalidValue;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_scatter, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, d_val, M, n, ws.part_mod, ws.part_res, ws.iota,
-                       ws.err);
+    if (vals)
+        hipLaunchKernelGGL(k_scatter, dim3(nblk(n)), dim3(BLOCK), 0, s, vals, d_val, M, n, ws.part_mod, ws.part_res, ws.iota,
+                           ws.err);
+    else
+        hipLaunchKernelGGL(k_iota, dim3(nblk(n)), dim3(BLOCK), 0, s, M, n, ws.iota);
     size_t tb = ws.tmp_bytes;
     if ((e = rocprim::merge_sort(ws.tmp, tb, ws.iota, ws.bsorted, (size_t)n, ValLess{d_val}, s)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_gap, dim3(nblk(n)), dim3(BLOCK), 0, s, d_val, sorted_old, M, ws.bsorted, n, ws.gap, ws.st,

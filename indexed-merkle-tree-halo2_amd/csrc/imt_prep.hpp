@@ -136,6 +136,8 @@ struct BulkOut {              // device pointers, any may be NULL; rows k in pro
 };
 // 1. the values into rows [M, M + n) of d_val, the batch sorted (ws.bsorted), its gaps (ws.gap) and every check of the
 // values into ws.err, by the kernels run() checks an insertion batch with.  Writes nothing else of the tree, no output.
+// vals == NULL, as for run(): the values are rows [M, M + n) of d_val already (imt_itree_view_bulk_witness) -- no row of
+// d_val is written, and stored values leave the error word as it is.
 hipError_t bulk_check(hipStream_t s, Workspace& ws, const uint8_t* vals, uint8_t* d_val, const uint32_t* sorted_old, uint32_t M,
                       uint32_t n);
 // 2. behind it, the batch accepted (bulk_row, imt_prep_logic.hpp): event k = row k's rewrite of its low leaf -- preimages
