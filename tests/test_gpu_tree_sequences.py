@@ -20,6 +20,20 @@ loaded with the model's preimages; every comparison is bit-exact.
                            right before (code and bytes) and size, root() and snapshot() are what they were
   after a refused step     the error code; size, root() and the whole snapshot unchanged; of a mixed batch also *bad_op and,
                            with device pointers, that no output byte was written
+  the third pass           (kinds 14 to 20, tree_model._ThirdGenerator; the model is MemberModel)
+      14 insert_bulk       every field of imt_bulk_out = tests/bulk_model.py over the oracle's hashes, orc_verify_non_inclusion
+                           == 0 per row
+      16 / 17 / 18         n_inserted, n_read, status, leaf_index, bad_op from the model; INSERT rows = the oracle's rows of
+                           the accepted INSERTs alone, READ and MEMBER rows = one walk of the oracle over the operations
+                           carried out, rows beyond the counts and the outputs a call does not have untouched; root_out
+      15 / 18 pipelined    the verdict and the INSERT count at once; root_out and the rows of every batch left in flight are
+                           compared behind the next light or full check, each batch's own; a refused one leaves its
+                           buffers and the batches in flight alone
+      19 load_values       bad_pos on refusal; afterwards imt_itree_root_lagged has no root to give
+      20 reserve           imt_itree_capacity; imt_itree_root_lagged answers what it answered; the full check runs over
+                           the capacity the tree has now, the empty slots included
+  no check                 (third pass only, behind a pipelined call) nothing is called before the next step, not even
+                           size: that step enters with the batches before it still in flight
   light check              size and root(): neither touches the two copies of the list
   full check               size, root(), get_leaves of every slot (host and device pointers), snapshot(), the proof of
                            every slot, find_low of the probe set (host and device pointers) and its refusals, lookup,
@@ -33,7 +47,11 @@ import ctypes
 import numpy as np
 import pytest
 
+import bulk_model as bm
+import oracle_lib
+import test_gpu_bulk as tgb
 import test_gpu_insert_matrix as tm
+import test_gpu_member_reads as tgr
 import test_gpu_mixed as tgm
 import tree_model as tmod
 from oracle_lib import arr_ints, ints_to_arr
@@ -44,9 +62,12 @@ pytestmark = pytest.mark.gpu
 SCRIPTS = {s.name: s for s in tmod.scripts()}
 KIND_NAMES = {1: "insert_batch", 2: "insert_batch host_prep", 3: "insert_batch device pipelined", 4: "insert_filtered",
               5: "insert_filtered host_prep", 6: "apply_batch", 7: "apply_batch host_prep", 8: "apply_filtered", 9: "rewind",
-              10: "load", 12: "mixed_batch", 13: "mixed_batch READs only"}
+              10: "load", 12: "mixed_batch", 13: "mixed_batch READs only", 14: "insert_bulk", 15: "apply_pipelined",
+              16: "mixed_filtered", 17: "apply_mixed / apply_mixed_filtered", 18: "mixed_pipelined / apply_mixed_pipelined",
+              19: "load_values", 20: "reserve"}
 N_PROBES = 24
 FOREIGN_PROBES = (5, 6, 8, 9)          # of another residue on the partitioned tree (v % 3 != 1)
+SENT = tgm.SENTINEL
 
 
 def _cases():
@@ -54,6 +75,8 @@ def _cases():
     for shape_name in ("d32", "part3"):          # two of the scripts on the other two forms of the hash kernels as well
         name = next(s.name for s in tmod.scripts() if s.shape.name == shape_name)
         out += [pytest.param(name, form, id=f"{name}-{form}") for form in ("thread", "quad")]
+    name = tmod.third_pass_d32().name            # and one of the third pass: all seven newer kinds at depth 32
+    out += [pytest.param(name, form, id=f"{name}-{form}") for form in ("thread", "quad")]
     return out
 
 
@@ -83,7 +106,7 @@ class Player:
 
     def __init__(self, imt, c, script):
         import torch
-        self.imt, self.c, self.script, self.shape, self.torch = imt, c, script, script.shape, torch
+        self.imt, self.c, self.script, self.torch = imt, c, script, torch
         sh = script.shape
         self.t = t = imt.IndexedTree(c, sh.depth, sh.cap)
         if sh.placement:
@@ -94,8 +117,16 @@ class Player:
         self.base = tmod.index_base(sh)
         self.dv = DeviceBatches(imt, c, t, t.global_depth)
         self.in_flight = []                       # (device buffers, the oracle's rows, tag) of pipelined batches
+        self.grew, self.entered = False, (1, False)
+        self.piped = []                           # the comparisons owed for kinds 15 and 18 in flight: run behind the next check
         self.last_mixed = None                    # (size before, the INSERT rows, level-major) of the last kind-12 step
+        self.last_bulk = self.last_block = None   # the same of the last kind-14 step and of the last kind-16 / 18 witness block
         self.err_name = {v: k for k, v in imt._ffi.ERR.items()}
+
+    @property
+    def shape(self):
+        """the script's shape at the capacity the tree has now (a reserve step changes it): what the oracle is loaded at"""
+        return self.script.shape._replace(cap=self.m.cap)
 
     def close(self):
         self.dv.sync()
@@ -208,10 +239,15 @@ class Player:
         came = f" after kind {tmod.writer_kind(prev)} and a {prev.check} check" if prev else ""
         tag = f"{self.script.name} step {i} kind {tmod.writer_kind(st)} ({what}, size {m.size}){came}"
         before = tuple(m.vals)
+        quiet = prev is None or prev.check != tmod.NO_CHECK        # nothing in flight: calls before the step are allowed
+        self.entered = (len(before), self.grew)                    # for check(): did this step insert; did the one before
+        if st.kind in tmod.NEW_KINDS:
+            self.new_kind(i, st, before, tag)
+            return self.check(st, tag)
         mixed = st.kind in (tmod.MIXED, tmod.MIXED_READS)
         if mixed:
-            if st.kind == tmod.MIXED_READS:
-                lagged = self.root_lagged()
+            if st.kind == tmod.MIXED_READS:               # behind a step with no check nothing is called before this one
+                lagged = self.root_lagged() if quiet else None
             code, bad_op, n_ins, ins, rd, untouched = self.mixed_call(st)
             tag += f", {'device' if st.arg['device'] else 'host'} pointers, {'item' if st.arg['item_major'] else 'level'}-major"
         else:
@@ -254,14 +290,210 @@ class Player:
                     assert rc == 0 and arr_ints(np.frombuffer(root, np.uint8)) == [tmod.oracle_root(sh, after)], \
                         f"{tag}: imt_itree_root_lagged(0) returned {rc}, not the root after the batch"
                 else:                                     # READs only: a writer that changes nothing
-                    assert self.root_lagged() == lagged, f"{tag}: imt_itree_root_lagged(0) sees a batch of READs only"
+                    if lagged is None:
+                        lagged = self.lagged_behind_flight()
+                    assert lagged is None or self.root_lagged() == lagged, f"{tag}: imt_itree_root_lagged(0) sees a batch of READs only"
                     assert t.size == len(before) and t.root() == tmod.oracle_root(sh, before), f"{tag}: size or root changed"
                     assert (t.snapshot() == tmod.pre_arr(m.preimages(range(m.size)))).all(), f"{tag}: snapshot changed"
+        self.check(st, tag)
+
+    def check(self, st, tag):
+        """the check behind a step; the device outputs of the pipelined calls of kinds 15 and 18 are compared behind the
+        synchronisation it makes.  NO_CHECK: nothing is called, not even size"""
+        t, m = self.t, self.m
+        self.grew = not st.refusal and st.kind not in (9, 10, tmod.LOAD_VALUES, tmod.RESERVE) and m.size > self.entered[0]
+        if st.check == tmod.NO_CHECK:
+            return
         if st.check == tmod.FULL:
             self.full_check(tag)
         else:
             assert t.size == m.size, f"{tag}: size {t.size}, the model has {m.size}"
-            assert t.root() == tmod.oracle_root(sh, m.vals), f"{tag}: root()"
+            assert t.root() == tmod.oracle_root(self.shape, m.vals), f"{tag}: root()"
+        if self.piped:
+            self.dv.sync()
+            for settle in self.piped:
+                settle(tag)
+            self.piped = []
+
+    def lagged_behind_flight(self):
+        """what imt_itree_root_lagged(0) must answer in a step that entered behind batches in flight and changes nothing,
+        where the model knows it: the step before was a batch that inserted, so its root is the root of the list as it
+        is.  (code, bytes), or None where the step before inserted nothing."""
+        if not self.entered[1]:
+            return None
+        return 0, self.imt.to_bytes(tmod.oracle_root(self.shape, self.m.vals)).tobytes()
+
+    # ---- the kinds of the third pass ----
+    def unchanged(self, before, tag):
+        t, m = self.t, self.m
+        assert t.size == len(before) and t.root() == tmod.oracle_root(self.shape, before), f"{tag}: size or root changed"
+        assert (t.snapshot() == tmod.pre_arr(m.preimages(range(m.size)))).all(), f"{tag}: snapshot changed"
+        assert t.capacity == m.cap, f"{tag}: capacity {t.capacity}, the model has {m.cap}"
+
+    def refused_as(self, st, code, bad, tag):
+        """the model refuses the step as the library did: the code and bad_op / bad_pos"""
+        assert code == tmod.REFUSAL_CODE[st.refusal], f"{tag}: returned {code}"
+        with pytest.raises(tmod.Refused) as e:
+            tmod.play(self.m, st)
+        assert e.value.code == code and bad == e.value.bad_op, f"{tag}: bad position {bad}, the model stops at {e.value.bad_op}"
+
+    def block_rows(self, st, before, out, h, n_ins, n_rd, im, tag):
+        """INSERT rows = the oracle's rows of the accepted INSERTs alone, READ and MEMBER rows = one walk of the oracle over
+        the operations carried out, nothing written beyond the counts; returns the INSERT rows level-major"""
+        sh, n = self.shape, len(st.vals)
+        assert (n_ins, n_rd) == (len(out["acc"]), len(out["reads"])), f"{tag}: {n_ins} INSERTs, {n_rd} READs / MEMBERs"
+        tgr.same_rows(h["ins"], tmod.oracle_rows(sh, before, out["acc"]), n_ins, n, im, 0, f"{tag}: INSERT rows")
+        want = tmod.oracle_read_rows(sh, before, st, out["carried"])
+        assert [int(x) for x in want["low_index"]] == [r[1] for r in out["reads"]], tag
+        tgr.same_rows(h["rd"], want, n_rd, n, im, 0, f"{tag}: READ / MEMBER rows")
+        level_major = lambda d: {k: (a.transpose(1, 0, 2) if k.endswith("_sib") and im else a) for k, a in d.items()}
+        ins, rd = level_major(tgm.cut(h["ins"], n_ins, n, im)), level_major(tgm.cut(h["rd"], n_rd, n, im))
+        ins["new_index"] = np.arange(len(before), len(before) + n_ins, dtype=np.uint64)
+        return ins, rd
+
+    def new_kind(self, i, st, before, tag):
+        imt, t, m, k, torch = self.imt, self.t, self.m, st.kind, self.torch
+        f, lib, depth = imt._ffi, imt.lib, self.script.shape.depth
+        prev = self.script.steps[i - 1] if i else None
+        quiet = prev is None or prev.check != tmod.NO_CHECK        # nothing in flight: calls before the step are allowed
+        now = st.check != tmod.NO_CHECK
+        arr = ints_to_arr(st.vals) if st.vals is not None else None
+        if k == tmod.BULK:
+            n, im = len(st.vals), st.arg["item_major"]
+            tag += f", {'device' if st.arg['device'] else 'host'} pointers, {'item' if im else 'level'}-major"
+            r = tgb.Raw(imt, depth, n, im, st.arg["device"])
+            rc = r.call(t, arr, f.SIB_ITEM_MAJOR if im else 0)
+            if st.refusal:
+                self.refused_as(st, self.err_name[rc], None, tag)
+                assert r.untouched(), f"{tag}: a refused call wrote into an output buffer"
+                return self.unchanged(before, tag)
+            assert rc == 0, f"{tag}: refused with {rc}: {lib.imt_last_error(self.c.h)}"
+            tmod.play(m, st)
+            orc, res = oracle_lib.load(), r.host()
+            tgb.check_model(res, bm.bulk_witness(orc, depth, list(before), list(st.vals)), n, im, tag)
+            for j in range(n):                                    # the reference's relation on every row
+                helper = np.zeros((depth, 32), np.uint8)
+                helper[:, 0] = [1 - ((int(res["low_index"][j]) >> l) & 1) for l in range(depth)]
+                sib = res["low_sib"][j] if im else res["low_sib"][:, j]
+                fail, _ = orc.verify_non_inclusion(arr_ints(res["root_before"][j])[0], arr_ints(res["low_leaf"][j]), sib, helper,
+                                                   st.vals[int(res["order"][j])], int(res["is_largest"][j]))
+                assert fail == 0, f"{tag}: orc_verify_non_inclusion rejects row {j}: {fail}"
+            self.last_bulk = (len(before), res, im, st)
+        elif k == tmod.APPLY_PIPE:
+            d, root = self.dev(arr), torch.zeros(32, dtype=torch.uint8, device="cuda")
+            if st.arg["inputs_ready"]:
+                torch.cuda.current_stream().synchronize()         # the copy of the values is done; the batches in flight go on
+            flags = f.DEVICE_PTRS | (f.HOST_PREP if st.arg["host_prep"] else 0) | (f.INPUTS_READY if st.arg["inputs_ready"] else 0)
+            tag += f", {'IMT_HOST_PREP' if st.arg['host_prep'] else 'GPU prepare'}{', IMT_INPUTS_READY' if st.arg['inputs_ready'] else ''}"
+            rc = lib.imt_itree_apply_pipelined(t.h, _ptr(d), len(st.vals), _ptr(root), flags)
+            if st.refusal:
+                self.refused_as(st, self.err_name[rc], None, tag)
+                self.piped.append(lambda at, keep=d: self.same_bytes(root, bytes(32), f"{tag}, read at {at}: root_out of a refused batch"))
+                return self.unchanged(before, tag) if now else None
+            assert rc == 0, f"{tag}: refused with {rc}: {lib.imt_last_error(self.c.h)}"
+            tmod.play(m, st)
+            want = imt.to_bytes(tmod.oracle_root(self.shape, m.vals)).tobytes()
+            self.piped.append(lambda at, keep=d: self.same_bytes(root, want, f"{tag}, read at {at}: the batch's own root_out"))
+        elif k in (tmod.MIXED_FILT, tmod.APPLY_MIXED, tmod.MIXED_PIPE):
+            ops, n, members = list(st.arg["ops"]), len(st.vals), st.arg["members"]
+            if k == tmod.MIXED_FILT:
+                which, dev, im = "mixed_filtered", st.arg["device"], st.arg["item_major"]
+            elif k == tmod.APPLY_MIXED:
+                which, dev, im = ("apply_mixed_filtered" if st.arg["filtered"] else "apply_mixed"), False, False
+            else:
+                which, dev, im = ("apply_mixed_pipelined" if st.arg["apply"] else "mixed_pipelined"), True, False
+            tag += f", {which}, {'device' if dev else 'host'} pointers, {'item' if im else 'level'}-major{', IMT_MEMBER_OPS' if members else ''}"
+            lagged = self.root_lagged() if quiet and k != tmod.MIXED_PIPE else None
+            call = tgr.Call(imt, depth, n, dev, im)
+            rc = call.run(which, t.h, arr, ops, (f.SIB_ITEM_MAJOR if im else 0) | (f.MEMBER_OPS if members else 0), wait=k != tmod.MIXED_PIPE)
+            witness, filtered = which in ("mixed_filtered", "mixed_pipelined"), which.endswith("filtered")
+            if st.refusal:
+                bad = None if filtered or call.bad == tgr.UNSET else call.bad
+                self.refused_as(st, self.err_name[rc], bad, tag)
+                if filtered:                                      # the filtered twins: both counts 0 on every error
+                    assert (call.n_ins, call.n_rd) == (0, 0), f"{tag}: counts {call.n_ins}, {call.n_rd} of a refused call"
+                    assert self.err_name[rc] == "ARG", f"{tag}: only IMT_ERR_ARG leaves status and leaf_index untouched"
+                else:
+                    assert call.n_ins == tgr.UNSET, f"{tag}: n_inserted written by a refused call"
+                if k == tmod.MIXED_PIPE:
+                    self.piped.append(lambda at: self.all_untouched(call, f"{tag}, read at {at}"))
+                    return self.unchanged(before, tag) if now else None
+                self.all_untouched(call, tag)
+                return self.unchanged(before, tag)
+            assert rc == 0, f"{tag}: refused with {rc}: {lib.imt_last_error(self.c.h)}"
+            out = tmod.play(m, st)
+            after = tuple(m.vals)
+            assert call.n_ins == len(out["acc"]), f"{tag}: n_inserted {call.n_ins}"
+            assert filtered or call.bad == tgr.UNSET, f"{tag}: bad_op written by an accepted call"
+            want_root = imt.to_bytes(tmod.oracle_root(self.shape, after)).tobytes()
+
+            def outputs(at=None):
+                where = tag if at is None else f"{tag}, read at {at}"
+                h = call.host()
+                if filtered:
+                    assert call.n_rd == len(out["reads"]), f"{where}: n_read {call.n_rd}"
+                    assert h["extra"]["status"][:n].tolist() == out["status"], f"{where}: status"
+                    assert h["extra"]["leaf_index"][:n].tolist() == out["leaf"], f"{where}: leaf_index"
+                else:
+                    assert all((h["extra"][x].view(np.uint8) == SENT).all() for x in ("status", "leaf_index")), f"{where}: status written"
+                if witness:
+                    n_rd = call.n_rd if filtered else n - call.n_ins
+                    ins, rd = self.block_rows(st, before, out, h, call.n_ins, n_rd, im, where)
+                    assert (h["extra"]["root_out"] == SENT).all(), f"{where}: root_out written"
+                    self.last_block = (len(before), ins, rd, out, st)
+                else:
+                    assert h["extra"]["root_out"].tobytes() == want_root, f"{where}: root_out"
+                    assert all((a.view(np.uint8) == SENT).all() for x in ("ins", "rd") for a in h[x].values()), f"{where}: a witness row written"
+
+            if k == tmod.MIXED_PIPE:
+                self.piped.append(outputs)
+            else:
+                outputs()
+                if out["acc"]:
+                    assert self.root_lagged() == (0, want_root), f"{tag}: imt_itree_root_lagged(0) is not the root after the block"
+                elif lagged is not None:                          # nothing inserted: a writer that changes nothing
+                    assert self.root_lagged() == lagged, f"{tag}: imt_itree_root_lagged(0) sees a block without an INSERT"
+                    self.unchanged(before, tag)
+        elif k == tmod.LOAD_VALUES:
+            vals = tm.to_fmt(ints_to_arr(st.arg["vals"]), st.arg["fmt"])
+            tag += f", {'device' if st.arg['device'] else 'host'} pointers, format {st.arg['fmt']}, {len(vals)} values ({st.arg['source']})"
+            code, bad = None, None
+            try:
+                if st.arg["device"]:
+                    d = self.dev(vals)
+                    t.load_values_device(d.data_ptr(), vals.shape[0], st.arg["fmt"])
+                else:
+                    t.load_values(vals, st.arg["fmt"])
+            except ValueError as e:
+                code, bad = "VALUE", e.bad_pos
+            except imt.ImtError as e:
+                code, bad = self.err_name[e.code], e.bad_pos
+            if st.refusal:
+                self.refused_as(st, code, bad, tag)
+                return self.unchanged(before, tag)
+            assert code is None, f"{tag}: refused with {code}: {lib.imt_last_error(self.c.h)}"
+            tmod.play(m, st)
+            assert self.root_lagged()[0] != 0, f"{tag}: imt_itree_root_lagged has a root to give right after load_values"
+        else:
+            lagged = self.root_lagged() if quiet else None
+            code, _ = self.code_of(lambda: t.reserve(st.arg))
+            if st.refusal:
+                self.refused_as(st, code, None, tag)
+                return self.unchanged(before, tag)
+            assert code is None, f"{tag}: refused with {code}: {lib.imt_last_error(self.c.h)}"
+            tmod.play(m, st)
+            assert t.capacity == m.cap == st.arg, f"{tag}: capacity {t.capacity}"
+            if lagged is None:                                    # behind batches in flight there was no call to ask before:
+                lagged = self.lagged_behind_flight()              # the root of the batch before, where that batch inserted
+            if lagged is not None:
+                assert self.root_lagged() == lagged, f"{tag}: imt_itree_root_lagged answers something else behind reserve"
+
+    def same_bytes(self, dev_buf, want, what):
+        got = dev_buf.cpu().numpy().tobytes()
+        assert got == want, f"{what}: {got.hex()}, expected {want.hex()}"
+
+    def all_untouched(self, call, tag):
+        assert call.untouched(), f"{tag}: a refused call wrote into an output buffer"
 
     # ---- every reader ----
     def full_check(self, tag):
@@ -340,6 +572,6 @@ def test_sequence(imt, forms, name, form):
     try:
         for i, st in enumerate(script.steps):
             p.step(i, st)
-        assert not p.in_flight
+        assert not p.in_flight and not p.piped
     finally:
         p.close()

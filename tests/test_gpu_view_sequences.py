@@ -18,7 +18,11 @@ vals[:size] of whatever the model then holds; every comparison is bit-exact.
       root, a stored value and 0 refused
       insert_witness of the next min(size of the tree - size of the view, 16) insertions: all nine fields and new_index;
       sibling rows [depth, global_depth) keep the caller's pattern; one insertion more than the tree holds is refused;
-      where the replayed range holds a whole mixed batch that has just run, its rows there are that batch's INSERT rows
+      where the replayed range holds a whole mixed batch that has just run, its rows there are that batch's INSERT rows;
+      where it is exactly one insert_bulk batch that has just run, imt_itree_view_bulk_witness of it equals that step's
+      rows; where it is exactly one mixed_filtered / mixed_pipelined block, imt_itree_view_mixed_witness of the operations
+      carried out equals that step's INSERT and READ rows
+      behind a step with no check (third pass) there is no round and no view is made: the next step follows at once
       stats: the hashes per level by imt_itree_rewind's definition, and one rebuild exactly where tree_model.view_rounds
       says: the first answered round, and every answered round behind a step that changed the contents
       while the tree is smaller than the view: every query IMT_ERR_RANGE, no rebuild
@@ -36,6 +40,7 @@ import numpy as np
 import pytest
 
 import oracle_lib
+import test_gpu_bulk as tgb
 import test_gpu_replay as trp
 import test_gpu_rewind as tr
 import tree_model as tmod
@@ -205,6 +210,7 @@ class ViewPlayer(Player):
         self.every, self.n_rounds = every, 0
         self.views = {}                                           # size -> [view, rebuilds expected so far]
         self.n_whole_mixed = 0                                    # replays compared with a mixed batch's own INSERT rows
+        self.n_whole_bulk = self.n_whole_block = 0                # and with a bulk batch's / a witness block's own rows
         self.open(1)
 
     def open(self, s):
@@ -223,8 +229,8 @@ class ViewPlayer(Player):
             self.views.pop(s)[0].close()
         for s in created:
             self.open(s)
-        if i % self.every:
-            assert not self.rounds[i]
+        if i % self.every or st.check == tmod.NO_CHECK:             # NO_CHECK: nothing is called before the next step
+            assert not self.rounds[i] and (st.check != tmod.NO_CHECK or not (closed or created))
             return
         device = bool(self.n_rounds & 1)
         self.n_rounds += 1
@@ -254,6 +260,26 @@ class ViewPlayer(Player):
                     got = res[k][:, a:b] if k.endswith("_sib") else res[k][a:b]
                     assert got.shape == ins[k].shape and (got == ins[k]).all(), f"{tag}: the replay of the mixed batch's INSERTs: {k}"
                 self.n_whole_mixed += 1
+            n_new = self.m.size - r.size
+            if st.kind == tmod.BULK and not st.refusal and self.last_bulk[3] is st and r.size == self.last_bulk[0]:
+                # the replayed range is exactly the bulk batch that has just run: its bulk witness is that step's rows
+                _, rows, im, _ = self.last_bulk
+                res = ent[0].bulk_witness(n_new, item_major=im)
+                for k in tgb.FIELDS:
+                    assert res[k].shape == rows[k].shape and (res[k] == rows[k]).all(), f"{tag}: the bulk witness of the batch: {k}"
+                self.n_whole_bulk += 1
+            blk = self.last_block
+            if st.kind in (tmod.MIXED_FILT, tmod.MIXED_PIPE) and not st.refusal and blk is not None and blk[4] is st and \
+                    r.size == blk[0] and n_new == len(blk[3]["acc"]) > 0:
+                # exactly one witness block: the replay of the operations it carried out gives its INSERT and READ rows
+                _, ins, rd, out, _ = blk
+                carried = out["carried"]
+                res = ent[0].mixed_witness(ints_to_arr([st.vals[p] for p in carried]), [st.arg["ops"][p] for p in carried],
+                                           members=st.arg["members"])
+                for got, want, what in ((res[0], ins, "INSERT"), (res[1], rd, "READ")):
+                    for k, a in want.items():
+                        assert got[k].shape == a.shape and (got[k] == a).all(), f"{tag}: the replay of the block's {what} rows: {k}"
+                self.n_whole_block += 1
 
 
 @pytest.mark.parametrize("name,form", _cases())
@@ -263,7 +289,16 @@ def test_view_sequence(imt, forms, name, form):
     try:
         for i, st in enumerate(script.steps):
             p.step(i, st)
-        assert not p.in_flight
+        assert not p.in_flight and not p.piped
+        # the comparisons with a step's own rows ran wherever the model says a view's replayed range was that step
+        played = list(zip(tmod.trace(script), p.rounds))
+        exact = [st for (st, before, after, res), rnd in played for r in rnd
+                 if not st.refusal and r.prefix is not None and r.size == len(before) < len(after)]
+        assert p.n_whole_bulk == sum(st.kind == tmod.BULK for st in exact), name
+        assert p.n_whole_block == sum(st.kind == tmod.MIXED_FILT or (st.kind == tmod.MIXED_PIPE and not st.arg["apply"]) for st in exact), name
+        assert p.n_whole_mixed == sum(1 for (st, before, after, res), rnd in played for r in rnd
+                                      if st.kind == tmod.MIXED and not st.refusal and r.size <= len(before) and
+                                      r.size + r.n_replay >= len(after)), name
     finally:
         p.close()
 

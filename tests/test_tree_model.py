@@ -16,6 +16,16 @@ step scripts that tests/test_gpu_tree_sequences.py plays on the GPU.
                                    mixed batch in them, its refusals with bad_op, pointer modes and layouts, READs on a
                                    full tree, more operations than room, reads at size 1, READs whose rows change
                                    inside one batch, where the READ values come from).
+  test_second_pass_scripts_are_unchanged  the digest of the five scripts of the second pass.
+  test_third_pass_coverage         what the third pass (kinds 14 to 20) owes by itself: every ordered pair of new kinds at
+                                   both check levels, every pair of a new and an older kind at some level, every new kind
+                                   right after a refused call, the new refusals, all five shapes, FULL - reserve - the same
+                                   batch accepted on d3, every one of the 19 kinds entering behind two batches in flight
+                                   of two pipelined kinds, two runs of five or more pipelined steps with no check between
+                                   them and a refused step inside one, every variant of every new kind; at most 20 scripts
+                                   of at most 40 steps.
+  test_model_load_values_and_reserve  TreeModel.load_values of corpus prefixes against the oracle, its refusals and bad_pos;
+                                   TreeModel.reserve changes nothing but the capacity.
   test_scripts_are_self_consistent every accepted step accepted by the model, every refused one refused with its code.
   test_view_schedule               view_schedule() and view_rounds(): the rules of the schedule and of the expected rebuilds.
   test_view_coverage               what tests/test_gpu_view_sequences.py sees with that schedule on the committed scripts:
@@ -31,6 +41,7 @@ import pytest
 import insert_corpus as ic
 import oracle_lib
 import tree_model as tmod
+from member_model import MemberModel
 from oracle_lib import P, arr_ints, ints_to_arr
 from tree_model import FULL, KINDS, LIGHT, Refused, TreeModel
 
@@ -237,6 +248,16 @@ def test_first_pass_scripts_are_unchanged():
     assert hashlib.sha256(repr(tmod.scripts()[:9]).encode()).hexdigest() == FIRST_PASS_DIGEST
 
 
+SECOND_PASS_DIGEST = "06ce560b0c4124a5f77226a85110764fb18a95c6e82c1cbcba78ab62ad1355b4"
+
+
+def test_second_pass_scripts_are_unchanged():
+    """the five scripts of the second pass as they were before kinds 14 to 20 were played: byte for byte"""
+    import hashlib
+    assert (tmod.N_FIRST_PASS, tmod.N_OLD_PASSES) == (9, 14)
+    assert hashlib.sha256(repr(tmod.scripts()[9:14]).encode()).hexdigest() == SECOND_PASS_DIGEST
+
+
 def survey(scripts):
     """what a set of scripts covers"""
     cov = dict(pairs=set(), after_refusal=set(), refusals=set(), refused_kinds=set(), rewinds=set(), loads=set(),
@@ -275,6 +296,7 @@ def survey(scripts):
 def test_script_coverage():
     scripts = tmod.scripts()
     assert scripts is tmod.scripts() and len({s.name for s in scripts}) == len(scripts)
+    scripts = scripts[:tmod.N_OLD_PASSES]                          # the third pass: test_third_pass_coverage
     first, second = scripts[:tmod.N_FIRST_PASS], scripts[tmod.N_FIRST_PASS:]
     # ---- the first pass: the ten older kinds, as before the mixed batch existed
     cov = survey(first)
@@ -377,6 +399,187 @@ def test_script_coverage():
     print(f"{len(second)} scripts of the second pass, {sum(len(s.steps) for s in second)} steps, READ values {sources}")
 
 
+def test_third_pass_coverage():
+    """What the third pass owes by itself: kinds 14 to 20 among themselves and against the twelve older kinds, their
+    refusals, and what only a step without a check behind it brings about -- several pipelined batches in flight."""
+    from collections import Counter
+    NEW, ALL, NO = tmod.NEW_KINDS, tmod.KINDS19, tmod.NO_CHECK
+    assert NEW == tuple(range(14, 21)) and len(ALL) == 19
+    old, third = tmod.scripts()[:tmod.N_OLD_PASSES], tmod.scripts()[tmod.N_OLD_PASSES:]
+    assert all(st.check in (LIGHT, FULL) and st.kind <= 13 for s in old for st in s.steps), "NO_CHECK and the new kinds: third pass only"
+    assert len(third) <= 20 and all(len(s.steps) <= 40 for s in third)
+    pairs, after_refusal, followed, refusals, variants = set(), set(), Counter(), {}, set()
+    entered, runs, run_with_refusal, d3_story, ran = set(), 0, 0, False, set()
+    for s in third:
+        assert s.shape in tmod.THIRD_SHAPES and s.steps[-1].check == FULL, s.name
+        plain = not (s.shape.placement or s.shape.partition[0])
+        tr, fl, cp = tmod.trace(s), tmod.flights(s), tmod.caps(s)
+        assert isinstance(tmod.new_model(s.shape), MemberModel), "the third pass is played on MemberModel, not a bare TreeModel"
+        for i, (st, before, after, res) in enumerate(tr):
+            tag = f"{s.name} step {i} kind {tmod.writer_kind(st)}"
+            n_ops = len(st.vals) if st.vals is not None else 0
+            assert len(after) <= tmod.SIZE_LIMIT and n_ops <= 16 and cp[i] <= 1 << s.shape.depth, tag
+            if st.kind == tmod.LOAD_VALUES:                        # a value log is a whole tree, not a batch: like the snapshot of
+                n_log = len(st.arg["vals"])                        # kind 10 it is bounded by the size of a tree, not by 16
+                assert 1 <= n_log < tmod.SIZE_LIMIT and (not st.refusal or n_log <= 32), f"{tag}: a log of {n_log} values"
+            if st.check == NO:
+                assert st.kind in tmod.PIPELINED and i + 1 < len(tr), f"{tag}: no check only behind a pipelined call, never last"
+            if st.kind in tmod.PLAIN_ONLY and not plain:
+                assert st.refusal and res.code == "ARG", f"{tag}: refused on a placed or partitioned tree"
+            nxt = tr[i + 1][0] if i + 1 < len(tr) else None
+            if st.refusal:
+                refusals.setdefault(st.refusal, []).append((s, i, st, res))
+                if nxt is not None and not nxt.refusal:
+                    after_refusal.add(nxt.kind)
+            else:
+                followed[st.kind, st.check] += 1
+                ran.add((s.shape.name, st.kind))
+                if nxt is not None and not nxt.refusal:
+                    pairs.add((st.kind, nxt.kind, st.check))
+                if len(fl[i]) >= 2 and len(set(fl[i])) >= 2:
+                    entered.add(st.kind)
+                if st.kind == tmod.BULK:
+                    variants |= {("bulk", st.arg["device"], st.arg["item_major"])}
+                elif st.kind == tmod.APPLY_PIPE:
+                    variants |= {("apply_pipelined", st.arg["host_prep"], st.arg["inputs_ready"])}
+                elif st.kind == tmod.MIXED_FILT:
+                    variants |= {("mixed_filtered", "device", st.arg["device"]), ("mixed_filtered", "item_major", st.arg["item_major"]),
+                                 ("mixed_filtered", "members", tmod.OP_MEMBER in st.arg["ops"])}
+                elif st.kind == tmod.APPLY_MIXED:
+                    variants |= {("apply_mixed", st.arg["filtered"], tmod.OP_MEMBER in st.arg["ops"])}
+                elif st.kind == tmod.MIXED_PIPE:
+                    variants |= {("mixed_pipelined", st.arg["apply"], tmod.OP_MEMBER in st.arg["ops"])}
+                elif st.kind == tmod.LOAD_VALUES:
+                    n = len(st.arg["vals"]) + 1
+                    variants |= {("load_values", "device", st.arg["device"]), ("load_values", "fmt", st.arg["fmt"]),
+                                 ("load_values", st.arg["source"]),
+                                 ("load_values", "shorter" if n < len(before) else "longer" if n > len(before) else "same")}
+                elif st.kind == tmod.RESERVE:
+                    variants |= {("reserve", "grow" if st.arg > cp[i] else "shrink" if st.arg < cp[i] else "same")}
+                    if st.arg < cp[i]:
+                        assert st.arg == max(2, 1 << (len(before) - 1).bit_length()), f"{tag}: shrinks to the smallest legal capacity"
+            # FULL, then reserve, then the same batch accepted
+            if s.shape.depth == 3 and st.refusal and res.code == "FULL" and i + 2 < len(tr):
+                (r, _, _, rres), (again, _, _, ares) = tr[i + 1][:4], tr[i + 2][:4]
+                if r.kind == tmod.RESERVE and not r.refusal and r.arg > cp[i + 1] and not again.refusal and \
+                        (again.kind, again.vals) == (st.kind, st.vals):
+                    d3_story = True
+        # runs of pipelined steps with nothing between them
+        i = 0
+        while i < len(tr):
+            j, n_acc, n_ref = i, 0, 0
+            while j < len(tr) and tr[j][0].kind in tmod.PIPELINED and (j == i or tr[j - 1][0].check == NO):
+                n_acc, n_ref = n_acc + (not tr[j][0].refusal), n_ref + bool(tr[j][0].refusal)
+                j += 1
+            if n_acc >= 5:
+                runs += 1
+                run_with_refusal += bool(n_ref)
+            i = max(j, i + 1)
+    lv = (LIGHT, FULL)
+    missing = [(a, b, l) for l in lv for a in NEW for b in NEW if (a, b, l) not in pairs]
+    assert not missing, f"pairs of new kinds never adjacent: {missing}"
+    some = {(a, b) for a, b, _ in pairs}
+    missing = [(a, b) for a in ALL for b in ALL if (a in NEW) != (b in NEW) and (a, b) not in some]
+    assert not missing, f"a new and an older kind never adjacent: {missing}"
+    assert after_refusal >= set(NEW), f"never right after a refused call: {sorted(set(NEW) - after_refusal)}"
+    assert all(followed[k, l] >= 5 for k in NEW for l in lv), followed
+    assert set(refusals) >= set(tmod.NEW_REFUSALS), f"refusals that never occur: {sorted(set(tmod.NEW_REFUSALS) - set(refusals))}"
+    assert {s.shape for s in third} == set(tmod.THIRD_SHAPES) and [sh.name for sh in tmod.THIRD_SHAPES] == [sh.name for sh in tmod.SHAPES]
+    missing = [(sh.name, k) for sh in tmod.THIRD_SHAPES for k in NEW
+               if (k not in tmod.PLAIN_ONLY or not (sh.placement or sh.partition[0])) and (sh.name, k) not in ran]
+    assert not missing, f"new kinds never accepted on a shape they run on: {missing}"
+    assert d3_story, "FULL, then reserve, then the same batch accepted: never on d3"
+    assert entered >= set(ALL), f"kinds that never enter behind two batches in flight of two kinds: {sorted(set(ALL) - entered)}"
+    assert runs >= 2 and run_with_refusal >= 1, (runs, run_with_refusal)
+    # the refusals are what their names say
+    for name, found in refusals.items():
+        for s, i, st, res in found:
+            tag = f"{s.name} step {i}: {name}"
+            before = tmod.trace(s)[i][1]
+            if name in ("lv_zero", "lv_repeat", "lv_ge_p"):
+                vals, b = st.arg["vals"], res.bad_pos
+                off = [p for p, v in enumerate(vals) if v >= P or v == 0 or v in vals[:p]]
+                assert b == off[0] and (name != "lv_ge_p" or any(v >= P for v in vals)), tag
+            elif name == "lv_full":
+                assert len(st.arg["vals"]) + 1 > tmod.caps(s)[i] and res.bad_pos is None, tag
+            elif name == "member_absent":
+                b = res.bad_op
+                assert st.arg["members"] and st.arg["ops"][b] == tmod.OP_MEMBER and st.vals[b] not in before, tag
+                assert not any(o == tmod.OP_INSERT and v == st.vals[b] for o, v in zip(st.arg["ops"][:b], st.vals[:b])), tag
+            elif name == "op2_no_flag":
+                assert not st.arg["members"] and tmod.OP_MEMBER in st.arg["ops"], tag
+            elif name.startswith("reserve"):
+                size, depth = len(before), s.shape.depth
+                pow2 = st.arg & (st.arg - 1) == 0
+                assert dict(reserve_below=pow2 and 2 <= st.arg < size, reserve_npot=not pow2 and size <= st.arg <= 1 << depth,
+                            reserve_above=pow2 and st.arg > 1 << depth)[name], tag
+    want = {("bulk", d, im) for d in (False, True) for im in (False, True)} | \
+        {("apply_pipelined", h, r) for h in (False, True) for r in (False, True)} | \
+        {("mixed_filtered", what, x) for what in ("device", "item_major", "members") for x in (False, True)} | \
+        {(call, x, mem) for call in ("apply_mixed", "mixed_pipelined") for x in (False, True) for mem in (False, True)} | \
+        {("load_values", "device", False), ("load_values", "device", True), ("load_values", "fmt", 0), ("load_values", "fmt", 1),
+         ("load_values", "fmt", 2), ("load_values", "earlier"), ("load_values", "unrelated"), ("load_values", "shorter"),
+         ("load_values", "longer"), ("load_values", "same"), ("reserve", "grow"), ("reserve", "shrink"), ("reserve", "same")}
+    assert variants >= want, f"variants never played: {sorted(map(str, want - variants))}"
+    d32 = tmod.third_pass_d32()
+    assert d32.shape.depth == 32 and {st.kind for st in d32.steps if not st.refusal} >= set(NEW)
+    print(f"{len(third)} scripts of the third pass, {sum(len(s.steps) for s in third)} steps, {runs} runs of five or more pipelined steps")
+
+
+def test_model_load_values_and_reserve(oracle):
+    """load_values of a corpus prefix gives the corpus's root and preimages; reserve leaves every answer as it was; the
+    refusals of both with their codes and bad_pos."""
+    sc = next(s for s in ic.SCENARIOS if s.depth <= ic.ORACLE_MAX_DEPTH and len(ic.expected(s.name)["vals"]) <= 4096 and
+              len(ic.batch_bounds(s)) >= 2)
+    exp, bounds = ic.expected(sc.name), ic.batch_bounds(sc)
+    for j, (a, b) in enumerate(bounds):
+        m, ref = TreeModel(sc.depth, sc.cap, sc.index_base), TreeModel(sc.depth, sc.cap, sc.index_base)
+        m.insert(exp["vals"][:3])                                  # whatever it held before is gone
+        m.load_values(exp["vals"][:b])
+        ref.insert(exp["vals"][:b])
+        assert m.vals == ref.vals and m.order == ref.order and m.where == ref.where, (sc.name, j)
+        assert m.preimages(range(m.size)) == ref.preimages(range(ref.size)), (sc.name, j)
+        assert loaded_root(oracle, sc, m) == exp["batch_roots"][j + 1], (sc.name, j)
+    fin = exp["final"]
+    assert [x for p in m.preimages([int(i) - sc.index_base for i in fin["index"]]) for x in p] == arr_ints(fin["preimages"])
+    # reserve: nothing but the capacity
+    m = TreeModel(8, 64, 0, 3, 1)
+    mine = [v for v in oracle_lib.synth_values(200, 0x544D0002) if m.mine(v)]
+    m.insert(mine[:20])
+    probes = m.probes()
+    answers = lambda: (m.preimages(range(64)), [m.find_low(v) for v in probes], [m.lookup(v) for v in probes + mine[:25] + [0, 5]],
+                       [m.nm_witness(v) for v in probes], m.vals[:], m.size)
+    was = answers()
+    for cap in (32, 256, 128, 32, 32):
+        m.reserve(cap)
+        assert m.cap == cap and answers() == was, cap
+    for bad in (16, 8, 0, 1, 3, 48, 33, 512, 1 << 32):             # below the size (21), no power of two, above 2^depth
+        with pytest.raises(Refused) as e:
+            m.reserve(bad)
+        assert e.value.code == "RANGE" and m.cap == 32 and answers() == was, bad
+    with pytest.raises(Refused) as e:                              # 21 leaves + 12 > 32: FULL until the tree is reserved larger
+        m.insert(mine[30:42])
+    assert e.value.code == "FULL"
+    m.reserve(64)
+    m.insert(mine[30:42])
+    assert TreeModel(3, 8).reserve(8) is None and TreeModel(32, 8).reserve(1 << 31) is None
+    for bad in (16, 1 << 32):
+        with pytest.raises(Refused):
+            TreeModel(3, 8).reserve(bad)
+    # load_values: the refusals
+    m = TreeModel(8, 8, 0, 3, 1)
+    a, b, c, d = mine[50:54]
+    foreign = a + 1
+    for vals, code, pos in (([], "ARG", None), ([a, b, c, d] + mine[60:64], "FULL", None), ([a, 0, b, P], "NONCANONICAL", 1),
+                            ([a, P + 1, 0], "NONCANONICAL", 1), ([a, b, 0, a], "VALUE", 2), ([a, b, a, 0], "VALUE", 2),
+                            ([a, foreign, b], "VALUE", 1), ([0], "VALUE", 0), ([a, b, c, b, a], "VALUE", 3)):
+        with pytest.raises(Refused) as e:
+            m.load_values(vals)
+        assert (e.value.code, e.value.bad_pos) == (code, pos) and m.vals == [0], vals
+    m.load_values([a, b, c, d, mine[60], mine[61], mine[62]])       # n + 1 == capacity
+    assert m.size == 8
+
+
 @pytest.mark.parametrize("script", tmod.scripts(), ids=lambda s: s.name)
 def test_scripts_are_self_consistent(script):
     for i, (st, before, after, res) in enumerate(tmod.trace(script)):
@@ -395,6 +598,19 @@ def test_scripts_are_self_consistent(script):
                 ops = st.arg["ops"]
                 assert after == before + tuple(v for v, o in zip(st.vals, ops) if o == tmod.OP_INSERT), tag
                 assert len(res["reads"]) == ops.count(tmod.OP_READ) and (after == before) == (st.kind == tmod.MIXED_READS), tag
+            elif st.kind in (tmod.BULK, tmod.APPLY_PIPE):
+                assert after == before + tuple(st.vals), tag
+            elif st.kind in (tmod.MIXED_FILT, tmod.APPLY_MIXED, tmod.MIXED_PIPE):
+                ops, carried = st.arg["ops"], res["carried"]
+                assert len(ops) == len(st.vals) and max(ops) <= (2 if st.arg["members"] else 1), tag
+                assert after == before + tuple(st.vals[p] for p in carried if ops[p] == tmod.OP_INSERT) == before + tuple(res["acc"]), tag
+                assert len(res["reads"]) == sum(ops[p] != tmod.OP_INSERT for p in carried), tag
+                if "status" not in res:
+                    assert carried == list(range(len(ops))), tag
+            elif st.kind == tmod.LOAD_VALUES:
+                assert after == (0, ) + st.arg["vals"], tag
+            elif st.kind == tmod.RESERVE:
+                assert after == before, tag
             else:
                 assert after == tuple(p[0] for p in st.arg["pre"]), tag
 
@@ -439,7 +655,33 @@ def test_scripts_reach_the_states_of_the_two_copies():
                     seen.add(("load, device index stale", "refused" if st.refusal else "accepted"))
                 if not st.refusal:
                     mirror, dev = False, True
-            if st.check == FULL or st.refusal:
+            # the kinds of the third pass: bulk and the mixed calls are GPU-prepared, apply_pipelined either way,
+            # load_values commits into the device index and drops the mirror, reserve keeps whatever it finds
+            elif k in (tmod.BULK, tmod.MIXED_FILT, tmod.APPLY_MIXED, tmod.MIXED_PIPE) and st.refusal != "plain_only":
+                behind = tr[i - 1][0] if i else None
+                if k == tmod.BULK and not dev:
+                    seen.add(("bulk, device index stale", "refused" if st.refusal else "accepted"))
+                if k != tmod.BULK and not st.refusal and tmod.OP_MEMBER in st.arg["ops"] and behind is not None and behind.refusal \
+                        and (behind.kind in (2, 5, 7) or (behind.kind == tmod.APPLY_PIPE and behind.arg["host_prep"])):
+                    seen.add(("MEMBERs right behind a refused host-prepared call", ))
+                mirror, dev = mirror and not changed, True
+            elif k == tmod.APPLY_PIPE:
+                behind = tr[i - 1][0] if i else None
+                if st.arg["host_prep"]:
+                    if not st.refusal and behind is not None and not behind.refusal and behind.check == tmod.NO_CHECK and \
+                            (behind.kind in (3, tmod.MIXED_PIPE) or (behind.kind == tmod.APPLY_PIPE and not behind.arg["host_prep"])):
+                        seen.add(("host-prepared apply_pipelined right behind a GPU-prepared pipelined block", ))
+                    mirror, dev = True, dev and not changed
+                else:
+                    mirror, dev = mirror and not changed, True
+            elif k == tmod.LOAD_VALUES:
+                if not dev and not st.refusal:
+                    seen.add(("load_values, device index stale", ))
+                if not st.refusal:
+                    mirror, dev = False, True
+            elif k == tmod.RESERVE and not st.refusal:
+                seen.add(("reserve", mirror, dev))
+            if st.check == FULL or (st.refusal and st.check != tmod.NO_CHECK):
                 if st.check == FULL:
                     seen.add(("full check", mirror, dev))
                 if st.refusal:
@@ -453,7 +695,11 @@ def test_scripts_reach_the_states_of_the_two_copies():
             ("mixed batch, device index stale", tmod.MIXED, "accepted"), ("mixed batch, device index stale", tmod.MIXED_READS, "accepted"),
             ("mixed batch right behind a refused host-prepared call, device index stale", tmod.MIXED),
             ("mixed batch right behind a refused host-prepared call, device index stale", tmod.MIXED_READS),
-            ("READs only with the mirror valid: it stays valid", )}
+            ("READs only with the mirror valid: it stays valid", ),
+            ("bulk, device index stale", "accepted"), ("bulk, device index stale", "refused"),
+            ("load_values, device index stale", ), ("reserve", True, False), ("reserve", False, True), ("reserve", True, True),
+            ("host-prepared apply_pipelined right behind a GPU-prepared pipelined block", ),
+            ("MEMBERs right behind a refused host-prepared call", )}
     assert want <= seen, f"states the scripts never reach: {sorted(map(str, want - seen))}"
 
 
@@ -472,9 +718,11 @@ def test_view_schedule():
             for c in created:
                 assert c not in live and 1 <= c <= len(after), f"{tag}: a view is created at a size the tree has reached"
                 live.append(c)
-            assert len(live) <= tmod.MAX_VIEWS and [r.size for r in rnd] == live, tag
+            if st.check == tmod.NO_CHECK:                          # not one call between this step and the next: no round,
+                assert not rnd and not closed and not created, tag      # no view made; what it changed is due in the next round
+            assert len(live) <= tmod.MAX_VIEWS and [r.size for r in rnd] == (live if st.check != tmod.NO_CHECK else []), tag
             if tmod.changes_content(st, before, after, res):
-                assert after != before or st.kind == 10, tag
+                assert after != before or st.kind in (10, tmod.LOAD_VALUES), tag
                 builds_due = dict.fromkeys(builds_due, True)
             else:
                 assert after == before, tag
@@ -494,15 +742,15 @@ def view_coverage(scripts, rounds_of):
     """what the rounds of `rounds_of(script)` cover, as a dict of counters and sets"""
     from collections import Counter, defaultdict
     cov = dict(stale_by=defaultdict(Counter), transitions=Counter(), history=Counter(), origins=Counter(), crossings=0,
-               quiet=Counter(), whole_mixed=0)
+               quiet=Counter(), whole_mixed=0, exactly=Counter())
     for s in scripts:
         origin, state, answered = [0], {}, {}                     # who wrote leaf i; per view its last state and prefix
         just_answered = set()                                     # the views that answered in the round before
         for (st, before, after, res), rnd in zip(tmod.trace(s), rounds_of(s)):
             k = tmod.writer_kind(st)
-            if not isinstance(res, Refused):
-                origin = origin + [st.kind] * len(res["acc"]) if st.kind <= 8 or st.kind >= tmod.MIXED else origin[:st.arg] if st.kind == 9 else \
-                    [0] + [10] * (len(after) - 1)
+            if not isinstance(res, Refused) and st.kind != tmod.RESERVE:
+                origin = origin + [st.kind] * len(res["acc"]) if st.kind <= 8 or tmod.MIXED <= st.kind <= tmod.MIXED_PIPE else \
+                    origin[:st.arg] if st.kind == 9 else [0] + [st.kind] * (len(after) - 1)
             assert len(origin) == len(after)
             live = {r.size for r in rnd}
             state = {x: v for x, v in state.items() if x in live}
@@ -522,11 +770,16 @@ def view_coverage(scripts, rounds_of):
                 if r.size > 2 and (r.size - 1).bit_length() != (r.size + r.n_replay - 1).bit_length():
                     cov["crossings"] += 1                         # ceil_log2 of the size changes inside the replayed range
                 if not r.build and not tmod.changes_content(st, before, after, res) and st.kind != 9:
-                    cov["quiet"]["refused" if st.refusal else "accepted nothing"] += 1
-                    if st.kind >= tmod.MIXED and r.size in just_answered:      # fresh one round ago, and fresh still
+                    cov["quiet"]["refused" if st.refusal else "reserve" if st.kind == tmod.RESERVE else "accepted nothing"] += 1
+                    if st.kind in (tmod.MIXED, tmod.MIXED_READS) and r.size in just_answered:      # fresh one round ago, and fresh still
                         cov["quiet"]["refused mixed batch" if st.refusal else "READs only"] += 1
                 if k == tmod.MIXED and r.size <= len(before) and r.size + r.n_replay >= len(after):
                     cov["whole_mixed"] += 1                       # the replay covers every INSERT of the mixed batch
+                if r.size == len(before) < len(after):            # the replayed range is exactly what this step put in
+                    if k == tmod.BULK:
+                        cov["exactly"]["bulk"] += 1
+                    elif k == tmod.MIXED_FILT or (k == tmod.MIXED_PIPE and not st.arg["apply"]):
+                        cov["exactly"]["members" if tmod.OP_MEMBER in st.arg["ops"] else "block"] += 1
             just_answered = {r.size for r in rnd if r.prefix is not None}
     return cov
 
@@ -575,6 +828,24 @@ def test_view_coverage():
         by = {k for rnd in thin for r in rnd if r.build for k in r.since}
         assert by == set(KINDS), f"{s.name}: writer kinds no rebuilt view is stale by: {sorted(set(KINDS) - by)}"
         assert {r.state for rnd in thin for r in rnd} == set(states), s.name
+    # (h) the third pass by itself: every content-changing new kind makes a live answering view stale on every shape it
+    # runs on, reserve is followed by an answered round that must not rebuild, replays hold leaves of kinds 14 to 19
+    third = scripts[tmod.N_OLD_PASSES:]
+    cov3 = view_coverage(third, tmod.view_rounds)
+    for sh in tmod.THIRD_SHAPES:
+        plain = not (sh.placement or sh.partition[0])
+        runs = [k for k in tmod.NEW_KINDS if k != tmod.RESERVE and (plain or k not in tmod.PLAIN_ONLY)]
+        missing = [k for k in runs if not cov3["stale_by"][sh.name][k]]
+        assert not missing, f"{sh.name}: new kinds that never make a view stale: {missing}"
+        assert not cov3["stale_by"][sh.name][tmod.RESERVE], f"{sh.name}: reserve makes nothing stale"
+    assert cov3["quiet"]["reserve"] >= 5, cov3["quiet"]
+    # views whose replayed range is exactly one bulk batch / one witness block that has just run (with and without MEMBERs):
+    # there imt_itree_view_bulk_witness / _view_mixed_witness must give that step's own rows
+    assert all(cov3["exactly"][x] for x in ("bulk", "block", "members")), cov3["exactly"]
+    assert all(cov3["origins"][k] for k in tmod.NEW_KINDS if k != tmod.RESERVE), cov3["origins"]
+    s = tmod.third_pass_d32()
+    thin = tmod.view_rounds(s, tmod.VIEW_ROUNDS_OTHER_FORMS)
+    assert all(not rnd for rnd in thin[1::2]) and any(r.build for rnd in thin for r in rnd), s.name
     # the view at size 1 alone is not enough: the tree is never smaller than it, and it never sees another history
     alone = view_coverage(scripts, lambda s: [[r for r in rnd if r.size == 1] for rnd in tmod.view_rounds(s)])
     assert not any(tmod.SMALLER in pair for pair in alone["transitions"]) and not alone["history"]

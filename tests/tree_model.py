@@ -23,6 +23,17 @@ which a mixed batch takes part.  The writer kinds:
      device pointers in turn, the sibling layout       host and device pointers in turn
      changing at half that rate
 
+A third pass (THIRD_SEEDS, _ThirdGenerator; the first two passes are frozen by digest) plays the seven ways into the tree
+merged since, on MemberModel, every pair of them adjacent at both check levels and every pair with an older kind at some:
+  14 insert_bulk, host / device pointers, both layouts    18 mixed_pipelined / apply_mixed_pipelined, left in flight
+  15 apply_pipelined, left in flight, root_out on the     19 load_values, host / device, the three formats; a prefix of
+     device; IMT_HOST_PREP and IMT_INPUTS_READY in turn       an earlier state or unrelated values
+  16 mixed_filtered, host / device, layouts, MEMBERs      20 reserve: grow, shrink to the smallest legal capacity, the same
+  17 apply_mixed / apply_mixed_filtered, MEMBERs
+Kinds 14, 16, 17 and 18 are IMT_ERR_ARG on placed and partitioned trees and appear there as refusals only.  A step of
+the third pass may carry the check level NO_CHECK: the next step follows with no call in between, so that writers enter
+with several pipelined batches (kinds 3, 15, 18) still in flight.
+
 view_schedule() and view_rounds() say which views (imt_itree_view_*) tests/test_gpu_view_sequences.py keeps alive beside a
 script, what each answers after every step and when its cache must be rebuilt; the scripts themselves do not change.
 """
@@ -39,15 +50,28 @@ from oracle_lib import P, ints_to_arr
 NEW, ZERO, PRESENT, REPEATED, FOREIGN = 0, 1, 2, 3, 4        # IMT_VAL_*
 NONE = (1 << 64) - 1
 LIGHT, FULL = "light", "full"
+NO_CHECK = "none"                    # the third check level: the next step follows with no call in between (third pass only)
 KINDS = tuple(range(1, 11))          # the ten older writer kinds: what the first pass of scripts() plays
 REFUSED = 11
 MIXED, MIXED_READS = 12, 13
 ALL_KINDS = KINDS + (MIXED, MIXED_READS)
+BULK, APPLY_PIPE, MIXED_FILT, APPLY_MIXED, MIXED_PIPE, LOAD_VALUES, RESERVE = NEW_KINDS = tuple(range(14, 21))
+KINDS19 = ALL_KINDS + NEW_KINDS      # what the third pass of scripts() plays
+PIPELINED = (3, APPLY_PIPE, MIXED_PIPE)                 # left in flight until the next check or a synchronous call's own wait
+PLAIN_ONLY = (MIXED, MIXED_READS, BULK, MIXED_FILT, APPLY_MIXED, MIXED_PIPE)     # IMT_ERR_ARG on placed and partitioned trees
 OP_INSERT, OP_READ = 0, 1            # IMT_OP_*
+OP_MEMBER = 2                        # under IMT_MEMBER_OPS
+NEW_REFUSALS = ("bulk_stored", "bulk_repeat", "bulk_zero", "bulk_full", "bulk_ge_p", "pipe_stored", "pipe_full", "lv_zero",
+                "lv_repeat", "lv_ge_p", "lv_full", "reserve_below", "reserve_npot", "reserve_above", "member_absent",
+                "op2_no_flag", "plain_only")
 REFUSALS = ("stored", "repeat", "zero", "full", "ge_p", "broken_link", "rewind_past")
 REFUSAL_CODE = dict(stored="VALUE", repeat="VALUE", zero="VALUE", full="FULL", ge_p="NONCANONICAL", broken_link="VALUE",
                     rewind_past="RANGE", mixed_read_stored="VALUE", mixed_read_inserted_earlier="VALUE",
-                    mixed_insert_repeat="VALUE", mixed_full="FULL", mixed_ge_p="NONCANONICAL")
+                    mixed_insert_repeat="VALUE", mixed_full="FULL", mixed_ge_p="NONCANONICAL",
+                    bulk_stored="VALUE", bulk_repeat="VALUE", bulk_zero="VALUE", bulk_full="FULL", bulk_ge_p="NONCANONICAL",
+                    pipe_stored="VALUE", pipe_full="FULL", lv_zero="VALUE", lv_repeat="VALUE", lv_ge_p="NONCANONICAL",
+                    lv_full="FULL", reserve_below="RANGE", reserve_npot="RANGE", reserve_above="RANGE",
+                    member_absent="VALUE", op2_no_flag="ARG", plain_only="ARG")
 MIXED_REFUSALS = ("mixed_read_stored", "mixed_read_inserted_earlier", "mixed_insert_repeat", "mixed_full", "mixed_ge_p")
 REWIND_VARIANTS = ("interior", "size-1", "noop", "one")
 REWIND_ORDER = ("interior", "size-1", "interior", "noop", "interior", "one")
@@ -61,6 +85,8 @@ class Refused(Exception):
     def __init__(self, code, bad_op=None):
         super().__init__(code)
         self.code, self.bad_op = code, bad_op
+
+    bad_pos = property(lambda self: self.bad_op)       # of imt_itree_load_values
 
 
 class TreeModel:
@@ -189,6 +215,31 @@ class TreeModel:
             raise Refused("VALUE")
         self._reset(vals)
 
+    def reserve(self, new_cap):
+        """imt_itree_reserve: another capacity, nothing else.  RANGE unless new_cap is a power of two in [2, 2^31], at most
+        2^depth and at least the size."""
+        if not 2 <= new_cap <= 1 << 31 or new_cap & (new_cap - 1) or new_cap > 1 << self.depth or new_cap < self.size:
+            raise Refused("RANGE")
+        self.cap = new_cap
+
+    def load_values(self, vals):
+        """imt_itree_load_values: the model a fresh one becomes after insert(vals).  ARG for no values, FULL, then
+        NONCANONICAL before VALUE (a 0, a repeat, a foreign residue), both with bad_pos = the smallest position that is
+        >= p, 0, foreign or equal to a value at a smaller position (it rides in Refused.bad_op)."""
+        vals = list(vals)
+        if not vals:
+            raise Refused("ARG")
+        if len(vals) + 1 > self.cap:
+            raise Refused("FULL")
+        seen, bad = set(), []
+        for p, v in enumerate(vals):
+            if v >= P or v == 0 or not self.mine(v) or v in seen:
+                bad.append(p)
+            seen.add(v)
+        if bad:
+            raise Refused("NONCANONICAL" if any(v >= P for v in vals) else "VALUE", bad[0])
+        self._reset([0] + vals)
+
     # ---- readers ----
     def preimages(self, indices):
         """{val, next_val, next_idx} of local leaves `indices`: next_idx global, all zero at and beyond size"""
@@ -266,7 +317,8 @@ def index_base(shape):
 
 
 def new_model(shape, vals=None):
-    m = TreeModel(shape.depth, shape.cap, index_base(shape), *shape.partition)
+    from member_model import MemberModel       # TreeModel with IMT_OP_MEMBER and the filtered twins; it imports this module
+    m = MemberModel(shape.depth, shape.cap, index_base(shape), *shape.partition)
     if vals is not None:
         m._reset(vals)
     return m
@@ -292,6 +344,29 @@ def play(m, step):
     if k in (MIXED, MIXED_READS):
         acc, reads = m.mixed(step.vals, step.arg["ops"])
         return dict(acc=acc, reads=reads)
+    if k == BULK:                                              # the tree of insert_batch; refused where a mixed batch is
+        if m.index_base or m.part_mod > 1:
+            raise Refused("ARG")
+        m.insert(step.vals)
+        return dict(acc=list(step.vals))
+    if k == APPLY_PIPE:
+        m.insert(step.vals)
+        return dict(acc=list(step.vals))
+    if k in (MIXED_FILT, APPLY_MIXED, MIXED_PIPE):
+        ops, members = step.arg["ops"], step.arg["members"]
+        if k == MIXED_FILT or (k == APPLY_MIXED and step.arg["filtered"]):
+            if m.index_base or m.part_mod > 1 or any(op > (OP_MEMBER if members else OP_READ) for op in ops):
+                raise Refused("ARG")
+            status, leaf, carried, (acc, reads) = m.mixed_filtered(step.vals, ops)
+            return dict(acc=acc, reads=reads, status=status, leaf=leaf, carried=carried)
+        acc, reads = m.mixed(step.vals, ops, members)
+        return dict(acc=acc, reads=reads, carried=list(range(len(ops))))
+    if k == LOAD_VALUES:
+        m.load_values(step.arg["vals"])
+        return {}
+    if k == RESERVE:
+        m.reserve(step.arg)
+        return {}
     m.load(step.arg["pre"])
     return {}
 
@@ -325,11 +400,11 @@ def changes_content(st, before, after, res):
     any kind that accepted something (a mixed batch with an INSERT among them), a load, a rewind below the current size.
     A refused call, a filtered batch that accepted nothing, a mixed batch of READs only and a rewind to the current size
     do not."""
-    if isinstance(res, Refused):
+    if isinstance(res, Refused) or st.kind == RESERVE:         # another capacity is no other content
         return False
-    if st.kind <= 8 or st.kind in (MIXED, MIXED_READS):
-        return bool(res["acc"])
-    return st.arg < len(before) if st.kind == 9 else True
+    if st.kind <= 8 or st.kind in (MIXED, MIXED_READS, BULK, APPLY_PIPE, MIXED_FILT, APPLY_MIXED, MIXED_PIPE):
+        return bool(res["acc"])                                # a block of READs / MEMBERs only, or nothing carried out: no change
+    return st.arg < len(before) if st.kind == 9 else True      # load and load_values: always
 
 
 def view_schedule(script):
@@ -341,7 +416,7 @@ def view_schedule(script):
     live, out, made = [1], [], 0
     for i, (st, before, after, res) in enumerate(trace(script)):
         closed, created = (), ()
-        if i % VIEW_EVERY == 0 and not isinstance(res, Refused):
+        if i % VIEW_EVERY == 0 and not isinstance(res, Refused) and st.check != NO_CHECK:      # NO_CHECK: not one call
             M = len(after)
             s = M if made % 2 == 0 else 1 + (M - 1) // 2
             if s not in live:
@@ -373,7 +448,7 @@ def view_rounds(script, every=1):
         for s in created:
             stale[s], since[s] = True, ()
         M, rnd = len(after), []
-        for s in stale if i % every == 0 else ():
+        for s in stale if i % every == 0 and st.check != NO_CHECK else ():       # no round behind a NO_CHECK step either
             if M < s:                                             # answers nothing, builds nothing, stays as stale as it is
                 rnd.append(ViewRound(s, SMALLER, None, False, since[s], 0))
                 continue
@@ -809,7 +884,395 @@ class _MixedGenerator(_Generator):
         return Step(kind, name, tuple(vals), dict(ops=tuple(ops), device=bool(c & 1), item_major=bool((c >> 1) & 1)), None)
 
 
+THIRD_SHAPES = (Shape("d3", 3, 2, None, (0, 0)), Shape("d8", 8, 16, None, (0, 0)), Shape("d32", 32, 64, None, (0, 0)),
+                SHAPES[3], SHAPES[4])          # the plain shapes start below their capacity: reserve has room to grow them
+THIRD_ORDER = (1, 2, 0, 3, 4, 1, 2, 0, 1, 2, 0, 1, 2, 0, 1, 2, 0, 1, 2, 0)      # the shape of every script, into THIRD_SHAPES
+THIRD_SEEDS = (0x54500001, 0x54500002, 0x54500003, 0x54500004, 0x54500005, 0x54500006, 0x54500007, 0x54500008, 0x54500009,
+               0x5450000A, 0x5450000B, 0x5450000C, 0x5450000D, 0x5450000E, 0x5450000F, 0x54500010, 0x54500011, 0x54500012,
+               0x54500013, 0x54500014)
+THIRD_STEPS = 40
+MAX_CAP = 256                        # no reserve of the scripts grows a tree past this capacity
+RUN_KINDS = ((3, APPLY_PIPE, MIXED_PIPE, APPLY_PIPE, MIXED_PIPE, 3, APPLY_PIPE), (3, APPLY_PIPE, 3, APPLY_PIPE, APPLY_PIPE, 3, APPLY_PIPE))
+STATE_STORIES = ("bulk, device index stale", "refused bulk, device index stale", "load_values, device index stale",
+                 "reserve, mirror valid, device index stale", "reserve, mirror stale, device index valid",
+                 "reserve, both valid", "MEMBERs behind a refused host-prepared call")
+
+
+class _ThirdGenerator(_MixedGenerator):
+    """The third pass: the seven kinds merged since the mixed batch (14 to 20).  Every ordered pair of them at both check
+    levels, every pair of one of them and an older kind at some level, each right after a refused call, their refusals;
+    and what no check between two steps makes possible: batches of several pipelined kinds in flight when the next writer
+    enters, runs of pipelined steps long enough for the back-pressure of the fifth.  Seeds and scripts of its own."""
+
+    def __init__(self):
+        super().__init__()
+        new = NEW_KINDS
+        self.need = {(a, b, lv) for a in new for b in new for lv in (LIGHT, FULL)}
+        self.need_any = {(a, b) for a in KINDS19 for b in KINDS19 if (a in new) != (b in new)}
+        self.need11 = set(new)
+        self.refusals = list(NEW_REFUSALS)
+        self.stories, self.d3_reads_full = [], True
+        self.n_new = dict.fromkeys(new, 0)
+        self.need_flight = set(KINDS19)      # kinds that have yet to enter behind two batches in flight of two kinds
+        self.n_runs, self.run_refusals = 0, 0
+        self.d3_grown = False                # FULL, then reserve, then the same batch accepted
+        self.state_stories = list(STATE_STORIES)
+        self.n_flight_story = 0
+
+    def done(self):
+        return not (self.need or self.need_any or self.need11 or self.refusals or self.need_flight or self.state_stories) \
+            and self.n_runs >= 2 and self.run_refusals >= 1 and self.d3_grown
+
+    def left(self):
+        return dict(pairs=sorted(self.need), pairs_any=sorted(self.need_any), after_refusal=sorted(self.need11), refusals=self.refusals,
+                    flight=sorted(self.need_flight), states=self.state_stories, runs=self.n_runs, d3_grown=self.d3_grown)
+
+    # -- what can follow --
+    def feasible(self, k):
+        if k in PLAIN_ONLY and not self.plain:
+            return False
+        return self.room() >= 1 if k in (1, 2, 3, 6, 7, MIXED, BULK, APPLY_PIPE) else True
+
+    def refusal_feasible(self, name):
+        m, room = self.m, self.m.cap - self.m.size
+        if name not in NEW_REFUSALS:
+            return super().refusal_feasible(name)
+        if name in ("member_absent", "op2_no_flag") or name.startswith("bulk"):
+            if not self.plain:
+                return False
+        if name == "plain_only":
+            return not self.plain
+        if name in ("bulk_stored", "pipe_stored"):
+            return room >= 1 and m.size > 1
+        if name == "bulk_repeat":
+            return room >= 2
+        if name in ("bulk_zero", "bulk_ge_p"):
+            return room >= 1
+        if name in ("bulk_full", "pipe_full"):
+            return room + 1 <= 16
+        if name == "lv_full":
+            return m.cap <= 32
+        if name == "lv_repeat":
+            return m.cap >= 4
+        if name == "reserve_below":
+            return m.size >= 3
+        if name == "reserve_npot":
+            return self.npot() <= 1 << m.depth
+        if name == "reserve_above":
+            return m.depth <= 30
+        return True
+
+    def npot(self):
+        v = 3
+        while v < self.m.size:
+            v *= 2
+        return v
+
+    def owed(self, a, b, lv):
+        return (a, b, lv) in self.need or (a, b) in self.need_any
+
+    def out_degree(self, k, levels=(LIGHT, FULL)):
+        return sum(self.owed(k, b, lv) for b in KINDS19 if self.feasible(b) for lv in levels)
+
+    def level(self, k):
+        a, b = (sum((k, x, lv) in self.need for x in NEW_KINDS) for lv in (LIGHT, FULL))
+        return LIGHT if a > b else FULL if b > a else self.rng.choice((LIGHT, FULL))
+
+    def choose(self, prev, pos):
+        rng = self.rng
+        after_refusal = prev is not None and bool(prev.refusal)
+        feas = [k for k in KINDS19 if self.feasible(k)]
+        if self.room() < 4 and not after_refusal and prev is not None and prev.kind not in (9, RESERVE):
+            grows = self.m.cap * 2 <= min(1 << self.m.depth, MAX_CAP)          # make room first: reserve where it can grow
+            return (RESERVE if grows else 9), None
+        if prev is None:
+            cands = []
+        elif after_refusal:
+            cands = [k for k in feas if k in self.need11]
+        else:
+            lv = prev.check
+            cands = [k for k in feas if self.owed(prev.kind, k, lv)]
+        if prev is not None and not after_refusal and (self.refusals or self.need11) and (not cands or pos % 5 == 3):
+            names = [r for r in self.refusals if self.refusal_feasible(r)] or \
+                    [r for r in NEW_REFUSALS[self.n_refused % 17:] + NEW_REFUSALS[:self.n_refused % 17] if self.refusal_feasible(r)]
+            return None, names[0]
+        pool = cands or feas
+        best = max(self.out_degree(k) for k in pool)
+        if best == 0 and not cands and not after_refusal:      # nothing owed can follow from here
+            if self.room() < 16 and self.m.size > 8:
+                return 9, None                                 # what is owed may need room
+            return None, None                                  # this shape has given what it can: the script ends
+        return rng.choice([k for k in pool if self.out_degree(k) == best]), None
+
+    # -- the stories: steps in a fixed order, for what the pair coverage does not bring about --
+    def plan(self, prev, pos):
+        m, rng, left, room = self.m, self.rng, THIRD_STEPS - pos, self.room()
+        if prev is not None and prev.refusal:
+            return []
+        d3 = self.shape.depth == 3
+        if d3 and not self.d3_grown and m.cap < 8 and m.cap - m.size + 1 <= 8 and left >= 4:
+            self.d3_grown = True
+            kind, name = ((BULK, "bulk_full"), (APPLY_PIPE, "pipe_full"))[self.n_refused & 1]
+            vals = tuple(self.fresh(m.cap - m.size + 1))
+            return [dict(refusal=name, vals=vals), dict(kind=RESERVE, grow=True), dict(kind=kind, vals=vals)]
+        if not d3 and pos in (1, 2) and m.cap < 64:            # room for the runs and the stories below
+            return [dict(kind=RESERVE, grow=True)]
+        if not d3 and self.n_runs < 2 and pos >= 4 and left >= 11 and room >= 16 and m.size > 1:
+            kinds = RUN_KINDS[0 if self.plain else 1]
+            run = [dict(kind=k, small=True, check=NO_CHECK, host_prep=(i == 3)) for i, k in enumerate(kinds)]
+            del run[-1]["check"]
+            bad = dict(refusal="member_absent", kind=MIXED_PIPE, check=NO_CHECK) if self.plain and self.n_runs else \
+                dict(refusal="pipe_stored", check=NO_CHECK)
+            run.insert(4, bad)
+            self.n_runs += 1
+            self.run_refusals += 1
+            return run
+        if pos % 5 == 1 and pos >= 3 and left >= 5 and room >= 6:
+            todo = sorted(k for k in self.need_flight if k not in PIPELINED and self.feasible(k))
+            if todo:
+                pipes = [k for k in PIPELINED if self.feasible(k)]
+                c = self.n_flight_story
+                self.n_flight_story += 1
+                a, b = pipes[c % len(pipes)], pipes[(c + 1) % len(pipes)]
+                new = [k for k in todo if k in NEW_KINDS]
+                return [dict(kind=a, small=True, check=NO_CHECK), dict(kind=b, small=True, check=NO_CHECK), dict(kind=(new or todo)[0])]
+        if pos % 5 == 0 and pos >= 5 and left >= 5 and room >= 8 and m.size > 2:
+            for name in self.state_stories:
+                i = STATE_STORIES.index(name)
+                if i in (0, 1, 6) and not self.plain:
+                    continue
+                self.state_stories.remove(name)
+                host = dict(kind=(2, 7)[pos & 1], check=LIGHT)
+                self.host_side = True
+                return [[host, dict(kind=BULK)], [host, dict(refusal="bulk_stored")], [host, dict(kind=LOAD_VALUES)],
+                        [host, dict(kind=RESERVE)], [dict(kind=6, check=LIGHT), dict(kind=RESERVE)],
+                        [dict(kind=2, check=FULL), dict(kind=RESERVE)],
+                        [host, dict(refusal="stored", check=LIGHT), dict(kind=(MIXED_FILT, APPLY_MIXED, MIXED_PIPE)[pos % 3], members=True)]][i]
+        return []
+
+    # -- the steps --
+    def make_block(self, n_ins, n, members, noisy, top):
+        """(vals, ops) of a block the unfiltered calls accept: n_ins INSERTs of fresh values, READs of absent ones and,
+        with members, MEMBERs of values stored or inserted earlier in the block.  noisy: up to three operations more that
+        a filtered twin skips -- a 0, a stored value, a value an earlier INSERT of the block put in, a MEMBER of an absent one."""
+        m, rng = self.m, self.rng
+        new = self.fresh(n_ins)
+        ops = [OP_INSERT] * n_ins + [rng.choice((OP_READ, OP_MEMBER)) if members else OP_READ for _ in range(n - n_ins)]
+        rng.shuffle(ops)
+        vals, inserted, read, later = [], [], [], list(new)
+        for i, op in enumerate(ops):
+            there = m.vals[1:] + inserted
+            if op == OP_INSERT:
+                v = later.pop(0)
+                inserted.append(v)
+            elif op == OP_MEMBER and there:
+                v = rng.choice(there)
+            else:
+                ops[i] = OP_READ
+                v = self.read_value(inserted, later, read)
+                read.append(v)
+            vals.append(v)
+        for _ in range(rng.randint(1, 3) if noisy else 0):
+            if len(vals) >= top:
+                break
+            at, r = rng.randint(0, len(vals)), rng.random()
+            earlier = [v for v, o in zip(vals[:at], ops[:at]) if o == OP_INSERT]
+            any_op = rng.choice((OP_INSERT, OP_READ, OP_MEMBER) if members else (OP_INSERT, OP_READ))
+            if r < 0.3:
+                bad = (any_op, 0)
+            elif r < 0.6 and m.size > 1:
+                bad = (rng.choice((OP_INSERT, OP_READ)), rng.choice(m.vals[1:]))
+            elif r < 0.85 and earlier:
+                bad = (rng.choice((OP_INSERT, OP_READ)), rng.choice(earlier))
+            elif members:
+                bad = (OP_MEMBER, self.fresh(1, vals)[0])
+            else:
+                bad = (OP_READ, 0)
+            ops.insert(at, bad[0])
+            vals.insert(at, bad[1])
+        return vals, ops
+
+    def make_load_values(self):
+        m, rng, c = self.m, self.rng, self.n_new[LOAD_VALUES] - 1
+        length, source = ("shorter", "longer", "same")[c % 3], ("earlier", "unrelated")[(c >> 2) & 1]
+        cur, top = m.size, min(m.cap, SIZE_LIMIT)
+        span = dict(shorter=(2, cur - 1), longer=(cur + 1, min(top, cur + 24)), same=(max(cur, 2), min(cur, top)))[length]
+        if span[0] > span[1]:
+            span = (2, min(top, 12))
+        vals = None
+        if source == "earlier":                                # a prefix of an earlier state, not of the present one
+            states = [s for s in self.history if len(s) >= span[0] and s[:span[0]] != tuple(m.vals[:span[0]])]
+            if states:
+                s = rng.choice(states)
+                vals = list(s[1:rng.randint(span[0], min(span[1], len(s)))])
+        if vals is None:
+            source = "unrelated"
+            vals = [self.other.pop() for _ in range(rng.randint(*span) - 1)]
+        return dict(vals=tuple(vals), device=bool(c & 1), fmt=(c >> 1) % 3, source=source)
+
+    def make_reserve(self, grow):
+        m, c = self.m, self.n_new[RESERVE] - 1
+        lo, hi = max(2, 1 << (m.size - 1).bit_length()), min(1 << m.depth, MAX_CAP)
+        order = ("grow", "shrink", "same")
+        order = order[c % 3:] + order[:c % 3]
+        if grow or (self.room() < 4 and m.cap < hi):
+            order = ("grow", ) + order
+        for v in order:
+            if v == "grow" and m.cap * 2 <= hi:
+                return m.cap * 2
+            if v == "shrink" and lo < m.cap:
+                return lo
+            if v == "same":
+                return m.cap
+
+    def make(self, kind, refusal, item=None):
+        item = item or {}
+        if refusal:
+            return self.make_refusal(refusal, item)
+        m, rng, room = self.m, self.rng, self.room()
+        small = item.get("small")
+        if kind in NEW_KINDS:
+            c = self.n_new[kind]
+            self.n_new[kind] += 1
+        if kind == 3 and small:
+            return Step(3, None, tuple(self.fresh(rng.randint(1, 2))), None, None)
+        if kind in (BULK, APPLY_PIPE):
+            vals = item.get("vals") or tuple(self.fresh(rng.randint(1, min(2 if small else 16, room))))
+            arg = dict(device=bool(c & 1), item_major=bool((c >> 1) & 1)) if kind == BULK else \
+                dict(host_prep=item.get("host_prep", bool(c & 1)), inputs_ready=bool((c >> 1) & 1))
+            return Step(kind, None, vals, arg, None)
+        if kind in (MIXED_FILT, APPLY_MIXED, MIXED_PIPE):
+            members = item.get("members", bool(c & 1))
+            if kind == MIXED_FILT:
+                arg, noisy = dict(device=bool((c >> 1) & 1), item_major=bool((c >> 2) & 1)), True
+            elif kind == APPLY_MIXED:
+                arg = dict(filtered=bool((c >> 1) & 1))
+                noisy = arg["filtered"]
+            else:
+                arg, noisy = dict(apply=bool((c >> 1) & 1)), False
+            top = MIXED_MAX_OPS[self.shape.depth]
+            n = rng.randint(1, 3 if small else top - 3 * noisy)
+            n_ins = rng.randint(1 if small and room else 0, min(room, n, 8))
+            vals, ops = self.make_block(n_ins, n, members, noisy, top)
+            arg.update(ops=tuple(ops), members=members)
+            return Step(kind, None, tuple(vals), arg, None)
+        if kind == LOAD_VALUES:
+            return Step(kind, None, None, self.make_load_values(), None)
+        if kind == RESERVE:
+            return Step(kind, None, None, self.make_reserve(item.get("grow")), None)
+        return super().make(kind, None)
+
+    def make_refusal(self, name, item=None):
+        item = item or {}
+        if name not in NEW_REFUSALS:
+            return super().make_refusal(name)
+        m, rng = self.m, self.rng
+        self.n_refused += 1
+        c, room = self.n_refused, m.cap - m.size
+        if name == "plain_only":
+            kind = (BULK, MIXED_FILT, APPLY_MIXED, MIXED_PIPE)[c % 4]
+            vals = tuple(self.fresh(1))
+            arg = dict(device=bool(c & 1), item_major=False) if kind == BULK else dict(ops=(OP_INSERT, ), members=bool(c & 2))
+            arg.update({MIXED_FILT: dict(device=bool(c & 1), item_major=False), APPLY_MIXED: dict(filtered=bool(c & 1)),
+                        MIXED_PIPE: dict(apply=bool(c & 1))}.get(kind, {}))
+            return Step(kind, name, vals, arg, None)
+        if name.startswith(("bulk", "pipe")):
+            kind, what = (BULK if name.startswith("bulk") else APPLY_PIPE), name.split("_", 1)[1]
+            if what == "full":
+                vals = list(item.get("vals") or self.fresh(room + 1))
+            else:
+                good = self.fresh(min(rng.randint(2, 5), room) - 1)
+                bad = dict(stored=lambda: rng.choice(m.vals[1:]), repeat=lambda: rng.choice(good), zero=lambda: 0,
+                           ge_p=lambda: P + rng.randrange(3))[what]()
+                vals = good + [bad]
+                rng.shuffle(vals)
+            arg = dict(device=bool(c & 1), item_major=bool(c & 2)) if kind == BULK else dict(host_prep=bool(c & 1), inputs_ready=False)
+            return Step(kind, name, tuple(vals), arg, None)
+        if name.startswith("lv"):
+            if name == "lv_full":
+                vals = [self.other.pop() for _ in range(m.cap)]
+            else:
+                vals = [self.other.pop() for _ in range(min(rng.randint(3, 8), m.cap - 1) - 1)]
+                bad = dict(lv_zero=lambda: 0, lv_repeat=lambda: rng.choice(vals), lv_ge_p=lambda: P + rng.randrange(3))[name]()
+                vals.insert(rng.randint(1 if name == "lv_repeat" else 0, len(vals)), bad)
+                if name == "lv_ge_p" and len(vals) + 2 <= m.cap:       # a 0 as well: still NONCANONICAL, bad_pos the smaller
+                    vals.insert(rng.randint(0, len(vals)), 0)
+            return Step(LOAD_VALUES, name, None, dict(vals=tuple(vals), device=bool(c & 1), fmt=0 if name == "lv_ge_p" else c % 3,
+                                                      source="refused"), None)
+        if name.startswith("reserve"):
+            cap = dict(reserve_below=lambda: max(2, 1 << ((m.size - 1).bit_length() - 1)), reserve_npot=self.npot,
+                       reserve_above=lambda: 2 << m.depth)[name]()
+            return Step(RESERVE, name, None, cap, None)
+        kind = item.get("kind") or ((APPLY_MIXED, MIXED_PIPE) if name == "member_absent" else (MIXED_FILT, APPLY_MIXED, MIXED_PIPE))[c % (2 if name == "member_absent" else 3)]
+        top = MIXED_MAX_OPS[self.shape.depth]
+        n = rng.randint(2, 5)
+        vals, ops = self.make_block(rng.randint(0, min(room, n, 3)), n, True, False, top)
+        if name == "member_absent":
+            at = rng.randint(0, len(ops))
+            ops.insert(at, OP_MEMBER)
+            vals.insert(at, self.fresh(1, vals)[0])
+        elif OP_MEMBER not in ops:
+            ops.append(OP_MEMBER)
+            vals.append(vals[0])
+        arg = dict(ops=tuple(ops), members=name == "member_absent")
+        arg.update({MIXED_FILT: dict(device=bool(c & 1), item_major=bool(c & 2)), APPLY_MIXED: dict(filtered=name != "member_absent" and bool(c & 1)),
+                    MIXED_PIPE: dict(apply=bool(c & 1))}[kind])
+        return Step(kind, name, tuple(vals), arg, None)
+
+    def script(self, number, shape, seed):
+        self.shape, self.rng, self.m = shape, random.Random(seed), new_model(shape)
+        self.plain = not (shape.placement or shape.partition[0])
+        own = lambda s, n: [v for v in oracle_lib.synth_values(n, s) if self.m.mine(v)]
+        self.pool, self.other = own(seed, 1500), own(seed ^ 0x00FF0000, 2400)
+        self.specials, self.history = [], [tuple(self.m.vals)]
+        self.stale_refusal = self.host_side = False
+        steps, prev, queue, flight, stuck = [], None, [], [], 0
+        while len(steps) < THIRD_STEPS and not (self.done() and len(steps) >= 8 and not queue):
+            queue = queue or self.plan(prev, len(steps))
+            if queue:
+                item = queue.pop(0)
+            else:
+                kind, refusal = self.choose(prev, len(steps))
+                if kind is None and refusal is None:
+                    if len(steps) >= 8:
+                        break
+                    kind = self.rng.choice([k for k in NEW_KINDS if self.feasible(k)])
+                item = dict(kind=kind, refusal=refusal)
+            if not self.feasible(item["kind"]) if not item.get("refusal") else not self.refusal_feasible(item["refusal"]):
+                queue, stuck = [], stuck + 1                   # the story has run out of room: drop the rest of it
+                assert stuck < 100, f"the third pass does not reach its coverage: {item} cannot be played"
+                continue
+            st = self.make(item.get("kind"), item.get("refusal"), item)
+            if st.refusal:
+                check = item.get("check") or self.refusal_level()
+                self.refusals = [r for r in self.refusals if r != st.refusal]
+                if st.kind not in PIPELINED:
+                    flight = []
+            else:
+                check = item.get("check") or self.level(st.kind)
+                if prev is not None and prev.refusal:
+                    self.need11.discard(st.kind)
+                elif prev is not None:
+                    self.need.discard((prev.kind, st.kind, prev.check))
+                    self.need_any.discard((prev.kind, st.kind))
+                if len(flight) >= 2 and len(set(flight)) >= 2:
+                    self.need_flight.discard(st.kind)
+                play(self.m, st)
+                self.history.append(tuple(self.m.vals))
+                flight = flight + [st.kind] if st.kind in PIPELINED else []
+            if check != NO_CHECK:
+                flight = []
+            st = st._replace(check=check)
+            steps.append(st)
+            prev = st
+            if not queue:
+                self.host_side = False
+        steps[-1] = steps[-1]._replace(check=FULL)
+        return Script(f"{shape.name}_{number:02d}", shape, tuple(steps))
+
+
 N_FIRST_PASS = 9                     # scripts of the first pass: the record of what ran before the mixed batch existed
+N_OLD_PASSES = 14                    # scripts of the first two passes: the record of what ran before kinds 14 to 20 did
 _SCRIPTS = None
 
 
@@ -827,8 +1290,48 @@ def scripts():
             k = len(out) - N_FIRST_PASS
             assert k < len(MIXED_SEEDS), "the second pass does not reach its coverage"
             out.append(g.script(len(out), MIXED_SHAPES[k % len(MIXED_SHAPES)], MIXED_SEEDS[k]))
+        assert len(out) == N_OLD_PASSES
+        g = _ThirdGenerator()
+        while not g.done() or len(out) - N_OLD_PASSES < len(THIRD_SHAPES):
+            k = len(out) - N_OLD_PASSES
+            assert k < len(THIRD_SEEDS), f"the third pass does not reach its coverage: {g.left()}"
+            out.append(g.script(len(out), THIRD_SHAPES[THIRD_ORDER[k]], THIRD_SEEDS[k]))
         _SCRIPTS = tuple(out)
     return _SCRIPTS
+
+
+def third_pass_d32():
+    """the script of the third pass the thread and quad contexts play as well: the first at depth 32 with all seven new kinds"""
+    return next(s for s in scripts()[N_OLD_PASSES:] if s.shape.depth == 32 and
+                {st.kind for st in s.steps if not st.refusal} >= set(NEW_KINDS))
+
+
+def flights(script):
+    """Per step the pipelined kinds still in flight when it enters, counted by the model: a batch of kind 3, 15 or 18
+    stays in flight until the next LIGHT / FULL check or the wait of a synchronous call; a refused pipelined call leaves
+    them alone, any other refused call is taken to have waited."""
+    out, flight = [], []
+    for st in script.steps:
+        out.append(tuple(flight))
+        if st.refusal:
+            flight = flight if st.kind in PIPELINED else []
+        else:
+            flight = flight + [st.kind] if st.kind in PIPELINED else []
+        if st.check != NO_CHECK:
+            flight = []
+    return out
+
+
+def caps(script):
+    """the capacity before every step (reserve changes it)"""
+    m, out = new_model(script.shape), []
+    for st in script.steps:
+        out.append(m.cap)
+        try:
+            play(m, st)
+        except Refused:
+            pass
+    return out
 
 
 # ---------------------------------------------------------------- the oracle's tree of a model state
@@ -909,26 +1412,29 @@ def oracle_rows(shape, before, acc):
     return rec
 
 
-def oracle_read_rows(shape, before, step):
+def oracle_read_rows(shape, before, step, carried=None):
     """the imt_read_out rows of the READs of mixed-batch `step` on the oracle's tree of state `before`: one walk on one
     handle, sparse_insert at every INSERT, and at every READ sparse_root and sparse_proof of the low leaf the model names
     (siblings item-major [n_reads, depth, 32], low_index global); the oracle's preimage of that leaf must be the model's"""
-    key = (shape, tuple(before), step.vals, step.arg["ops"])
+    vals, ops = step.vals, step.arg["ops"]
+    if carried is not None:                                    # a filtered twin: the operations it carried out
+        vals, ops = tuple(vals[p] for p in carried), tuple(ops[p] for p in carried)
+    key = (shape, tuple(before), vals, ops)
     if key in _READ_ROWS:
         return _READ_ROWS[key]
     orc, depth, base = oracle_lib.load(), shape.depth, index_base(shape)
     m = new_model(shape, before)
-    n = step.arg["ops"].count(OP_READ)
+    n = len(ops) - ops.count(OP_INSERT)
     rec = dict(low_index=np.empty(n, np.uint64), is_largest=np.empty(n, np.uint8), low_leaf=np.empty((n, 3, 32), np.uint8),
                root=np.empty((n, 32), np.uint8), low_sib=np.empty((n, depth, 32), np.uint8))
     h, q = _handle(orc, shape, before), 0
     try:
-        for p, (v, op) in enumerate(zip(step.vals, step.arg["ops"])):
+        for p, (v, op) in enumerate(zip(vals, ops)):
             if op == OP_INSERT:
                 m.insert([v])
                 assert orc.sparse_insert(h, depth, v)["rc"] == 0, (shape.name, p)
                 continue
-            low, leaf, largest = m.nm_witness(v)
+            low, leaf, largest = m.nm_witness(v) if op == OP_READ else m.member_witness(v)      # a MEMBER: the leaf that holds v
             pre = orc.sparse_preimage(h, low - base)
             assert (pre == pre_arr([leaf])[0]).all(), f"{shape.name}: the oracle's leaf {low} at operation {p} is not the model's"
             rec["low_index"][q], rec["is_largest"][q], rec["low_leaf"][q] = low, largest, pre
